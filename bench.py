@@ -310,6 +310,45 @@ def timed_steps(tr, first_step, n_steps, barrier, parallel, device):
     return elapsed, per, losses
 
 
+DUMP_SAMPLE = 1 << 22           # weights sampled per dumped model: 16 MB of f32 each
+
+
+def weight_sample(module, seed=0):
+    """A fixed, seeded sample of every state_dict entry of `module`, concatenated in key order, as f32 on the host: one random
+    element from each of DUMP_SAMPLE equal strides of the concatenation (all of it when it is smaller)."""
+    import numpy as np
+    sd = module.state_dict()
+    sizes = [v.numel() for v in sd.values()]
+    total = sum(sizes)
+    if total <= DUMP_SAMPLE:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        stride = total // DUMP_SAMPLE
+        idx = np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, DUMP_SAMPLE)
+    out, off = [], 0
+    for v, n in zip(sd.values(), sizes):
+        lo, hi = np.searchsorted(idx, [off, off + n])
+        if hi > lo:
+            sel = torch.from_numpy(idx[lo:hi] - off).to(v.device)
+            out.append(v.detach().reshape(-1)[sel].float().cpu())
+        off += n
+    return torch.cat(out).numpy()
+
+
+def dump_outputs(path, tr, model, ema_model, loss):
+    """--dump-outputs: what the last timed train_step handed its caller -- the loss it returned, Trainer.last_mse, and the model
+    and EMA weights it updated (a fixed sample of each: weight_sample) -- as <path>/<name>.npy.  Rank 0 only."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": np.asarray([float(loss)], dtype=np.float64),
+              "mse": np.asarray([float(tr.last_mse)], dtype=np.float64),
+              "weights_sample": weight_sample(model)}
+    if ema_model is not None:
+        arrays["ema_weights_sample"] = weight_sample(ema_model)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -334,7 +373,12 @@ def main():
     ap.add_argument("--graph", action="store_true", help="capture the step into one hipGraph (Trainer args.hip_graph); implies --no-trace")
     ap.add_argument("--no-graph", action="store_true", help="never capture (default: the Trainer decides -- args.hip_graph='auto' -- on one GPU: "
                                                             "a launch-bound step is captured, a GPU-bound one stays eager)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed (loss, mse, a fixed sample of the updated model and "
+                         "EMA weights) as DIR/<name>.npy; the inputs depend only on the arguments")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(a.gpus)
 
@@ -384,8 +428,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(per_gpu, first_step):
-        """W untimed + K timed steps at `per_gpu` images per rank -> result fields."""
+    def run(per_gpu, first_step, dump=None):
+        """W untimed + K timed steps at `per_gpu` images per rank -> result fields; `dump`: directory for dump_outputs."""
         loader = _Loader(synth_batches(per_gpu, 4, device, 123 + rank, wl))
         tr = run.tr
         if tr is None:
@@ -396,6 +440,10 @@ def main():
             tr.train_step(first_step + s)
         elapsed, per, losses = timed_steps(tr, first_step + a.warmup, a.steps, barrier, parallel, device)
         last = float(losses[-1])
+        if dump:
+            tr.consolidate()                # sharded optimizer: gather the masters and the EMA (a collective: every rank)
+            if rank == 0:
+                dump_outputs(dump, tr, model, ema_model, losses[-1])
         if not (last == last) or abs(last) > 1e4:
             raise SystemExit(f"non-finite / diverged loss {last}: the measurement is void")
         per.sort()
@@ -404,7 +452,7 @@ def main():
                 "last_loss": round(last, 5)}
     run.tr = None
 
-    main_res = run(B // world if scaling == "strong" else B, 0)
+    main_res = run(B // world if scaling == "strong" else B, 0, a.dump_outputs)
     weak_res = run(B, a.warmup + a.steps) if (parallel and scaling == "strong") else None
 
     # roofline of the dominant kernel: extra steps AFTER the timed region (the HIP-event brackets fence the launch stream and

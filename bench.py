@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training images/sec of the variance-aware-weighted diffusion step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dit_b4] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dit_b4] [--scaling strong|weak] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 (a plain `python bench.py --gpus N` starts its N ranks itself, before anything touches the GPU, and relays rank 0's line)
@@ -11,12 +11,16 @@ latent sampling, noise + timestep draw, q_sample, DiT forward, weighted-MSE loss
 (N>1: bucketed RCCL all-reduce overlapped with backward), fused AdamW + EMA.  Nothing is skipped or cached.
 Default workload = BASELINE.json config 4, the one its MFMA target is quoted on: DiT-B/4 on 4x32x32 latents, GLOBAL batch
 256 sharded over the N GPUs as the reference shards it (main.py:166-180: per-GPU batch = batch_size // world_size; strong
-scaling), bf16 MFMA with f32 accumulation, weight_type 'lambda'.  For N > 1 the same process then also times the weak
-configuration (256 per GPU) and reports it in the extra field "weak".
+scaling), bf16 MFMA with f32 accumulation, weight_type 'lambda'.
 
-Prints ONE JSON line on rank 0 (contract in the project brief) with two extra objects:
-  roofline      the dominant kernel (bf16 MFMA GEMM): algorithmic FLOP / HIP-event launch time, vs 2.5 PFLOP/s
-  cpu_baseline  the CPU oracle (oracle/, kind "port") timed on this host on a bounded sample of the same workload
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints ONE JSON line on rank 0 (contract in the
+project brief).  With --full the same process then also measures what the headline figure does not need, and adds it to the
+line:
+  weak          N > 1, strong scaling: the weak configuration (256 per GPU), timed after the headline steps
+  roofline      the dominant kernel (bf16 MFMA GEMM): algorithmic FLOP / HIP-event launch time, vs 2.5 PFLOP/s, from extra
+                traced steps (--no-trace skips them; --shape-table FILE also writes them by shape)
+  cpu_baseline  N = 1: the CPU oracle (oracle/, kind "port") timed on this host on a bounded sample of the same workload
+                (--no-cpu-baseline skips it)
 """
 import argparse
 import copy
@@ -357,8 +361,8 @@ def main():
     ap.add_argument("--workload", default="dit_b4", choices=list(WORKLOADS))
     ap.add_argument("--batch", type=int, default=None, help="GLOBAL batch of the strong configuration = per-GPU batch of the weak one (default: the workload's)")
     ap.add_argument("--scaling", default=None, choices=["strong", "weak"],
-                    help="strong (default): global batch fixed, batch // N per GPU (reference main.py:166-180), plus a weak pass "
-                         "reported as the field 'weak' when N > 1; weak: only the batch-per-GPU-fixed measurement")
+                    help="strong (default): global batch fixed, batch // N per GPU (reference main.py:166-180), plus (--full, N > 1) "
+                         "a weak pass reported as the field 'weak'; weak: only the batch-per-GPU-fixed measurement")
     ap.add_argument("--bucket-dtype", default="bf16", choices=["bf16", "f32"], help="gradient all-reduce buckets on the wire")
     ap.add_argument("--shard-optimizer", action="store_true",
                     help="N > 1: ZeRO-1 split (reduce-scatter, AdamW + EMA on 1/N of every bucket, all-gather of the bf16 weights) "
@@ -366,10 +370,15 @@ def main():
                          "(main.py:347).  Opt-in: its RCCL in-place reduce-scatter / all-gather paths have only run with one rank "
                          "and over gloo, so the default multi-GPU number stays on the path whose semantics are the reference's")
     ap.add_argument("--no-shard-optimizer", action="store_true", help=argparse.SUPPRESS)      # (round-3 spelling: now the default)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-trace", action="store_true", help="skip the extra (untimed) steps that bracket GEMM launches with HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run the weak-scaling pass (N > 1), the traced steps behind "
+                         "'roofline' and the CPU baseline (N = 1); a plain run does none of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-trace", action="store_true",
+                    help="with --full: skip the extra (untimed) steps that bracket GEMM launches with HIP events")
     ap.add_argument("--fp32", action="store_true", help="parity-mode kernels (not the headline number)")
-    ap.add_argument("--shape-table", default=None, metavar="FILE", help="also write the traced launches per (variant, M, N, K): launches, total us, TFLOP/s")
+    ap.add_argument("--shape-table", default=None, metavar="FILE",
+                    help="with --full: also write the traced launches per (variant, M, N, K): launches, total us, TFLOP/s")
     ap.add_argument("--graph", action="store_true", help="capture the step into one hipGraph (Trainer args.hip_graph); implies --no-trace")
     ap.add_argument("--no-graph", action="store_true", help="never capture (default: the Trainer decides -- args.hip_graph='auto' -- on one GPU: "
                                                             "a launch-bound step is captured, a GPU-bound one stays eager)")
@@ -379,6 +388,8 @@ def main():
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.shape_table and not a.full:
+        ap.error("--shape-table writes the traced steps of --full: add --full")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(a.gpus)
 
@@ -453,29 +464,29 @@ def main():
     run.tr = None
 
     main_res = run(B // world if scaling == "strong" else B, 0, a.dump_outputs)
-    weak_res = run(B, a.warmup + a.steps) if (parallel and scaling == "strong") else None
+    weak_res = run(B, a.warmup + a.steps) if (a.full and parallel and scaling == "strong") else None
 
     # roofline of the dominant kernel: extra steps AFTER the timed region (the HIP-event brackets fence the launch stream and
     # cost ~3 % of a step, so the timed steps carry none), at the batch of the headline measurement
     trace = None
+    traced = a.full and not a.no_trace
     graph_timed = getattr(run.tr, "_graph", None) is not None
-    if graph_timed and not a.no_trace:
+    if graph_timed and traced:
         run.tr.eager_from_now_on()           # the timed steps replayed a captured graph: the traced ones launch kernel by kernel
-    if not a.no_trace and rank == 0:
+    if traced and rank == 0:
         trace = vaw_amd.ops.GemmTrace()
     traced_steps = 3
-    if parallel or trace is not None:       # every rank runs them: the steps contain collectives
+    if traced:                              # every rank runs them: the steps contain collectives
         if weak_res is not None:
             loader = _Loader(synth_batches(main_res["per_gpu_batch"], 4, device, 123 + rank, wl))
             run.tr.train_loader, run.tr.datalooper = loader, iter(loader)
-        if not a.no_trace:
-            run.tr.train_step(10 ** 6)
-            barrier()
-            vaw_amd.ops.gemm_trace = trace
-            for s in range(traced_steps):
-                run.tr.train_step(10 ** 6 + 1 + s)
-            barrier()
-            vaw_amd.ops.gemm_trace = None
+        run.tr.train_step(10 ** 6)
+        barrier()
+        vaw_amd.ops.gemm_trace = trace
+        for s in range(traced_steps):
+            run.tr.train_step(10 ** 6 + 1 + s)
+        barrier()
+        vaw_amd.ops.gemm_trace = None
 
     if rank == 0:
         ips, ms = main_res["value"], main_res["ms_per_step"]
@@ -529,7 +540,7 @@ def main():
                     "by_variant": {k: {"launches_per_step": v["launches"] / traced_steps,
                                        "tflops": round(v["flop"] / (v["ms"] * 1e-3) / 1e12, 1),
                                        "avg_us": round(1e3 * v["ms"] / v["launches"], 2)} for k, v in summ.items()}}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             run.tr = None
             del opt, model, ema_model, net
             torch.cuda.empty_cache()

@@ -15,7 +15,7 @@ for wl in $WLS; do
   base=${TAG}_${wl}_bs${BS[$wl]}_${dt}
   d=gpurun_out/prof_$wl; rm -rf $d
   echo "== $wl: kernel stats"
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $d -o p -- python3 bench.py --workload $wl ${FLAGS[$wl]} --no-cpu-baseline --no-graph > $d.log 2>&1 || { tail -5 $d.log; exit 1; }
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $d -o p -- python3 bench.py --workload $wl ${FLAGS[$wl]} --full --no-cpu-baseline --no-graph > $d.log 2>&1 || { tail -5 $d.log; exit 1; }
   cp $d/p_kernel_stats.csv $OUT/${base}_kernel_stats.csv
   grep '^{"metric"' $d.log | tail -1 > $OUT/${base}_bench_under_rocprof.json
   if [ $wl = dit_b4 ] || [ $wl = dit_xl2_fp8 ] || [ $wl = unet64 ] || [ "$PMC_ALL" = 1 ]; then
@@ -32,7 +32,7 @@ for wl in $WLS; do
   fi
   rm -rf $d
 done
-echo "== dit_b4 unprofiled (defaults, with the CPU baseline)"
-timeout -k 10 900 python3 bench.py > gpurun_out/bench_default.log 2>&1 || { tail -5 gpurun_out/bench_default.log; exit 1; }
-grep '^{"metric"' gpurun_out/bench_default.log | tail -1 > $OUT/${TAG}_dit_b4_bs256_bf16_bench.json
+echo "== dit_b4 unprofiled (defaults, --full: with the roofline and the CPU baseline)"
+timeout -k 10 900 python3 bench.py --full > $OUT/bench_default.log 2>&1 || { tail -5 $OUT/bench_default.log; exit 1; }
+grep '^{"metric"' $OUT/bench_default.log | tail -1 > $OUT/${TAG}_dit_b4_bs256_bf16_bench.json
 ls -la $OUT

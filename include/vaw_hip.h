@@ -260,6 +260,32 @@ int vaw_gate_bwd_fp8(const float* dres, const void* y, const float* gate, int64_
  * separate workgroups (small per-GPU batches would otherwise leave most CUs idle: one workgroup per sample) and the
  * per-sample column sums are folded over the chunks in a fixed order by a second kernel.  NULL = one workgroup per sample. */
 int64_t vaw_row_bwd_workspace_floats(int B, int T, int D);
+/* Launch plan of the row kernels: the one host function their entry points take every launch choice from (pure arithmetic: no
+ * device call, so it can be asked without a GPU).  kind = the entry point; dt = its act dtype (the fp8 entries: VAW_BF16);
+ * rows: B, T, D as the entry point's, workspace_floats = what the caller would pass (0 = none), ldx / base_addr unused;
+ * colsum: M = B * T rows (pass T = 1), N = D columns, row stride ldx, base_addr = the address of X (its alignment picks the path).
+ *   nc: workgroups per sample (grid.y; > 1: row_bwd_finish_kernel folds them), rows_per_chunk: T rows per chunk;
+ *   colsum: nc = partial rows of the workspace (grid.y), rows_per_chunk = rows per partial row. */
+typedef enum { VAW_ROW_LN_FWD = 0, VAW_ROW_LN_FWD_FP8 = 1, VAW_ROW_LN_BWD = 2, VAW_ROW_GATE_BWD = 3, VAW_ROW_GATE_BWD_FP8 = 4,
+               VAW_ROW_LN_BWD_GATE = 5, VAW_ROW_LN_BWD_GATE_FP8 = 6, VAW_ROW_COLSUM = 7 } vaw_row_kind;
+typedef enum {
+    VAW_RV_LN_FWD = 0,          /* ln_modulate_fwd_kernel<T, NV> */
+    VAW_RV_ROW_BWD = 1,         /* row_bwd_kernel<T, NV, false>: LayerNorm backward */
+    VAW_RV_ROW_GATE = 2,        /* row_bwd_kernel<T, NV, true>: gate backward */
+    VAW_RV_ROW_FUSE = 3,        /* row_bwd_kernel<T, NV, false, QOUT, true>: fused, per-sample sums in registers */
+    VAW_RV_ROW_FUSE8 = 4,       /* row_bwd_fuse8_kernel<NV, QOUT>: fused, per-wave sums in LDS slabs (bf16) */
+    VAW_RV_COLSUM_BF16X8 = 5, VAW_RV_COLSUM_VEC4 = 6, VAW_RV_COLSUM_SCALAR = 7
+} vaw_row_variant;
+typedef struct {
+    int variant;                /* vaw_row_variant */
+    int nv;                     /* template slab count: 256-column slabs a lane walks (1..6, 8); colsum: 0 */
+    int nc, rows_per_chunk;     /* see above */
+    int grid_x, block;          /* grid.x (forward: before the launcher's cap to one resident round), threads per workgroup */
+    int64_t lds_bytes;          /* dynamic LDS per workgroup */
+    int64_t workspace_floats;   /* f32 workspace the launch uses (0: none) */
+} vaw_row_launch;
+int vaw_row_plan(vaw_row_kind kind, vaw_dtype dt, int64_t B, int64_t T, int64_t D, int64_t ldx, int64_t base_addr,
+                 int64_t workspace_floats, vaw_row_launch* out);
 /* Backward of `x + gate.unsqueeze(1) * y` :135-136 w.r.t. the branch:
  *   dy[b,t,:] = dres[b,t,:] * gate[b,:] (act dtype) ; dgate[b,:] = sum_t dres * y ;
  *   dy_colsum_partial (f32 [B, D] or NULL): per-sample sum_t dy -- reduce over B with vaw_reduce_rows to get the

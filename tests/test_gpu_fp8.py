@@ -252,11 +252,27 @@ def test_fp8_transpose_kernels(R, C):
     assert torch.equal(qt, q.t())
 
 
+# (2, 96, 1280): the register form (the LDS slabs of 8 waves do not fit); (64, 5, 1280): the LDS-slab form at 5 waves; DiT-L/2 and
+# DiT-XL/2 at their per-GPU batches (B * T a multiple of 64 and D of 128 for the Fp8 transpose)
+FP8_FUSED_PAIR_SHAPES = [(4, 64, 256), (2, 128, 1152), (2, 96, 1280), (64, 5, 1280), (32, 256, 1024), (128, 256, 1152)]
+
+
 @pytest.mark.parametrize("fmt", ["e4m3", "e5m2"])
-@pytest.mark.parametrize("B,T,D", [(4, 64, 256), (2, 128, 1152)])
+@pytest.mark.parametrize("B,T,D", FP8_FUSED_PAIR_SHAPES)
 def test_ln_bwd_gate_fp8_matches_the_pair(fmt, B, T, D):
     """vaw_ln_modulate_bwd_gate_fp8 = vaw_ln_modulate_bwd followed by vaw_gate_bwd_fp8 on its dx: bytes, running max, dx and every
     per-sample sum bitwise equal (D = 1152: the 512-thread variant with the rows of a sample cut into chunks)."""
+    _fp8_fused_vs_pair(fmt, B, T, D, alias=False)
+
+
+@pytest.mark.parametrize("fmt", ["e4m3", "e5m2"])
+@pytest.mark.parametrize("B,T,D", FP8_FUSED_PAIR_SHAPES[:4])
+def test_ln_bwd_gate_fp8_in_place_matches_the_pair(fmt, B, T, D):
+    """As above with dres_in == dx, the way dit.py calls both."""
+    _fp8_fused_vs_pair(fmt, B, T, D, alias=True)
+
+
+def _fp8_fused_vs_pair(fmt, B, T, D, alias):
     code, E, FMAX = FMT[fmt]
     dev = torch.device(DEV)
     M = B * T
@@ -277,9 +293,11 @@ def test_ln_bwd_gate_fp8_matches_the_pair(fmt, B, T, D):
         f = ops.Fp8(M, D, dev, fmt=code, state=st[0])
         dmod = torch.zeros(B, 6 * D, device=DEV)
         dx, part = torch.empty(M, D, device=DEV), torch.empty(B, D, device=DEV)
-        a = (ptr(dout), ptr(x), ptr(mean), ptr(rstd), ptr(mod) + 4 * 4 * D, 6 * D, ptr(dres), ptr(dx), ptr(dmod) + 4 * 3 * D,
-             ptr(dmod) + 4 * 4 * D, 6 * D)
-        if fused:       # the C entry point itself (ops.ln_modulate_bwd_gate_fp8 sends rows wider than 768 to the pair)
+        if alias:
+            dx.copy_(dres)
+        a = (ptr(dout), ptr(x), ptr(mean), ptr(rstd), ptr(mod) + 4 * 4 * D, 6 * D, ptr(dx) if alias else ptr(dres), ptr(dx),
+             ptr(dmod) + 4 * 3 * D, ptr(dmod) + 4 * 4 * D, 6 * D)
+        if fused:       # the C entry point itself (ops.ln_modulate_bwd_gate_fp8 sends rows wider than 1280 to the pair)
             ws = ops._row_ws(B, T, D)
             ops.check(vaw_amd._lib.lib().vaw_ln_modulate_bwd_gate_fp8(*a, ptr(y), ptr(mod) + 4 * 5 * D, f.epilogue_target(2), f.state.data_ptr(),
                                                                      f.fmt, ptr(dmod) + 4 * 5 * D, ptr(part), B, T, D, ws.data_ptr(), ws.numel(),

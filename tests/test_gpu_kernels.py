@@ -610,11 +610,28 @@ def test_gate_bwd(dtype):
     torch.testing.assert_close(out.cpu().double(), 1.0 + dy.cpu().double().sum(0), rtol=1e-5, atol=1e-4)
 
 
+# DiT-L/2 and DiT-XL/2 at their per-GPU batches: the fused entry aims at 512 workgroups there, so the pair must cut rows the same way;
+# D = 1216 / 1280 at 8 waves: the fused pass's LDS slabs do not fit, it runs the register form
+FUSED_PAIR_SHAPES = [(3, 16, 64), (2, 64, 768), (2, 24, 1152), (300, 8, 192), (2, 24, 1216), (2, 100, 1280), (3, 5, 1280),
+                     (2, 40, 260), (2, 40, 1028), (32, 256, 1024), (128, 256, 1152)]
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("B,T,D", [(3, 16, 64), (2, 64, 768), (2, 24, 1152), (300, 8, 192)])
+@pytest.mark.parametrize("B,T,D", FUSED_PAIR_SHAPES)
 def test_ln_modulate_bwd_fused_with_gate_bwd_is_bitwise_the_pair(dtype, B, T, D):
     """vaw_ln_modulate_bwd_gate = vaw_ln_modulate_bwd followed by vaw_gate_bwd on its dx, one pass: every output bitwise equal
     (B = 2, 3: rows split over several workgroups + fold launch; B = 300: one workgroup per sample)."""
+    _fused_vs_pair(dtype, B, T, D, alias=False)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B,T,D", FUSED_PAIR_SHAPES[:9])
+def test_ln_modulate_bwd_fused_with_gate_bwd_in_place_is_bitwise_the_pair(dtype, B, T, D):
+    """As above with dres_in == dx, the way dit.py calls both (the residual-stream gradient accumulates in place)."""
+    _fused_vs_pair(dtype, B, T, D, alias=True)
+
+
+def _fused_vs_pair(dtype, B, T, D, alias):
     x = (_rand(B * T, D, seed=1) * 2 + 0.5).to(DEV)
     mod = (_rand(B, 6 * D, seed=2) * 0.5).to(DEV)
     dout = _rand(B * T, D, seed=3).to(dtype).to(DEV)
@@ -628,9 +645,11 @@ def test_ln_modulate_bwd_fused_with_gate_bwd_is_bitwise_the_pair(dtype, B, T, D)
     def run(fused):
         dmod = torch.zeros(B, 6 * D, device=DEV)
         dx, dy, part = torch.empty(B * T, D, device=DEV), torch.empty(B * T, D, device=DEV, dtype=dtype), torch.empty(B, D, device=DEV)
-        a = (dt, ptr(dout), ptr(x), ptr(mean), ptr(rstd), ptr(mod) + 4 * 4 * D, 6 * D, ptr(dres), ptr(dx), ptr(dmod) + 4 * 3 * D,
-             ptr(dmod) + 4 * 4 * D, 6 * D)
-        if fused:       # the C entry point itself (ops.ln_modulate_bwd_gate sends rows wider than 768 to the pair)
+        if alias:
+            dx.copy_(dres)
+        a = (dt, ptr(dout), ptr(x), ptr(mean), ptr(rstd), ptr(mod) + 4 * 4 * D, 6 * D, ptr(dx) if alias else ptr(dres), ptr(dx),
+             ptr(dmod) + 4 * 3 * D, ptr(dmod) + 4 * 4 * D, 6 * D)
+        if fused:       # the C entry point itself (ops.ln_modulate_bwd_gate sends rows wider than 1280 to the pair)
             ws = ops._row_ws(B, T, D)
             ops.check(lib().vaw_ln_modulate_bwd_gate(*a, ptr(y), ptr(mod) + 4 * 5 * D, ptr(dy), ptr(dmod) + 4 * 5 * D, ptr(part), B, T, D,
                                                      ws.data_ptr(), ws.numel(), stream_ptr()), "vaw_ln_modulate_bwd_gate")

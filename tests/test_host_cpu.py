@@ -441,3 +441,105 @@ def test_latent_h5_dataset_contract_and_loader():
     assert torch.equal(ds2[3][0], torch.from_numpy(lat[3]))
     with pytest.raises(ValueError):
         vaw_amd.LatentH5Dataset({"train_latents": lat, "train_labels": lab[:-1]})
+
+
+# ------------------------------------------------------------------------------------------------
+# Launch plan of the row kernels (vaw_row_plan: host arithmetic only, the launchers take every choice from it)
+# ------------------------------------------------------------------------------------------------
+ROW_LDS_MAX = 160 * 1024          # gfx950: LDS per CU
+
+
+def _row_bound(p):
+    """__launch_bounds__ of the variant (layernorm.hip); the register-fused kernel drops to 512 threads from NV = 4 on"""
+    from vaw_amd import _lib as L
+    if p.variant == L.RV_ROW_FUSE:
+        return 512 if p.nv > 3 else 1024
+    return {L.RV_LN_FWD: 256, L.RV_ROW_BWD: 1024, L.RV_ROW_GATE: 1024, L.RV_ROW_FUSE8: 512}.get(p.variant, 256)
+
+
+def test_row_plan_sweep_respects_lds_launch_bounds_chunking_and_workspace():
+    """Every entry point, D = 4 ... 2048: the LDS a launch asks for fits a CU, the block fits the variant's launch bounds, the chunks
+    cover the T rows with none empty, vaw_row_bwd_workspace_floats is enough for the chunking the plan wants, and the fused pass
+    cuts rows exactly as the pair it replaces (nc and waves) wherever it promises bitwise equality with it (D <= 1280)."""
+    from vaw_amd import _lib as L
+    from vaw_amd.ops import row_plan
+    lib = vaw_amd.lib()
+    bwd = [(L.ROW_LN_BWD, L.F32), (L.ROW_LN_BWD, L.BF16), (L.ROW_GATE_BWD, L.F32), (L.ROW_GATE_BWD, L.BF16),
+           (L.ROW_GATE_BWD_FP8, L.BF16), (L.ROW_LN_BWD_GATE, L.F32), (L.ROW_LN_BWD_GATE, L.BF16), (L.ROW_LN_BWD_GATE_FP8, L.BF16)]
+    bad = []
+    for D in range(4, 2049, 4):
+        nv = -(-D // 256)
+        for T in (1, 7, 8, 9, 64, 100, 256, 1024):
+            for B in (1, 2, 32, 128, 256, 300):
+                wsf = lib.vaw_row_bwd_workspace_floats(B, T, D)
+                for kind in (L.ROW_LN_FWD, L.ROW_LN_FWD_FP8):
+                    p = row_plan(kind, L.BF16, B, T, D)
+                    assert (p.variant, p.nv, p.block, p.lds_bytes, p.workspace_floats) == (L.RV_LN_FWD, nv if nv <= 6 else 8, 256, 0, 0)
+                    assert p.grid_x >= 1 and (kind == L.ROW_LN_FWD or p.grid_x <= 2048)
+                plans = {}
+                for kind, dt in bwd:
+                    for ws in (0, wsf, 1 << 60):
+                        p = row_plan(kind, dt, B, T, D, workspace_floats=ws)
+                        plans[kind, dt, ws] = p
+                        where = f"kind={kind} dt={dt} B={B} T={T} D={D} ws={ws}: variant {p.variant} nc {p.nc} rpc {p.rows_per_chunk} " \
+                                f"block {p.block} lds {p.lds_bytes}"
+                        if p.lds_bytes > ROW_LDS_MAX:
+                            bad.append("LDS " + where)
+                        if not (64 <= p.block <= _row_bound(p) and p.block % 64 == 0):
+                            bad.append("block " + where)
+                        assert p.nv == (nv if nv <= 6 else 8) and p.nv * 256 >= D, where
+                        assert p.grid_x == B and p.nc >= 1 and p.rows_per_chunk >= 1, where
+                        assert p.nc * p.rows_per_chunk >= T and (p.nc - 1) * p.rows_per_chunk < T, where
+                        assert p.block // 64 == min(p.rows_per_chunk, 8 if (nv <= 5 or kind in (L.ROW_LN_BWD_GATE, L.ROW_LN_BWD_GATE_FP8)) else 16), where
+                        assert p.workspace_floats <= ws and (p.nc == 1) == (p.workspace_floats == 0), where
+                        if ws == 0:
+                            assert p.nc == 1, where
+                    # the workspace the library sizes is what the plan wants: same chunking as with an unlimited one
+                    assert (plans[kind, dt, wsf].nc, plans[kind, dt, wsf].block) == (plans[kind, dt, 1 << 60].nc, plans[kind, dt, 1 << 60].block)
+                if D <= 1280:         # bitwise fused == pair: the same row partition (chunks x waves) on both sides
+                    for ws in (0, wsf):
+                        for fused, pair in (((L.ROW_LN_BWD_GATE, L.F32), [(L.ROW_LN_BWD, L.F32), (L.ROW_GATE_BWD, L.F32)]),
+                                            ((L.ROW_LN_BWD_GATE, L.BF16), [(L.ROW_LN_BWD, L.BF16), (L.ROW_GATE_BWD, L.BF16)]),
+                                            ((L.ROW_LN_BWD_GATE_FP8, L.BF16), [(L.ROW_LN_BWD, L.BF16), (L.ROW_GATE_BWD_FP8, L.BF16)])):
+                            f = plans[fused + (ws,)]
+                            for k in pair:
+                                u = plans[k + (ws,)]
+                                if (u.nc, u.rows_per_chunk, u.block) != (f.nc, f.rows_per_chunk, f.block):
+                                    bad.append(f"split fused {fused} vs {k}: B={B} T={T} D={D} ws={ws}: nc {f.nc} / {u.nc}, "
+                                               f"block {f.block} / {u.block}")
+                    f = plans[L.ROW_LN_BWD_GATE, L.BF16, wsf]
+                    assert f.variant in (L.RV_ROW_FUSE8, L.RV_ROW_FUSE)
+                    # the LDS-slab kernel wherever its slabs fit, the register form only where they do not
+                    if (f.variant == L.RV_ROW_FUSE8) != ((2 + 4 * f.block // 64) * D * 4 <= ROW_LDS_MAX):
+                        bad.append(f"variant B={B} T={T} D={D}: {f.variant}")
+    widths = {}
+    for b in bad:
+        widths.setdefault(b.split()[0], set()).add(int(re.search(r"D=(\d+)", b).group(1)))
+    summary = {k: f"D in [{min(v)}, {max(v)}] ({len(v)} widths)" for k, v in widths.items()}
+    assert not bad, f"{len(bad)} bad plans: {summary}, e.g.\n" + "\n".join(bad[:6] + bad[-6:])
+
+
+def test_row_plan_colsum_paths():
+    """vaw_colsum's path: bf16 x 8 (bf16, N and ldx multiples of 8, 16-byte aligned base, M >= 1024), vec4 (ldx % 4 == 0 and aligned
+    base), scalar otherwise; the workspace is vaw_colsum_workspace_floats for the 128-row kernel, less for the 512-row ones."""
+    from vaw_amd import _lib as L
+    from vaw_amd.ops import row_plan
+    lib = vaw_amd.lib()
+    for dt in (L.F32, L.BF16):
+        for M in (1, 3, 511, 512, 1023, 1024, 1100, 4097):
+            for N, ldx in ((8, 8), (264, 264), (264, 1584), (260, 1560), (3, 3), (7, 9), (768, 7 * 768)):
+                for base in (0x10000, 0x10004, 0x10008, 0x10010 + 2):
+                    p = row_plan(L.ROW_COLSUM, dt, M, 1, N, ldx=ldx, base_addr=base)
+                    aligned = base % 16 == 0
+                    if dt == L.BF16 and N % 8 == 0 and ldx % 8 == 0 and aligned and M >= 1024:
+                        want, rows = L.RV_COLSUM_BF16X8, 128
+                    elif ldx % 4 == 0 and aligned:
+                        want, rows = L.RV_COLSUM_VEC4, 512
+                    else:
+                        want, rows = L.RV_COLSUM_SCALAR, 512
+                    assert (p.variant, p.rows_per_chunk, p.nc, p.block, p.lds_bytes) == (want, rows, -(-M // rows), 256, 0)
+                    assert p.grid_x == -(-N // 256) and p.workspace_floats == p.nc * N <= lib.vaw_colsum_workspace_floats(M, N)
+    with pytest.raises(vaw_amd.VawError):
+        row_plan(L.ROW_COLSUM, L.F32, 10, 1, 8, ldx=4)
+    with pytest.raises(vaw_amd.VawError):
+        row_plan(L.ROW_LN_BWD, L.F32, 2, 8, 2052)

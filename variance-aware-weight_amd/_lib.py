@@ -26,6 +26,16 @@ class AttnDesc(C.Structure):
                 ("o_sb", _l), ("o_sh", _l), ("o_st", _l), ("o_sd", _l), ("scale", _f)]
 
 
+class RowLaunch(C.Structure):
+    """vaw_row_launch of include/vaw_hip.h: the launch vaw_row_plan picks for a row-kernel entry point."""
+    _fields_ = [("variant", _i), ("nv", _i), ("nc", _i), ("rows_per_chunk", _i), ("grid_x", _i), ("block", _i), ("lds_bytes", _l),
+                ("workspace_floats", _l)]
+
+
+# vaw_row_kind / vaw_row_variant
+ROW_LN_FWD, ROW_LN_FWD_FP8, ROW_LN_BWD, ROW_GATE_BWD, ROW_GATE_BWD_FP8, ROW_LN_BWD_GATE, ROW_LN_BWD_GATE_FP8, ROW_COLSUM = range(8)
+RV_LN_FWD, RV_ROW_BWD, RV_ROW_GATE, RV_ROW_FUSE, RV_ROW_FUSE8, RV_COLSUM_BF16X8, RV_COLSUM_VEC4, RV_COLSUM_SCALAR = range(8)
+
 # name -> argtypes (every function returns int status unless noted)
 _PROTOS = {
     "vaw_qsample_fwd": [_p, _p, _p, _p, _p, _i, _p, _i, _l, _p],
@@ -96,6 +106,7 @@ _PROTOS = {
     "vaw_fp8_transpose": [_p, _l, _l, _l, _p, _l, _p],
     "vaw_ln_modulate_fwd_fp8": [_p, _p, _p, _l, _p, _p, _i, _p, _p, _i, _i, _i, _f, _p],
     "vaw_gate_bwd_fp8": [_p, _p, _p, _l, _p, _p, _i, _p, _l, _p, _i, _i, _i, _p, _l, _p],
+    "vaw_row_plan": [_i, _i, _l, _l, _l, _l, _l, _l, C.POINTER(RowLaunch)],
 }
 
 _lib = None

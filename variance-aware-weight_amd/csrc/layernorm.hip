@@ -422,9 +422,13 @@ __global__ void row_bwd_finish_kernel(const float* __restrict__ part, int NC, in
 }
 
 static int pick_nv(int D) { return (D + 255) / 256; }
-// chunks per sample so that small batches still fill the chip: aim at >= 256 workgroups (one per CU; at B >= 256 the
-// single 1024-thread workgroup per sample already runs at 4.5 TB/s and the extra fold launch only costs), >= 8 rows per chunk
-static int pick_chunks(int B, int Tt, bool have_ws, int target_wgs = 256) {
+// chunks per sample so that small batches still fill the chip: aim at >= target_wgs workgroups, >= 8 rows per chunk.  One rule for
+// every backward entry: the fused pass and the pair of kernels it replaces must cut a sample's rows the same way to stay bitwise equal.
+// Wide rows (D > 768: the fused pass's four accumulator sets need 176-190 registers) run 512-thread workgroups, two per CU: cut the
+// samples into enough chunks for 512 of them (DiT-XL/2 at 128 images: 200 us with 256 workgroups at 3.2 TB/s); narrower rows aim at
+// 256 (one per CU; at B >= 256 the single workgroup per sample already streams and the extra fold launch only costs)
+static int chunk_target(int nv) { return nv > 3 ? 512 : 256; }
+static int pick_chunks(int B, int Tt, bool have_ws, int target_wgs) {
     if (!have_ws) return 1;
     int nc = (target_wgs + B - 1) / B;
     const int max_nc = Tt / 8 > 0 ? Tt / 8 : 1;
@@ -441,6 +445,73 @@ static int pick_block(int Tt, int max_waves = 16) {
     if (nw < 1) nw = 1;
     return nw * 64;
 }
+static constexpr size_t kRowLdsMax = 160 * 1024;     // gfx950: LDS per CU, the most one workgroup may ask for
+
+extern "C" int vaw_row_plan(vaw_row_kind kind, vaw_dtype dt, int64_t B, int64_t T, int64_t D, int64_t ldx, int64_t base_addr,
+                            int64_t workspace_floats, vaw_row_launch* out) {
+    VAW_CHECK_ARG(out && kind >= VAW_ROW_LN_FWD && kind <= VAW_ROW_COLSUM, "row_plan: bad kind %d", (int)kind);
+    vaw_row_launch p = {};
+    if (kind == VAW_ROW_COLSUM) {
+        const int64_t M = B * T, N = D;
+        VAW_CHECK_ARG(B > 0 && T > 0 && N > 0 && ldx >= N, "colsum: bad sizes");
+        const bool vec = (ldx % 4 == 0) && ((base_addr & 15) == 0);
+        const bool wide = dt == VAW_BF16 && N % 8 == 0 && ldx % 8 == 0 && ((base_addr & 15) == 0) && M >= 1024;
+        const int64_t rows = wide ? 128 : 512, RB = (M + rows - 1) / rows;
+        VAW_CHECK_ARG(RB < 65536 && (N + 255) / 256 < (1LL << 31), "colsum: M too large");
+        p.variant = wide ? VAW_RV_COLSUM_BF16X8 : vec ? VAW_RV_COLSUM_VEC4 : VAW_RV_COLSUM_SCALAR;
+        p.nc = (int)RB;
+        p.rows_per_chunk = (int)rows;
+        p.grid_x = (int)((N + 255) / 256);
+        p.block = 256;
+        p.workspace_floats = RB * N;
+        *out = p;
+        return VAW_OK;
+    }
+    VAW_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 2048 && B < (1 << 30) && T < (1 << 30),
+                  "row_plan: need D%%4==0, D<=2048 (D=%ld)", (long)D);
+    VAW_CHECK_ARG(dt == VAW_F32 || dt == VAW_BF16, "row_plan: dt");
+    const int nv = pick_nv((int)D);
+    p.nv = nv <= 6 ? nv : 8;
+    if (kind == VAW_ROW_LN_FWD || kind == VAW_ROW_LN_FWD_FP8) {
+        const int64_t wgs = (B * T + 3) / 4;        // four rows per workgroup, one per wave; the launch caps the grid (see the kernel)
+        p.variant = VAW_RV_LN_FWD;
+        p.nc = 1;
+        p.rows_per_chunk = (int)T;
+        p.grid_x = (int)(kind == VAW_ROW_LN_FWD_FP8 ? (wgs < 2048 ? wgs : 2048) : (wgs < (1LL << 30) ? wgs : (1LL << 30)));
+        p.block = 256;
+        *out = p;
+        return VAW_OK;
+    }
+    const bool fused = kind == VAW_ROW_LN_BWD_GATE || kind == VAW_ROW_LN_BWD_GATE_FP8;
+    const int nq = fused ? 4 : 2;           // per-sample column sums carried through the workspace
+    int nc = pick_chunks((int)B, (int)T, workspace_floats > 0, chunk_target(nv));
+    if (nc > 1 && workspace_floats < (int64_t)nc * B * nq * D) nc = 1;
+    p.nc = nc;
+    p.rows_per_chunk = (int)((T + nc - 1) / nc);
+    p.grid_x = (int)B;
+    p.workspace_floats = nc > 1 ? (int64_t)nc * B * nq * D : 0;
+    if (!fused) {
+        p.variant = kind == VAW_ROW_LN_BWD ? VAW_RV_ROW_BWD : VAW_RV_ROW_GATE;
+        p.block = pick_block(p.rows_per_chunk, row_waves(nv, 16));
+        p.lds_bytes = 2 * D * (int64_t)sizeof(float);
+    } else {
+        p.block = pick_block(p.rows_per_chunk, 8);
+        // bf16 rows up to 1280 wide: the LDS-slab kernel, while its (1 + scale) and gate rows and one [4][D] slab per wave fit in
+        // the CU's LDS (8 waves: D <= 1204).  Otherwise the register-accumulator form: same waves, same row partition, so still
+        // bitwise the pair (fewer waves would change the per-wave partial sums).
+        const int64_t lds8 = (2 + 4 * (int64_t)(p.block / 64)) * D * (int64_t)sizeof(float);
+        const bool bf = kind == VAW_ROW_LN_BWD_GATE_FP8 || dt == VAW_BF16;
+        if (bf && nv <= 5 && lds8 <= (int64_t)kRowLdsMax) {
+            p.variant = VAW_RV_ROW_FUSE8;
+            p.lds_bytes = lds8;
+        } else {
+            p.variant = VAW_RV_ROW_FUSE;
+            p.lds_bytes = 6 * D * (int64_t)sizeof(float);
+        }
+    }
+    *out = p;
+    return VAW_OK;
+}
 
 #define DISPATCH_NV(nv, CALL)                                       \
     switch (nv) {                                                   \
@@ -453,16 +524,24 @@ static int pick_block(int Tt, int max_waves = 16) {
         default: { constexpr int NV = 8; CALL; } break;             \
     }
 
+#define ROW_PLAN(kind, dt, B, T, D, ldx, base, wsf)                                      \
+    vaw_row_launch plan;                                                               \
+    {                                                                                  \
+        const int rc_ = vaw_row_plan(kind, dt, B, T, D, ldx, base, wsf, &plan);        \
+        if (rc_ != VAW_OK) return rc_;                                                 \
+    }
+
 extern "C" int vaw_ln_modulate_fwd(vaw_dtype dt, const float* x, const float* shift, const float* scale, int64_t mod_ld,
                                    void* out, float* mean, float* rstd, int B, int T, int D, float eps,
                                    vaw_stream stream) {
     VAW_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 2048 && mod_ld % 4 == 0,
                   "ln_modulate_fwd: need D%%4==0, D<=2048, mod_ld%%4==0 (D=%d)", D);
+    ROW_PLAN(VAW_ROW_LN_FWD, dt, B, T, D, 0, 0, 0);
     const int64_t M = (int64_t)B * T;
     // one resident round of workgroups (what the registers allow per CU x 256 CUs: 7 x 256 for 768-wide bf16 rows -- a grid of
     // 8 per CU left the eighth to a second, nearly empty round), every wave several rows: see the kernel
     static int per_cu[2][9] = {};
-    const int nvk = pick_nv(D) <= 6 ? pick_nv(D) : 8, ti = dt == VAW_F32 ? 0 : 1;
+    const int nvk = plan.nv, ti = dt == VAW_F32 ? 0 : 1;
     if (!per_cu[ti][nvk]) {
         int nb = 0;
         if (dt == VAW_F32) { DISPATCH_NV(nvk, (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ln_modulate_fwd_kernel<float, NV>, 256, 0)); }
@@ -470,12 +549,12 @@ extern "C" int vaw_ln_modulate_fwd(vaw_dtype dt, const float* x, const float* sh
         per_cu[ti][nvk] = nb > 0 && nb <= 8 ? nb : 8;
     }
     const int64_t cap = 256LL * per_cu[ti][nvk];
-    const int grid = (int)(ceil_div(M, 4) < cap ? ceil_div(M, 4) : cap);
+    const int grid = (int)(plan.grid_x < cap ? plan.grid_x : cap);
     hipStream_t s = (hipStream_t)stream;
     if (dt == VAW_F32) {
-        DISPATCH_NV(pick_nv(D), (ln_modulate_fwd_kernel<float, NV><<<grid, 256, 0, s>>>(x, shift, scale, mod_ld, (float*)out, mean, rstd, M, T, D, eps)));
+        DISPATCH_NV(nvk, (ln_modulate_fwd_kernel<float, NV><<<grid, plan.block, 0, s>>>(x, shift, scale, mod_ld, (float*)out, mean, rstd, M, T, D, eps)));
     } else {
-        DISPATCH_NV(pick_nv(D), (ln_modulate_fwd_kernel<bf16_t, NV><<<grid, 256, 0, s>>>(x, shift, scale, mod_ld, (bf16_t*)out, mean, rstd, M, T, D, eps)));
+        DISPATCH_NV(nvk, (ln_modulate_fwd_kernel<bf16_t, NV><<<grid, plan.block, 0, s>>>(x, shift, scale, mod_ld, (bf16_t*)out, mean, rstd, M, T, D, eps)));
     }
     VAW_CHECK_LAUNCH("ln_modulate_fwd");
     return VAW_OK;
@@ -489,11 +568,11 @@ extern "C" int vaw_ln_modulate_fwd_fp8(const float* x, const float* shift, const
     VAW_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 2048 && mod_ld % 4 == 0 && q_out && q_state,
                   "ln_modulate_fwd_fp8: need D%%4==0, D<=2048, mod_ld%%4==0 (D=%d)", D);
     VAW_CHECK_ARG(q_format == VAW_FP8 || q_format == VAW_BF8, "ln_modulate_fwd_fp8: q_format");
+    ROW_PLAN(VAW_ROW_LN_FWD_FP8, VAW_BF16, B, T, D, 0, 0, 0);      // grid: 8 workgroups per CU, every wave several rows: see the kernel
     const int64_t M = (int64_t)B * T;
-    const int grid = ceil_div(M, 4) < 2048 ? ceil_div(M, 4) : 2048;       // 8 workgroups per CU, every wave several rows: see the kernel
     hipStream_t s = (hipStream_t)stream;
-    DISPATCH_NV(pick_nv(D), (ln_modulate_fwd_kernel<bf16_t, NV><<<grid, 256, 0, s>>>(x, shift, scale, mod_ld, nullptr, mean, rstd, M, T, D, eps,
-                                                                                  (unsigned char*)q_out, q_state, q_format == VAW_BF8)));
+    DISPATCH_NV(plan.nv, (ln_modulate_fwd_kernel<bf16_t, NV><<<plan.grid_x, plan.block, 0, s>>>(x, shift, scale, mod_ld, nullptr, mean, rstd, M, T, D, eps,
+                                                                                             (unsigned char*)q_out, q_state, q_format == VAW_BF8)));
     VAW_CHECK_LAUNCH("ln_modulate_fwd_fp8");
     return VAW_OK;
 }
@@ -504,27 +583,26 @@ extern "C" int vaw_ln_modulate_bwd(vaw_dtype dt, const void* dout, const float* 
                                    int64_t workspace_floats, vaw_stream stream) {
     VAW_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 2048 && mod_ld % 4 == 0,
                   "ln_modulate_bwd: need D%%4==0, D<=2048, mod_ld%%4==0 (D=%d)", D);
+    ROW_PLAN(VAW_ROW_LN_BWD, dt, B, T, D, 0, 0, workspace ? workspace_floats : 0);
     hipStream_t s = (hipStream_t)stream;
-    int nc = pick_chunks(B, T, workspace != nullptr);
-    if (nc > 1 && workspace_floats < (int64_t)nc * B * 2 * D) nc = 1;
-    const int rpc = (T + nc - 1) / nc;
+    const int nc = plan.nc, rpc = plan.rows_per_chunk, block = plan.block;
     float* part = nc > 1 ? workspace : nullptr;
-    const int block = pick_block(rpc, row_waves(pick_nv(D), 16));
-    const size_t lds = 2 * (size_t)D * sizeof(float);
+    const size_t lds = plan.lds_bytes;
     dim3 grid(B, nc);
     if (dt == VAW_F32) {
-        DISPATCH_NV(pick_nv(D), (row_bwd_kernel<float, NV, false><<<grid, block, lds, s>>>((const float*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rpc, part)));
+        DISPATCH_NV(plan.nv, (row_bwd_kernel<float, NV, false><<<grid, block, lds, s>>>((const float*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rpc, part)));
     } else {
-        DISPATCH_NV(pick_nv(D), (row_bwd_kernel<bf16_t, NV, false><<<grid, block, lds, s>>>((const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rpc, part)));
+        DISPATCH_NV(plan.nv, (row_bwd_kernel<bf16_t, NV, false><<<grid, block, lds, s>>>((const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rpc, part)));
     }
     if (nc > 1) row_bwd_finish_kernel<<<ceil_div((int64_t)B * D, 256), 256, 0, s>>>(part, nc, B, D, dshift, dmod_ld, dscale, dmod_ld);
     VAW_CHECK_LAUNCH("ln_modulate_bwd");
     return VAW_OK;
 }
 
-// vaw_ln_modulate_bwd followed by vaw_gate_bwd of the branch in front of this LayerNorm, as ONE pass (row_bwd_kernel<FUSE>):
-// dx = the residual-stream gradient as before; dy_next = dx * gate_next (act dtype), dgate_next[b] = sum_t dx * y_next,
-// dy_colsum_partial [B][D] = per-sample sum_t dy_next (as stored).  Bitwise equal to the two separate launches.
+// vaw_ln_modulate_bwd followed by vaw_gate_bwd of the branch in front of this LayerNorm, as ONE pass (row_bwd_fuse8_kernel for bf16
+// rows whose slabs fit in LDS, row_bwd_kernel<FUSE> otherwise): dx = the residual-stream gradient as before; dy_next = dx * gate_next
+// (act dtype), dgate_next[b] = sum_t dx * y_next, dy_colsum_partial [B][D] = per-sample sum_t dy_next (as stored).  Bitwise equal to
+// the two separate launches wherever those run 8 waves per workgroup too (D <= 1280).
 extern "C" int vaw_ln_modulate_bwd_gate(vaw_dtype dt, const void* dout, const float* x, const float* mean, const float* rstd,
                                         const float* scale, int64_t mod_ld, const float* dres_in, float* dx, float* dshift,
                                         float* dscale, int64_t dmod_ld, const void* y_next, const float* gate_next, void* dy_next,
@@ -533,27 +611,23 @@ extern "C" int vaw_ln_modulate_bwd_gate(vaw_dtype dt, const void* dout, const fl
     VAW_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 2048 && mod_ld % 4 == 0,
                   "ln_modulate_bwd_gate: need D%%4==0, D<=2048, mod_ld%%4==0 (D=%d)", D);
     VAW_CHECK_ARG(y_next && gate_next && dy_next && dgate_next, "ln_modulate_bwd_gate: the gate operands are required");
+    ROW_PLAN(VAW_ROW_LN_BWD_GATE, dt, B, T, D, 0, 0, workspace ? workspace_floats : 0);
     hipStream_t s = (hipStream_t)stream;
-    const int nv = pick_nv(D);
-    // wide rows (D > 768: four accumulator sets need 176-190 registers) run 512-thread workgroups, two per CU: cut the samples
-    // into enough chunks for 512 of them (DiT-XL/2 at 128 images: 200 us with 256 workgroups at 3.2 TB/s)
-    int nc = pick_chunks(B, T, workspace != nullptr, nv > 3 ? 512 : 256);
-    if (nc > 1 && workspace_floats < (int64_t)nc * B * 4 * D) nc = 1;
-    const int rpc = (T + nc - 1) / nc;
+    const int nc = plan.nc, rpc = plan.rows_per_chunk, block = plan.block;
     float* part = nc > 1 ? workspace : nullptr;
-    const int block = pick_block(rpc, 8);
-    const size_t lds = 6 * (size_t)D * sizeof(float);
+    const size_t lds = plan.lds_bytes;
     dim3 grid(B, nc);
-    if (dt == VAW_F32) {
-        DISPATCH_NV(nv, (row_bwd_kernel<float, NV, false, false, true><<<grid, block, lds, s>>>((const float*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, (const float*)y_next, gate_next, (float*)dy_next, dgate_next, dy_colsum_partial, rpc, part)));
-    } else if (nv <= 5) {
+    if (plan.variant == VAW_RV_ROW_FUSE8) {
 #define LAUNCH_FUSE8(NVv)                                                                                                              \
     row_bwd_fuse8_kernel<NVv, false><<<grid, block, row_fuse8_lds<NVv, false>(D, block), s>>>(                                          \
         (const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, (const bf16_t*)y_next, gate_next, \
         (bf16_t*)dy_next, dgate_next, dy_colsum_partial, rpc, part, nullptr, nullptr, 0)
+        const int nv = plan.nv;
         if (nv == 1) LAUNCH_FUSE8(1); else if (nv == 2) LAUNCH_FUSE8(2); else if (nv == 3) LAUNCH_FUSE8(3); else if (nv == 4) LAUNCH_FUSE8(4); else LAUNCH_FUSE8(5);
+    } else if (dt == VAW_F32) {
+        DISPATCH_NV(plan.nv, (row_bwd_kernel<float, NV, false, false, true><<<grid, block, lds, s>>>((const float*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, (const float*)y_next, gate_next, (float*)dy_next, dgate_next, dy_colsum_partial, rpc, part)));
     } else {
-        DISPATCH_NV(nv, (row_bwd_kernel<bf16_t, NV, false, false, true><<<grid, block, lds, s>>>((const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, (const bf16_t*)y_next, gate_next, (bf16_t*)dy_next, dgate_next, dy_colsum_partial, rpc, part)));
+        DISPATCH_NV(plan.nv, (row_bwd_kernel<bf16_t, NV, false, false, true><<<grid, block, lds, s>>>((const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, (const bf16_t*)y_next, gate_next, (bf16_t*)dy_next, dgate_next, dy_colsum_partial, rpc, part)));
     }
     if (nc > 1)
         row_bwd_finish_kernel<<<ceil_div((int64_t)B * D, 256), 256, 0, s>>>(part, nc, B, D, dshift, dmod_ld, dscale, dmod_ld, 4, dgate_next, dmod_ld,
@@ -572,25 +646,21 @@ extern "C" int vaw_ln_modulate_bwd_gate_fp8(const void* dout, const float* x, co
                   "ln_modulate_bwd_gate_fp8: need D%%4==0, D<=2048, mod_ld%%4==0 (D=%d)", D);
     VAW_CHECK_ARG(y_next && gate_next && dy_q && q_state && dgate_next, "ln_modulate_bwd_gate_fp8: the gate operands are required");
     VAW_CHECK_ARG(q_format == VAW_FP8 || q_format == VAW_BF8, "ln_modulate_bwd_gate_fp8: q_format");
+    ROW_PLAN(VAW_ROW_LN_BWD_GATE_FP8, VAW_BF16, B, T, D, 0, 0, workspace ? workspace_floats : 0);
     hipStream_t s = (hipStream_t)stream;
-    const int nv = pick_nv(D);
-    // wide rows (D > 768: four accumulator sets need 176-190 registers) run 512-thread workgroups, two per CU: cut the samples
-    // into enough chunks for 512 of them (DiT-XL/2 at 128 images: 200 us with 256 workgroups at 3.2 TB/s)
-    int nc = pick_chunks(B, T, workspace != nullptr, nv > 3 ? 512 : 256);
-    if (nc > 1 && workspace_floats < (int64_t)nc * B * 4 * D) nc = 1;
-    const int rpc = (T + nc - 1) / nc;
+    const int nc = plan.nc, rpc = plan.rows_per_chunk, block = plan.block;
     float* part = nc > 1 ? workspace : nullptr;
-    const int block = pick_block(rpc, 8);
-    const size_t lds = 6 * (size_t)D * sizeof(float);
+    const size_t lds = plan.lds_bytes;
     dim3 grid(B, nc);
-    if (nv <= 5) {
+    if (plan.variant == VAW_RV_ROW_FUSE8) {
 #define LAUNCH_FUSE8Q(NVv)                                                                                                             \
     row_bwd_fuse8_kernel<NVv, true><<<grid, block, row_fuse8_lds<NVv, true>(D, block), s>>>(                                            \
         (const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, (const bf16_t*)y_next, gate_next, \
         nullptr, dgate_next, dy_colsum_partial, rpc, part, (unsigned char*)dy_q, q_state, q_format == VAW_BF8)
+        const int nv = plan.nv;
         if (nv == 1) LAUNCH_FUSE8Q(1); else if (nv == 2) LAUNCH_FUSE8Q(2); else if (nv == 3) LAUNCH_FUSE8Q(3); else if (nv == 4) LAUNCH_FUSE8Q(4); else LAUNCH_FUSE8Q(5);
     } else {
-        DISPATCH_NV(nv, (row_bwd_kernel<bf16_t, NV, false, true, true><<<grid, block, lds, s>>>((const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, (const bf16_t*)y_next, gate_next, nullptr, dgate_next, dy_colsum_partial, rpc, part, (unsigned char*)dy_q, q_state, q_format == VAW_BF8)));
+        DISPATCH_NV(plan.nv, (row_bwd_kernel<bf16_t, NV, false, true, true><<<grid, block, lds, s>>>((const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, (const bf16_t*)y_next, gate_next, nullptr, dgate_next, dy_colsum_partial, rpc, part, (unsigned char*)dy_q, q_state, q_format == VAW_BF8)));
     }
     if (nc > 1)
         row_bwd_finish_kernel<<<ceil_div((int64_t)B * D, 256), 256, 0, s>>>(part, nc, B, D, dshift, dmod_ld, dscale, dmod_ld, 4, dgate_next, dmod_ld,
@@ -604,18 +674,16 @@ extern "C" int vaw_gate_bwd(vaw_dtype dt, const float* dres, const void* y, cons
                             int64_t workspace_floats, vaw_stream stream) {
     VAW_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 2048 && mod_ld % 4 == 0,
                   "gate_bwd: need D%%4==0, D<=2048, mod_ld%%4==0 (D=%d)", D);
+    ROW_PLAN(VAW_ROW_GATE_BWD, dt, B, T, D, 0, 0, workspace ? workspace_floats : 0);
     hipStream_t s = (hipStream_t)stream;
-    int nc = pick_chunks(B, T, workspace != nullptr);
-    if (nc > 1 && workspace_floats < (int64_t)nc * B * 2 * D) nc = 1;
-    const int rpc = (T + nc - 1) / nc;
+    const int nc = plan.nc, rpc = plan.rows_per_chunk, block = plan.block;
     float* part = nc > 1 ? workspace : nullptr;
-    const int block = pick_block(rpc, row_waves(pick_nv(D), 16));
-    const size_t lds = 2 * (size_t)D * sizeof(float);
+    const size_t lds = plan.lds_bytes;
     dim3 grid(B, nc);
     if (dt == VAW_F32) {
-        DISPATCH_NV(pick_nv(D), (row_bwd_kernel<float, NV, true><<<grid, block, lds, s>>>(nullptr, nullptr, nullptr, nullptr, nullptr, mod_ld, nullptr, nullptr, nullptr, nullptr, dmod_ld, T, D, dres, (const float*)y, gate, (float*)dy, dgate, dy_colsum_partial, rpc, part)));
+        DISPATCH_NV(plan.nv, (row_bwd_kernel<float, NV, true><<<grid, block, lds, s>>>(nullptr, nullptr, nullptr, nullptr, nullptr, mod_ld, nullptr, nullptr, nullptr, nullptr, dmod_ld, T, D, dres, (const float*)y, gate, (float*)dy, dgate, dy_colsum_partial, rpc, part)));
     } else {
-        DISPATCH_NV(pick_nv(D), (row_bwd_kernel<bf16_t, NV, true><<<grid, block, lds, s>>>(nullptr, nullptr, nullptr, nullptr, nullptr, mod_ld, nullptr, nullptr, nullptr, nullptr, dmod_ld, T, D, dres, (const bf16_t*)y, gate, (bf16_t*)dy, dgate, dy_colsum_partial, rpc, part)));
+        DISPATCH_NV(plan.nv, (row_bwd_kernel<bf16_t, NV, true><<<grid, block, lds, s>>>(nullptr, nullptr, nullptr, nullptr, nullptr, mod_ld, nullptr, nullptr, nullptr, nullptr, dmod_ld, T, D, dres, (const bf16_t*)y, gate, (bf16_t*)dy, dgate, dy_colsum_partial, rpc, part)));
     }
     if (nc > 1) row_bwd_finish_kernel<<<ceil_div((int64_t)B * D, 256), 256, 0, s>>>(part, nc, B, D, dgate, dmod_ld, dy_colsum_partial, D);
     VAW_CHECK_LAUNCH("gate_bwd");
@@ -629,15 +697,13 @@ extern "C" int vaw_gate_bwd_fp8(const float* dres, const void* y, const float* g
     VAW_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 2048 && mod_ld % 4 == 0 && dy_q && q_state,
                   "gate_bwd_fp8: need D%%4==0, D<=2048, mod_ld%%4==0 (D=%d)", D);
     VAW_CHECK_ARG(q_format == VAW_FP8 || q_format == VAW_BF8, "gate_bwd_fp8: q_format");
+    ROW_PLAN(VAW_ROW_GATE_BWD_FP8, VAW_BF16, B, T, D, 0, 0, workspace ? workspace_floats : 0);
     hipStream_t s = (hipStream_t)stream;
-    int nc = pick_chunks(B, T, workspace != nullptr);
-    if (nc > 1 && workspace_floats < (int64_t)nc * B * 2 * D) nc = 1;
-    const int rpc = (T + nc - 1) / nc;
+    const int nc = plan.nc, rpc = plan.rows_per_chunk, block = plan.block;
     float* part = nc > 1 ? workspace : nullptr;
-    const int block = pick_block(rpc, row_waves(pick_nv(D), 16));
-    const size_t lds = 2 * (size_t)D * sizeof(float);
+    const size_t lds = plan.lds_bytes;
     dim3 grid(B, nc);
-    DISPATCH_NV(pick_nv(D), (row_bwd_kernel<bf16_t, NV, true, true><<<grid, block, lds, s>>>(nullptr, nullptr, nullptr, nullptr, nullptr, mod_ld, nullptr, nullptr, nullptr, nullptr, dmod_ld, T, D, dres, (const bf16_t*)y, gate, nullptr, dgate, dy_colsum_partial, rpc, part, (unsigned char*)dy_q, q_state, q_format == VAW_BF8)));
+    DISPATCH_NV(plan.nv, (row_bwd_kernel<bf16_t, NV, true, true><<<grid, block, lds, s>>>(nullptr, nullptr, nullptr, nullptr, nullptr, mod_ld, nullptr, nullptr, nullptr, nullptr, dmod_ld, T, D, dres, (const bf16_t*)y, gate, nullptr, dgate, dy_colsum_partial, rpc, part, (unsigned char*)dy_q, q_state, q_format == VAW_BF8)));
     if (nc > 1) row_bwd_finish_kernel<<<ceil_div((int64_t)B * D, 256), 256, 0, s>>>(part, nc, B, D, dgate, dmod_ld, dy_colsum_partial, D);
     VAW_CHECK_LAUNCH("gate_bwd_fp8");
     return VAW_OK;
@@ -805,22 +871,20 @@ extern "C" int vaw_reduce_rows(const float* partial, int64_t R, int64_t N, float
 extern "C" int vaw_colsum(vaw_dtype dt, const void* X, int64_t M, int64_t N, int64_t ldx, float* out, float beta,
                           float* workspace, int64_t workspace_floats, vaw_stream stream) {
     VAW_CHECK_ARG(M > 0 && N > 0 && ldx >= N, "colsum: bad sizes");
-    const bool vec = (ldx % 4 == 0) && (((uintptr_t)X & 15) == 0);
-    const bool wide = dt == VAW_BF16 && N % 8 == 0 && ldx % 8 == 0 && (((uintptr_t)X & 15) == 0) && M >= 1024;
-    const int64_t RB = wide ? (M + 127) / 128 : (M + 511) / 512;
-    VAW_CHECK_ARG(workspace && workspace_floats >= RB * N, "colsum: workspace too small (%ld < %ld floats)",
-                  (long)workspace_floats, (long)(RB * N));
-    VAW_CHECK_ARG(RB < 65536, "colsum: M too large");
+    ROW_PLAN(VAW_ROW_COLSUM, dt, M, 1, N, ldx, (int64_t)(uintptr_t)X, workspace_floats);
+    const int64_t RB = plan.nc;
+    VAW_CHECK_ARG(workspace && workspace_floats >= plan.workspace_floats, "colsum: workspace too small (%ld < %ld floats)",
+                  (long)workspace_floats, (long)plan.workspace_floats);
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid(ceil_div(N, 256), (int)RB);
-    if (wide) {
-        colsum_partial_bf16x8_kernel<<<grid, 256, 0, s>>>((const bf16_t*)X, M, N, ldx, workspace);
-    } else if (vec) {
-        if (dt == VAW_F32) colsum_partial_kernel<float><<<grid, 256, 0, s>>>((const float*)X, M, N, ldx, workspace);
-        else colsum_partial_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)X, M, N, ldx, workspace);
+    dim3 grid(plan.grid_x, (int)RB);
+    if (plan.variant == VAW_RV_COLSUM_BF16X8) {
+        colsum_partial_bf16x8_kernel<<<grid, plan.block, 0, s>>>((const bf16_t*)X, M, N, ldx, workspace);
+    } else if (plan.variant == VAW_RV_COLSUM_VEC4) {
+        if (dt == VAW_F32) colsum_partial_kernel<float><<<grid, plan.block, 0, s>>>((const float*)X, M, N, ldx, workspace);
+        else colsum_partial_kernel<bf16_t><<<grid, plan.block, 0, s>>>((const bf16_t*)X, M, N, ldx, workspace);
     } else {
-        if (dt == VAW_F32) colsum_partial_scalar_kernel<float><<<grid, 256, 0, s>>>((const float*)X, M, N, ldx, workspace);
-        else colsum_partial_scalar_kernel<bf16_t><<<grid, 256, 0, s>>>((const bf16_t*)X, M, N, ldx, workspace);
+        if (dt == VAW_F32) colsum_partial_scalar_kernel<float><<<grid, plan.block, 0, s>>>((const float*)X, M, N, ldx, workspace);
+        else colsum_partial_scalar_kernel<bf16_t><<<grid, plan.block, 0, s>>>((const bf16_t*)X, M, N, ldx, workspace);
     }
     colsum_final_kernel<<<ceil_div(N, 32), 1024, 0, s>>>(workspace, RB, N, out, beta);
     VAW_CHECK_LAUNCH("colsum");

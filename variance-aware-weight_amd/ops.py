@@ -486,6 +486,14 @@ def gate_bwd_fp8(dres, y, gate, mod_ld, f8, dgate, dmod_ld, B, T, D, dy_colpart=
                                    ws.data_ptr(), ws.numel(), stream_ptr()), "vaw_gate_bwd_fp8")
 
 
+def row_plan(kind, dt, B, T, D, workspace_floats=0, ldx=0, base_addr=0):
+    """The launch the row-kernel entry point `kind` (_lib.ROW_*) makes for these sizes (vaw_row_plan: host arithmetic, no GPU).
+    Colsum: B = M rows, T = 1, D = N columns, ldx and the address of X."""
+    p = L.RowLaunch()
+    check(L.lib().vaw_row_plan(kind, dt, B, T, D, ldx, base_addr, workspace_floats, C.byref(p)), "vaw_row_plan")
+    return p
+
+
 def _row_ws(B, T, D):
     return scratch_f32(torch.device("cuda", torch.cuda.current_device()), L.lib().vaw_row_bwd_workspace_floats(B, T, D))
 

@@ -359,6 +359,38 @@ int vaw_attn_bwd_colsum(vaw_dtype dt, const vaw_attn_desc* d, const void* q, con
                         const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv, float* colsum_partial,
                         int64_t* rows_out, vaw_stream stream);
 
+/* Launch plan of the attention entry points: the one host function vaw_attn_fwd / vaw_attn_bwd / vaw_attn_bwd_colsum take every
+ * launch choice from (pure arithmetic: no device call, so it can be asked without a GPU).  q / k / v / o_or_do / dq / dk / dv are the
+ * addresses the entry point would be given (only their alignment matters; o_or_do: o for the forward, d_o for the backward; dq / dk
+ * / dv are ignored by the forward).  Reads VAW_ATTN_FWD_BIG, VAW_ATTN_BWD_BIG, VAW_ATTN_QG2 and VAW_ATTN_BWD_G2 on every call.
+ * VAW_ERR_INVALID where the descriptor is refused (T > 1024, B*H >= 65536, a size <= 0, a rowwise LDS request over 64 KiB). */
+typedef enum { VAW_ATTN_DIR_FWD = 0, VAW_ATTN_DIR_BWD = 1, VAW_ATTN_DIR_BWD_COLSUM = 2 } vaw_attn_dir;
+typedef enum {
+    VAW_AV_ROWWISE = 0,         /* attention.hip: attn_fwd_rowwise / attn_bwd_q_rowwise + attn_bwd_kv_rowwise <T> */
+    VAW_AV_FWD_T64 = 1,         /* attn_fwd_mfma<HD, 1, false>: T == 64 */
+    VAW_AV_FWD_G1 = 2,          /* attn_fwd_mfma<HD, 1> */
+    VAW_AV_FWD_G2 = 3,          /* attn_fwd_mfma<HD, 2>: T % 128 == 0 */
+    VAW_AV_FWD_BIG = 4,         /* attn_fwd_big<HD, 2>: T % 128 == 0 */
+    VAW_AV_BWD_T64 = 5,         /* attn_bwd_t64_mfma<HD>: T == 64, one launch */
+    VAW_AV_BWD_G1 = 6,          /* attn_bwd_dq_mfma + attn_bwd_dkv_mfma <HD, 1> */
+    VAW_AV_BWD_G2 = 7,          /* attn_bwd_dq_mfma + attn_bwd_dkv_mfma <96, 2>: T % 128 == 0 */
+    VAW_AV_BWD_BIG_NT2 = 8,     /* attn_bwd_big<HD, 1 | 0, 2>: T % 128 == 0 */
+    VAW_AV_BWD_BIG_NT4 = 9      /* attn_bwd_big<HD, 1 | 0, 4>: T % 256 == 0 */
+} vaw_attn_variant;
+typedef struct {
+    int variant;                /* vaw_attn_variant */
+    int hd_image;               /* head width of the kernel's LDS image: 32 / 64 / 96 / 128; 0 = rowwise */
+    int launches;               /* kernels enqueued */
+    int grid_x, grid_y, block;  /* workgroups per (sample, head) along the tokens, B * H, threads per workgroup (VAW_AV_BWD_T64
+                                 * enqueues its grid_x * grid_y workgroups as a 1-D grid) */
+    int64_t lds_bytes;          /* largest dynamic LDS of its launches */
+    int lds_cap_raised;         /* 1: that launch raises its LDS cap with hipFuncSetAttribute (else it must fit the 64 KiB default) */
+    int64_t colsum_rows;        /* VAW_ATTN_DIR_BWD_COLSUM: partial rows written; 0 = column sums not offered (and other directions) */
+    int status;                 /* vaw_status: VAW_OK, or what the entry point returns before launching anything */
+} vaw_attn_launch;
+int vaw_attn_plan(int dir, vaw_dtype dt, const vaw_attn_desc* d, int64_t q, int64_t k, int64_t v, int64_t o_or_do, int64_t dq,
+                  int64_t dk, int64_t dv, vaw_attn_launch* out);
+
 /* ---------------------------------------------------------------------------
  * UNet pieces  (models/unet.py, tools/nn.py) -- activations are NHWC: [B*H*W pixels, C channels], act dtype
  * ------------------------------------------------------------------------- */

@@ -543,3 +543,247 @@ def test_row_plan_colsum_paths():
         row_plan(L.ROW_COLSUM, L.F32, 10, 1, 8, ldx=4)
     with pytest.raises(vaw_amd.VawError):
         row_plan(L.ROW_LN_BWD, L.F32, 2, 8, 2052)
+
+
+# ------------------------------------------------------------------------------------------------
+# Launch plan of the attention kernels (vaw_attn_plan: host arithmetic only, vaw_attn_fwd / _bwd / _bwd_colsum take every choice
+# from it)
+# ------------------------------------------------------------------------------------------------
+ATTN_LDS_DEFAULT = 64 * 1024      # what a launch may ask for without raising its cap
+_ATTN_SWITCHES = ("VAW_ATTN_FWD_BIG", "VAW_ATTN_BWD_BIG", "VAW_ATTN_QG2", "VAW_ATTN_BWD_G2")
+
+
+class _attn_env:
+    """set the attention switches of vaw_attn_plan (read on every call) for a block; None = unset (the default)"""
+
+    def __init__(self, **kw):
+        self.kw = kw
+
+    def __enter__(self):
+        self.saved = {k: os.environ.get(k) for k in _ATTN_SWITCHES}
+        for k in _ATTN_SWITCHES:
+            v = self.kw.get(k)
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+
+    def __exit__(self, *a):
+        for k, v in self.saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def _attn_layouts(B, H, T, hd):
+    """(name, desc, k offset, v offset) in elements for the four layouts the library serves"""
+    from vaw_amd import ops
+    D = H * hd
+    out = [("token", ops.attn_desc_token_major(B, H, T, hd), D, 2 * D)]
+    for new in (True, False):
+        desc, ko, vo = ops.attn_desc_nhwc(B, H, T, hd, new)
+        out.append(("nhwc_new" if new else "nhwc_legacy", desc, ko, vo))
+    out.append(("channel", ops.attn_desc_channel_major(B, H, T, hd), D * T, 2 * D * T))
+    return out
+
+
+def _check_attn_plan(p, direction, dt, desc, addrs, sw):
+    """the preconditions of the variant the plan picked, its grid, LDS and column-sum rows; returns a failure string or None"""
+    from vaw_amd import _lib as L
+    B, H, T, hd = desc.B, desc.H, desc.T, desc.hd
+    q, k, v, o, dq, dk, dv = addrs
+    fwd = direction == L.ATTN_FWD
+    strides_ok = desc.q_sd == 1 and desc.o_sd == 1 and all(s % 8 == 0 for s in (desc.q_sb, desc.q_sh, desc.q_st, desc.o_sb,
+                                                                                      desc.o_sh, desc.o_st))
+    mfma_ok = (dt == L.BF16 and 8 <= hd <= 128 and hd % 8 == 0 and T % 64 == 0 and strides_ok and all(a % 16 == 0 for a in (q, k, v, o))
+               and (fwd or all(a % 8 == 0 for a in (dq, dk, dv))))
+    name = L.AV_NAMES[p.variant]
+    where = f"dir={direction} dt={dt} B={B} H={H} T={T} hd={hd} sw={sw} -> {name}/{p.hd_image} grid {p.grid_x}x{p.grid_y} lds {p.lds_bytes}"
+    if p.status != 0 or p.block != 256 or p.grid_y != B * H:
+        return "grid " + where
+    if p.lds_bytes > ROW_LDS_MAX or (not p.lds_cap_raised and p.lds_bytes > ATTN_LDS_DEFAULT) or p.lds_bytes <= 0:
+        return "LDS " + where
+    if mfma_ok != (p.variant != L.AV_ROWWISE):
+        return "mfma eligibility " + where
+    cap = B * max(T // 64, 1)
+    if p.variant == L.AV_ROWWISE:
+        want_lds = 16 * (hd + T) if fwd else 16 * (2 * hd + 2 * T)
+        ok = (p.hd_image == 0 and p.launches == (1 if fwd else 2) and p.grid_x == -(-T // 4) and p.lds_bytes == want_lds
+              and not p.lds_cap_raised and p.colsum_rows == 0)
+        return None if ok else "rowwise " + where
+    fwd_variants = (L.AV_FWD_T64, L.AV_FWD_G1, L.AV_FWD_G2, L.AV_FWD_BIG)
+    if (p.variant in fwd_variants) != fwd or not p.lds_cap_raised:
+        return "direction " + where
+    wgr = {L.AV_FWD_T64: 64, L.AV_FWD_G1: 64, L.AV_FWD_G2: 128, L.AV_FWD_BIG: 128, L.AV_BWD_T64: 64, L.AV_BWD_G1: 64, L.AV_BWD_G2: 128,
+           L.AV_BWD_BIG_NT2: 128, L.AV_BWD_BIG_NT4: 256}[p.variant]
+    big = p.variant in (L.AV_FWD_BIG, L.AV_BWD_BIG_NT2, L.AV_BWD_BIG_NT4)
+    pre = {L.AV_FWD_T64: T == 64, L.AV_BWD_T64: T == 64,
+           L.AV_FWD_G1: True, L.AV_BWD_G1: True,
+           L.AV_FWD_G2: hd <= 96 and sw["VAW_ATTN_QG2"] != "0",
+           L.AV_BWD_G2: 64 < hd <= 96 and p.hd_image == 96 and sw["VAW_ATTN_BWD_G2"] != "0",
+           L.AV_FWD_BIG: 32 < hd <= 96 and (hd > 64 or sw["VAW_ATTN_FWD_BIG"] == "1") and sw["VAW_ATTN_FWD_BIG"] != "0",
+           L.AV_BWD_BIG_NT2: 32 < hd <= 96 and sw["VAW_ATTN_BWD_BIG"] in (None, "2"),
+           L.AV_BWD_BIG_NT4: 32 < hd <= 96 and sw["VAW_ATTN_BWD_BIG"] == "1"}[p.variant]
+    if not pre or T % wgr != 0 or T > 1024 or p.grid_x * wgr != T and p.variant not in (L.AV_FWD_T64, L.AV_BWD_T64):
+        return "preconditions " + where
+    if p.variant in (L.AV_FWD_T64, L.AV_BWD_T64) and p.grid_x != 1:
+        return "t64 grid " + where
+    img_ok = p.hd_image in ((64, 96) if big else (32, 64, 96, 128)) and hd <= p.hd_image and (big or p.hd_image - hd < 32)
+    if not img_ok:
+        return "image " + where
+    want_launches = 1 if fwd or p.variant == L.AV_BWD_T64 else 2
+    if p.launches != want_launches:
+        return "launches " + where
+    if direction == L.ATTN_BWD_COLSUM:
+        want = B if p.variant == L.AV_BWD_T64 else B * T // wgr
+        if p.colsum_rows != want or p.colsum_rows > cap:
+            return "colsum rows " + where
+    elif p.colsum_rows != 0:
+        return "colsum rows " + where
+    return None
+
+
+def test_attn_plan_sweep_preconditions_lds_grid_and_colsum_rows():
+    """Every (T, hd, B*H, dtype, layout, alignment, switch) case: each variant is picked only where its kernel's preconditions hold
+    (sequence multiple, head width, strides, 16-byte operands, 8-byte gradients), the MFMA kernels wherever those hold, the LDS a
+    launch asks for fits a CU (and 64 KiB where the cap is not raised), grid.y = B*H, and the column-sum rows are the variant's
+    and within the capacity vaw_attn_bwd_colsum checks."""
+    from vaw_amd import _lib as L
+    from vaw_amd.ops import attn_plan
+    Ts = (1, 2, 17, 63, 64, 65, 100, 128, 192, 256, 320, 512, 768, 1024, 1025)
+    hds = (1, 8, 16, 24, 32, 33, 40, 64, 72, 96, 100, 104, 120, 128, 136, 256)
+    aligns = {"aligned": (0, 0), "base+2": (2, 2), "base+8": (8, 8), "grad+2": (0, 2), "grad+8": (0, 8)}
+    fwd_sw = [dict(VAW_ATTN_FWD_BIG=f, VAW_ATTN_QG2=g) for f in (None, "0", "1", "2") for g in (None, "0", "1")]
+    bwd_sw = [dict(VAW_ATTN_BWD_BIG=b, VAW_ATTN_BWD_G2=g) for b in (None, "0", "1", "2") for g in (None, "0", "1")]
+    bad, seen = [], set()
+    for direction, switches in ((L.ATTN_FWD, fwd_sw), (L.ATTN_BWD, bwd_sw), (L.ATTN_BWD_COLSUM, bwd_sw)):
+        for sw in switches:
+            full = {k: sw.get(k) for k in _ATTN_SWITCHES}
+            with _attn_env(**sw):
+                for T in Ts:
+                    for hd in hds:
+                        for B, H in ((1, 1), (3, 2)) + (((65535, 1), (1, 65536), (256, 256)) if T in (64, 256) and hd in (64, 72) else ()):
+                            for lay, desc, ko, vo in _attn_layouts(B, H, T, hd):
+                                for dt in (L.F32, L.BF16):
+                                    es = 4 if dt == L.F32 else 2
+                                    for al, (off, goff) in aligns.items():
+                                        base, obase, gbase = 1 << 20, 1 << 32, 1 << 36
+                                        addrs = (base + off, base + off + es * ko, base + off + es * vo, obase + off, gbase + goff,
+                                                 gbase + goff + es * ko, gbase + goff + es * vo)
+                                        if B * H >= 65536 or T > 1024:
+                                            with pytest.raises(vaw_amd.VawError):
+                                                attn_plan(direction, dt, desc, *addrs)
+                                            continue
+                                        p = attn_plan(direction, dt, desc, *addrs)
+                                        seen.add((direction, p.variant, p.hd_image))
+                                        err = _check_attn_plan(p, direction, dt, desc, addrs, full)
+                                        if err:
+                                            bad.append(f"{err} layout={lay} align={al}")
+    assert not bad, f"{len(bad)} bad plans, e.g.\n" + "\n".join(bad[:10])
+    # every kernel instantiation is reachable by some case of the sweep
+    want = ({(L.ATTN_FWD, L.AV_ROWWISE, 0), (L.ATTN_BWD, L.AV_ROWWISE, 0), (L.ATTN_FWD, L.AV_FWD_BIG, 64), (L.ATTN_FWD, L.AV_FWD_BIG, 96)}
+            | {(L.ATTN_FWD, v, i) for v in (L.AV_FWD_T64, L.AV_FWD_G1) for i in (32, 64, 96, 128)}
+            | {(L.ATTN_FWD, L.AV_FWD_G2, i) for i in (32, 64, 96)}
+            | {(L.ATTN_BWD, v, i) for v in (L.AV_BWD_T64, L.AV_BWD_G1) for i in (32, 64, 96, 128)}
+            | {(L.ATTN_BWD, L.AV_BWD_G2, 96)} | {(L.ATTN_BWD, v, i) for v in (L.AV_BWD_BIG_NT2, L.AV_BWD_BIG_NT4) for i in (64, 96)})
+    assert {s for s in seen if s[0] != L.ATTN_BWD_COLSUM} == want
+
+
+def test_attn_plan_refusals():
+    """check_desc's refusals and a rowwise LDS request that could not launch come back as errors (before any launch)"""
+    from vaw_amd import _lib as L
+    from vaw_amd.ops import AttnDesc, attn_desc_token_major, attn_plan
+    for direction in (L.ATTN_FWD, L.ATTN_BWD, L.ATTN_BWD_COLSUM):
+        for desc in (attn_desc_token_major(1, 2, 1025, 64), attn_desc_token_major(1, 65536, 64, 64), attn_desc_token_major(256, 256, 64, 64),
+                     AttnDesc(1, 2, 64, 0, 64, 0, 64, 1, 64, 0, 64, 1, 1.0), AttnDesc(1, 2, 64, -8, 64, 8, 64, 1, 64, 8, 64, 1, 1.0),
+                     attn_desc_token_major(0, 2, 64, 64),
+                     AttnDesc(1, 1, 0, 64, 64, 64, 64, 1, 64, 64, 64, 1, 0.125)):
+            for dt in (L.F32, L.BF16):
+                with pytest.raises(vaw_amd.VawError):
+                    attn_plan(direction, dt, desc, 0, 0, 0, 0)
+        with pytest.raises(vaw_amd.VawError, match="dt"):
+            attn_plan(direction, L.FP8, attn_desc_token_major(1, 2, 64, 64), 0, 0, 0, 0)
+    # rowwise: 16 (hd + T) bytes forward, 16 (2 hd + 2 T) backward, with the default cap of 64 KiB
+    for T, hd, fwd_ok, bwd_ok in ((1024, 3072, True, False), (1024, 3073, False, False), (1024, 1024, True, True),
+                                  (1024, 1025, True, False), (1, 2047, True, True), (1, 2048, True, False)):
+        desc = attn_desc_token_major(1, 1, T, hd)
+        for direction, ok in ((L.ATTN_FWD, fwd_ok), (L.ATTN_BWD, bwd_ok)):
+            if ok:
+                assert attn_plan(direction, L.F32, desc, 0, 0, 0, 0).variant == L.AV_ROWWISE
+            else:
+                with pytest.raises(vaw_amd.VawError, match="LDS"):
+                    attn_plan(direction, L.F32, desc, 0, 0, 0, 0)
+
+
+def _production_attention_shapes():
+    """(model, H, T, hd, new_order) of every attention block of the DiT and UNet presets, walked on the meta device"""
+    from vaw_amd import dit, unet
+    shapes = set()
+    with torch.device("meta"):
+        for name, patch in (("DiT-B", 4), ("DiT-XL", 2)):
+            m = dit.DiT_models[name](image_size=32, patch_size=patch, in_channels=4, class_dropout_prob=0.1, num_classes=1000,
+                                     learn_sigma=True)
+            T = m.x_embedder.num_patches
+            for blk in m.blocks:
+                H = blk.attn.num_heads
+                shapes.add((f"{name}/{patch}", H, T, blk.attn.qkv.weight.shape[1] // H, True))
+        for name, build in unet.UNet_models.items():
+            m = build(compute_dtype="fp32")
+            res = m.image_size
+            for seq in list(m.input_blocks) + [m.middle_block] + list(m.output_blocks):
+                for layer in seq:
+                    if isinstance(layer, unet.AttentionBlock):
+                        shapes.add((name, layer.num_heads, res * res, layer.channels // layer.num_heads, layer.attention.new_order))
+                    elif isinstance(layer, unet.Downsample) or (isinstance(layer, unet.ResBlock) and layer.down):
+                        res //= 2
+                    elif isinstance(layer, unet.Upsample) or (isinstance(layer, unet.ResBlock) and layer.up):
+                        res *= 2
+    return sorted(shapes)
+
+
+# today's launch for every production attention shape, default switches, bf16, aligned: (variant, hd_image, grid_x, lds_bytes)
+# forward and backward, keyed by (T, hd)
+_PINNED_ATTN = {
+    (64, 64): (("fwd_t64", 64, 1, 24576), ("bwd_t64", 64, 1, 32768)),
+    (256, 72): (("fwd_big", 96, 2, 53248), ("bwd_big_nt2", 96, 2, 56832)),
+    (256, 96): (("fwd_big", 96, 2, 53248), ("bwd_big_nt2", 96, 2, 56832)),
+    (64, 96): (("fwd_t64", 96, 1, 39936), ("bwd_t64", 96, 1, 53248)),
+    (1024, 64): (("fwd_g2", 64, 8, 49152), ("bwd_big_nt2", 64, 8, 41984)),
+    (256, 64): (("fwd_g2", 64, 2, 49152), ("bwd_big_nt2", 64, 2, 35840)),
+    (1024, 32): (("fwd_g2", 32, 8, 24576), ("bwd_g1", 32, 16, 16896)),
+    (256, 32): (("fwd_g2", 32, 2, 24576), ("bwd_g1", 32, 4, 16896)),
+    (64, 32): (("fwd_t64", 32, 1, 12288), ("bwd_t64", 32, 1, 16384)),
+    (16, 64): (("rowwise", 0, 4, 1280), ("rowwise", 0, 4, 2560)),         # the 4 x 4 middle blocks of UNet-32 / ADM-32
+    (16, 32): (("rowwise", 0, 4, 768), ("rowwise", 0, 4, 1536)),
+}
+
+
+def test_attn_plan_pins_production_shapes():
+    """The launch each model's attention takes today (the refactor onto vaw_attn_plan changed none): every (H, T, hd) of the
+    DiT-B/4, DiT-XL/2 and UNet presets, in the layout the model uses, with the default switches."""
+    from vaw_amd import _lib as L
+    from vaw_amd import ops
+    shapes = _production_attention_shapes()
+    got = {(m, H, T, hd) for m, H, T, hd, _ in shapes}
+    # the table of the model zoo, as the presets build it
+    assert {(m, T, hd) for m, _, T, hd in got} == ({
+        ("DiT-B/4", 64, 64), ("DiT-XL/2", 256, 72), ("UNet-64", 256, 96), ("UNet-64", 64, 96), ("UNet-32", 256, 64), ("UNet-32", 64, 64),
+        ("UNet-32", 16, 64), ("ADM-32", 256, 32), ("ADM-32", 64, 32), ("ADM-32", 16, 32), ("LDM", 1024, 32), ("LDM", 256, 32), ("LDM", 64, 32)}
+        | {(m, T, 64) for m in ("ADM-64", "ADM-128", "ADM-256", "ADM-512") for T in (1024, 256, 64)})
+    with _attn_env():
+        for m, H, T, hd, new_order in shapes:
+            for B in (1, 32):
+                if m.startswith("DiT"):
+                    desc, ko, vo = ops.attn_desc_token_major(B, H, T, hd), H * hd, 2 * H * hd
+                else:
+                    desc, ko, vo = ops.attn_desc_nhwc(B, H, T, hd, new_order)
+                q = 1 << 20
+                addrs = (q, q + 2 * ko, q + 2 * vo, 1 << 30)
+                fwd = ops.attn_plan(L.ATTN_FWD, L.BF16, desc, *addrs)
+                bwd = ops.attn_plan(L.ATTN_BWD_COLSUM, L.BF16, desc, *addrs, q + (1 << 28), q + (1 << 28) + 2 * ko, q + (1 << 28) + 2 * vo)
+                got_f = (L.AV_NAMES[fwd.variant], fwd.hd_image, fwd.grid_x, fwd.lds_bytes)
+                got_b = (L.AV_NAMES[bwd.variant], bwd.hd_image, bwd.grid_x, bwd.lds_bytes)
+                assert (got_f, got_b) == _PINNED_ATTN[T, hd], (m, H, T, hd)
+                assert fwd.grid_y == bwd.grid_y == B * H
+                assert bwd.colsum_rows == (0 if T % 64 else B if T == 64 else B * T // (64 * (1 if got_b[0] == "bwd_g1" else 2)))

@@ -32,6 +32,18 @@ class RowLaunch(C.Structure):
                 ("workspace_floats", _l)]
 
 
+class AttnLaunch(C.Structure):
+    """vaw_attn_launch of include/vaw_hip.h: the launch vaw_attn_plan picks for an attention entry point."""
+    _fields_ = [("variant", _i), ("hd_image", _i), ("launches", _i), ("grid_x", _i), ("grid_y", _i), ("block", _i), ("lds_bytes", _l),
+                ("lds_cap_raised", _i), ("colsum_rows", _l), ("status", _i)]
+
+
+# vaw_attn_dir / vaw_attn_variant
+ATTN_FWD, ATTN_BWD, ATTN_BWD_COLSUM = range(3)
+(AV_ROWWISE, AV_FWD_T64, AV_FWD_G1, AV_FWD_G2, AV_FWD_BIG, AV_BWD_T64, AV_BWD_G1, AV_BWD_G2, AV_BWD_BIG_NT2,
+ AV_BWD_BIG_NT4) = range(10)
+AV_NAMES = ("rowwise", "fwd_t64", "fwd_g1", "fwd_g2", "fwd_big", "bwd_t64", "bwd_g1", "bwd_g2", "bwd_big_nt2", "bwd_big_nt4")
+
 # vaw_row_kind / vaw_row_variant
 ROW_LN_FWD, ROW_LN_FWD_FP8, ROW_LN_BWD, ROW_GATE_BWD, ROW_GATE_BWD_FP8, ROW_LN_BWD_GATE, ROW_LN_BWD_GATE_FP8, ROW_COLSUM = range(8)
 RV_LN_FWD, RV_ROW_BWD, RV_ROW_GATE, RV_ROW_FUSE, RV_ROW_FUSE8, RV_COLSUM_BF16X8, RV_COLSUM_VEC4, RV_COLSUM_SCALAR = range(8)
@@ -107,6 +119,7 @@ _PROTOS = {
     "vaw_ln_modulate_fwd_fp8": [_p, _p, _p, _l, _p, _p, _i, _p, _p, _i, _i, _i, _f, _p],
     "vaw_gate_bwd_fp8": [_p, _p, _p, _l, _p, _p, _i, _p, _l, _p, _i, _i, _i, _p, _l, _p],
     "vaw_row_plan": [_i, _i, _l, _l, _l, _l, _l, _l, C.POINTER(RowLaunch)],
+    "vaw_attn_plan": [_i, _i, C.POINTER(AttnDesc), _l, _l, _l, _l, _l, _l, _l, C.POINTER(AttnLaunch)],
 }
 
 _lib = None

@@ -177,12 +177,16 @@ attn_bwd_kv_rowwise(AttnDev a, const T* __restrict__ q, const T* __restrict__ k,
     }
 }
 
-// bf16 MFMA path (attention_mfma.hip)
-bool vaw_attn_mfma_ok(vaw_dtype dt, const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o);
-int vaw_attn_fwd_mfma(const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse, hipStream_t s);
-int vaw_attn_bwd_mfma(const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const void* d_o,
-                      const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s, float* cs_part = nullptr,
-                      int64_t* cs_rows_out = nullptr);
+// bf16 MFMA path (attention_mfma.hip, attention_bwd_big.hip): launchers and the LDS sizes of their images
+bool vaw_attn_mfma_ok(vaw_dtype dt, const vaw_attn_desc* d, int64_t q, int64_t k, int64_t v, int64_t o);
+int64_t vaw_attn_img_bytes(int hd_image);
+int64_t vaw_attn_fwd_big_lds(int hd_image);
+int64_t vaw_attn_bwd_big_lds(int hd_image, int nt, int T);
+int vaw_attn_fwd_mfma(const vaw_attn_launch& p, const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse,
+                      hipStream_t s);
+int vaw_attn_bwd_mfma(const vaw_attn_launch& p, const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o,
+                      const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s,
+                      float* cs_part = nullptr);
 static int g_force_rowwise = 0;
 extern "C" void vaw_debug_force_rowwise_attention(int on) { g_force_rowwise = on; }
 
@@ -196,16 +200,117 @@ static AttnDev to_dev(const vaw_attn_desc* d) {
     AttnDev a{d->B, d->H, d->T, d->hd, d->q_sb, d->q_sh, d->q_st, d->q_sd, d->o_sb, d->o_sh, d->o_st, d->o_sd, d->scale};
     return a;
 }
+static int env_switch(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+static constexpr int64_t kAttnLdsDefault = 64 * 1024;     // a launch that does not raise its cap with hipFuncSetAttribute
+
+extern "C" int vaw_attn_plan(int dir, vaw_dtype dt, const vaw_attn_desc* d, int64_t q, int64_t k, int64_t v, int64_t o_or_do,
+                             int64_t dq, int64_t dk, int64_t dv, vaw_attn_launch* out) {
+    VAW_CHECK_ARG(out && dir >= VAW_ATTN_DIR_FWD && dir <= VAW_ATTN_DIR_BWD_COLSUM, "attn_plan: bad direction %d", dir);
+    vaw_attn_launch p = {};
+    p.status = VAW_ERR_INVALID;
+    *out = p;
+    const char* who = dir == VAW_ATTN_DIR_FWD ? "attn_fwd" : dir == VAW_ATTN_DIR_BWD ? "attn_bwd" : "attn_bwd_colsum";
+    int rc = check_desc(d, who);
+    if (rc) return rc;
+    VAW_CHECK_ARG(dt == VAW_F32 || dt == VAW_BF16, "%s: dt must be f32 or bf16", who);
+    const bool fwd = dir == VAW_ATTN_DIR_FWD;
+    const int T = d->T, hd = d->hd;
+    p.block = 256;
+    p.grid_y = d->B * d->H;
+    const bool mfma = !g_force_rowwise && vaw_attn_mfma_ok(dt, d, q, k, v, o_or_do) && (fwd || ((dq | dk | dv) & 7) == 0);
+    if (!mfma) {
+        // four query (key) rows per workgroup, one per wave, each wave with its rows of f32 in LDS (the cap is not raised)
+        p.variant = VAW_AV_ROWWISE;
+        p.launches = fwd ? 1 : 2;
+        p.grid_x = (T + 3) / 4;
+        p.lds_bytes = fwd ? 16 * ((int64_t)hd + T) : 16 * (2 * (int64_t)hd + 2 * T);
+        VAW_CHECK_ARG(p.lds_bytes <= kAttnLdsDefault, "%s: the rowwise kernels need %ld bytes of LDS at hd=%d, T=%d (at most %ld)", who,
+                      (long)p.lds_bytes, hd, T, (long)kAttnLdsDefault);
+        p.status = VAW_OK;
+        *out = p;
+        return VAW_OK;
+    }
+    const int img = hd <= 32 ? 32 : hd <= 64 ? 64 : hd <= 96 ? 96 : 128;     // zero-padded head width of the LDS images
+    const int64_t ib = vaw_attn_img_bytes(img);
+    p.lds_cap_raised = 1;
+    p.hd_image = img;
+    if (fwd) {
+        p.launches = 1;
+        // attention_bwd_big.hip: the owner-rows forward.  VAW_ATTN_FWD_BIG 2 (default) = head dims 72 .. 96, 1 = 40 .. 96, 0 = off
+        const int big = env_switch("VAW_ATTN_FWD_BIG", 2);
+        if (big != 0 && T % 128 == 0 && hd > (big == 1 ? 32 : 64) && hd <= 96) {
+            p.variant = VAW_AV_FWD_BIG;
+            p.hd_image = hd <= 64 ? 64 : 96;
+            p.grid_x = T / 128;
+            p.lds_bytes = vaw_attn_fwd_big_lds(p.hd_image);
+        } else if (T % 128 == 0 && hd <= 96 && env_switch("VAW_ATTN_QG2", 1) != 0) {
+            // two 16-query groups per wave: +10..17 % for head dims <= 64 (tools/attn_bench.py), +30 % for the padded 96-wide images
+            // (DiT-XL's 72, UNet_64's 96) now that their rows are conflict-free; 128-wide images keep one group (accumulators)
+            p.variant = VAW_AV_FWD_G2;
+            p.grid_x = T / 128;
+            p.lds_bytes = (img <= 64 ? 6 : 4) * ib;
+        } else if (T == 64) {     // a single key block: nothing to double-buffer, keep the LDS footprint (and residency) small
+            p.variant = VAW_AV_FWD_T64;
+            p.grid_x = 1;
+            p.lds_bytes = 3 * ib;
+        } else {
+            p.variant = VAW_AV_FWD_G1;
+            p.grid_x = T / 64;
+            p.lds_bytes = (img <= 64 ? 5 : 3) * ib;
+        }
+        p.status = VAW_OK;
+        *out = p;
+        return VAW_OK;
+    }
+    p.launches = 2;
+    const int bwd_big = env_switch("VAW_ATTN_BWD_BIG", 2);
+    if (T == 64) {        // single block of queries and keys: one fused launch
+        p.variant = VAW_AV_BWD_T64;
+        p.launches = 1;
+        p.grid_x = 1;
+        p.lds_bytes = 4 * ib;
+        p.colsum_rows = d->B;
+    } else if ((bwd_big == 1 || bwd_big == 2) && T % (bwd_big == 2 ? 128 : 256) == 0 && T <= 1024 && hd > 32 && hd <= 96) {
+        // attention_bwd_big.hip: VAW_ATTN_BWD_BIG 2 (default) = 32 owner rows per wave (T % 128), 1 = 64 (T % 256), 0 = off
+        const int nt = bwd_big == 2 ? 2 : 4, wgr = 64 * nt;
+        p.variant = nt == 2 ? VAW_AV_BWD_BIG_NT2 : VAW_AV_BWD_BIG_NT4;
+        p.hd_image = hd <= 64 ? 64 : 96;
+        p.grid_x = T / wgr;
+        p.lds_bytes = vaw_attn_bwd_big_lds(p.hd_image, nt, T);
+        p.colsum_rows = (int64_t)d->B * (T / wgr);
+    } else if (T % 128 == 0 && hd > 64 && hd <= 96 && env_switch("VAW_ATTN_BWD_G2", 1) != 0) {
+        // measured (tools/attn_bench.py, T = 256 / 1024): two groups are +10 % on the 96-wide images with 96 real channels
+        // (UNet_64), neutral on DiT-XL's 72-in-96, and 10-20 % SLOWER on 64-wide images, where the third resident workgroup is
+        // worth more than the shared fragments: these kernels are occupancy-, not DMA-latency-bound
+        p.variant = VAW_AV_BWD_G2;
+        p.grid_x = T / 128;
+        p.lds_bytes = 6 * ib + 2 * 64 * 4;
+        p.colsum_rows = (int64_t)d->B * (T / 128);
+    } else {
+        p.variant = VAW_AV_BWD_G1;
+        p.grid_x = T / 64;
+        p.lds_bytes = 4 * ib + 2 * 64 * 4;
+        p.colsum_rows = (int64_t)d->B * (T / 64);
+    }
+    if (dir != VAW_ATTN_DIR_BWD_COLSUM) p.colsum_rows = 0;
+    p.status = VAW_OK;
+    *out = p;
+    return VAW_OK;
+}
 
 extern "C" int vaw_attn_fwd(vaw_dtype dt, const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o,
                             float* lse, vaw_stream stream) {
-    int rc = check_desc(d, "attn_fwd");
+    vaw_attn_launch p;
+    int rc = vaw_attn_plan(VAW_ATTN_DIR_FWD, dt, d, (int64_t)q, (int64_t)k, (int64_t)v, (int64_t)o, 0, 0, 0, &p);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (!g_force_rowwise && vaw_attn_mfma_ok(dt, d, q, k, v, o)) return vaw_attn_fwd_mfma(d, q, k, v, o, lse, s);
+    if (p.variant != VAW_AV_ROWWISE) return vaw_attn_fwd_mfma(p, d, q, k, v, o, lse, s);
     AttnDev a = to_dev(d);
-    dim3 grid(ceil_div(a.T, 4), a.B * a.H);
-    const size_t lds = 4 * (size_t)(a.hd + a.T) * sizeof(float);
+    dim3 grid(p.grid_x, p.grid_y);
+    const size_t lds = 16 * (size_t)(a.hd + a.T);
     if (dt == VAW_F32)
         attn_fwd_rowwise<float><<<grid, 256, lds, s>>>(a, (const float*)q, (const float*)k, (const float*)v, (float*)o, lse);
     else
@@ -214,18 +319,14 @@ extern "C" int vaw_attn_fwd(vaw_dtype dt, const vaw_attn_desc* d, const void* q,
     return VAW_OK;
 }
 
-extern "C" int vaw_attn_bwd(vaw_dtype dt, const vaw_attn_desc* d, const void* q, const void* k, const void* v,
-                            const void* o, const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv,
-                            vaw_stream stream) {
-    int rc = check_desc(d, "attn_bwd");
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (!g_force_rowwise && vaw_attn_mfma_ok(dt, d, q, k, v, d_o) && (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 7) == 0)
-        return vaw_attn_bwd_mfma(d, q, k, v, o, d_o, lse, delta, dq, dk, dv, s);
+static int attn_bwd_go(const vaw_attn_launch& p, vaw_dtype dt, const vaw_attn_desc* d, const void* q, const void* k, const void* v,
+                       const void* o, const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s,
+                       float* cs_part) {
+    if (p.variant != VAW_AV_ROWWISE) return vaw_attn_bwd_mfma(p, d, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part);
     AttnDev a = to_dev(d);
-    dim3 grid(ceil_div(a.T, 4), a.B * a.H);
-    const size_t lds_q = 4 * (size_t)(2 * a.hd + a.T) * sizeof(float);
-    const size_t lds_kv = 4 * (size_t)(2 * a.hd + 2 * a.T) * sizeof(float);
+    dim3 grid(p.grid_x, p.grid_y);
+    const size_t lds_q = 16 * (size_t)(2 * a.hd + a.T);
+    const size_t lds_kv = p.lds_bytes;
     if (dt == VAW_F32) {
         attn_bwd_q_rowwise<float><<<grid, 256, lds_q, s>>>(a, (const float*)q, (const float*)k, (const float*)v, (const float*)o, (const float*)d_o, lse, delta, (float*)dq);
         attn_bwd_kv_rowwise<float><<<grid, 256, lds_kv, s>>>(a, (const float*)q, (const float*)k, (const float*)v, (const float*)d_o, lse, delta, (float*)dk, (float*)dv);
@@ -237,19 +338,34 @@ extern "C" int vaw_attn_bwd(vaw_dtype dt, const vaw_attn_desc* d, const void* q,
     return VAW_OK;
 }
 
+extern "C" int vaw_attn_bwd(vaw_dtype dt, const vaw_attn_desc* d, const void* q, const void* k, const void* v,
+                            const void* o, const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv,
+                            vaw_stream stream) {
+    vaw_attn_launch p;
+    int rc = vaw_attn_plan(VAW_ATTN_DIR_BWD, dt, d, (int64_t)q, (int64_t)k, (int64_t)v, (int64_t)d_o, (int64_t)dq, (int64_t)dk,
+                           (int64_t)dv, &p);
+    if (rc) return rc;
+    return attn_bwd_go(p, dt, d, q, k, v, o, d_o, lse, delta, dq, dk, dv, (hipStream_t)stream, nullptr);
+}
+
 // vaw_attn_bwd that also leaves the column sums of dq | dk | dv behind as partial rows (packed-qkv column order [3][H][hd], the
 // bias layout of timm Attention's qkv Linear): colsum_partial [*rows_out][3 H hd] f32, at most B * T / 64 rows.  Only the bf16
 // MFMA kernels offer it: VAW_ERR_UNSUPPORTED (nothing launched) otherwise -- call vaw_attn_bwd and vaw_colsum then.
 extern "C" int vaw_attn_bwd_colsum(vaw_dtype dt, const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o,
                                    const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv,
                                    float* colsum_partial, int64_t* rows_out, vaw_stream stream) {
-    int rc = check_desc(d, "attn_bwd_colsum");
+    vaw_attn_launch p;
+    int rc = vaw_attn_plan(VAW_ATTN_DIR_BWD_COLSUM, dt, d, (int64_t)q, (int64_t)k, (int64_t)v, (int64_t)d_o, (int64_t)dq, (int64_t)dk,
+                           (int64_t)dv, &p);
     if (rc) return rc;
     VAW_CHECK_ARG(colsum_partial && rows_out, "attn_bwd_colsum: colsum_partial and rows_out are required");
     VAW_CHECK_ARG(*rows_out >= (int64_t)d->B * (d->T / 64 > 0 ? d->T / 64 : 1), "attn_bwd_colsum: *rows_out states a capacity of %ld rows, up to %ld are written",
                   (long)*rows_out, (long)((int64_t)d->B * (d->T / 64 > 0 ? d->T / 64 : 1)));
-    if (!g_force_rowwise && vaw_attn_mfma_ok(dt, d, q, k, v, d_o) && (((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 7) == 0 && d->hd % 4 == 0)
-        return vaw_attn_bwd_mfma(d, q, k, v, o, d_o, lse, delta, dq, dk, dv, (hipStream_t)stream, colsum_partial, rows_out);
-    vaw_set_error("attn_bwd_colsum: only the bf16 MFMA attention kernels carry column sums");
-    return VAW_ERR_UNSUPPORTED;
+    if (p.colsum_rows == 0) {
+        vaw_set_error("attn_bwd_colsum: only the bf16 MFMA attention kernels carry column sums");
+        return VAW_ERR_UNSUPPORTED;
+    }
+    rc = attn_bwd_go(p, dt, d, q, k, v, o, d_o, lse, delta, dq, dk, dv, (hipStream_t)stream, colsum_partial);
+    if (rc == VAW_OK) *rows_out = p.colsum_rows;
+    return rc;
 }

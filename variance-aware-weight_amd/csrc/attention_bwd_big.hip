@@ -604,12 +604,18 @@ static AttnMfmaArgs mk_args_big(const vaw_attn_desc* d) {
     return a;
 }
 
-// true when the shape is taken (both launches enqueued); cs_part / cs_rows_out as in vaw_attn_bwd_mfma
+int64_t vaw_attn_bwd_big_lds(int hd_image, int nt, int T) {
+    return hd_image == 64 ? (nt == 2 ? BigLds<64, 2>::bytes(T) : BigLds<64, 4>::bytes(T))
+                          : (nt == 2 ? BigLds<96, 2>::bytes(T) : BigLds<96, 4>::bytes(T));
+}
+int64_t vaw_attn_fwd_big_lds(int hd_image) { return hd_image == 64 ? FwdLds<64, 2>::FRONT : FwdLds<96, 2>::FRONT; }
+
+// both launches of the pair: the grid and LDS size come from vaw_attn_plan (attention.hip); cs_part as in vaw_attn_bwd_mfma
 template <int HD, int NT>
-static void big_go(const AttnMfmaArgs& a, const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const void* d_o,
+static void big_go(const vaw_attn_launch& p, const AttnMfmaArgs& a, const void* q, const void* k, const void* v, const void* o, const void* d_o,
                    const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s, float* cs_part, int64_t cs_ld) {
-    const int lds = BigLds<HD, NT>::bytes(d->T);
-    dim3 grid(d->T / BigLds<HD, NT>::WGR, d->B * d->H);
+    const int lds = (int)p.lds_bytes;
+    dim3 grid(p.grid_x, p.grid_y);
     static bool attr_done = false;                       // (once per instantiation: the limit for the longest sequence taken, T = 1024)
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)attn_bwd_big<HD, 1, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, BigLds<HD, NT>::bytes(1024));
@@ -622,26 +628,19 @@ static void big_go(const AttnMfmaArgs& a, const vaw_attn_desc* d, const void* q,
                                                    lse, delta, (bf16_t*)dk, (bf16_t*)dv, cs_part, cs_ld);
 }
 
-bool vaw_attn_bwd_big(const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const void* d_o,
-                      const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s, float* cs_part, int64_t* cs_rows_out) {
-    // VAW_ATTN_BWD_BIG: 2 (default) = 32 owner rows per wave, two workgroups per CU (T % 128 == 0); 1 = 64 owner rows per wave, one
-    // workgroup per CU (T % 256 == 0; the experiment of the header); 0 = the 16-row kernels of attention_mfma.hip.  Read per call.
-    const char* e = getenv("VAW_ATTN_BWD_BIG");
-    const int on = e ? atoi(e) : 2;
-    const int wgr = on == 2 ? 128 : 256;
-    if ((on != 1 && on != 2) || d->T % wgr != 0 || d->T > 1024 || d->hd <= 32 || d->hd > 96) return false;
+void vaw_attn_bwd_big(const vaw_attn_launch& p, const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o,
+                      const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s, float* cs_part) {
     const AttnMfmaArgs a = mk_args_big(d);
     const int64_t cs_ld = 3LL * d->H * d->hd;
-    if (d->hd <= 64) { if (on == 2) big_go<64, 2>(a, d, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part, cs_ld); else big_go<64, 4>(a, d, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part, cs_ld); }
-    else { if (on == 2) big_go<96, 2>(a, d, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part, cs_ld); else big_go<96, 4>(a, d, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part, cs_ld); }
-    if (cs_rows_out) *cs_rows_out = (int64_t)d->B * (d->T / wgr);
-    return true;
+    const bool nt2 = p.variant == VAW_AV_BWD_BIG_NT2;
+    if (p.hd_image == 64) { if (nt2) big_go<64, 2>(p, a, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part, cs_ld); else big_go<64, 4>(p, a, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part, cs_ld); }
+    else { if (nt2) big_go<96, 2>(p, a, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part, cs_ld); else big_go<96, 4>(p, a, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part, cs_ld); }
 }
 
 template <int HD, int NT>
-static void big_fwd_go(const AttnMfmaArgs& a, const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse, hipStream_t s) {
-    const int lds = FwdLds<HD, NT>::FRONT;
-    dim3 grid(d->T / FwdLds<HD, NT>::WGR, d->B * d->H);
+static void big_fwd_go(const vaw_attn_launch& p, const AttnMfmaArgs& a, const void* q, const void* k, const void* v, void* o, float* lse, hipStream_t s) {
+    const int lds = (int)p.lds_bytes;
+    dim3 grid(p.grid_x, p.grid_y);
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)attn_fwd_big<HD, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -652,14 +651,10 @@ static void big_fwd_go(const AttnMfmaArgs& a, const vaw_attn_desc* d, const void
 
 // The owner-rows forward (T % 128 == 0).  Measured against attn_fwd_mfma (tools/attn_bench.py, interleaved): the 96-wide images win
 // (DiT-XL/2 138.7 -> 120.8 us, UNet_64 16 x 16 39.2 -> 36.6), the 64-wide ones -- where attn_fwd_mfma double-buffers K / V by LDS-DMA and
-// keeps three workgroups per CU -- lose 2-4 % (DiT-B/2 103.0 -> 105.5, ADM_64 32 x 32 641 -> 668).  So: head dims 72 .. 96 by default;
-// VAW_ATTN_FWD_BIG=1 all of 40 .. 96, =0 none.  Read per call.
-bool vaw_attn_fwd_big(const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse, hipStream_t s) {
-    const char* e = getenv("VAW_ATTN_FWD_BIG");
-    const int on = e ? atoi(e) : 2;
-    const int hd_lo = on == 1 ? 32 : 64;
-    if (on == 0 || d->T % 128 != 0 || d->hd <= hd_lo || d->hd > 96) return false;
+// keeps three workgroups per CU -- lose 2-4 % (DiT-B/2 103.0 -> 105.5, ADM_64 32 x 32 641 -> 668).  So vaw_attn_plan takes head dims
+// 72 .. 96 here by default; VAW_ATTN_FWD_BIG=1 all of 40 .. 96, =0 none.
+void vaw_attn_fwd_big(const vaw_attn_launch& p, const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse,
+                      hipStream_t s) {
     const AttnMfmaArgs a = mk_args_big(d);
-    if (d->hd <= 64) big_fwd_go<64, 2>(a, d, q, k, v, o, lse, s); else big_fwd_go<96, 2>(a, d, q, k, v, o, lse, s);
-    return true;
+    if (p.hd_image == 64) big_fwd_go<64, 2>(p, a, q, k, v, o, lse, s); else big_fwd_go<96, 2>(p, a, q, k, v, o, lse, s);
 }

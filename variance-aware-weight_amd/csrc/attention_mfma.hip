@@ -637,13 +637,17 @@ attn_bwd_t64_mfma(AttnMfmaArgs a, const bf16_t* __restrict__ q, const bf16_t* __
 // ------------------------------------------------------------------------------------------------
 // host dispatch (called from attention.hip)
 // ------------------------------------------------------------------------------------------------
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static bool aligned16(int64_t p) { return (p & 15) == 0; }
 
-bool vaw_attn_mfma_ok(vaw_dtype dt, const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o) {
+bool vaw_attn_mfma_ok(vaw_dtype dt, const vaw_attn_desc* d, int64_t q, int64_t k, int64_t v, int64_t o) {
     const bool hd_ok = d->hd >= 8 && d->hd <= 128 && d->hd % 8 == 0;      // padded up to 32 / 64 / 96 / 128 in LDS
     return dt == VAW_BF16 && hd_ok && d->T % 64 == 0 && d->q_sd == 1 && d->o_sd == 1 && d->q_st % 8 == 0 && d->q_sh % 8 == 0 &&
            d->q_sb % 8 == 0 && d->o_st % 8 == 0 && d->o_sh % 8 == 0 && d->o_sb % 8 == 0 && aligned16(q) && aligned16(k) &&
            aligned16(v) && aligned16(o) && (int64_t)d->B * d->H < 65536;
+}
+
+int64_t vaw_attn_img_bytes(int hd_image) {
+    return hd_image == 32 ? Img<32>::BYTES : hd_image == 64 ? Img<64>::BYTES : hd_image == 96 ? Img<96>::BYTES : Img<128>::BYTES;
 }
 
 static AttnMfmaArgs mk_args(const vaw_attn_desc* d) {
@@ -651,108 +655,85 @@ static AttnMfmaArgs mk_args(const vaw_attn_desc* d) {
     return a;
 }
 
-static bool attn_qg2() {
-    static int on = -1;
-    if (on < 0) { const char* v = getenv("VAW_ATTN_QG2"); on = v ? atoi(v) : 1; }
-    return on != 0;
-}
-
-#define DISPATCH_HD(hd, ...)                                \
-    switch (((hd) + 31) / 32) {                             \
-        case 1: { constexpr int HD = 32; __VA_ARGS__ } break;    \
-        case 2: { constexpr int HD = 64; __VA_ARGS__ } break;    \
-        case 3: { constexpr int HD = 96; __VA_ARGS__ } break;    \
-        default: { constexpr int HD = 128; __VA_ARGS__ } break;  \
+// the head width of the plan's LDS images (vaw_attn_plan, attention.hip)
+#define DISPATCH_HD(img, ...)                                     \
+    switch (img) {                                                \
+        case 32: { constexpr int HD = 32; __VA_ARGS__ } break;    \
+        case 64: { constexpr int HD = 64; __VA_ARGS__ } break;    \
+        case 96: { constexpr int HD = 96; __VA_ARGS__ } break;    \
+        default: { constexpr int HD = 128; __VA_ARGS__ } break;   \
     }
 
-bool vaw_attn_fwd_big(const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse, hipStream_t s);
+void vaw_attn_fwd_big(const vaw_attn_launch& p, const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse,
+                      hipStream_t s);
 
-int vaw_attn_fwd_mfma(const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse,
+int vaw_attn_fwd_mfma(const vaw_attn_launch& p, const vaw_attn_desc* d, const void* q, const void* k, const void* v, void* o, float* lse,
                       hipStream_t s) {
-    if (vaw_attn_fwd_big(d, q, k, v, o, lse, s)) {        // attention_bwd_big.hip
+    if (p.variant == VAW_AV_FWD_BIG) {        // attention_bwd_big.hip
+        vaw_attn_fwd_big(p, d, q, k, v, o, lse, s);
         VAW_CHECK_LAUNCH("attn_fwd_big");
         return VAW_OK;
     }
     AttnMfmaArgs a = mk_args(d);
-    // two 16-query groups per wave: +10..17 % for head dims <= 64 (tools/attn_bench.py), +30 % for the padded 96-wide images
-    // (DiT-XL's 72, UNet_64's 96) now that their rows are conflict-free; 128-wide images keep one group (accumulators)
-    if (d->T % 128 == 0 && d->hd <= 96 && attn_qg2()) {
-        dim3 grid(d->T / 128, d->B * d->H);
-        DISPATCH_HD(d->hd,
-            const int lds = (HD <= 64 ? 6 : 4) * Img<HD>::BYTES;
-            (void)hipFuncSetAttribute((const void*)attn_fwd_mfma<HD, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attn_fwd_mfma<HD, 2><<<grid, 256, lds, s>>>(a, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse);
-        )
-        VAW_CHECK_LAUNCH("attn_fwd_mfma");
-        return VAW_OK;
+    dim3 grid(p.grid_x, p.grid_y);
+    const int lds = (int)p.lds_bytes;
+#define ATTN_FWD_GO(...)                                                                                                         \
+    do {                                                                                                                         \
+        (void)hipFuncSetAttribute((const void*)attn_fwd_mfma<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);     \
+        attn_fwd_mfma<__VA_ARGS__><<<grid, 256, lds, s>>>(a, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse); \
+    } while (0)
+    if (p.variant == VAW_AV_FWD_G2) {
+        DISPATCH_HD(p.hd_image, if constexpr (HD <= 96) ATTN_FWD_GO(HD, 2);)      // (the plan takes 128-wide images to G1)
+    } else if (p.variant == VAW_AV_FWD_T64) {
+        DISPATCH_HD(p.hd_image, ATTN_FWD_GO(HD, 1, false);)
+    } else {
+        DISPATCH_HD(p.hd_image, ATTN_FWD_GO(HD, 1);)
     }
-    dim3 grid(d->T / 64, d->B * d->H);
-    if (d->T == 64) {        // a single key block: nothing to double-buffer, keep the LDS footprint (and residency) small
-        DISPATCH_HD(d->hd,
-            const int lds = 3 * Img<HD>::BYTES;
-            (void)hipFuncSetAttribute((const void*)attn_fwd_mfma<HD, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attn_fwd_mfma<HD, 1, false><<<grid, 256, lds, s>>>(a, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse);
-        )
-        VAW_CHECK_LAUNCH("attn_fwd_mfma");
-        return VAW_OK;
-    }
-    DISPATCH_HD(d->hd,
-        const int lds = (HD <= 64 ? 5 : 3) * Img<HD>::BYTES;
-        (void)hipFuncSetAttribute((const void*)attn_fwd_mfma<HD, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attn_fwd_mfma<HD, 1><<<grid, 256, lds, s>>>(a, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse);
-    )
+#undef ATTN_FWD_GO
     VAW_CHECK_LAUNCH("attn_fwd_mfma");
     return VAW_OK;
 }
 
-bool vaw_attn_bwd_big(const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const void* d_o,
-                      const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s, float* cs_part, int64_t* cs_rows_out);
+void vaw_attn_bwd_big(const vaw_attn_launch& p, const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o,
+                      const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s, float* cs_part);
 
-// cs_part (may be NULL): [cs_rows][3 H hd] f32 partial column sums of dq | dk | dv, one row per (sample, 64 G-token block);
-// *cs_rows_out receives the row count
-int vaw_attn_bwd_mfma(const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o, const void* d_o,
-                      const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s, float* cs_part, int64_t* cs_rows_out) {
+// cs_part (may be NULL): [p.colsum_rows][3 H hd] f32 partial column sums of dq | dk | dv, one row per (sample, workgroup of tokens)
+int vaw_attn_bwd_mfma(const vaw_attn_launch& p, const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o,
+                      const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv, hipStream_t s, float* cs_part) {
     AttnMfmaArgs a = mk_args(d);
     const int64_t cs_ld = 3LL * d->H * d->hd;
-    dim3 grid(d->T / 64, d->B * d->H);
-    if (d->T == 64) {      // single block of queries and keys: one fused launch
-        DISPATCH_HD(d->hd,
-            const int lds = 4 * Img<HD>::BYTES;
+    const int lds = (int)p.lds_bytes;
+    if (p.variant == VAW_AV_BWD_T64) {      // single block of queries and keys: one fused launch
+        DISPATCH_HD(p.hd_image,
             (void)hipFuncSetAttribute((const void*)attn_bwd_t64_mfma<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attn_bwd_t64_mfma<HD><<<d->B * d->H, 256, lds, s>>>(a, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o,
+            attn_bwd_t64_mfma<HD><<<p.grid_x * p.grid_y, 256, lds, s>>>(a, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o,
                                                               (const bf16_t*)d_o, lse, delta, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, cs_part, cs_ld);
         )
-        if (cs_rows_out) *cs_rows_out = d->B;
         VAW_CHECK_LAUNCH("attn_bwd_t64_mfma");
         return VAW_OK;
     }
-    // T a multiple of 256, head dims 40 .. 96: the 64-rows-per-wave pair (attention_bwd_big.hip)
-    if (vaw_attn_bwd_big(d, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part, cs_rows_out)) {
+    // T a multiple of 128 / 256, head dims 40 .. 96: the 32 / 64-rows-per-wave pair (attention_bwd_big.hip)
+    if (p.variant == VAW_AV_BWD_BIG_NT2 || p.variant == VAW_AV_BWD_BIG_NT4) {
+        vaw_attn_bwd_big(p, d, q, k, v, o, d_o, lse, delta, dq, dk, dv, s, cs_part);
         VAW_CHECK_LAUNCH("attn_bwd_big");
         return VAW_OK;
     }
-    static int g2 = -1;
-    if (g2 < 0) { const char* e = getenv("VAW_ATTN_BWD_G2"); g2 = e ? atoi(e) : 1; }
+    dim3 gridg(p.grid_x, p.grid_y);
 #define ATTN_BWD_GO(Gv)                                                                                                          \
     do {                                                                                                                         \
-        dim3 gridg(d->T / (64 * Gv), d->B * d->H);                                                                               \
-        const int lds = (2 * Gv + 2) * Img<HD>::BYTES + 2 * 64 * 4;                                                              \
         (void)hipFuncSetAttribute((const void*)attn_bwd_dq_mfma<HD, Gv>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);       \
         (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_mfma<HD, Gv>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);      \
         attn_bwd_dq_mfma<HD, Gv><<<gridg, 256, lds, s>>>(a, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)o, \
                                                         (const bf16_t*)d_o, lse, delta, (bf16_t*)dq, cs_part, cs_ld);            \
         attn_bwd_dkv_mfma<HD, Gv><<<gridg, 256, lds, s>>>(a, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o, \
                                                          lse, delta, (bf16_t*)dk, (bf16_t*)dv, cs_part, cs_ld);                  \
-        if (cs_rows_out) *cs_rows_out = (int64_t)d->B * (d->T / (64 * Gv));                                                      \
     } while (0)
-    // measured (tools/attn_bench.py, T = 256 / 1024): two groups are +10 % on the 96-wide images with 96 real channels
-    // (UNet_64), neutral on DiT-XL's 72-in-96, and 10-20 % SLOWER on 64-wide images, where the third resident workgroup is
-    // worth more than the shared fragments: these kernels are occupancy-, not DMA-latency-bound
-    if (d->T % 128 == 0 && d->hd > 64 && d->hd <= 96 && g2) {
-        DISPATCH_HD(d->hd, if constexpr (HD == 96) ATTN_BWD_GO(2); else ATTN_BWD_GO(1);)
+    if (p.variant == VAW_AV_BWD_G2) {       // (the plan takes only 96-wide images to G2)
+        DISPATCH_HD(p.hd_image, if constexpr (HD == 96) ATTN_BWD_GO(2);)
     } else {
-        DISPATCH_HD(d->hd, ATTN_BWD_GO(1);)
+        DISPATCH_HD(p.hd_image, ATTN_BWD_GO(1);)
     }
+#undef ATTN_BWD_GO
     VAW_CHECK_LAUNCH("attn_bwd_mfma");
     return VAW_OK;
 }

@@ -584,6 +584,22 @@ def attn_desc_channel_major(B, H, T, ch):
     return AttnDesc(B, H, T, ch, 3 * H * ch * T, ch * T, 1, T, H * ch * T, ch * T, 1, T, ch ** -0.5)
 
 
+def attn_desc_nhwc(B, H, T, ch, new_order):
+    """qkv rows [B*T, 3*H*ch] (the UNet's attention on NHWC activations); channels [3][H][ch] (new order) or [H][3][ch]
+    (legacy order); output rows [B*T, H*ch].  k and v start ko / vo elements after q: returns (desc, ko, vo)."""
+    C_ = H * ch
+    desc = AttnDesc(B, H, T, ch, T * 3 * C_, ch if new_order else 3 * ch, 3 * C_, 1, T * C_, ch, C_, 1, ch ** -0.5)
+    return (desc, C_, 2 * C_) if new_order else (desc, ch, 2 * ch)
+
+
+def attn_plan(direction, dt, desc, q, k, v, o_or_do, dq=0, dk=0, dv=0):
+    """The launch the attention entry point `direction` (_lib.ATTN_FWD / ATTN_BWD / ATTN_BWD_COLSUM) makes for this descriptor
+    and these addresses (vaw_attn_plan: host arithmetic, no GPU; o_or_do: o for the forward, d_o for the backward)."""
+    p = L.AttnLaunch()
+    check(L.lib().vaw_attn_plan(direction, dt, C.byref(desc), q, k, v, o_or_do, dq, dk, dv, C.byref(p)), "vaw_attn_plan")
+    return p
+
+
 def attn_fwd(dt, desc, q, k, v, o, lse):
     check(L.lib().vaw_attn_fwd(dt, C.byref(desc), q, k, v, o, lse, stream_ptr()), "vaw_attn_fwd")
 

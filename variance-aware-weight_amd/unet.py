@@ -446,12 +446,8 @@ class UNetModel(FlatModule):
         n = self._gn(a, mod.norm, silu=False)
         qkv = self._linear(n, name + ".qkv.weight", name + ".qkv.bias", 3 * C)
         es = self._wsize
-        if mod.attention.new_order:      # channels [3][H][ch]
-            desc = L.AttnDesc(B, H, T, ch, T * 3 * C, ch, 3 * C, 1, T * C, ch, C, 1, ch ** -0.5)
-            ko, vo = es * C, 2 * es * C
-        else:                            # legacy: channels [H][3][ch]
-            desc = L.AttnDesc(B, H, T, ch, T * 3 * C, 3 * ch, 3 * C, 1, T * C, ch, C, 1, ch ** -0.5)
-            ko, vo = es * ch, 2 * es * ch
+        desc, ko, vo = ops.attn_desc_nhwc(B, H, T, ch, mod.attention.new_order)     # channels [3][H][ch] or legacy [H][3][ch]
+        ko, vo = es * ko, es * vo
         o = _Act(self._new(a.M, C), B, a.H, a.W, C)
         lse = self._new(B * H * T, dtype=torch.float32)
         q = ptr(qkv.t)

@@ -81,6 +81,41 @@ int vaw_sample_step(int kind, const float* mean_out, const float* var_out, const
                     const float* coef, int mean_mode, int var_mode, int clip_denoised, float eta, float* sample,
                     float* pred_xstart, float* mean, float* log_variance, int B, int64_t per_sample, vaw_stream stream);
 
+/* Likelihood evaluation, one timestep of calc_bpd_loop (gaussian_diffusion.py:950-1005) after the model call, fused:
+ * _vb_terms_bpd :775-808 WITH clip_denoised (p_mean_variance :343-368; the training-side kernel above has no clip) and
+ * the two report metrics of :989-991.  Per row b, with pred_xstart / model mean / log variance formed per element as
+ * in the sampling step above and never stored:
+ *   vb         = mean_flat(t[b]==0 ? decoder NLL : KL(q(x_{t-1}|x_t,x_0) || p(x_{t-1}|x_t))) / ln 2
+ *   xstart_mse = mean_flat((pred_xstart - x0)^2)
+ *   mse        = mean_flat((eps - noise)^2),  eps = (sqrt_recip_abar*x_t - pred_xstart) / sqrt_recipm1_abar  (:411-415,
+ *                evaluated in f32 in exactly this order: the difference cancels heavily at small t)
+ * coef: f32 [B][16], the rows of the sampling step.  mean_out / var_out: row b starts model_ld floats after row b-1
+ * (model_ld = per_sample when contiguous, 2*per_sample for the halves of a [B, 2C, H, W] output read in place);
+ * x0, x_t, noise are [B, per_sample] contiguous.  mean_mode / var_mode as above.  The three scalars of row b go to
+ * out[(b % group)*out_ld + b / group] of each output: with B = K*group rows (K timesteps of `group` samples stacked)
+ * one launch fills K adjacent columns of [group, T] row-major outputs whose column 0 the pointers name; group = B,
+ * out_ld = 1 gives plain [B] vectors.  Sums run in a fixed order (no atomics): bitwise reproducible, and a row's
+ * result does not depend on B.  16-byte loads when per_sample % 4 == 0, model_ld % 4 == 0 and every tensor is 16-byte
+ * aligned, scalar loads otherwise. */
+int vaw_bpd_terms(const float* mean_out, const float* var_out, int64_t model_ld, const float* x0, const float* x_t,
+                  const float* noise, const float* coef, int mean_mode, int var_mode, int clip_denoised, float* vb,
+                  float* xstart_mse, float* mse, int64_t out_ld, int group, int B, int64_t per_sample, vaw_stream stream);
+
+/* _prior_bpd :932-948 = q_mean_variance :217-232 at t = T-1 + normal_kl (tools/losses.py:12-39) against N(0, I) +
+ * mean_flat / ln 2:  prior_bpd[b] = mean_flat(0.5*(-1 - lv + exp(lv) + (a*x0)^2)) / ln 2  with the two table scalars
+ * a = float(sqrt_alphas_cumprod[T-1]), lv = float(log_one_minus_alphas_cumprod[T-1]). */
+int vaw_prior_bpd(const float* x0, float sqrt_abar_last, float log_one_minus_abar_last, float* prior_bpd, int B,
+                  int64_t per_sample, vaw_stream stream);
+
+/* ddim_reverse_sample :653-689 after the model call (eta = 0, the DDIM ODE run from data towards noise):
+ *   pred_xstart as in the sampling step (clip included), eps = (sqrt_recip_abar*x - pred_xstart) / sqrt_recipm1_abar,
+ *   sample = pred_xstart*sqrt(abar_next) + sqrt(1 - abar_next)*eps.
+ * coef: the [B][16] rows of the sampling step, column 13 = alphas_cumprod_next; columns 0-1 already encode the mean
+ * type (EPSILON / START_X / PREVIOUS_X) and the model variance does not enter, so there are no mode arguments.
+ * mean_out rows are model_ld floats apart.  pred_xstart may be NULL. */
+int vaw_ddim_reverse_step(const float* mean_out, int64_t model_ld, const float* x, const float* coef, int clip_denoised,
+                          float* sample, float* pred_xstart, int B, int64_t per_sample, vaw_stream stream);
+
 /* ---------------------------------------------------------------------------
  * Dense layers  (nn.Linear / Conv2d(k=p,s=p) / Conv1d(k=1) in models/dit.py, models/unet.py;
  * cuBLAS in the reference).  One GEMM entry point, MFMA inside.

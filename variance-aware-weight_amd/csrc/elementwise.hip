@@ -254,7 +254,8 @@ extern "C" int vaw_vb_bwd(const float* mean_out, const float* var_out, const flo
 
 // ---------------------------------------------------------------------------------------------
 // One reverse-process step (sampling side): p_mean_variance + p_sample / ddim_sample fused.
-// coef[b][16] = {pa, pb, c1, c2, plv, lv_aux, ra, rm1, sqrt_abp, s1, abp, is_t0, s2, -, -, -}:
+// coef[b][16] = {pa, pb, c1, c2, plv, lv_aux, ra, rm1, sqrt_abp, s1, abp, is_t0, s2, abn, -, -}  (abn = alphas_cumprod_next: read by
+// ddim_reverse_kernel only):
 //   pred_xstart = pa*x + pb*mean_out (clamped to [-1,1] if clip), model mean = c1*pred + c2*x (or mean_out itself),
 //   eps = (ra*x - pred)/rm1, sigma = (eta*s1)*s2, ddim mean = pred*sqrt_abp + sqrt(1 - abp - sigma^2)*eps.
 // kind 0: no sample (p_mean_variance only)   1: ancestral p_sample   2: ddim_sample.  Outputs may be NULL.
@@ -307,6 +308,195 @@ extern "C" int vaw_sample_step(int kind, const float* mean_out, const float* var
     sample_step_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(mean_out, var_out, x, noise, coef, kind, mean_mode, var_mode,
                                                              clip_denoised, eta, sample, pred_xstart, mean, log_variance, per_sample);
     VAW_CHECK_LAUNCH("sample_step");
+    return VAW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Likelihood evaluation (calc_bpd_loop): the three per-sample scalars of one evaluated timestep in one pass over
+// (model mean output, model var values, x0, x_t, noise): 20 B/element read (16 with a fixed variance), nothing of
+// [B, per_sample] shape written.  coef rows are those of sample_step_kernel (SS_NCOEF, same columns).
+//   pred  = pa*x_t + pb*mean_out, clamped to [-1,1] if clip          (p_mean_variance :343-368)
+//   vb    = mean(t==0 ? decoder NLL : KL(q(x_{t-1}|x_t,x0) || p(x_{t-1}|x_t))) / ln 2    (vb_elem, as vb_fwd_kernel)
+//   xmse  = mean((pred - x0)^2)                                       (:989)
+//   mse   = mean((eps - noise)^2),  eps = (ra*x_t - pred) / rm1       (:990-991, :411-415; not re-associated)
+// One workgroup per row; a thread sums its elements in index order, then wave shuffles + one LDS hop (block_sum): a fixed
+// order that depends on per_sample and the path (VEC) only, never on B.  Row b writes out[(b % group)*out_ld + b / group]:
+// a launch over K stacked timesteps of `group` samples fills K adjacent columns of the [N, T] outputs.
+// mean_out / var_out rows are model_ld elements apart (the two halves of one [B, 2C, H, W] model output are read in
+// place); every other tensor is [B, per_sample] contiguous.
+// ---------------------------------------------------------------------------------------------
+struct BpdAcc { float vb, xm, ms; };
+__device__ __forceinline__ void bpd_elem(const float* c, int mean_mode, int var_mode, int clip, bool t0, float m, float v, float x,
+                                         float z, float nz, BpdAcc& a) {
+    float pred = c[0] * z + c[1] * m;
+    if (clip) pred = fminf(fmaxf(pred, -1.f), 1.f);
+    float lv;
+    if (var_mode == 1) lv = v;
+    else if (var_mode == 2) { const float frac = (v + 1.f) / 2.f; lv = frac * c[5] + (1.f - frac) * c[4]; }
+    else lv = c[5];
+    const float mean = mean_mode == 1 ? m : c[2] * pred + c[3] * z;
+    a.vb += vb_elem(x, c[2] * x + c[3] * z, c[4], mean, lv, t0).val;
+    const float dx = pred - x;
+    a.xm += dx * dx;
+    const float de = (c[6] * z - pred) / c[7] - nz;
+    a.ms += de * de;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(1024)
+bpd_terms_kernel(const float* __restrict__ mean_out, const float* __restrict__ var_out, int64_t model_ld,
+                 const float* __restrict__ x0, const float* __restrict__ xt, const float* __restrict__ noise,
+                 const float* __restrict__ coef, int mean_mode, int var_mode, int clip, float* __restrict__ vb,
+                 float* __restrict__ xmse, float* __restrict__ mse, int64_t out_ld, int group, int64_t n) {
+    __shared__ float scratch[16];
+    const int b = blockIdx.x;
+    float c[SS_NCOEF];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) c[i] = coef[b * SS_NCOEF + i];
+    const bool t0 = c[11] != 0.f;
+    const float* mr = mean_out + (int64_t)b * model_ld;
+    const float* vr = var_out ? var_out + (int64_t)b * model_ld : nullptr;
+    const float* xr = x0 + (int64_t)b * n;
+    const float* zr = xt + (int64_t)b * n;
+    const float* nr = noise + (int64_t)b * n;
+    BpdAcc a = {0.f, 0.f, 0.f};
+    if (VEC) {
+        const int64_t n4 = n / 4;
+        for (int64_t i = threadIdx.x; i < n4; i += blockDim.x) {
+            const f32x4 m = load4(mr + 4 * i), x = load4(xr + 4 * i), z = load4(zr + 4 * i), e = load4(nr + 4 * i);
+            const f32x4 v = vr ? load4(vr + 4 * i) : f32x4{0, 0, 0, 0};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) bpd_elem(c, mean_mode, var_mode, clip, t0, m[j], v[j], x[j], z[j], e[j], a);
+        }
+    } else {
+        for (int64_t i = threadIdx.x; i < n; i += blockDim.x)
+            bpd_elem(c, mean_mode, var_mode, clip, t0, mr[i], vr ? vr[i] : 0.f, xr[i], zr[i], nr[i], a);
+    }
+    const float tv = block_sum(a.vb, scratch), tx = block_sum(a.xm, scratch), tm = block_sum(a.ms, scratch);
+    if (threadIdx.x == 0) {
+        const int64_t o = (int64_t)(b % group) * out_ld + b / group;
+        vb[o] = (tv / (float)n) / 0.6931471805599453f;
+        xmse[o] = tx / (float)n;
+        mse[o] = tm / (float)n;
+    }
+}
+
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" int vaw_bpd_terms(const float* mean_out, const float* var_out, int64_t model_ld, const float* x0, const float* x_t,
+                             const float* noise, const float* coef, int mean_mode, int var_mode, int clip_denoised, float* vb,
+                             float* xstart_mse, float* mse, int64_t out_ld, int group, int B, int64_t per_sample,
+                             vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "bpd_terms: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(mean_out && x0 && x_t && noise && coef && vb && xstart_mse && mse, "bpd_terms: null pointer");
+    VAW_CHECK_ARG(model_ld >= per_sample, "bpd_terms: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
+    VAW_CHECK_ARG((mean_mode == 0 || mean_mode == 1) && var_mode >= 0 && var_mode <= 2 && (var_mode == 0 || var_out),
+                  "bpd_terms: bad modes (mean_mode %d, var_mode %d; learned variance needs var_out)", mean_mode, var_mode);
+    VAW_CHECK_ARG(group > 0 && B % group == 0 && out_ld >= B / group, "bpd_terms: bad output layout (group %d, out_ld %ld, B %d)",
+                  group, (long)out_ld, B);
+    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(mean_out) && al16(var_out) && al16(x0) && al16(x_t) &&
+                     al16(noise);
+    if (vec)
+        bpd_terms_kernel<true><<<B, 1024, 0, (hipStream_t)stream>>>(mean_out, var_out, model_ld, x0, x_t, noise, coef, mean_mode,
+                                                                    var_mode, clip_denoised, vb, xstart_mse, mse, out_ld, group,
+                                                                    per_sample);
+    else
+        bpd_terms_kernel<false><<<B, 1024, 0, (hipStream_t)stream>>>(mean_out, var_out, model_ld, x0, x_t, noise, coef, mean_mode,
+                                                                     var_mode, clip_denoised, vb, xstart_mse, mse, out_ld, group,
+                                                                     per_sample);
+    VAW_CHECK_LAUNCH("bpd_terms");
+    return VAW_OK;
+}
+
+// _prior_bpd :932-948: KL(q(x_T | x_0) || N(0, I)) / ln 2 per sample; q_mean_variance :217-232 at t = T-1 gives
+// mean = sqrt_abar * x0 and log variance = log_1m_abar, normal_kl (tools/losses.py:33-39) against mean 0, log variance 0.
+__global__ void __launch_bounds__(1024)
+prior_bpd_kernel(const float* __restrict__ x0, float sqrt_abar, float log_1m_abar, float* __restrict__ out, int64_t n, int vec) {
+    __shared__ float scratch[16];
+    const int b = blockIdx.x;
+    const float* xr = x0 + (int64_t)b * n;
+    const float k = -1.0f + 0.f - log_1m_abar + expf(log_1m_abar - 0.f);
+    float acc = 0.f;
+    const int64_t n4 = vec ? n / 4 : 0;
+    for (int64_t i = threadIdx.x; i < n4; i += blockDim.x) {
+        const f32x4 m = sqrt_abar * load4(xr + 4 * i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc += 0.5f * (k + (m[j] * m[j]) * 1.f);
+    }
+    for (int64_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
+        const float m = sqrt_abar * xr[i];
+        acc += 0.5f * (k + (m * m) * 1.f);
+    }
+    const float tot = block_sum(acc, scratch);
+    if (threadIdx.x == 0) out[b] = (tot / (float)n) / 0.6931471805599453f;
+}
+
+extern "C" int vaw_prior_bpd(const float* x0, float sqrt_abar_last, float log_one_minus_abar_last, float* prior_bpd, int B,
+                             int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "prior_bpd: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(x0 && prior_bpd, "prior_bpd: null pointer");
+    prior_bpd_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(x0, sqrt_abar_last, log_one_minus_abar_last, prior_bpd, per_sample,
+                                                          per_sample % 4 == 0 && al16(x0));
+    VAW_CHECK_LAUNCH("prior_bpd");
+    return VAW_OK;
+}
+
+// ddim_reverse_sample :653-689 after the model call (eta = 0: the deterministic DDIM ODE run towards noise).  Rows of
+// sample_step_kernel's table, column 13 = alphas_cumprod_next:
+//   pred = pa*x + pb*mean_out (clamped if clip),  eps = (ra*x - pred)/rm1,  sample = pred*sqrt(abn) + sqrt(1 - abn)*eps.
+// The model variance does not enter; mean_out rows are model_ld elements apart.
+__device__ __forceinline__ void ddim_rev_elem(const float* c, int clip, float sa, float sb, float m, float xv, float& s, float& p) {
+    float pred = c[0] * xv + c[1] * m;
+    if (clip) pred = fminf(fmaxf(pred, -1.f), 1.f);
+    const float eps = (c[6] * xv - pred) / c[7];
+    p = pred;
+    s = pred * sa + sb * eps;
+}
+template <bool VEC>
+__global__ void ddim_reverse_kernel(const float* __restrict__ mean_out, int64_t model_ld, const float* __restrict__ x,
+                                    const float* __restrict__ coef, int clip, float* __restrict__ sample,
+                                    float* __restrict__ pred_out, int64_t n) {
+    const int b = blockIdx.y;
+    float c[SS_NCOEF];
+#pragma unroll
+    for (int i = 0; i < SS_NCOEF; ++i) c[i] = coef[b * SS_NCOEF + i];
+    const float sa = sqrtf(c[13]), sb = sqrtf(1.f - c[13]);
+    const float* mr = mean_out + (int64_t)b * model_ld;
+    const int64_t base = (int64_t)b * n;
+    if (VEC) {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
+            const f32x4 m = load4(mr + 4 * i), xv = load4(x + base + 4 * i);
+            f32x4 s, p;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { float sj, pj; ddim_rev_elem(c, clip, sa, sb, m[j], xv[j], sj, pj); s[j] = sj; p[j] = pj; }
+            store4(sample + base + 4 * i, s);
+            if (pred_out) store4(pred_out + base + 4 * i, p);
+        }
+    } else {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            float s, p;
+            ddim_rev_elem(c, clip, sa, sb, mr[i], x[base + i], s, p);
+            sample[base + i] = s;
+            if (pred_out) pred_out[base + i] = p;
+        }
+    }
+}
+
+extern "C" int vaw_ddim_reverse_step(const float* mean_out, int64_t model_ld, const float* x, const float* coef, int clip_denoised,
+                                     float* sample, float* pred_xstart, int B, int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "ddim_reverse_step: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(mean_out && x && coef && sample, "ddim_reverse_step: null pointer");
+    VAW_CHECK_ARG(model_ld >= per_sample, "ddim_reverse_step: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
+    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(mean_out) && al16(x) && al16(sample) && al16(pred_xstart);
+    int gx = stream_grid(vec ? per_sample / 4 : per_sample, 256);
+    dim3 grid(gx > 64 ? 64 : gx, B);
+    if (vec)
+        ddim_reverse_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(mean_out, model_ld, x, coef, clip_denoised, sample,
+                                                                         pred_xstart, per_sample);
+    else
+        ddim_reverse_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(mean_out, model_ld, x, coef, clip_denoised, sample,
+                                                                          pred_xstart, per_sample);
+    VAW_CHECK_LAUNCH("ddim_reverse_step");
     return VAW_OK;
 }
 

@@ -9,6 +9,8 @@ What runs where
   vaw_qsample_fwd x_t = sqrt(abar_t) x0 + sqrt(1-abar_t) eps, table gather fused        (12 B/element)
   vaw_wmse_fwd    target + (target-out)^2 + mean over CHW + per-sample weight, one pass  (12 B/element)
   vaw_wmse_bwd    d(out) in one pass                                                       (16 B/element)
+  vaw_bpd_terms   calc_bpd_loop's per-timestep tail: bound with clip, x0 MSE, eps MSE, one pass      (20 B/element)
+  vaw_prior_bpd / vaw_ddim_reverse_step   the prior KL of the bound; one step of the DDIM ODE towards noise
 Only the selected target is computed (the reference evaluates all four, :823-830).
 """
 import enum
@@ -221,9 +223,9 @@ class GaussianDiffusion:
 
     # ---- sampling side (reference :278-384, :461-601, :603-790; no denoised_fn / cond_fn) ----------------------
     def _sample_table(self):
-        """[T, 16] f32 rows for vaw_sample_step.  Every entry is the reference's float64 table cast to f32 as
-        _extract_into_tensor does; products of tables (ddim sigma) are formed in f32 in the kernel, as the reference's
-        tensor ops do."""
+        """[T, 16] f32 rows for vaw_sample_step, vaw_bpd_terms and vaw_ddim_reverse_step.  Every entry is the reference's
+        float64 table cast to f32 as _extract_into_tensor does; products of tables (ddim sigma) are formed in f32 in the
+        kernel, as the reference's tensor ops do.  Column 13 (alphas_cumprod_next) is read by the DDIM reverse step only."""
         f = lambda arr: torch.from_numpy(np.asarray(arr, dtype=np.float64)).float()
         T = self.num_timesteps
         vt, mt = self.model_var_type, self.model_mean_type
@@ -246,7 +248,8 @@ class GaussianDiffusion:
         t0[0] = 1.0
         z = torch.zeros(T)
         return torch.stack([pa, pb, f(self.posterior_mean_coef1), f(self.posterior_mean_coef2),
-                            f(self.posterior_log_variance_clipped), lv_aux, ra, rm1, torch.sqrt(abp), s1, abp, t0, s2, z, z, z],
+                            f(self.posterior_log_variance_clipped), lv_aux, ra, rm1, torch.sqrt(abp), s1, abp, t0, s2,
+                            f(self.alphas_cumprod_next), z, z],
                            dim=1).contiguous()
 
     def _reverse_step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0, want_all=False):
@@ -270,6 +273,8 @@ class GaussianDiffusion:
         tb = self._tables(x.device)
         if key not in tb:
             tb[key] = self._sample_table().to(x.device)
+        if kind == 3:                                                      # ddim_reverse_sample: deterministic, no noise draw
+            return ops.ddim_reverse_step(out, x, tb[key][t], clip_denoised)
         noise = None
         if kind:
             if getattr(self.args, "cpu_rng", False):
@@ -279,6 +284,35 @@ class GaussianDiffusion:
         var_mode = {ModelVarType.LEARNED: 1, ModelVarType.LEARNED_RANGE: 2}.get(vt, 0)
         return ops.sample_step(kind, out, var_out, x, noise, tb[key][t], 1 if mt == ModelMeanType.PREVIOUS_X else 0, var_mode,
                                clip_denoised, eta, want_all)
+
+    def _model_halves(self, model, x, t, model_kwargs):
+        """Model call of p_mean_variance (:304-314): (mean output, variance values or None), the halves as views."""
+        self._refuse_unsupported_mean_type()
+        vt = self.model_var_type
+        B, C = x.shape[:2]
+        assert t.shape == (B,)
+        out = model(x, self._scale_timesteps(t), **(model_kwargs or {}))
+        out = out[0] if isinstance(out, tuple) else out
+        var_out = None
+        if vt in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE):
+            assert out.shape == (B, C * 2, *x.shape[2:])
+            out, var_out = torch.split(out, C, dim=1)
+        assert out.shape == x.shape
+        return out, var_out
+
+    def _refuse_unsupported_mean_type(self):
+        mt = self.model_mean_type
+        if mt == ModelMeanType.VELOCITY:
+            # the reference gathers with t.shape in _predict_xstart_from_v (:394-399) and cannot broadcast
+            raise RuntimeError("VELOCITY with a variational-bound term: the reference's _predict_xstart_from_v fails to broadcast")
+        if mt not in (ModelMeanType.EPSILON, ModelMeanType.START_X, ModelMeanType.PREVIOUS_X):
+            raise NotImplementedError(mt)
+
+    def _sample_rows(self, t):
+        tb = self._tables(t.device)
+        if "ss" not in tb:
+            tb["ss"] = self._sample_table().to(t.device)
+        return tb["ss"][t]
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         r = self._reverse_step(0, model, x, t, clip_denoised, denoised_fn, None, model_kwargs, want_all=True)
@@ -338,14 +372,112 @@ class GaussianDiffusion:
             pass
         return final["sample"]
 
+    # ---- likelihood evaluation (reference :217-232, :254-276, :411-415, :653-689, :932-1005) -------------------------
+    def q_mean_variance(self, x_start, t):
+        """q(x_t | x_0): (mean, variance, log_variance), each of x_start's shape.  Table gathers; CPU or GPU tensors."""
+        shape = x_start.shape
+        return (_extract_into_tensor(self.sqrt_alphas_cumprod, t, shape) * x_start,
+                _extract_into_tensor(1.0 - self.alphas_cumprod, t, shape),
+                _extract_into_tensor(self.log_one_minus_alphas_cumprod, t, shape))
+
+    def q_posterior_mean_variance(self, x_start, x_t, t):
+        """q(x_{t-1} | x_t, x_0): (mean, variance, clipped log variance).  Table gathers; CPU or GPU tensors."""
+        assert x_start.shape == x_t.shape
+        shape = x_t.shape
+        mean = (_extract_into_tensor(self.posterior_mean_coef1, t, shape) * x_start
+                + _extract_into_tensor(self.posterior_mean_coef2, t, shape) * x_t)
+        return (mean, _extract_into_tensor(self.posterior_variance, t, shape),
+                _extract_into_tensor(self.posterior_log_variance_clipped, t, shape))
+
+    def _predict_eps_from_xstart(self, x_t, t, pred_xstart):
+        return ((_extract_into_tensor(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t - pred_xstart)
+                / _extract_into_tensor(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape))
+
+    def _prior_coefs(self):
+        """The two table scalars of _prior_bpd as f32: sqrt(abar_{T-1}) and log(1 - abar_{T-1})."""
+        return (float(np.float32(self.sqrt_alphas_cumprod[-1])), float(np.float32(self.log_one_minus_alphas_cumprod[-1])))
+
+    def _prior_bpd(self, x_start):
+        """KL(q(x_T | x_0) || N(0, I)) in bits/dim, [N] (vaw_prior_bpd)."""
+        with torch.no_grad():
+            return ops.prior_bpd(x_start.contiguous(), *self._prior_coefs())
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, t_chunk=1):
+        """The whole variational bound in bits/dim and the per-timestep report metrics (reference :950-1005):
+        {"total_bpd" [N], "prior_bpd" [N], "vb" [N, T], "xstart_mse" [N, T], "mse" [N, T]}; column j is timestep T-1-j.
+
+        One noise draw per timestep in that order (the CPU stream with args.cpu_rng), q_sample, the model, then ONE fused
+        pass (vaw_bpd_terms) that writes the three scalars of each sample straight into column j.
+
+        t_chunk (extension; 1 = the reference's loop exactly): K timesteps are stacked into one [K*N, ...] model call and one
+        kernel launch over K*N rows.  The K noises are still drawn one at a time in the reference's order; tensors in
+        model_kwargs whose leading dimension is N are repeated K times.  K need not divide T."""
+        T, N = self.num_timesteps, x_start.shape[0]
+        K = int(t_chunk)
+        if K < 1:
+            raise ValueError(f"t_chunk must be >= 1, got {t_chunk}")
+        K = min(K, T)
+        self._refuse_unsupported_mean_type()
+        mt, vt = self.model_mean_type, self.model_var_type
+        mean_mode = 1 if mt == ModelMeanType.PREVIOUS_X else 0
+        var_mode = {ModelVarType.LEARNED: 1, ModelVarType.LEARNED_RANGE: 2}.get(vt, 0)
+        model_kwargs = model_kwargs or {}
+        cpu_rng = getattr(self.args, "cpu_rng", False)
+        with torch.no_grad():
+            x_start = x_start.contiguous()
+            dev = x_start.device
+            tb = self._tables(dev)
+            rep = lambda v: v if K == 1 else v.repeat(K, *([1] * (v.dim() - 1)))
+            x0_rep = rep(x_start)
+            per_sample_kw = {k for k, v in model_kwargs.items() if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == N}
+            kw_rep = {k: rep(v) if k in per_sample_kw else v for k, v in model_kwargs.items()}
+            outs = tuple(torch.empty(N, T, device=dev, dtype=torch.float32) for _ in range(3))
+            for j0 in range(0, T, K):
+                k = min(K, T - j0)
+                noise = [torch.randn(x_start.shape, dtype=torch.float32).to(dev) if cpu_rng else torch.randn_like(x_start)
+                         for _ in range(k)]
+                noise = noise[0] if k == 1 else torch.cat(noise, dim=0)
+                t_rows = (T - 1 - j0 - torch.arange(k, device=dev)).repeat_interleave(N)
+                x0_k = x0_rep if k == K else x0_rep[: k * N]
+                kw_k = kw_rep if k == K else {kk: v[: k * N] if kk in per_sample_kw else v for kk, v in kw_rep.items()}
+                x_t = ops.qsample(x0_k, noise, t_rows, tb["a"], tb["s"])
+                mean_out, var_out = self._model_halves(model, x_t, t_rows, kw_k)
+                ops.bpd_terms(mean_out, var_out, x0_k, x_t, noise, self._sample_rows(t_rows), mean_mode, var_mode, clip_denoised,
+                              out=outs, col=j0, group=N)
+            prior = ops.prior_bpd(x_start, *self._prior_coefs())
+            vb, xstart_mse, mse = outs
+            return {"total_bpd": vb.sum(dim=1) + prior, "prior_bpd": prior, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+        """x_{t+1} from x_t along the deterministic DDIM ODE (reference :653-689): {"sample", "pred_xstart"}."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        return self._reverse_step(3, model, x, t, clip_denoised, denoised_fn, None, model_kwargs)
+
+    def ddim_reverse_sample_loop_progressive(self, model, x_start, clip_denoised=True, model_kwargs=None, progress=False):
+        """Extension (the reference has only the step): walk t = 0 .. T-1 from data towards noise, yielding each step."""
+        indices = list(range(self.num_timesteps))
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        x = x_start
+        for i in indices:
+            t = torch.full((x.shape[0],), i, device=x.device, dtype=torch.long)
+            with torch.no_grad():
+                out = self.ddim_reverse_sample(model, x, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)
+                yield out
+                x = out["sample"]
+
+    def ddim_reverse_sample_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, progress=False):
+        """Extension: DDIM inversion of x_start, the final `sample` of the t = 0 .. T-1 walk (the latent x_T)."""
+        final = None
+        for final in self.ddim_reverse_sample_loop_progressive(model, x_start, clip_denoised, model_kwargs, progress):
+            pass
+        return final["sample"]
+
     def _vb_terms_bpd(self, mean_out, var_out, x_start, x_t, t, scale=1.0):
         """reference :775-808 on the fused kernel.  mean_out / var_out: the two halves of the model output."""
+        self._refuse_unsupported_mean_type()
         mt, vt = self.model_mean_type, self.model_var_type
-        if mt == ModelMeanType.VELOCITY:
-            # the reference gathers with t.shape in _predict_xstart_from_v (:394-399) and cannot broadcast
-            raise RuntimeError("VELOCITY with a variational-bound term: the reference's _predict_xstart_from_v fails to broadcast")
-        if mt not in (ModelMeanType.EPSILON, ModelMeanType.START_X, ModelMeanType.PREVIOUS_X):
-            raise NotImplementedError(mt)
         var_mode = {ModelVarType.LEARNED: 1, ModelVarType.LEARNED_RANGE: 2}.get(vt, 0)
         coef = self._tables(x_start.device)["vb"][t]
         return ops.vb_terms(mean_out, var_out, x_start, x_t, coef, 1 if mt == ModelMeanType.PREVIOUS_X else 0, var_mode, scale)

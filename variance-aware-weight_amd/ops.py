@@ -138,6 +138,90 @@ def sample_step(kind, mean_out, var_out, x, noise, coef, mean_mode, var_mode, cl
     return res
 
 
+def _dense_rows(t, n):
+    """f32 [B, ...] tensor -> (tensor, elements between row starts).  A tensor whose rows are dense but further apart
+    than their length (one half of a [B, 2C, H, W] model output split along dim 1) is read in place; anything else that
+    is not contiguous is copied."""
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.shape[0] == 1 or t.is_contiguous():
+        return t.contiguous(), n
+    if t[0].is_contiguous() and t.stride(0) >= n:
+        return t, t.stride(0)
+    return t.contiguous(), n
+
+
+def _model_halves(mean_out, var_out, n):
+    mean_out, ld = _dense_rows(mean_out, n)
+    if var_out is not None:
+        var_out, ldv = _dense_rows(var_out, n)
+        if ldv != ld:
+            mean_out, var_out, ld = mean_out.contiguous(), var_out.contiguous(), n
+    return mean_out, var_out, ld
+
+
+def bpd_terms(mean_out, var_out, x0, x_t, noise, coef, mean_mode, var_mode, clip_denoised, out=None, col=0, group=None):
+    """The three per-sample scalars of one calc_bpd_loop timestep (vaw_bpd_terms): returns (vb, xstart_mse, mse).
+    out=None: three new [B] vectors.  Otherwise out = three f32 [N, T] tensors of equal strides with unit column stride,
+    group = N and B = K*N stacked rows (K timesteps of the N samples): row b fills out[.][b % N, col + b // N]."""
+    need_cuda(mean_out, var_out, x0, x_t, noise, coef)
+    _f32c(x0, x_t, noise, coef)
+    B = x0.shape[0]
+    n = x0.numel() // max(B, 1)
+    if not (mean_out.shape == x0.shape == x_t.shape == noise.shape and coef.shape == (B, 16)):
+        raise L.VawError(f"bpd_terms: shapes {tuple(mean_out.shape)} {tuple(x0.shape)} {tuple(x_t.shape)} {tuple(noise.shape)} "
+                         f"coef {tuple(coef.shape)} do not agree")
+    if var_out is not None and var_out.shape != x0.shape:
+        raise L.VawError(f"bpd_terms: var_out shape {tuple(var_out.shape)} != {tuple(x0.shape)}")
+    mean_out, var_out, ld = _model_halves(mean_out, var_out, n)
+    if out is None:
+        res = tuple(torch.empty(B, device=x0.device, dtype=torch.float32) for _ in range(3))
+        ptrs, out_ld, group = [ptr(r) for r in res], 1, B
+    else:
+        res = tuple(out)
+        group = B if group is None else int(group)
+        k = B // group if group > 0 else 0
+        for r in res:
+            need_cuda(r)
+            if not (r.dtype == torch.float32 and r.dim() == 2 and r.shape[0] == group and r.stride(1) == 1 and
+                    r.stride(0) == res[0].stride(0) and r.stride(0) >= r.shape[1] and group * k == B and
+                    0 <= col and col + k <= r.shape[1]):
+                raise L.VawError(f"bpd_terms: output {tuple(r.shape)} strides {r.stride()} cannot take {B} rows in groups of "
+                                 f"{group} from column {col}")
+        ptrs, out_ld = [r.data_ptr() + 4 * col for r in res], res[0].stride(0)
+    check(L.lib().vaw_bpd_terms(ptr(mean_out), ptr(var_out), ld, ptr(x0), ptr(x_t), ptr(noise), ptr(coef), int(mean_mode),
+                                int(var_mode), 1 if clip_denoised else 0, ptrs[0], ptrs[1], ptrs[2], out_ld, group, B, n,
+                                stream_ptr()), "vaw_bpd_terms")
+    return res
+
+
+def prior_bpd(x0, sqrt_abar_last, log_one_minus_abar_last):
+    """KL(q(x_T | x_0) || N(0, I)) in bits/dim per sample (vaw_prior_bpd)."""
+    need_cuda(x0)
+    _f32c(x0)
+    B = x0.shape[0]
+    out = torch.empty(B, device=x0.device, dtype=torch.float32)
+    check(L.lib().vaw_prior_bpd(ptr(x0), float(sqrt_abar_last), float(log_one_minus_abar_last), ptr(out), B,
+                                x0.numel() // max(B, 1), stream_ptr()), "vaw_prior_bpd")
+    return out
+
+
+def ddim_reverse_step(mean_out, x, coef, clip_denoised):
+    """One step of the DDIM ODE towards noise (vaw_ddim_reverse_step, eta = 0): {"sample", "pred_xstart"}."""
+    need_cuda(mean_out, x, coef)
+    x = x.contiguous().float()
+    coef = coef.contiguous()
+    B = x.shape[0]
+    n = x.numel() // max(B, 1)
+    if not (mean_out.shape == x.shape and coef.shape == (B, 16) and coef.dtype == torch.float32):
+        raise L.VawError(f"ddim_reverse_step: shapes {tuple(mean_out.shape)} {tuple(x.shape)} coef {tuple(coef.shape)} do not agree")
+    mean_out, _, ld = _model_halves(mean_out, None, n)
+    res = {"sample": torch.empty_like(x), "pred_xstart": torch.empty_like(x)}
+    check(L.lib().vaw_ddim_reverse_step(ptr(mean_out), ld, ptr(x), ptr(coef), 1 if clip_denoised else 0, ptr(res["sample"]),
+                                        ptr(res["pred_xstart"]), B, n, stream_ptr()), "vaw_ddim_reverse_step")
+    return res
+
+
 # ---- dense -------------------------------------------------------------------------------------
 def gemm(dt, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, Cp, ldc, *, bias=None, act=0, aux_in=None, aux_out=None,
          gate=None, gate_ld=0, resid=None, rowadd=None, rows_per_batch=0, alpha=1.0, beta=0.0, out_f32=False,

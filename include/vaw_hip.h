@@ -530,6 +530,35 @@ int vaw_cast_bf16(const float* src, void* dst, int64_t n, vaw_stream stream);
  * collective summed.  src and dst 16-byte aligned. */
 int vaw_uncast_bf16(const void* src, float* dst, int64_t n, float scale, vaw_stream stream);
 
+/* ---- activation workspace of the DiT engine (dit.py: _Workspace) -------------------------------------------------------------
+ * The one place the engine's buffer sizes are decided (pure host arithmetic: no device call, so it can be asked without a GPU).
+ * dtype = the act dtype; B images of T tokens (M = B * T rows), hidden D, MLP width Dm, `depth` blocks, `heads` heads, patch
+ * embedding K = Kp, final layer N = No.  defer_wgrad: the caller wants the blocks' weight gradients as grouped launches (granted
+ * for bf16 with M % 64 == 0: own_dy says so).  checkpoint = 0: every block keeps a record of its own from forward to backward.
+ * checkpoint = 1 (activation recomputation): a block keeps only its input row of the f32 residual stream; ONE record is shared by
+ * all blocks, refilled by re-running a block's forward right before its backward.
+ *   one record = the act-dtype rows xm, qkv, ao, y1, xm2, hpre, a, y2 ((8 D + 2 Dm) per token), lse and the four LayerNorm
+ *   statistics rows (f32), and with own_dy the dy operands dy2, dDm, dy1, dqkv ((5 D + Dm) per token) of the grouped launch.
+ * VAW_ERR_INVALID (with a message) for a dtype other than VAW_F32 / VAW_BF16, a size <= 0, D % heads != 0 or a flag not 0 / 1. */
+typedef struct {
+    int records;                /* block records allocated: depth, or 1 with checkpoint */
+    int colsum_sets;            /* sets of bias-gradient partial buffers: depth, or 1 with checkpoint (a block folds its own before the next runs) */
+    int own_dy;                 /* 1: a record carries its four dy operands (grouped weight gradients) */
+    int Bk;                     /* batch rows of the conditioning path's GEMM operands: B, for bf16 padded to the next multiple of 64 */
+    int64_t block_bytes;        /* [M, *] rows ONE block keeps resident from its forward to its backward (x depth): its record's
+                                 * rows + both of its residual-stream rows, or with checkpoint the input row alone (4 D per token) */
+    int64_t block_stat_bytes;   /* the lse and statistics rows ONE block keeps (0 with checkpoint) */
+    int64_t shared_bytes;       /* checkpoint: the shared record, its xres_mid row and the scratch row fc2's residual output goes to
+                                 * when a block is recomputed; 0 otherwise */
+    int64_t colsum_bytes;       /* all sets of partial column sums */
+    int64_t scratch_bytes;      /* backward scratch shared by all blocks (with checkpoint and own_dy: without dDm, dqkv, dyb --
+                                 * the shared record's dy operands serve) */
+    int64_t cond_bytes;         /* conditioning path, patch embedding, final layer and the last residual-stream row */
+    int64_t total;              /* depth * (block_bytes + block_stat_bytes) + shared + colsum + scratch + cond */
+} vaw_dit_ws_plan_t;
+int vaw_dit_ws_plan(int dtype, int B, int T, int D, int Dm, int depth, int heads, int Kp, int No, int defer_wgrad, int checkpoint,
+                    vaw_dit_ws_plan_t* out);
+
 /* ---- gradient-bucket collectives straight on RCCL ------------------------------------------------
  * Replaces the bucket all-reduce torch DDP does for the reference (main.py:347; process group set up in tools/dist_util.py:55).
  * One communicator per process (= per GPU) with a side HIP stream of its own; RCCL is opened with dlopen at the first call

@@ -38,6 +38,12 @@ class AttnLaunch(C.Structure):
                 ("lds_cap_raised", _i), ("colsum_rows", _l), ("status", _i)]
 
 
+class DitWsPlan(C.Structure):
+    """vaw_dit_ws_plan_t of include/vaw_hip.h: the byte sizes of the DiT engine's activation workspace."""
+    _fields_ = [("records", _i), ("colsum_sets", _i), ("own_dy", _i), ("Bk", _i), ("block_bytes", _l), ("block_stat_bytes", _l),
+                ("shared_bytes", _l), ("colsum_bytes", _l), ("scratch_bytes", _l), ("cond_bytes", _l), ("total", _l)]
+
+
 # vaw_attn_dir / vaw_attn_variant
 ATTN_FWD, ATTN_BWD, ATTN_BWD_COLSUM = range(3)
 (AV_ROWWISE, AV_FWD_T64, AV_FWD_G1, AV_FWD_G2, AV_FWD_BIG, AV_BWD_T64, AV_BWD_G1, AV_BWD_G2, AV_BWD_BIG_NT2,
@@ -123,6 +129,7 @@ _PROTOS = {
     "vaw_gate_bwd_fp8": [_p, _p, _p, _l, _p, _p, _i, _p, _l, _p, _i, _i, _i, _p, _l, _p],
     "vaw_row_plan": [_i, _i, _l, _l, _l, _l, _l, _l, C.POINTER(RowLaunch)],
     "vaw_attn_plan": [_i, _i, C.POINTER(AttnDesc), _l, _l, _l, _l, _l, _l, _l, C.POINTER(AttnLaunch)],
+    "vaw_dit_ws_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(DitWsPlan)],
 }
 
 _lib = None

@@ -108,38 +108,68 @@ class _FinalLayer(_Holder):
 
 
 class _Workspace:
-    """Activation buffers for one batch size; reused every step (no allocator traffic in the loop)."""
+    """Activation buffers for one batch size; reused every step (no allocator traffic in the loop).  How many block records
+    there are, whether they carry their dy operands and how many bytes all of it takes is decided by ops.dit_ws_plan
+    (vaw_dit_ws_plan); the allocations below are checked against its total."""
 
     def __init__(self, m, B, adt):
         dev = m._flat.device
         f32, T, D, Lyr = torch.float32, m.T, m.D, m.depth
         M = B * T
-        e = lambda *s, dtype=adt: torch.empty(*s, device=dev, dtype=dtype)
+        self._bufs = []             # every buffer the workspace owns (nbytes)
+
+        def e(*s, dtype=adt):
+            t = torch.empty(*s, device=dev, dtype=dtype)
+            self._bufs.append(t)
+            return t
+
         self.B, self.adt, self.gen = B, adt, 0
+        self.fp8 = bool(m._fp8)
+        self.ckpt = ckpt = bool(m.activation_checkpointing)
+        # (fp8 mode keeps transposed fp8 copies instead of dy operands, on top of what the plan counts)
+        self.plan = plan = ops.dit_ws_plan(m._dt, B, T, D, m.Dm, Lyr, m.num_heads, m.Kp, m.No, bool(m.defer_wgrad) and not self.fp8, ckpt)
         # The conditioning path's weight gradients are dy^T x products with K = BATCH.  The MFMA GEMMs take K in whole 64s, so the
         # bf16 operands of those products (tfreq, h1s, cs here; dmod_a, dc_a, dh1_a below) carry zero rows up to the next multiple of
         # 64: nothing ever writes them, the products run with K = Bk on the MFMA kernels instead of the generic one (32 images per
         # GPU: 0.19 ms of the 4.5 ms step), and the bias gradients (column sums) still walk the first B rows only.
-        self.Bk = Bk = ((B + 63) // 64) * 64 if adt == torch.bfloat16 else B
-        z = lambda cols: torch.zeros(Bk, cols, device=dev, dtype=adt)
+        self.Bk = Bk = plan.Bk
+
+        def z(cols):
+            t = torch.zeros(Bk, cols, device=dev, dtype=adt)
+            self._bufs.append(t)
+            return t
+
         self.tfreq, self.h1, self.h1s = z(256), e(B, D, dtype=f32), z(D)
         self.temb, self.c, self.cs = e(B, D, dtype=f32), e(B, D, dtype=f32), z(D)
         self.mod = e(B, m.mod_cols, dtype=f32)
         self.xp = e(M, m.Kp)
-        self.xres = [e(M, D, dtype=f32) for _ in range(2 * Lyr + 1)]   # inputs of LN1/LN2 of each block, + final
-        self.blk = [dict(xm=e(M, D), qkv=e(M, 3 * D), ao=e(M, D), lse=e(B * m.num_heads * T, dtype=f32), y1=e(M, D),
-                         xm2=e(M, D), hpre=e(M, m.Dm), a=e(M, m.Dm), y2=e(M, D),
-                         mean1=e(M, dtype=f32), rstd1=e(M, dtype=f32), mean2=e(M, dtype=f32), rstd2=e(M, dtype=f32))
-                    for _ in range(Lyr)]
+        record = lambda: dict(xm=e(M, D), qkv=e(M, 3 * D), ao=e(M, D), lse=e(B * m.num_heads * T, dtype=f32), y1=e(M, D),
+                              xm2=e(M, D), hpre=e(M, m.Dm), a=e(M, m.Dm), y2=e(M, D),
+                              mean1=e(M, dtype=f32), rstd1=e(M, dtype=f32), mean2=e(M, dtype=f32), rstd2=e(M, dtype=f32))
+        if ckpt:
+            # activation recomputation: a block keeps its input row only; ONE record, one xres_mid row, and a scratch row that takes
+            # fc2's residual output when a block is re-run in backward (the next block's input row must survive it)
+            rows = [e(M, D, dtype=f32) for _ in range(Lyr + 1)]
+            mid, self.xscr = e(M, D, dtype=f32), e(M, D, dtype=f32)
+            self.xres = [rows[i // 2] if i % 2 == 0 else mid for i in range(2 * Lyr + 1)]
+            self.blk = [record()] * Lyr
+        else:
+            self.xres = [e(M, D, dtype=f32) for _ in range(2 * Lyr + 1)]   # inputs of LN1/LN2 of each block, + final
+            self.blk = [record() for _ in range(Lyr)]
+        assert len({id(b) for b in self.blk}) == plan.records
         self.xf, self.meanf, self.rstdf = e(M, D), e(M, dtype=f32), e(M, dtype=f32)
         self.otok = e(M, m.No, dtype=f32)
         # backward scratch (shared by all blocks)
         self.dotok, self.dres, self.dD = e(M, m.No), e(M, D, dtype=f32), e(M, D)
-        self.dDm, self.dqkv, self.dao = e(M, m.Dm), e(M, 3 * D), e(M, D)
         # deferred weight gradients (bf16 mode): every block keeps the four dy operands of its Linear layers until ONE grouped
-        # launch at the end of backward consumes them (226 MB per DiT-B/4 block at batch 256; sized for 288 GB of HBM)
-        self.fp8 = bool(m._fp8)
-        self.defer = (bool(m.defer_wgrad) or self.fp8) and adt == torch.bfloat16 and M % 64 == 0
+        # launch at the end of backward consumes them (226 MB per DiT-B/4 block at batch 256; sized for 288 GB of HBM) -- or, with
+        # activation recomputation, the shared record keeps them until the block's own grouped launch right after its backward
+        self.defer = bool(plan.own_dy) or (self.fp8 and M % 64 == 0)
+        if ckpt and plan.own_dy:
+            self.dDm = self.dqkv = self.dyb = None      # the shared record's dy operands serve
+        else:
+            self.dDm, self.dqkv = e(M, m.Dm), e(M, 3 * D)
+        self.dao = e(M, D)
         if self.fp8:
             # per block: the transposed fp8 copies the grouped weight gradients read (x^T and dy^T, [features][M]); the row-major
             # copies live in a shared scratch just long enough for the GEMM that follows the quantiser
@@ -152,24 +182,37 @@ class _Workspace:
                 F = lambda i, cols: ops.Fp8(M, cols, dev, transposed=True, plain=False, fmt=fmts[i], state=self.fp8_states[8 * l + i])
                 b.update(f_xm=F(0, D), f_ao=F(1, D), f_xm2=F(2, D), f_a=F(3, m.Dm), f_dy2=F(4, D), f_dhid=F(5, m.Dm), f_dy1=F(6, D),
                          f_dqkv=F(7, 3 * D))
-        elif self.defer:
-            for b in self.blk:
+        elif plan.own_dy:
+            for b in self.blk[:plan.records]:
                 b.update(dy2=e(M, D), dDm=e(M, m.Dm), dy1=e(M, D), dqkv=e(M, 3 * D))
         self.wgrad_groups = {}
         # bias gradients: the kernels that produce dy leave partial column sums per block (gate backward: one row per sample;
         # fc2's GELU' epilogue: one per 64 or 128 token rows; attention backward: one per sample and 64-token block); ONE batched fold
-        # per group of blocks turns them into the four bias gradients of every block (ops.ReduceGroup)
+        # per group of blocks turns them into the four bias gradients of every block (ops.ReduceGroup).  With activation
+        # recomputation a block folds its own right after its backward, so all blocks share one set
         self.bias_groups = {}
-        for b in self.blk:
-            b.update(cp_fc2=ops.ColsumPartial(B, D, dev), cp_proj=ops.ColsumPartial(B, D, dev),
-                     cp_fc1=ops.ColsumPartial((M + 63) // 64, m.Dm, dev), cp_qkv=ops.ColsumPartial(max(B, M // 64), 3 * D, dev))
-            b["cp_fc2"].rows.value = b["cp_proj"].rows.value = B
-        self.dyb = e(M, D)          # dy of a gated branch when the block keeps no buffer of its own (f32 / fp8 / per-layer wgrad modes)
+
+        def cp_set():
+            cps = dict(fc2=ops.ColsumPartial(B, D, dev), proj=ops.ColsumPartial(B, D, dev),
+                       fc1=ops.ColsumPartial((M + 63) // 64, m.Dm, dev), qkv=ops.ColsumPartial(max(B, M // 64), 3 * D, dev))
+            cps["fc2"].rows.value = cps["proj"].rows.value = B
+            self._bufs += [c.buf for c in cps.values()]
+            return cps
+
+        self.cp = [cp_set()] * Lyr if ckpt else [cp_set() for _ in range(Lyr)]
+        if not (ckpt and plan.own_dy):
+            self.dyb = e(M, D)      # dy of a gated branch when the block keeps no buffer of its own (f32 / fp8 / per-layer wgrad modes)
         self.delta = e(B * m.num_heads * T, dtype=f32)
         self.dmod, self.dmod_a = e(B, m.mod_cols, dtype=f32), z(m.mod_cols)
         self.dcs, self.dc, self.dc_a = e(B, D, dtype=f32), e(B, D, dtype=f32), z(D)
         self.dh1s, self.dh1, self.dh1_a = e(B, D, dtype=f32), e(B, D, dtype=f32), z(D)
         self.dxp = e(M, m.Kp, dtype=f32)
+        if not self.fp8 and self.nbytes() != plan.total:
+            raise L.VawError(f"DiT workspace: allocated {self.nbytes()} bytes, vaw_dit_ws_plan says {plan.total}")
+
+    def nbytes(self):
+        """Bytes of the workspace's buffers (not the launch descriptor tables of the cached groups, nor the fp8 copies)."""
+        return sum(t.numel() * t.element_size() for t in self._bufs)
 
 
 class _DiTFn(torch.autograd.Function):
@@ -185,6 +228,9 @@ class _DiTFn(torch.autograd.Function):
         m = ctx.model
         if m._ws_cur.gen != ctx.gen:
             raise L.VawError("DiT backward: activations were overwritten by a later forward of the same batch size")
+        if m._ws_cur.ckpt != bool(m.activation_checkpointing):
+            raise L.VawError("DiT backward: activation_checkpointing was switched between this forward and its backward "
+                             "(the workspace of the forward was laid out for the other mode)")
         dx = m._backward_impl(dout.contiguous(), ctx.need_dx)
         return torch.zeros_like(m._anchor), None, dx, None, None
 
@@ -192,7 +238,7 @@ class _DiTFn(torch.autograd.Function):
 class DiT(FlatModule):
     def __init__(self, image_size=32, patch_size=2, in_channels=4, hidden_size=1152, depth=28, num_heads=16,
                  mlp_ratio=4.0, class_dropout_prob=0.1, num_classes=1000, learn_sigma=False, learn_align=False,
-                 encoder_depth=8, z_dims=768, projector_dim=2048, compute_dtype="bf16"):
+                 encoder_depth=8, z_dims=768, projector_dim=2048, compute_dtype="bf16", activation_checkpointing=False):
         super().__init__()
         if learn_align:
             raise NotImplementedError("learn_align (REPA feature alignment) is outside the hot path (SURVEY §2.1 row 12)")
@@ -227,9 +273,12 @@ class DiT(FlatModule):
         self.fp8_fuse_epilogue = os.environ.get("VAW_FP8_FUSE", "1") != "0"
         self.fp8_fuse_rows = os.environ.get("VAW_FP8_FUSE_ROWS", "1") != "0"      # ... and LN-modulate / gate backward their outputs
         self._fp8_w, self._fp8_epoch, self._fp8_wstates, self._fp8_wgroup = {}, None, None, None
+        self.activation_checkpointing = False
         self.set_compute_dtype(compute_dtype)
         self._anchor = torch.zeros(1, requires_grad=True)
         self._ws, self._ws_cur = {}, None
+        self.set_activation_checkpointing(activation_checkpointing)
+        self._ckpt_debug_hook = None     # callable(l, record) -> None, right after block l was recomputed in backward (tests)
         self.grad_ready_hook = None      # callable(stage:int) -> None; stage counts down from depth+1 to 0
         # bf16 mode: the weight gradients of the blocks' Linear layers are deferred and run as grouped launches
         # (vaw_wgrad_grouped): one for all blocks at the end of backward, or two (upper / lower half of the blocks) when a
@@ -269,12 +318,26 @@ class DiT(FlatModule):
             raise ValueError(f"compute_dtype must be 'bf16', 'fp32' or 'fp8', got {name}")
         if name == "fp8" and (self.D % 128 or self.Dm % 128):
             raise ValueError("compute_dtype='fp8' needs hidden and MLP widths that are multiples of 128 (one fp8 MFMA K tile)")
+        if name == "fp8" and getattr(self, "activation_checkpointing", False):
+            raise ValueError(self._CKPT_FP8)
         if name != getattr(self, "compute_dtype", name):
             self.require_fresh_masters("set_compute_dtype()")      # (every other mode derives its weights from the f32 masters)
         self.compute_dtype = name
         self._dt = F32 if name == "fp32" else BF16
         self._fp8 = name == "fp8"
         self._fp8_w, self._fp8_epoch, self._fp8_wstates, self._fp8_wgroup = {}, None, None, None
+        self._ws = {}
+
+    _CKPT_FP8 = ("activation_checkpointing does not combine with compute_dtype='fp8': re-running a block's forward would update its "
+                 "delayed-scaling state twice per step, and the per-block transposed fp8 copies would have to be shared too")
+
+    def set_activation_checkpointing(self, on):
+        """Activation recomputation: a block keeps only its input row of the residual stream; backward re-runs each block's
+        forward into one record shared by all blocks right before that block's backward.  Drops the workspaces."""
+        on = bool(on)
+        if on and self._fp8:
+            raise ValueError(self._CKPT_FP8)
+        self.activation_checkpointing = on
         self._ws = {}
 
     def _flat_groups(self):
@@ -367,7 +430,8 @@ class DiT(FlatModule):
             if (B * self.T) % 128:
                 raise L.VawError("compute_dtype='fp8': batch * tokens must be a multiple of 128 (K tile of the weight gradients)")
             self._refresh_fp8_weights()
-        key = (B, adt, self._fp8)
+        # (the layout also depends on the two modes the plan takes: a workspace built for another one is never picked up)
+        key = (B, adt, self._fp8, bool(self.activation_checkpointing), bool(self.defer_wgrad))
         if key not in self._ws:
             self._ws[key] = _Workspace(self, B, adt)
         self._ws_cur = ws = self._ws[key]
@@ -448,30 +512,8 @@ class DiT(FlatModule):
                  bias=self._p32("x_embedder.proj.bias"), rowadd=self._p32("pos_embed"), rows_per_batch=T, out_f32=True)
         mod = ptr(ws.mod)
         for l in range(Lyr):
-            b, pre = ws.blk[l], f"blocks.{l}."
-            mo = mod + 4 * (6 * l * D)
-            xin, xmid, xout = ptr(ws.xres[2 * l]), ptr(ws.xres[2 * l + 1]), ptr(ws.xres[2 * l + 2])
             self._need(l + 1)
-            fuse_rows = ws.fp8 and ws.d_fwd and self.fp8_fuse_epilogue and self.fp8_fuse_rows and M % 64 == 0 and D % 128 == 0    # LN writes fp8 itself
-            if fuse_rows:
-                ops.ln_modulate_fwd_fp8(xin, mo, mo + 4 * D, ld, b["f_xm"], ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
-            else:
-                ops.ln_modulate_fwd(dt, xin, mo, mo + 4 * D, ld, ptr(b["xm"]), ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
-            self._linear_fwd(ws, b, "f_xm", None if fuse_rows else b["xm"], pre + "attn.qkv.", M, 3 * D, D, ptr(b["qkv"]), 3 * D)
-            q = ptr(b["qkv"])
-            es = self._wsize
-            ops.attn_fwd(dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(b["lse"]))
-            self._linear_fwd(ws, b, "f_ao", b["ao"], pre + "attn.proj.", M, D, D, xmid, D, aux_out=ptr(b["y1"]), gate=mo + 4 * 2 * D,
-                             gate_ld=ld, resid=xin, rows_per_batch=T, out_f32=True)
-            if fuse_rows:
-                ops.ln_modulate_fwd_fp8(xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, b["f_xm2"], ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
-            else:
-                ops.ln_modulate_fwd(dt, xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, ptr(b["xm2"]), ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
-            fuse_a = ws.fp8 and ws.d_fwd and self.fp8_fuse_epilogue and M % 64 == 0      # fc1's epilogue writes `a` as e4m3 itself
-            self._linear_fwd(ws, b, "f_xm2", None if fuse_rows else b["xm2"], pre + "mlp.fc1.", M, Dm, D, b["f_a"].epilogue_target() if fuse_a else ptr(b["a"]), Dm,
-                             act=1, aux_out=ptr(b["hpre"]), **({"out_fp8": b["f_a"]} if fuse_a else {}))
-            self._linear_fwd(ws, b, "f_a", None if fuse_a else b["a"], pre + "mlp.fc2.", M, D, Dm, xout, D, aux_out=ptr(b["y2"]),
-                             gate=mo + 4 * 5 * D, gate_ld=ld, resid=xmid, rows_per_batch=T, out_f32=True)
+            self._block_fwd(ws, l)
         mo = mod + 4 * (6 * Lyr * D)
         self._need(Lyr + 1)
         ops.ln_modulate_fwd(dt, ptr(ws.xres[2 * Lyr]), mo, mo + 4 * D, ld, ptr(ws.xf), ptr(ws.meanf), ptr(ws.rstdf), B, T, D)
@@ -482,6 +524,39 @@ class DiT(FlatModule):
         if ws.fp8:
             ws.calib_fwd = True
         return out
+
+    def _block_fwd(self, ws, l, xout=None):
+        """Forward of block l from its input row ws.xres[2l] and the resident modulation into its record: seven launches (LN +
+        modulate, qkv, attention, proj + gated residual, LN + modulate, fc1 + GELU, fc2 + gated residual).  _forward_impl runs it
+        for every block; with activation recomputation _backward_impl runs it again right before the block's backward, with fc2's
+        residual output sent to the scratch row `xout` -- the kernels are deterministic, so the record is refilled bit for bit."""
+        B, dt, D, T, Dm, ld = ws.B, self._dt, self.D, self.T, self.Dm, self.mod_cols
+        M = B * T
+        b, pre = ws.blk[l], f"blocks.{l}."
+        mo = ptr(ws.mod) + 4 * (6 * l * D)
+        xin, xmid = ptr(ws.xres[2 * l]), ptr(ws.xres[2 * l + 1])
+        if xout is None:
+            xout = ptr(ws.xres[2 * l + 2])
+        fuse_rows = ws.fp8 and ws.d_fwd and self.fp8_fuse_epilogue and self.fp8_fuse_rows and M % 64 == 0 and D % 128 == 0    # LN writes fp8 itself
+        if fuse_rows:
+            ops.ln_modulate_fwd_fp8(xin, mo, mo + 4 * D, ld, b["f_xm"], ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
+        else:
+            ops.ln_modulate_fwd(dt, xin, mo, mo + 4 * D, ld, ptr(b["xm"]), ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
+        self._linear_fwd(ws, b, "f_xm", None if fuse_rows else b["xm"], pre + "attn.qkv.", M, 3 * D, D, ptr(b["qkv"]), 3 * D)
+        q = ptr(b["qkv"])
+        es = self._wsize
+        ops.attn_fwd(dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(b["lse"]))
+        self._linear_fwd(ws, b, "f_ao", b["ao"], pre + "attn.proj.", M, D, D, xmid, D, aux_out=ptr(b["y1"]), gate=mo + 4 * 2 * D,
+                         gate_ld=ld, resid=xin, rows_per_batch=T, out_f32=True)
+        if fuse_rows:
+            ops.ln_modulate_fwd_fp8(xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, b["f_xm2"], ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
+        else:
+            ops.ln_modulate_fwd(dt, xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, ptr(b["xm2"]), ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
+        fuse_a = ws.fp8 and ws.d_fwd and self.fp8_fuse_epilogue and M % 64 == 0      # fc1's epilogue writes `a` as e4m3 itself
+        self._linear_fwd(ws, b, "f_xm2", None if fuse_rows else b["xm2"], pre + "mlp.fc1.", M, Dm, D, b["f_a"].epilogue_target() if fuse_a else ptr(b["a"]), Dm,
+                         act=1, aux_out=ptr(b["hpre"]), **({"out_fp8": b["f_a"]} if fuse_a else {}))
+        self._linear_fwd(ws, b, "f_a", None if fuse_a else b["a"], pre + "mlp.fc2.", M, D, Dm, xout, D, aux_out=ptr(b["y2"]),
+                         gate=mo + 4 * 5 * D, gate_ld=ld, resid=xmid, rows_per_batch=T, out_f32=True)
 
     def _linear_fwd(self, ws, b, fkey, x, name, M, N, K, out, ldc, **epi):
         """y = x W^T + bias with the block's epilogue: bf16 / f32 MFMA GEMM, or (fp8 mode) quantise x (keeping x^T for the weight
@@ -539,12 +614,20 @@ class DiT(FlatModule):
         self._gbase = self.flat_grads().data_ptr()
         hook = self.grad_ready_hook
         ada_half = self._ada_split_block() if hook else None      # early adaLN bucket only when somebody listens (DDP)
+        # (ws.dDm / ws.dqkv / ws.dyb are None, and ptr() of them 0, when the shared record carries its own dy operands: activation
+        # recomputation in the deferred mode.  They are read only on the `not own_dy` side below, which that mode never takes.)
         dres, dD, dDm, dmod = ptr(ws.dres), ptr(ws.dD), ptr(ws.dDm), ptr(ws.dmod)
         mod = ptr(ws.mod)
         es = self._wsize
         defer = ws.defer and dt == BF16
         fp8 = ws.fp8
         own_dy = defer and not fp8            # every block keeps its four dy operands for the grouped weight-gradient launch
+        # activation recomputation: block l's record is refilled (_block_fwd) at the top of its iteration below.  The fused
+        # LayerNorm-backward + gate-backward pass hands block l+1's residual gradient to block l's MLP branch and reads y2 of block l
+        # together with the statistics of block l+1 -- two blocks' records at once, which the shared record cannot hold.  So with the
+        # flag on that hand-off runs as the unfused pair (bitwise the same results): LayerNorm backward of block l+1, recompute of
+        # block l, gate backward of block l.  The weight gradients of a block then run right after its own backward.
+        ckpt = ws.ckpt
         # fp8, delayed scaling: the row kernels write dy as fp8 themselves
         fuse_rows = fp8 and ws.d_bwd and self.fp8_fuse_epilogue and self.fp8_fuse_rows and M % 64 == 0 and D % 128 == 0
 
@@ -559,7 +642,7 @@ class DiT(FlatModule):
             nb = ws.blk[l2]
             mo2, dmo2 = mod + 4 * (6 * l2 * D), dmod + 4 * (6 * l2 * D)
             gcol = 5 if which == "mlp" else 2
-            y, cp = (nb["y2"], nb["cp_fc2"]) if which == "mlp" else (nb["y1"], nb["cp_proj"])
+            y, cp = (nb["y2"], ws.cp[l2]["fc2"]) if which == "mlp" else (nb["y1"], ws.cp[l2]["proj"])
             if fuse_rows:
                 ops.ln_modulate_bwd_gate_fp8(dout_p, x_p, mean_p, rstd_p, scale_p, ld, dres_in, dres, dsh, dsc, ld, ptr(y),
                                              mo2 + 4 * gcol * D, nb["f_dy2" if which == "mlp" else "f_dy1"], dmo2 + 4 * gcol * D,
@@ -575,7 +658,7 @@ class DiT(FlatModule):
         ops.gemm(dt, 1, 0, M, D, self.No, ptr(ws.dotok), self.No, self._w("final_layer.linear.weight"), D, dD, D)
         mo, dmo = mod + 4 * (6 * Lyr * D), dmod + 4 * (6 * Lyr * D)
         ln_bwd_and_gate(dD, ptr(ws.xres[2 * Lyr]), ptr(ws.meanf), ptr(ws.rstdf), mo + 4 * D, 0, dmo, dmo + 4 * D,
-                        (Lyr - 1, "mlp") if Lyr else None)
+                        (Lyr - 1, "mlp") if (Lyr and not ckpt) else None)
         if hook:
             hook(Lyr + 1)
         pending = []                      # blocks whose weight gradients wait for the next grouped launch
@@ -586,9 +669,9 @@ class DiT(FlatModule):
             key = (blocks[0], blocks[-1], self._gbase, qkv_too)
             cps = []
             for l in blocks:
-                b, pre = ws.blk[l], f"blocks.{l}."
-                names = [("cp_fc2", "mlp.fc2."), ("cp_fc1", "mlp.fc1."), ("cp_proj", "attn.proj.")] + ([("cp_qkv", "attn.qkv.")] if qkv_too else [])
-                cps += [(b[key_cp], pre + nm) for key_cp, nm in names]
+                cp, pre = ws.cp[l], f"blocks.{l}."
+                names = [("fc2", "mlp.fc2."), ("fc1", "mlp.fc1."), ("proj", "attn.proj.")] + ([("qkv", "attn.qkv.")] if qkv_too else [])
+                cps += [(cp[key_cp], pre + nm) for key_cp, nm in names]
             # the number of partial rows a producer leaves is NOT a function of the shape alone: vaw_gemm writes one row per 64, 128
             # or 256 rows of C depending on the kernel it picks (which moves with the CUs reserved for a collective, with
             # vaw_debug_gemm_tile, ...), the attention backward one per 64 / 128 / 256 query rows by VAW_ATTN_BWD_BIG.  The device
@@ -629,18 +712,23 @@ class DiT(FlatModule):
             pending.clear()
 
         for l in reversed(range(Lyr)):
-            b, pre = ws.blk[l], f"blocks.{l}."
+            b, cp, pre = ws.blk[l], ws.cp[l], f"blocks.{l}."
             mo, dmo = mod + 4 * (6 * l * D), dmod + 4 * (6 * l * D)
             xin, xmid = ptr(ws.xres[2 * l]), ptr(ws.xres[2 * l + 1])
             dy2, dhid, dy1, dq = ((ptr(b["dy2"]), ptr(b["dDm"]), ptr(b["dy1"]), ptr(b["dqkv"])) if own_dy
                                   else (ptr(ws.dyb), dDm, ptr(ws.dyb), ptr(ws.dqkv)))
+            if ckpt:
+                self._block_fwd(ws, l, xout=ptr(ws.xscr))
+                if self._ckpt_debug_hook is not None:
+                    self._ckpt_debug_hook(l, b)
+                ops.gate_bwd(dt, dres, ptr(b["y2"]), mo + 4 * 5 * D, ld, dy2, dmo + 4 * 5 * D, ld, B, T, D, cp["fc2"].buf.data_ptr())
             # MLP branch.  dy2, dgate and the partial column sums of dy2 (fc2's bias gradient) came out of the row kernel that
             # produced this block's incoming residual gradient; bias gradients are folded per group (fold_bias)
             if not defer:
                 self._wgrad(dt, pre + "mlp.fc2.", dy2, ptr(b["a"]), D, Dm, M, beta, bias=False)
             fuse_dh = fp8 and ws.d_bwd and self.fp8_fuse_epilogue and M % 64 == 0       # fc2's input-gradient epilogue writes dhid as fp8
             self._linear_dgrad(ws, b, "f_dy2", None if fuse_rows else dy2, pre + "mlp.fc2.", M, D, Dm, b["f_dhid"].epilogue_target() if fuse_dh else dhid, act=2,
-                               aux_in=ptr(b["hpre"]), colsum_partial=b["cp_fc1"], **({"out_fp8": b["f_dhid"]} if fuse_dh else {}))
+                               aux_in=ptr(b["hpre"]), colsum_partial=cp["fc1"], **({"out_fp8": b["f_dhid"]} if fuse_dh else {}))
             if not defer:
                 self._wgrad(dt, pre + "mlp.fc1.", dhid, ptr(b["xm2"]), Dm, D, M, beta, bias=False)
             self._linear_dgrad(ws, b, "f_dhid", None if (fp8 and fuse_dh) else dhid, pre + "mlp.fc1.", M, Dm, D, dD)
@@ -653,20 +741,21 @@ class DiT(FlatModule):
             qkv_bias_folded = False
             if defer:      # the qkv bias gradient = column sums of dqkv: partial rows from the attention kernels where they offer it
                 qkv_bias_folded = ops.attn_bwd_colsum(dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(ws.dao),
-                                                      ptr(b["lse"]), ptr(ws.delta), dq, dq + es * D, dq + 2 * es * D, b["cp_qkv"])
+                                                      ptr(b["lse"]), ptr(ws.delta), dq, dq + es * D, dq + 2 * es * D, cp["qkv"])
             if not qkv_bias_folded:
                 ops.attn_bwd(dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(ws.dao), ptr(b["lse"]),
                              ptr(ws.delta), dq, dq + es * D, dq + 2 * es * D)
                 if defer:
-                    ops.colsum(dt, dq, M, 3 * D, 3 * D, b["cp_qkv"].buf.data_ptr(), 0.0, device=dout.device)     # one complete row
-                    b["cp_qkv"].rows.value = 1
+                    ops.colsum(dt, dq, M, 3 * D, 3 * D, cp["qkv"].buf.data_ptr(), 0.0, device=dout.device)     # one complete row
+                    cp["qkv"].rows.value = 1
                 else:      # (the per-layer launch takes the bias gradient from its staged dy tiles)
                     self._wgrad(dt, pre + "attn.qkv.", dq, ptr(b["xm"]), 3 * D, D, M, beta)
             self._linear_dgrad(ws, b, "f_dqkv", dq, pre + "attn.qkv.", M, 3 * D, D, dD)
-            ln_bwd_and_gate(dD, xin, ptr(b["mean1"]), ptr(b["rstd1"]), mo + 4 * D, dres, dmo, dmo + 4 * D, (l - 1, "mlp") if l else None)
+            ln_bwd_and_gate(dD, xin, ptr(b["mean1"]), ptr(b["rstd1"]), mo + 4 * D, dres, dmo, dmo + 4 * D,
+                            (l - 1, "mlp") if (l and not ckpt) else None)
             if defer:
                 pending.append(l)
-                if l == group_cut:
+                if ckpt or l == group_cut:      # (recomputation: the operands are gone once the next block is re-run)
                     pending.reverse()
                     flush()
             else:

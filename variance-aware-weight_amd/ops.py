@@ -684,6 +684,14 @@ def attn_plan(direction, dt, desc, q, k, v, o_or_do, dq=0, dk=0, dv=0):
     return p
 
 
+def dit_ws_plan(dt, B, T, D, Dm, depth, heads, Kp, No, defer_wgrad=True, checkpoint=False):
+    """Byte sizes of the DiT engine's activation workspace for these sizes (vaw_dit_ws_plan: host arithmetic, no GPU):
+    what one block keeps resident, the record all blocks share under activation checkpointing, backward scratch, the total."""
+    p = L.DitWsPlan()
+    check(L.lib().vaw_dit_ws_plan(dt, B, T, D, Dm, depth, heads, Kp, No, int(defer_wgrad), int(checkpoint), C.byref(p)), "vaw_dit_ws_plan")
+    return p
+
+
 def attn_fwd(dt, desc, q, k, v, o, lse):
     check(L.lib().vaw_attn_fwd(dt, C.byref(desc), q, k, v, o, lse, stream_ptr()), "vaw_attn_fwd")
 

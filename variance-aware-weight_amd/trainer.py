@@ -67,6 +67,15 @@ class Trainer:
             want = low if args.amp else "fp32"
             if inner.compute_dtype != want:
                 inner.set_compute_dtype(want)
+        # args.activation_checkpointing (optional, default off; an extension): the DiT recomputes each block's activations in
+        # backward instead of keeping them (dit.py).  The UNets' use_checkpoint stays a no-op, which is numerically what the
+        # reference's flag does
+        ckpt = getattr(args, "activation_checkpointing", None)      # absent: the model stays as it was built (default: off)
+        if ckpt is not None and hasattr(inner, "set_activation_checkpointing"):
+            if inner.activation_checkpointing != bool(ckpt):
+                inner.set_activation_checkpointing(ckpt)
+        elif ckpt:
+            raise ValueError(f"args.activation_checkpointing: {type(inner).__name__} has no activation recomputation (the DiT models do)")
         if hasattr(inner, "host_dropout_rng"):
             inner.host_dropout_rng = bool(getattr(args, "cpu_rng", False))      # dropout masks from the CPU stream in parity runs
         self._fused = isinstance(optimizer, FusedAdamW)

@@ -240,10 +240,72 @@ int vaw_fp8_transpose(const void* q, int64_t R, int64_t C, int64_t ldq, void* qt
 /* Keep n CUs out of every persistent-GEMM grid from now on (0 = none): for the time a kernel of another stream (a collective)
  * holds CUs of its own -- a persistent workgroup cannot share its CU, and a grid that does not fit runs a second pass. */
 void vaw_p8_set_reserved_cus(int n);
-/* 1 when vaw_gemm would run these operands on the bf16 MFMA kernel (M%128==0, N%128==0, K%64==0, 16-byte
- * aligned rows), 0 when it takes the exact-f32 generic kernel.  For measurement and tests. */
+/* 1 when these operands can go to a bf16 MFMA kernel: dt = bf16, M >= 16, N >= 16 (any M and N: edge tiles are predicated),
+ * N % 8 == 0, K % 64 == 0, lda % 8 == 0, ldb % 8 == 0, A and B 16-byte aligned, and vaw_debug_force_generic_gemm off.  0: the
+ * exact-f32 generic kernel.  The OPERAND half of the rule only: vaw_gemm also sends a launch to the generic kernel when C or an
+ * epilogue operand is not 16-byte aligned, ldc % 8 != 0, gate_ld % 4 != 0, or A is stored [K][M] with M % 8 != 0 -- ask
+ * vaw_gemm_plan for the kernel a whole call gets.  For measurement and tests. */
 int vaw_gemm_uses_bf16_mfma(vaw_dtype dt, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
                             int64_t ldb);
+
+/* Launch plan of vaw_gemm: the one host function it takes every launch choice from (pure arithmetic, so it can be asked without
+ * a GPU).  A / B / C are the addresses vaw_gemm would be given and the pointers of `epi_host` are used for null-ness and alignment
+ * only (colsum_rows_out is read: the stated capacity); workspace_floats = 0 stands for a NULL workspace.
+ * knobs: NULL = the process's own -- the environment, read once on first use (VAW_GEMM_BIG, _BK, _PD, _WS, _XCDSPLIT, _EPI, _DEBUG,
+ * VAW_SM_MAX_M, _WIDE_M, _NB, _STAGES, VAW_WS_LOADERS, VAW_P8_NT, _NT_AUX: DESIGN.md lists them), vaw_debug_gemm_tile /
+ * vaw_debug_force_generic_gemm, and the CUs the persistent kernels may use now; or an explicit set (cus <= 0: the process's). */
+typedef struct {
+    int tile;           /* vaw_debug_gemm_tile / VAW_GEMM_BIG: -1 by shape, 0 128 x 128, 1 256 x 256 ring, 2 / 3 persistent with 256 / 192
+                         * columns, 4 persistent (width by shape), 5-8 small-M ring (by shape / 64 x 64 / 64 x 128 / 128 x 128),
+                         * 9 / 10 / 11 parked-drain and 12 / 13 / 14 warp-specialised (width by shape / 256 / 192) wherever they apply */
+    int force_generic;  /* vaw_debug_force_generic_gemm */
+    int bk;             /* VAW_GEMM_BK: 32 / 64 pins the 128 x 128 kernel's stage depth (and keeps the other MFMA kernels out); 0 by shape */
+    int pd, ws;         /* VAW_GEMM_PD / _WS: parked-drain / warp-specialised kernel by shape (default 0) */
+    int xcdsplit;       /* VAW_GEMM_XCDSPLIT: K-range-per-XCD mapping of split-K 128 x 128 launches (default 1) */
+    int sm_max_m, sm_wide_m, sm_nb, sm_stages;   /* VAW_SM_*: small-M ring kernel up to this M (8192), 128 x 128 tiles up to this M
+                                                  * (0 = off), tile columns / 64 and ring depth (0 = by shape) */
+    int ws_loaders;     /* VAW_WS_LOADERS: 8 = eight loader waves for the 192-column warp-specialised kernel (default 4) */
+    int epi, debug;     /* VAW_GEMM_EPI (1: register-direct epilogue), VAW_GEMM_DEBUG: kernel flags, no launch choice */
+    int p8_nt, nt_aux;  /* VAW_P8_NT (0), VAW_P8_NT_AUX (1): store cache policy of the persistent kernels, no launch choice */
+    int cus;            /* CUs the persistent / parked-drain / warp-specialised grids may use */
+} vaw_gemm_knobs;
+void vaw_gemm_default_knobs(vaw_gemm_knobs* out);   /* every knob at its default (no environment), 256 CUs */
+typedef enum {
+    VAW_GV_GENERIC = 0,        /* gemm_generic_kernel: any shape, alignment, dtype; exact f32 */
+    VAW_GV_T128_BK32 = 1,      /* gemm_bf16_kernel<.., 32, 0>: 128 x 128 tiles */
+    VAW_GV_T128_BK64 = 2,      /* gemm_bf16_kernel<.., 64, 0> */
+    VAW_GV_RING256 = 3,        /* gemm_bf16_big_kernel: 256 x 256 tiles */
+    VAW_GV_PERSISTENT = 4,     /* gemm_p8_kernel<.., ntw, epi_kind>: 256 x 64 ntw tiles */
+    VAW_GV_SMALL_M = 5,        /* gemm_sm_kernel<.., nb, stages, mb>: 64 mb x 64 nb tiles */
+    VAW_GV_PARKED_DRAIN = 6,   /* gemm_pd_kernel<.., ntw, epi_kind>: 128 x 64 ntw tiles */
+    VAW_GV_WARP_SPEC = 7       /* gemm_ws_kernel<.., ntw, epi_kind>: 128 x 64 ntw tiles */
+} vaw_gemm_variant;
+typedef enum { VAW_GR_NONE = 0, VAW_GR_F32 = 1, VAW_GR_BF16 = 2, VAW_GR_F32_ROWSUM = 3 } vaw_gemm_reduce;    /* splitk_reduce_kernel */
+typedef enum { VAW_GS_NONE = 0, VAW_GS_FUSED = 1, VAW_GS_SEPARATE = 2 } vaw_gemm_rowsum_mode;
+typedef enum { VAW_GC_NONE = 0, VAW_GC_FOLD = 1, VAW_GC_DEFERRED = 2, VAW_GC_SEPARATE = 3 } vaw_gemm_colsum_mode;
+typedef struct {
+    int variant;                    /* vaw_gemm_variant */
+    int ntw;                        /* persistent / parked-drain / warp-specialised: tile columns / 64 (3 | 4); else 0 */
+    int mb, nb, stages;             /* small-M ring: tile rows / 64, tile columns / 64, ring depth; else 0 */
+    int bkt;                        /* K depth of one stage: 16 generic, 32 / 64 128 x 128, 32 ring, 64 the others */
+    int epi_kind;                   /* persistent / parked-drain / warp-specialised: the P8_* epilogue kind (gemm_epi.h); else -1 */
+    int split;                      /* K splits (1 = none) */
+    int xcd_parts;                  /* 8 / split for the 128 x 128 kernel's K-range-per-XCD mapping, else 0 */
+    int grid_x, grid_y, grid_z, block;
+    int64_t lds_bytes;              /* dynamic LDS of the launch (generic: its static LDS) */
+    int reduce;                     /* vaw_gemm_reduce: the pass over the split-K slabs (F32_ROWSUM: it also folds the row sums of A) */
+    int rowsum_mode;                /* vaw_gemm_rowsum_mode: rowsum_a_out on the MFMA kernel, or a vaw_colsum pass over A */
+    int colsum_mode;                /* vaw_gemm_colsum_mode: partial rows folded by vaw_reduce_rows, left to the caller
+                                     * (colsum_partial_out), or a vaw_colsum pass over C (generic kernel) */
+    int64_t colsum_rows;            /* partial rows of column sums the launch writes (0 without column sums) */
+    int64_t workspace_floats_used;  /* slabs [split][M][N], then row-sum partials [split][M]; column-sum rows [colsum_rows][N]
+                                     * from 0 (never with slabs); a separate pass reuses the workspace after them (the rows are folded first) */
+    int launches;                   /* kernels enqueued, passes included */
+    int status;                     /* vaw_status: VAW_OK, or what vaw_gemm returns before launching anything */
+} vaw_gemm_launch;
+int vaw_gemm_plan(vaw_dtype dt, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                  int64_t ldc, int64_t A, int64_t B, int64_t C, const vaw_epilogue* epi_host, int64_t workspace_floats,
+                  const vaw_gemm_knobs* knobs, vaw_gemm_launch* out);
 
 /* out[n] = beta*out[n] + sum_m X[m,n]  (bias gradients). X act dtype, out f32.  Two fixed-order stages through a
  * caller-provided f32 workspace of vaw_colsum_workspace_floats(M,N) elements: no atomics, bitwise reproducible. */

@@ -426,6 +426,9 @@ def test_gemm_colsum_partial_each_path(tile, M):
         torch.cuda.synchronize()
         R = part.rows.value
         assert 1 <= R <= cap, (tile, M, R)
+        plan = ops.gemm_plan(BF16, 1, 0, M, N, K, ptr(Ad), K, ptr(Bd), N, ptr(out), N, colsum_partial_rows=cap,
+                             workspace_floats=ops.scratch_f32(out.device, 0).numel())       # the workspace ops.gemm passed
+        assert R == plan.colsum_rows, (tile, M, R, plan.colsum_rows, plan.variant)
         assert bool((big[R:] == CANARY).all()), (tile, M, R, "rows beyond the reported count were written")
         assert not bool((big[:R] == CANARY).any())
         torch.testing.assert_close(big[:R].double().sum(0).cpu(), out.double().sum(0).cpu(), rtol=1e-5, atol=2e-2)

@@ -787,3 +787,302 @@ def test_attn_plan_pins_production_shapes():
                 assert (got_f, got_b) == _PINNED_ATTN[T, hd], (m, H, T, hd)
                 assert fwd.grid_y == bwd.grid_y == B * H
                 assert bwd.colsum_rows == (0 if T % 64 else B if T == 64 else B * T // (64 * (1 if got_b[0] == "bwd_g1" else 2)))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Launch plan of vaw_gemm (vaw_gemm_plan: host arithmetic only, vaw_gemm takes every launch choice from it)
+# ------------------------------------------------------------------------------------------------------------------------------
+_GEMM_WS = 1 << 26          # floats of the grow-only scratch ops.gemm hands to vaw_gemm
+_GEMM_ADDR = 1 << 20
+# tile rows per partial row of column sums, dynamic LDS and workgroup size of each variant (csrc/gemm_plan.h and the kernels)
+_GEMM_CS_ROWS = {"t128_bk32": 128, "t128_bk64": 128, "ring256": 256, "persistent": 128, "parked_drain": 64, "warp_spec": 64}
+
+
+def _gemm_lds(name, p):
+    return {"generic": 2 * 16 * 144 * 4, "t128_bk32": 64 * 132 * 4 + 2048, "t128_bk64": 4 * 128 * 64 * 2 + 2048,
+            "ring256": 4 * 32768 + 8192, "persistent": 2 * (4 + p.ntw) * 8192 + 32768, "small_m": p.stages * (p.mb + p.nb) * 8192,
+            "parked_drain": 3 * (2 + p.ntw) * 8192 + 16384, "warp_spec": 3 * (2 + p.ntw) * 8192}[name]
+
+
+def _gemm_epilogues(M, N):
+    """name -> (epilogue keywords, wants a colsum_partial capacity, the smallest workspace the call can need)"""
+    a = _GEMM_ADDR
+    slabs, cs = 2 * M * N, -(-M // 128) * N
+    return {"plain_f32": (dict(out_f32=True), False, slabs), "plain_bf16": ({}, False, slabs),
+            "bias_gelu_aux": (dict(bias=a, act=1, aux_out=a), False, 0),
+            "gate_resid": (dict(bias=a, aux_out=a, gate=a, gate_ld=N, resid=a, rows_per_batch=8, out_f32=True), False, 0),
+            "colsum_out": (dict(colsum_out=a), False, cs), "colsum_partial": ({}, True, cs),
+            "rowsum_a_out": (dict(rowsum_a_out=a, out_f32=True), False, 64 * M),
+            # both at once: the column-sum rows are folded before the separate row-sum pass takes the workspace over (vaw_gemm)
+            "rowsum_colsum": (dict(rowsum_a_out=a, colsum_out=a, out_f32=True), False, max(64 * M, cs))}
+
+
+def _check_gemm_plan(p, L, dt, ak, bk, M, N, K, off, epi, cap, ws, knobs, seen):
+    """the invariants of one planned launch; -> its variant name"""
+    name = L.GV_NAMES[p.variant]
+    ctx = (name, dt, ak, bk, M, N, K, off, sorted(epi), cap, ws, knobs.tile)
+    lda, ldb = (K if ak else M), (K if bk else N)
+    es = 2 if dt == L.BF16 else 4
+    colsum, rowsum = bool(epi.get("colsum_out")) or cap is not None, bool(epi.get("rowsum_a_out"))
+    if name != "generic":       # the preconditions of the MFMA kernels
+        assert dt == L.BF16 and not knobs.force_generic and N % 8 == 0 and K % 64 == 0 and lda % 8 == 0 and ldb % 8 == 0, ctx
+        assert off == 0 and M >= 16 and N >= 16 and (ak or M % 8 == 0) and N % 8 == 0 and epi.get("gate_ld", 0) % 4 == 0, ctx
+        assert (ak and not rowsum) if name in ("small_m", "parked_drain", "warp_spec") else True, ctx
+        if name in ("parked_drain", "warp_spec"):
+            assert K // 64 >= 12 and M >= 128 and p.split == 1 and p.epi_kind in (L.P8_STORE, L.P8_GELU, L.P8_DGELU, L.P8_GATE), ctx
+            assert (p.epi_kind == L.P8_DGELU) <= (not bk) and (p.epi_kind in (L.P8_GELU, L.P8_GATE)) <= bool(bk), ctx
+        if name == "persistent":
+            assert (p.epi_kind == L.P8_SLAB) == (p.split > 1) and 0 <= p.epi_kind <= L.P8_RESID and p.epi_kind != L.P8_WGRAD, ctx
+            seen.add(("persistent", p.epi_kind))
+        elif p.epi_kind >= 0:
+            seen.add((name, p.epi_kind))
+        assert (p.epi_kind >= 0) == (name in ("persistent", "parked_drain", "warp_spec")), ctx
+    assert p.lds_bytes == _gemm_lds(name, p) <= 160 * 1024, ctx
+    # tile parameters, grid and block
+    tiles = lambda bm, bn: -(-M // bm) * -(-N // bn)
+    if name == "generic":
+        assert (p.grid_x, p.grid_y, p.grid_z, p.block, p.bkt) == (-(-N // 128), -(-M // 128), p.split, 256, 16), ctx
+        nk = -(-K // 16)
+    elif name.startswith("t128"):
+        assert p.bkt == (32 if name == "t128_bk32" else 64) and p.block == 256, ctx
+        want = (8 * -(-tiles(128, 128) // p.xcd_parts), 1) if p.xcd_parts else (tiles(128, 128), p.split)
+        assert (p.grid_x, p.grid_y, p.grid_z) == want + (1,), ctx
+        nk = K // p.bkt
+    elif name == "ring256":
+        assert (p.grid_x, p.grid_y, p.grid_z, p.block, p.bkt) == (tiles(256, 256), p.split, 1, 512, 32), ctx
+        nk = K // 32
+    elif name == "small_m":
+        assert (p.mb, p.nb) in ((1, 1), (1, 2), (2, 2)) and p.stages in (3, 4) and p.split == 1 and p.block == 256, ctx
+        assert (p.grid_x, p.grid_y, p.grid_z) == (tiles(64 * p.mb, 64 * p.nb), 1, 1), ctx
+        nk = K // 64
+    else:
+        bm = 256 if name == "persistent" else 128
+        assert p.ntw in (3, 4) and (p.grid_y, p.grid_z) == (1, 1), ctx
+        assert p.grid_x == min(tiles(bm, 64 * p.ntw) * p.split, knobs.cus), ctx
+        loaders = 8 if (p.ntw == 3 and knobs.ws_loaders == 8) else 4
+        assert p.block == (512 + 64 * loaders if name == "warp_spec" else 512), ctx
+        nk = K // 64
+    assert 0 < p.grid_x < 2 ** 31 and 0 < p.grid_y < 2 ** 31 and 0 < p.grid_z < 2 ** 31, ctx
+    assert (p.ntw != 0) == (name in ("persistent", "parked_drain", "warp_spec")) and (p.mb != 0) == (name == "small_m"), ctx
+    # split-K: no empty split, only where slabs can be reduced; the XCD mapping exactly where it applies
+    assert p.split >= 1 and -(-nk // -(-nk // p.split)) == p.split, ctx
+    xcd_on = name.startswith("t128") and knobs.xcdsplit and p.split in (2, 4, 8)
+    assert p.xcd_parts == (8 // p.split if xcd_on else 0), ctx
+    out_f32 = bool(epi.get("out_f32")) or dt == L.F32
+    if p.split > 1:
+        assert not colsum and not (set(epi) & {"bias", "act", "aux_out", "gate", "resid"}), ctx
+    assert p.reduce == (L.GR_NONE if p.split == 1 else L.GR_BF16 if not out_f32 else
+                        L.GR_F32_ROWSUM if p.rowsum_mode == L.GS_FUSED else L.GR_F32), ctx
+    # row sums of A, column sums of C
+    assert (p.rowsum_mode != L.GS_NONE) == rowsum and (p.rowsum_mode == L.GS_FUSED) <= (name.startswith("t128") and not ak), ctx
+    want_cs = L.GC_NONE if not colsum else L.GC_SEPARATE if name == "generic" else L.GC_DEFERRED if cap is not None else L.GC_FOLD
+    assert p.colsum_mode == want_cs, ctx
+    rows_per = 64 * p.mb if name == "small_m" else _GEMM_CS_ROWS.get(name)
+    assert p.colsum_rows == (0 if not colsum else 1 if name == "generic" else -(-M // rows_per)), ctx
+    # workspace: slabs, then row-sum partials; column-sum rows from 0, never with slabs; a pass reuses it afterwards
+    slab = p.split * M * N if p.split > 1 else 0
+    rowp = p.split * M if p.rowsum_mode == L.GS_FUSED else 0
+    fold = p.colsum_rows * N if p.colsum_mode == L.GC_FOLD else 0
+    assert not (fold and (slab or rowp)), ctx
+    passes = (p.rowsum_mode == L.GS_SEPARATE and not ak) + (p.colsum_mode == L.GC_SEPARATE)
+    assert p.workspace_floats_used >= slab + rowp + fold and (passes or p.workspace_floats_used == slab + rowp + fold), ctx
+    assert p.launches == 1 + (p.split > 1) + (p.rowsum_mode == L.GS_FUSED and p.split == 1) + (fold > 0) + 2 * passes, ctx
+    # the status: exactly the refusals the call earns
+    refused = (cap is not None and p.colsum_rows > cap) or (p.rowsum_mode == L.GS_SEPARATE and ak) or p.workspace_floats_used > ws
+    assert (p.status != 0) == bool(refused), ctx
+    seen.add(name)
+    return name
+
+
+def _sweep_gemm_plans(L, ops, knobs, dts, offs, wss, seen, Ms=(1, 15, 16, 64, 100, 128, 256, 2048, 4096, 8192, 16384, 32768)):
+    import ctypes as C
+    plan_fn, p = L.lib().vaw_gemm_plan, L.GemmLaunch()
+    n = 0
+    for M in Ms:
+        for N in (8, 16, 64, 192, 768, 1152, 2304, 3072):
+            for ename, (epi, partial, tight) in _gemm_epilogues(M, N).items():
+                caps = (None,) if not partial else (-(-M // 64), "below")
+                for dt in dts:
+                    for K in (4, 64, 768, 2048, 3072, 16384, 65536):
+                        for ak, bk in ((1, 1), (1, 0), (0, 0), (0, 1)):
+                            lda, ldb = (K if ak else M), (K if bk else N)
+                            for off in offs:
+                                for ws in wss:
+                                    if off not in (0, "A") and (dt != L.BF16 or ws != "ample"):
+                                        continue       # B, C and the epilogue operands off by 2 bytes: where an MFMA kernel was possible
+                                    ws = {"none": 0, "tight": tight, "ample": _GEMM_WS}[ws]
+                                    if "rowsum_a_out" in epi and ws < 64 * M:
+                                        continue       # refused before planning (test_gemm_plan_refusals)
+                                    if "colsum_out" in epi and ws < tight:
+                                        continue
+                                    addr = {o: _GEMM_ADDR + (2 if off == o else 0) for o in "ABC"}
+                                    epi_off = dict(epi)
+                                    if off == "epi":
+                                        first = next((f for f in ("bias", "aux_out", "gate", "resid") if f in epi), None)
+                                        if first is None:
+                                            continue
+                                        epi_off[first] = epi[first] + 2
+                                    for cap in caps:
+                                        if cap == "below":      # one row less than the launch just planned writes
+                                            if p.colsum_rows < 2 or p.status != 0:
+                                                continue
+                                            cap = p.colsum_rows - 1
+                                        p = ops.gemm_plan(dt, ak, bk, M, N, K, addr["A"], lda, addr["B"], ldb, addr["C"], N,
+                                                          workspace_floats=ws, knobs=knobs, colsum_partial_rows=cap, check_status=False,
+                                                          **epi_off)
+                                        _check_gemm_plan(p, L, dt, ak, bk, M, N, K, off, epi, cap, ws, knobs, seen)
+                                        n += 1
+    return n
+
+
+def test_gemm_plan_sweep_default_knobs():
+    """Every launch vaw_gemm_plan makes with the default knobs on 256 CUs, over the cross of sizes (multiples of no tile, of every
+    tile, beyond every threshold), the four layouts, both dtypes, aligned operands and A, B, C or an epilogue operand 2 bytes off, eight epilogues (colsum_partial with
+    capacity above and one row below need) and no / tight / ample workspace: each variant only where its kernel's preconditions
+    hold, LDS by the variant's formula and within 160 KiB, no empty split, the XCD mapping exactly where it applies, grids below
+    2^31, workspace regions within the workspace and disjoint, column-sum rows by the variant's tile rows, launches counted, and a
+    refusal exactly where capacity, layout or workspace earn one."""
+    from vaw_amd import _lib as L
+    from vaw_amd import ops
+    seen = set()
+    n = _sweep_gemm_plans(L, ops, ops.default_gemm_knobs(), (L.BF16, L.F32), (0, "A", "B", "C", "epi"), ("none", "tight", "ample"), seen)
+    assert n > 100000
+    # (the 256 x 256 ring is behind the persistent kernel in the order of preference: by shape it gets what that one declines, which
+    #  with these epilogues is nothing; the parked-drain and warp-specialised kernels are off by default: the knob sweep reaches them)
+    assert {"generic", "t128_bk32", "t128_bk64", "persistent", "small_m"} <= seen, seen
+    assert {("persistent", k) for k in (L.P8_STORE, L.P8_GELU, L.P8_GATE, L.P8_SLAB)} <= seen, seen
+
+
+_GEMM_KNOB_CASES = ([dict(tile=t) for t in (0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 13, 14)] +
+                    [dict(force_generic=1), dict(bk=32), dict(bk=64), dict(pd=1), dict(ws=1), dict(ws=1, ws_loaders=8), dict(ws=1, ws_loaders=5), dict(xcdsplit=0),
+                     dict(sm_max_m=2048), dict(sm_wide_m=4096), dict(sm_nb=2), dict(sm_stages=3), dict(cus=248), dict(tile=9), dict(tile=12)])
+
+def _gemm_plan_linear_layers(L, ops, knobs, seen):
+    """the launches of a DiT block's Linear layers (and a UNet skip add, a pos-embed row add, a weight gradient) at three sizes"""
+    a = _GEMM_ADDR
+    layers = ((1, 1, dict(bias=a)), (1, 1, dict(bias=a, act=1, aux_out=a)), (1, 0, dict(act=2, aux_in=a)), (1, 0, dict(act=2, aux_in=a, colsum_out=a)),
+              (1, 1, dict(bias=a, aux_out=a, gate=a, gate_ld=768, resid=a, rows_per_batch=64, out_f32=True)), (1, 0, {}),
+              (1, 1, dict(bias=a, resid=a, resid_is_act=True)), (1, 1, dict(bias=a, rowadd=a, rows_per_batch=8)), (0, 0, dict(out_f32=True)))
+    for M, N, K in ((256, 768, 768), (16384, 768, 3072), (32768, 3072, 768)):
+        for ak, bk, epi in layers:
+            p = ops.gemm_plan(L.BF16, ak, bk, M, N, K, a, K if ak else M, a, K if bk else N, a, N, workspace_floats=_GEMM_WS, knobs=knobs, **epi)
+            _check_gemm_plan(p, L, L.BF16, ak, bk, M, N, K, 0, epi, None, _GEMM_WS, knobs, seen)
+
+
+@pytest.mark.parametrize("case", _GEMM_KNOB_CASES, ids=lambda c: ",".join(f"{k}={v}" for k, v in c.items()))
+def test_gemm_plan_sweep_knobs(case):
+    """The same invariants with every vaw_debug_gemm_tile value the tests use and each knob at a non-default value (bf16, aligned:
+    the knobs act on the MFMA kernels only), on the sweep's shapes and on the launches of the Linear layers."""
+    from vaw_amd import _lib as L
+    from vaw_amd import ops
+    knobs, seen = ops.default_gemm_knobs(**case), set()
+    n = _sweep_gemm_plans(L, ops, knobs, (L.BF16,), (0,), ("none", "ample"), seen, Ms=(16, 100, 256, 2048, 4096, 16384, 32768))
+    assert n > 5000
+    _gemm_plan_linear_layers(L, ops, knobs, seen)
+
+
+def test_gemm_plan_reaches_every_variant_and_epilogue_kind():
+    """Over the knob cases, the Linear-layer launches reach every variant and every epilogue kind of the three kernels that
+    specialise on it."""
+    from vaw_amd import _lib as L
+    from vaw_amd import ops
+    seen = set()
+    for case in [{}] + _GEMM_KNOB_CASES:
+        _gemm_plan_linear_layers(L, ops, ops.default_gemm_knobs(**case), seen)
+    assert set(L.GV_NAMES) <= seen, seen
+    for name, kinds in (("persistent", (L.P8_STORE, L.P8_GELU, L.P8_DGELU, L.P8_GATE, L.P8_SLAB, L.P8_ANY, L.P8_RESID)),
+                        ("parked_drain", (L.P8_STORE, L.P8_GELU, L.P8_DGELU, L.P8_GATE)),
+                        ("warp_spec", (L.P8_STORE, L.P8_GELU, L.P8_DGELU, L.P8_GATE))):
+        assert {(name, k) for k in kinds} <= seen, (name, seen)
+
+
+def _gemm_kernel_name(L, name, p, dt, ak, bk):
+    """the kernel a variant launches, template arguments included, as a kernel trace spells it (prefix)"""
+    b = lambda v: "true" if v else "false"
+    return {"generic": "gemm_generic_kernel<float, %s, %s>" % (b(ak), b(bk)) if dt == L.F32 else "gemm_generic_kernel",
+            "t128_bk32": "gemm_bf16_kernel<%s, %s, 32, 0>" % (b(ak), b(bk)), "t128_bk64": "gemm_bf16_kernel<%s, %s, 64, 0>" % (b(ak), b(bk)),
+            "ring256": "gemm_bf16_big_kernel<%s, %s>" % (b(ak), b(bk)),
+            "persistent": "gemm_p8_kernel<%s, %s, %d, %d, " % (b(ak), b(bk), p.ntw, p.epi_kind),
+            "small_m": "gemm_sm_kernel<%s, %d, %d, %d>" % (b(bk), p.nb, p.stages, p.mb),
+            "parked_drain": "gemm_pd_kernel<%s, %d, %d>" % (b(bk), p.ntw, p.epi_kind),
+            "warp_spec": "gemm_ws_kernel<%s, %d, %d, %d>" % (b(bk), p.ntw, p.epi_kind, (p.block - 512) // 64)}[name]
+
+
+def test_gemm_plan_matches_recorded_launches():
+    """tests/golden/gemm_launches.json (GEMM_LAUNCHES.md) is a kernel trace of the commit BEFORE the plan existed: every distinct
+    vaw_gemm call of a training step of DiT-B/4 (batch 256, 32, 64), DiT-XL/2 and the 32 x 32 UNet, plus the calls by which the GPU
+    tests force each kernel.  For every entry the plan, with default knobs (the entry's forced tile) and 256 CUs, gives the recorded
+    kernel -- template arguments included: layout, stage depth, tile shape, ring depth, epilogue kind, loader waves --, grid and
+    workgroup size, and its passes account for every further kernel the call enqueued.  (The trace reports a kernel's static LDS
+    only: it is held where there is any, i.e. on the generic kernel.)"""
+    from vaw_amd import _lib as L
+    from vaw_amd import ops
+    rec = load_json("gemm_launches.json")["entries"]
+    assert len(rec) >= 150
+    seen = set()
+    for ent in rec:
+        c, ks = ent["call"], ent["kernels"]
+        epi = {f: _GEMM_ADDR for f in ("bias", "aux_in", "aux_out", "gate", "resid", "rowadd", "colsum_out", "rowsum_a_out") if c[f]}
+        epi.update({f: c[f] for f in ("act", "gate_ld", "rows_per_batch", "alpha", "beta", "out_f32", "colsum_beta", "resid_is_act",
+                                      "rowsum_a_beta")})
+        p = ops.gemm_plan(c["dt"], c["a_kmajor"], c["b_kmajor"], c["M"], c["N"], c["K"], _GEMM_ADDR + c["off"][0], c["lda"],
+                          _GEMM_ADDR + c["off"][1], c["ldb"], _GEMM_ADDR + c["off"][2], c["ldc"], workspace_floats=c["ws"],
+                          knobs=ops.default_gemm_knobs(tile=c["tile"]), colsum_partial_rows=c["colsum_partial_cap"], **epi)
+        name = L.GV_NAMES[p.variant]
+        ctx = (c, name, ks)
+        want = _gemm_kernel_name(L, name, p, c["dt"], c["a_kmajor"], c["b_kmajor"])
+        assert ks[0]["name"].startswith(want) if "<" in want else want in ks[0]["name"], ctx + (want,)
+        assert ks[0]["grid"] == [p.grid_x, p.grid_y, p.grid_z] and ks[0]["block"] == [p.block, 1, 1], ctx + (p.grid_x, p.grid_y, p.grid_z, p.block)
+        assert ks[0]["lds"] in (0, p.lds_bytes) and (name != "generic" or ks[0]["lds"] == p.lds_bytes), ctx + (p.lds_bytes,)
+        # the kernels behind it: the split-K reduce (by output type), the fold of the column-sum rows, the vaw_colsum passes
+        rest = [k["name"] for k in ks[1:]]
+        assert len(ks) == p.launches, ctx + (p.launches,)
+        reduces = [n for n in rest if "splitk_reduce_kernel" in n]
+        assert len(reduces) == (p.reduce != L.GR_NONE), ctx + (p.reduce,)
+        if reduces:
+            assert ("splitk_reduce_kernel<float>" in reduces[0]) == (p.reduce != L.GR_BF16), ctx + (p.reduce,)
+            assert ks[1]["name"] == reduces[0], ctx
+        assert sum("colsum_final_kernel" in n for n in rest) == (p.colsum_mode == L.GC_FOLD) + (p.rowsum_mode == L.GS_FUSED and p.split == 1) + \
+            (p.colsum_mode == L.GC_SEPARATE) + (p.rowsum_mode == L.GS_SEPARATE), ctx
+        seen.add(name if c["tile"] < 0 else name + "/forced")
+    # by shape, the training steps reach these; the other three kernels are reached through the tests' forced tiles
+    assert {"generic", "t128_bk32", "t128_bk64", "persistent", "small_m", "ring256/forced", "parked_drain/forced", "warp_spec/forced"} <= seen, seen
+
+
+def test_gemm_plan_refusals():
+    """Every argument check of vaw_gemm is the plan's: status VAW_ERR_INVALID with the reason, before anything could be launched."""
+    from vaw_amd import _lib as L
+    from vaw_amd import ops
+    a, k = _GEMM_ADDR, ops.default_gemm_knobs()
+
+    def refused(match, dt=L.BF16, ak=1, bk=1, M=256, N=256, K=256, A=a, lda=None, B=a, ldb=None, Cp=a, ldc=None, **kw):
+        p = ops.gemm_plan(dt, ak, bk, M, N, K, A, K if lda is None else lda, B, K if ldb is None else ldb, Cp, N if ldc is None else ldc,
+                          knobs=k, check_status=False, **kw)
+        assert p.status == -1 and match in L.lib().vaw_last_error_string().decode(), (match, p.status, L.lib().vaw_last_error_string())
+        with pytest.raises(vaw_amd.VawError, match=match):
+            ops.gemm_plan(dt, ak, bk, M, N, K, A, K if lda is None else lda, B, K if ldb is None else ldb, Cp, N if ldc is None else ldc,
+                          knobs=k, **kw)
+    for bad in (dict(M=0), dict(N=0), dict(K=0), dict(A=0), dict(B=0), dict(Cp=0)):
+        refused("bad sizes", **bad)
+    refused("must fit 31 bits", M=1 << 31, ak=1)
+    refused("must fit 31 bits", N=1 << 31, ldb=256, ldc=1 << 31)
+    refused("leading dimension too small", lda=255)
+    refused("leading dimension too small", ldb=255)
+    refused("leading dimension too small", ldc=255)
+    refused("leading dimension too small", ak=0, M=512, lda=256)
+    refused("excludes colsum_out", colsum_partial_rows=8, colsum_out=a, workspace_floats=_GEMM_WS)
+    refused("rowsum_a_out needs a workspace", ak=0, rowsum_a_out=a, out_f32=True)
+    refused("rowsum_a_out needs a workspace", ak=0, rowsum_a_out=a, out_f32=True, workspace_floats=64 * 256 - 1)
+    refused("unknown act", act=3)
+    refused("act=2 needs aux_in", act=2)
+    refused("need rows_per_batch", gate=a, gate_ld=256)
+    refused("need rows_per_batch", rowadd=a)
+    refused("beta needs f32 output", beta=1.0)
+    refused("colsum_out needs a workspace", colsum_out=a)
+    refused("colsum_out needs a workspace", colsum_out=a, workspace_floats=2 * 256 - 1)
+    refused("colsum_partial_out holds 3 rows, this launch writes 4", colsum_partial_rows=3)
+    refused("rowsum_a_out is defined for a_kmajor = 0", rowsum_a_out=a, out_f32=True, workspace_floats=_GEMM_WS)
+    refused("needs a workspace", dt=L.F32, colsum_partial_rows=8)          # generic kernel: the column sums are a pass of their own
+    refused("grid too large", M=(1 << 31) - 8, N=(1 << 31) - 8, K=64, lda=64, ldb=64, bias=a)
+    # and a call that passes them all
+    assert ops.gemm_plan(L.BF16, 1, 1, 256, 256, 256, a, 256, a, 256, a, 256, knobs=k).status == 0

@@ -38,6 +38,20 @@ class AttnLaunch(C.Structure):
                 ("lds_cap_raised", _i), ("colsum_rows", _l), ("status", _i)]
 
 
+class GemmKnobs(C.Structure):
+    """vaw_gemm_knobs of include/vaw_hip.h: the switches and the CU count vaw_gemm_plan decides by (default_gemm_knobs())."""
+    _fields_ = [(n, _i) for n in ("tile", "force_generic", "bk", "pd", "ws", "xcdsplit", "sm_max_m", "sm_wide_m", "sm_nb", "sm_stages",
+                                  "ws_loaders", "epi", "debug", "p8_nt", "nt_aux", "cus")]
+
+
+class GemmLaunch(C.Structure):
+    """vaw_gemm_launch of include/vaw_hip.h: the launch vaw_gemm_plan picks for a vaw_gemm call."""
+    _fields_ = [("variant", _i), ("ntw", _i), ("mb", _i), ("nb", _i), ("stages", _i), ("bkt", _i), ("epi_kind", _i), ("split", _i),
+                ("xcd_parts", _i), ("grid_x", _i), ("grid_y", _i), ("grid_z", _i), ("block", _i), ("lds_bytes", _l), ("reduce", _i),
+                ("rowsum_mode", _i), ("colsum_mode", _i), ("colsum_rows", _l), ("workspace_floats_used", _l), ("launches", _i),
+                ("status", _i)]
+
+
 class DitWsPlan(C.Structure):
     """vaw_dit_ws_plan_t of include/vaw_hip.h: the byte sizes of the DiT engine's activation workspace."""
     _fields_ = [("records", _i), ("colsum_sets", _i), ("own_dy", _i), ("Bk", _i), ("block_bytes", _l), ("block_stat_bytes", _l),
@@ -49,6 +63,14 @@ ATTN_FWD, ATTN_BWD, ATTN_BWD_COLSUM = range(3)
 (AV_ROWWISE, AV_FWD_T64, AV_FWD_G1, AV_FWD_G2, AV_FWD_BIG, AV_BWD_T64, AV_BWD_G1, AV_BWD_G2, AV_BWD_BIG_NT2,
  AV_BWD_BIG_NT4) = range(10)
 AV_NAMES = ("rowwise", "fwd_t64", "fwd_g1", "fwd_g2", "fwd_big", "bwd_t64", "bwd_g1", "bwd_g2", "bwd_big_nt2", "bwd_big_nt4")
+
+# vaw_gemm_variant / vaw_gemm_reduce / vaw_gemm_rowsum_mode / vaw_gemm_colsum_mode; the P8_* epilogue kinds of csrc/gemm_epi.h
+GV_GENERIC, GV_T128_BK32, GV_T128_BK64, GV_RING256, GV_PERSISTENT, GV_SMALL_M, GV_PARKED_DRAIN, GV_WARP_SPEC = range(8)
+GV_NAMES = ("generic", "t128_bk32", "t128_bk64", "ring256", "persistent", "small_m", "parked_drain", "warp_spec")
+GR_NONE, GR_F32, GR_BF16, GR_F32_ROWSUM = range(4)
+GS_NONE, GS_FUSED, GS_SEPARATE = range(3)
+GC_NONE, GC_FOLD, GC_DEFERRED, GC_SEPARATE = range(4)
+P8_STORE, P8_GELU, P8_DGELU, P8_GATE, P8_SLAB, P8_ANY, P8_WGRAD, P8_RESID = range(8)
 
 # vaw_row_kind / vaw_row_variant
 ROW_LN_FWD, ROW_LN_FWD_FP8, ROW_LN_BWD, ROW_GATE_BWD, ROW_GATE_BWD_FP8, ROW_LN_BWD_GATE, ROW_LN_BWD_GATE_FP8, ROW_COLSUM = range(8)
@@ -129,6 +151,7 @@ _PROTOS = {
     "vaw_gate_bwd_fp8": [_p, _p, _p, _l, _p, _p, _i, _p, _l, _p, _i, _i, _i, _p, _l, _p],
     "vaw_row_plan": [_i, _i, _l, _l, _l, _l, _l, _l, C.POINTER(RowLaunch)],
     "vaw_attn_plan": [_i, _i, C.POINTER(AttnDesc), _l, _l, _l, _l, _l, _l, _l, C.POINTER(AttnLaunch)],
+    "vaw_gemm_plan": [_i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _l, _l, C.POINTER(Epilogue), _l, C.POINTER(GemmKnobs), C.POINTER(GemmLaunch)],
     "vaw_dit_ws_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(DitWsPlan)],
 }
 
@@ -179,6 +202,9 @@ def lib():
         L.vaw_debug_force_generic_gemm.restype = None
         L.vaw_debug_gemm_tile.argtypes = [_i]
         L.vaw_debug_gemm_tile.restype = None
+        if hasattr(L, "vaw_gemm_default_knobs"):
+            L.vaw_gemm_default_knobs.argtypes = [C.POINTER(GemmKnobs)]
+            L.vaw_gemm_default_knobs.restype = None
         for dbg in ("vaw_debug_gn_coop", "vaw_debug_gn_flat"):      # absent from older measurement builds loaded through VAW_HIP_LIB
             if hasattr(L, dbg):
                 getattr(L, dbg).argtypes = [_i]
@@ -195,7 +221,8 @@ def exported_symbols():
     return sorted(list(_PROTOS) + ["vaw_version", "vaw_last_error_string", "vaw_colsum_workspace_floats",
                                    "vaw_sumsq_workspace_floats", "vaw_groupnorm_workspace_floats", "vaw_wgrad_grouped_desc_bytes",
                                    "vaw_conv3x3_wgrad_small_workspace_floats", "vaw_row_bwd_workspace_floats",
-                                   "vaw_fp8_quantize_workspace_floats", "vaw_p8_set_reserved_cus", "vaw_reduce_rows_batched_desc_bytes", "vaw_fp8_quantize_batched_desc_bytes"])
+                                   "vaw_fp8_quantize_workspace_floats", "vaw_p8_set_reserved_cus", "vaw_reduce_rows_batched_desc_bytes", "vaw_fp8_quantize_batched_desc_bytes",
+                                   "vaw_gemm_default_knobs"])
 
 
 def check(rc, what):

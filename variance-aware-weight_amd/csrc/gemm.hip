@@ -15,12 +15,10 @@
 //   16x16x32 bf16: lane l holds A[row l&15][k = 8(l>>4)+j], B[k = 8(l>>4)+j][col l&15], j=0..7
 //   16x16x4  f32 : lane l holds A[row l&15][k = l>>4],       B[k = l>>4][col l&15]
 //   C/D (both)   : col = l&15, row = 4(l>>4) + reg
-#include <stdlib.h>
-
 #include "common.h"
 #include <type_traits>
 
-#include "gemm_epi.h"
+#include "gemm_plan.h"
 
 // =============================================================================================
 // Fast path: bf16, M%128==0, N%128==0, K%64==0, 16-byte aligned rows.
@@ -723,415 +721,140 @@ gemm_generic_kernel(const T* __restrict__ A, int64_t lda, const T* __restrict__ 
             epi_store4<T>(e, m0 + wm + 16 * i + 4 * (lane >> 4), n0 + wn + 16 * j + (lane & 15), acc[i][j]);
 }
 
-// Shapes where the 256 x 256 kernel is the faster one (tools/gemm_bench.py --tile both: +4..16 % on 4096^3 / 8192^3,
-// slower whenever its grid leaves CUs idle or K is short): whole rounds of 256 workgroups, long K, no edge tiles.
-static bool big_tile_pays(int64_t M, int64_t N, int64_t K, int64_t n_wg_big) {
-    if (M % 256 || N % 256 || K < 2048 || n_wg_big < 256) return false;
-    const int64_t rounds = (n_wg_big + 255) / 256;
-    return rounds * 256 * 100 <= n_wg_big * 110;      // at most 10 % of the last round idle
-}
+// =============================================================================================
+// vaw_gemm: validate -> plan -> launch.  Every choice -- kernel, tile, split, grid, LDS, which passes follow -- is made by
+// vaw_gemm_plan (gemm_plan.hip); the code below only carries it out.
+// =============================================================================================
+static_assert(FastCfg<32>::lds_bytes == vaw_lds_t128(32) && FastCfg<64>::lds_bytes == vaw_lds_t128(64) && BIG_LDS == vaw_lds_ring256() &&
+              2 * GBK * GLD * 4 == vaw_lds_generic(), "gemm_plan.h: LDS sizes of the kernels in this file");
 
-// ---- the persistent 256-row-tile kernel (gemm_p8.hip) ----
-struct P8Plan {
-    bool use;
-    int ntw, split, grid;
-};
-P8Plan vaw_p8_plan(int64_t M, int64_t N, int64_t K, bool plain_f32, bool want_colsum, int64_t ws_floats, int force);
+// launchers of the other translation units: the tile parameters, epilogue kind and grid are the plan's
 void vaw_sm_launch(int mb, int nb, int stages, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda,
                    const bf16_t* b, int64_t ldb, const EpiDev& e, hipStream_t s);      // gemm_sm.hip
 bool vaw_p8_conv(int mode, const bf16_t* act, const bf16_t* act2, const bf16_t* w, void* out, int B, int H, int W, int Ci, int Co,
                  EpiDev e, float* workspace, int64_t workspace_floats, int force, hipStream_t s, float* bias_grad, float bias_beta,
                  int* bias_done);
-void vaw_p8_launch(const P8Plan& pl, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda,
+void vaw_p8_launch(const P8Plan& pl, int epi, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda,
                    const bf16_t* b, int64_t ldb, const EpiDev& e, hipStream_t s);
-
-// the parked-drain kernel (gemm_pd.hip)
-int vaw_pd_epi_kind(const EpiDev& e, bool a_kmajor, bool b_kmajor, int64_t M, int64_t N, int64_t K);
-int vaw_pd_pick_ntw(int64_t M, int64_t N, int cus_avail);
 void vaw_pd_launch(int ntw, int epi, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda, const bf16_t* b,
-                   int64_t ldb, const EpiDev& e, int cus_avail, hipStream_t s);
-int vaw_p8_cus_available();
-// the warp-specialised kernel (gemm_ws.hip)
+                   int64_t ldb, const EpiDev& e, int grid, hipStream_t s);
 void vaw_ws_launch(int ntw, int epi, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda, const bf16_t* b,
-                   int64_t ldb, const EpiDev& e, int cus, hipStream_t s);
+                   int64_t ldb, const EpiDev& e, int grid, bool loaders8, hipStream_t s);
 
-static int g_force_generic = 0;
-extern "C" void vaw_debug_force_generic_gemm(int on) { g_force_generic = on; }
-// bf16 MFMA tile choice: -1 = by shape (default), 0 = always 128 x 128, 1 = always the 256 x 256 ring kernel,
-// 2 / 3 = always the persistent kernel with 256 / 192 columns, 4 = always the persistent kernel (width by shape),
-// 5-8 = the small-M ring kernel, 9 / 10 / 11 = the parked-drain kernel wherever it applies (width by shape / 256 / 192 columns).
-// Env VAW_GEMM_BIG seeds it.
-static int g_gemm_tile = -2;
-extern "C" void vaw_debug_gemm_tile(int mode) { g_gemm_tile = mode; }
-
-static bool takes_fast_path(vaw_dtype dt, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B,
-                            int64_t ldb) {
-    // any M and N (edge tiles are predicated), as long as rows are whole 16-byte chunks
-    return dt == VAW_BF16 && !g_force_generic && N % 8 == 0 && K % BK == 0 && lda % 8 == 0 && ldb % 8 == 0 &&
-           (((uintptr_t)A | (uintptr_t)B) & 15) == 0 && M >= 16 && N >= 16;
-}
-static bool fast_layout_ok(int a_kmajor, int64_t M) { return a_kmajor || M % 8 == 0; }
-extern "C" int vaw_gemm_uses_bf16_mfma(vaw_dtype dt, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda,
-                                       const void* B, int64_t ldb) {
-    return takes_fast_path(dt, M, N, K, A, lda, B, ldb) ? 1 : 0;
+// the fixed-order pass over the split-K slabs (reduce: vaw_gemm_reduce; rowpart / rowsum_out: VAW_GR_F32_ROWSUM and conv3x3 mode 2)
+static void splitk_reduce(int reduce, const float* slab, int split, int64_t M, int64_t N, int64_t ldc, void* C, float alpha, float beta,
+                          hipStream_t s, const float* rowpart = nullptr, float* rowsum_out = nullptr, float rowsum_beta = 0.f) {
+    const int grid = ceil_div(M * N / 4, 256) > 2048 ? 2048 : ceil_div(M * N / 4, 256);
+    if (reduce == VAW_GR_BF16) splitk_reduce_kernel<bf16_t><<<grid, 256, 0, s>>>(slab, split, M, N, ldc, C, alpha, 0.f, 0);
+    else splitk_reduce_kernel<float><<<grid, 256, 0, s>>>(slab, split, M, N, ldc, C, alpha, beta, 1, rowpart, rowsum_out, rowsum_beta);
 }
 
-// Split-K factor: only for plain f32-output epilogues (the weight gradients: long K = B*T, few output tiles),
-// sized so the launch has ~2 workgroups per CU, each split keeping >= 256 of K, within the workspace.
-static int pick_split(int64_t tiles, int64_t K, int64_t MN, int64_t ws_floats, bool plain_f32) {
-    if (!plain_f32 || ws_floats <= 0) return 1;
-    int64_t s = 512 / tiles;
-    if (s > K / 256) s = K / 256;
-    if (s > ws_floats / MN) s = ws_floats / MN;
-    if (s > 64) s = 64;
-    return s < 2 ? 1 : (int)s;
+// A kernel has one instantiation per operand layout, tabled as [a_kmajor][b_kmajor]; each raises its dynamic-LDS cap on first use.
+template <typename Fn>
+static Fn by_layout(Fn const (&tab)[2][2], bool (&raised)[2][2], int a_kmajor, int b_kmajor, int lds) {
+    const int ak = a_kmajor != 0, bk = b_kmajor != 0;
+    if (lds > 0 && !raised[ak][bk]) {
+        (void)hipFuncSetAttribute((const void*)tab[ak][bk], hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        raised[ak][bk] = true;
+    }
+    return tab[ak][bk];
 }
+#define LAYOUT_TABLE(KERNEL, ...) \
+    {{KERNEL<false, false, ##__VA_ARGS__>, KERNEL<false, true, ##__VA_ARGS__>}, {KERNEL<true, false, ##__VA_ARGS__>, KERNEL<true, true, ##__VA_ARGS__>}}
 
-// rowsum_a_out without the fused path: A stored [K][M] (a_kmajor = 0) is a column sum over its K rows.
-static int rowsum_a_separate(vaw_dtype dt, int a_kmajor, int64_t M, int64_t K, const void* A, int64_t lda, float* out, float beta,
-                             float* workspace, int64_t workspace_floats, vaw_stream stream) {
-    VAW_CHECK_ARG(!a_kmajor, "gemm: rowsum_a_out is defined for a_kmajor = 0 (weight-gradient layout) only");
-    return vaw_colsum(dt, A, K, M, lda, out, beta, workspace, workspace_floats, stream);
+template <int BKT>
+static void launch_t128(const vaw_gemm_launch& p, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a,
+                        int64_t lda, const bf16_t* b, int64_t ldb, const EpiDev& e, hipStream_t s) {
+    using Fn = decltype(&gemm_bf16_kernel<true, true, BKT, 0>);
+    static const Fn tab[2][2] = LAYOUT_TABLE(gemm_bf16_kernel, BKT, 0);
+    static bool raised[2][2];
+    const int tiles_n = (int)((N + BN - 1) / BN), n_wg = (int)((M + BM - 1) / BM) * tiles_n;
+    by_layout(tab, raised, a_kmajor, b_kmajor, (int)p.lds_bytes)<<<dim3(p.grid_x, p.grid_y), p.block, p.lds_bytes, s>>>(
+        a, lda, b, ldb, (int)(K / BKT), tiles_n, n_wg, p.split, e, ConvGeom{}, p.xcd_parts);
 }
-
-// split-K launches whose split count divides 8 use the K-range-per-XCD mapping of gemm_bf16_kernel (xcd_parts = 8 / split)
-static int xcd_parts_for(int split) {
-    static int on = -1;
-    if (on < 0) { const char* v = getenv("VAW_GEMM_XCDSPLIT"); on = v ? atoi(v) : 1; }
-    return (on && (split == 2 || split == 4 || split == 8)) ? 8 / split : 0;
+static void launch_ring256(const vaw_gemm_launch& p, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a,
+                           int64_t lda, const bf16_t* b, int64_t ldb, const EpiDev& e, hipStream_t s) {
+    using Fn = decltype(&gemm_bf16_big_kernel<true, true>);
+    static const Fn tab[2][2] = LAYOUT_TABLE(gemm_bf16_big_kernel);
+    static bool raised[2][2];
+    const int tiles_n = (int)((N + BIG_BN - 1) / BIG_BN), n_wg = (int)((M + BIG_BM - 1) / BIG_BM) * tiles_n;
+    by_layout(tab, raised, a_kmajor, b_kmajor, (int)p.lds_bytes)<<<dim3(p.grid_x, p.grid_y), p.block, p.lds_bytes, s>>>(
+        a, lda, b, ldb, (int)(K / p.bkt), tiles_n, n_wg, p.split, e);
+}
+template <typename T>
+static void launch_generic(const vaw_gemm_launch& p, int a_kmajor, int b_kmajor, int64_t K, const void* A, int64_t lda, const void* B,
+                           int64_t ldb, const EpiDev& e, hipStream_t s) {
+    using Fn = decltype(&gemm_generic_kernel<T, true, true>);
+    static const Fn tab[2][2] = {{gemm_generic_kernel<T, false, false>, gemm_generic_kernel<T, false, true>},
+                                 {gemm_generic_kernel<T, true, false>, gemm_generic_kernel<T, true, true>}};
+    static bool raised[2][2];
+    const int64_t kchunk = p.split > 1 ? ((K + p.split - 1) / p.split + GBK - 1) / GBK * GBK : K;     // (splits of whole GBK steps)
+    by_layout(tab, raised, a_kmajor, b_kmajor, 0)<<<dim3(p.grid_x, p.grid_y, p.grid_z), p.block, 0, s>>>(
+        (const T*)A, lda, (const T*)B, ldb, K, kchunk, e);
 }
 
 extern "C" int vaw_gemm(vaw_dtype dt, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, const void* A,
                         int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const vaw_epilogue* ep,
                         float* workspace, int64_t workspace_floats, vaw_stream stream) {
-    VAW_CHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && C, "gemm: bad sizes M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-    VAW_CHECK_ARG(M < (1LL << 31) && N < (1LL << 31), "gemm: M, N must fit 31 bits");
-    VAW_CHECK_ARG(lda >= (a_kmajor ? K : M) && ldb >= (b_kmajor ? K : N) && ldc >= N, "gemm: leading dimension too small");
-    EpiDev e{};
-    e.alpha = 1.f;
-    if (ep) {
-        e.bias = ep->bias; e.act = ep->act; e.aux_in = ep->aux_in; e.aux_out = ep->aux_out; e.gate = ep->gate;
-        e.gate_ld = ep->gate_ld; e.resid = ep->resid; e.rowadd = ep->rowadd; e.rpb = ep->rows_per_batch;
-        e.alpha = ep->alpha; e.beta = ep->beta; e.out_f32 = ep->out_f32; e.resid_act = ep->resid_is_act;
-    }
-    float* const colsum_final = ep ? ep->colsum_out : nullptr;
-    float* const colsum_part = ep ? ep->colsum_partial_out : nullptr;      // deferred fold: partial rows stay with the caller
-    VAW_CHECK_ARG(!colsum_part || (!colsum_final && ep->colsum_rows_out), "gemm: colsum_partial_out excludes colsum_out and needs colsum_rows_out");
-    const bool colsum_out = colsum_final || colsum_part;                  // "this launch carries column sums"
-    float* const colsum_dst = colsum_part ? colsum_part : workspace;      // where the kernels leave their partial rows
-    const float colsum_beta = ep ? ep->colsum_beta : 0.f;
-    // colsum_rows_out is in / out: the caller states the capacity of colsum_partial_out in rows, the call answers with the rows
-    // written -- checked BEFORE anything is launched (a kernel path that needs more rows than the buffer has is an error)
-    const int64_t colsum_cap = colsum_part ? *ep->colsum_rows_out : 0;
-#define CS_CAP_CHECK(R) VAW_CHECK_ARG(!colsum_part || (R) <= colsum_cap, "gemm: colsum_partial_out holds %ld rows, this launch writes %ld", (long)colsum_cap, (long)(R))
-    auto fold_colsum = [&](int64_t R) -> int {
-        if (colsum_part) { *ep->colsum_rows_out = R; return VAW_OK; }
-        return vaw_reduce_rows(workspace, R, N, colsum_final, colsum_beta, stream);
-    };
-    float* rowsum_out = ep ? ep->rowsum_a_out : nullptr;
-    const float rowsum_beta = ep ? ep->rowsum_a_beta : 0.f;
-    VAW_CHECK_ARG(!rowsum_out || (workspace && workspace_floats >= 64 * M), "gemm: rowsum_a_out needs a workspace");
-    VAW_CHECK_ARG(e.act >= 0 && e.act <= 2, "gemm: unknown act %d", e.act);
-    VAW_CHECK_ARG(e.act != 2 || e.aux_in, "gemm: act=2 needs aux_in");
-    VAW_CHECK_ARG(!(e.gate || e.rowadd) || e.rpb > 0, "gemm: gate/rowadd need rows_per_batch");
-    VAW_CHECK_ARG(e.beta == 0.f || e.out_f32 || dt == VAW_F32, "gemm: beta needs f32 output");
-    if (e.rpb <= 0) e.rpb = 1;
+    vaw_gemm_launch p;
+    int rc = vaw_gemm_plan(dt, a_kmajor, b_kmajor, M, N, K, lda, ldb, ldc, (int64_t)(uintptr_t)A, (int64_t)(uintptr_t)B,
+                           (int64_t)(uintptr_t)C, ep, workspace ? workspace_floats : 0, nullptr, &p);
+    if (rc) return rc;         // (every refusal: nothing has been launched)
+    const GemmKnobs& k = vaw_gemm_knobs_state();
+    EpiDev e = vaw_epi_dev(ep, k);
     if (dt == VAW_F32) e.out_f32 = 1;
     e.M = M; e.N = N; e.ldc = ldc; e.C = C; e.slab = workspace;
-    {
-        static int dbg = -1;
-        if (dbg < 0) { const char* v = getenv("VAW_GEMM_DEBUG"); dbg = v ? atoi(v) : 0; }
-        e.debug = dbg;
-        static int depi = -1;
-        if (depi < 0) { const char* v = getenv("VAW_GEMM_EPI"); depi = v ? atoi(v) : 1; }
-        e.direct_epi = depi;
-    }
+    // column sums: the kernel leaves partial rows in the workspace (folded below) or with the caller (colsum_partial_out)
+    if (p.colsum_mode == VAW_GC_FOLD) e.colpart = workspace;
+    if (p.colsum_mode == VAW_GC_DEFERRED) e.colpart = ep->colsum_partial_out;
+    if (p.rowsum_mode == VAW_GS_FUSED) e.rowpart = workspace + (p.split > 1 ? (int64_t)p.split * M * N : 0);      // behind the slabs
+    const bf16_t* a = (const bf16_t*)A;
+    const bf16_t* b = (const bf16_t*)B;
     hipStream_t s = (hipStream_t)stream;
-    const bool plain_f32 = e.out_f32 && !e.bias && !e.act && !e.aux_out && !e.gate && !e.resid && !e.rowadd && N % 4 == 0 &&
-                           ldc % 4 == 0 && ((uintptr_t)C & 15) == 0;
-
-    // the vector epilogue of the fast path needs every epilogue operand 16-byte aligned
-    const bool epi_aligned = ldc % 8 == 0 && e.gate_ld % 4 == 0 &&
-                             ((((uintptr_t)C | (uintptr_t)e.bias | (uintptr_t)e.aux_in | (uintptr_t)e.aux_out |
-                                (uintptr_t)e.gate | (uintptr_t)e.resid | (uintptr_t)e.rowadd) & 15) == 0);
-    VAW_CHECK_ARG(!colsum_final || (workspace && workspace_floats >= vaw_colsum_workspace_floats(M, N) &&
-                                    workspace_floats >= ((M + 127) / 128) * N),
-                  "gemm: colsum_out needs a workspace of max(ceil(M/128), ceil(M/512))*N floats");
-    if (takes_fast_path(dt, M, N, K, A, lda, B, ldb) && epi_aligned && fast_layout_ok(a_kmajor, M)) {
-        // small M (strong-scaling batches: a few thousand token rows): 64-row tiles with a deep LDS-DMA ring (gemm_sm.hip)
-        // -- the launches the 128- and 256-row kernels can only give a quarter of the chip, one exposed memory latency per K step
-        {
-            static int sm_max_m = -1, sm_nb = 0, sm_st = 0, sm_wide_m = 0;
-            if (sm_max_m < 0) {
-                const char* v = getenv("VAW_SM_MAX_M"); sm_max_m = v ? atoi(v) : 8192;
-                v = getenv("VAW_SM_WIDE_M"); sm_wide_m = v ? atoi(v) : 0;        // 128 x 128 tiles for the wide launches up to this M (0 = off)
-                v = getenv("VAW_SM_NB"); sm_nb = v ? atoi(v) : 0;
-                v = getenv("VAW_SM_STAGES"); sm_st = v ? atoi(v) : 0;
-            }
-            const int64_t rows64 = (M + 63) / 64;
-            const bool cs_room = !colsum_out || colsum_part || workspace_floats >= rows64 * N;
-            // measured (tools/gemm_bench.py --m 2048 / 4096 / 8192 --tile sm, DiT-B/4 shapes): 1.2-1.8x faster than the 128- and
-            // 256-row kernels on the launches that give those less than one workgroup per CU (the 768-wide layers up to 4096
-            // rows: 16.0 -> 11.3, 39.4 -> 24.4, 30.2 -> 17.2, 34.2 -> 21.1 us at 2048 rows), slower on the wide ones (its 64-row
-            // tiles move twice the operand bytes per MFMA): taken only below one 128 x 128 tile per CU
-            // (and only for the K of the blocks' Linear layers: the long-K launches -- adaLN's input gradient, K = 6 L D -- keep
-            //  their split-K path: 161 us on 48 workgroups here against 40 + 38 us split)
-            // With the LDS-staged epilogue (round 3, late) the ring kernel wins on every 768-wide layer up to 4096 rows, and up to
-            // 8192 rows on those with K = 768 (proj: 33.2 -> 24.4, 23.3 -> 17.9 us) and on fc2's forward (K = 3072: 72.7 -> 61.2 with
-            // 128-column tiles); the wide layers (N >= 2304) tie at 2048 rows and lose above: they keep the other kernels
-            const bool sm_few_tiles = N <= 1024 && K <= 4096 &&
-                                      (M <= 4096 || (M <= 8192 && (K <= 1024 || b_kmajor)));
-            // wide layers at small M (fc1, fc2's GELU' input gradient, qkv at 2048-4096 rows: 128-288 items of the larger kernels):
-            // 128 x 128 tiles on the same ring
-            const bool sm_wide = !sm_few_tiles && M <= sm_wide_m && K <= 4096 && ((M + 127) / 128) * ((N + 127) / 128) <= 1024;
-            const bool sm_forced = g_gemm_tile >= 5 && g_gemm_tile <= 8;     // vaw_debug_gemm_tile: 5 always, 6 / 7 / 8 always with 64 x 64 / 64 x 128 / 128 x 128 tiles
-            if (a_kmajor && ((M <= sm_max_m && (sm_few_tiles || sm_wide) && g_gemm_tile < 0) || sm_forced) && !rowsum_out && cs_room && N % 8 == 0) {
-                // 64 x 128 tiles when they still give every CU a workgroup, 64 x 64 otherwise; ring depth by the LDS it leaves:
-                // 3 stages = two (64 x 128) or three (64 x 64) workgroups per CU for multi-round launches, 4 for single rounds
-                const int mb = g_gemm_tile == 8 ? 2 : (g_gemm_tile >= 5 ? 1 : (sm_wide && !sm_few_tiles) ? 2 : 1);
-                const int nb = mb == 2 ? 2 : g_gemm_tile == 6 ? 1 : g_gemm_tile == 7 ? 2 : sm_nb ? sm_nb : ((M >= 4096 && K >= 2048) ? 2 : 1);
-                const int64_t rows_t = (M + 64 * mb - 1) / (64 * mb);
-                const int64_t tiles = rows_t * ((N + 64 * nb - 1) / (64 * nb));
-                const int stages = sm_st ? sm_st : (tiles > 256 ? 3 : 4);
-                EpiDev es = e;
-                CS_CAP_CHECK(rows_t);
-                if (colsum_out) es.colpart = colsum_dst;
-                vaw_sm_launch(mb, nb, stages, b_kmajor, M, N, K, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, es, s);
-                VAW_CHECK_LAUNCH("gemm_sm");
-                if (colsum_out) return fold_colsum(rows_t);
-                return VAW_OK;
-            }
+    switch (p.variant) {
+        case VAW_GV_SMALL_M: vaw_sm_launch(p.mb, p.nb, p.stages, b_kmajor, M, N, K, a, lda, b, ldb, e, s); break;
+        case VAW_GV_PARKED_DRAIN:
+        case VAW_GV_WARP_SPEC: {
+            EpiDev ed = e;
+            ed.nt_off = 1, ed.nt_aux = k.nt_aux;
+            if (p.variant == VAW_GV_WARP_SPEC) vaw_ws_launch(p.ntw, p.epi_kind, b_kmajor, M, N, K, a, lda, b, ldb, ed, p.grid_x, p.block == 1024, s);
+            else vaw_pd_launch(p.ntw, p.epi_kind, b_kmajor, M, N, K, a, lda, b, ldb, ed, p.grid_x, s);
+            break;
         }
-        const int tiles_n = (int)((N + BN - 1) / BN);
-        const int64_t n_wg = ((M + BM - 1) / BM) * tiles_n;
-        VAW_CHECK_ARG(n_wg < (1LL << 31), "gemm: grid too large");
-        // stage depth: 64 for long K (weight gradients), 32 for the K <= 1024 forward / input-gradient launches
-        static int bk_env = -1;
-        if (bk_env < 0) { const char* v = getenv("VAW_GEMM_BK"); bk_env = v ? atoi(v) : 0; }
-        // measured on MI355X (tools/gemm_bench.py, DiT-B/4 shapes): the 32-deep stage (3 workgroups per CU) wins for
-        // the input-gradient layout (k-major x mn-major) when there are at least ~3 tiles per CU to overlap its K steps
-        // (768 output tiles at batch 256); with fewer tiles (per-GPU batches of 32 / 64 under strong scaling: 96 / 192 tiles)
-        // every K step is exposed latency and the 64-deep stage halves their number (step 7.05 -> 6.46 ms at batch 32)
-        const bool many_tiles = n_wg >= 3 * 256;
-        const int bkt = bk_env == 32 || bk_env == 64 ? bk_env : ((a_kmajor && !b_kmajor && K <= 4096 && many_tiles) ? 32 : 64);
-        const int nk_total = (int)(K / bkt);
-        const bool fused_rowsum = rowsum_out && !a_kmajor && !colsum_out;     // row sums of A ride on the MFMA kernel
-        int split = colsum_out ? 1 : pick_split(n_wg, K, M * N, workspace_floats - (fused_rowsum ? 64 * M : 0), plain_f32);
-        // small-M input gradients (per-GPU batches of 32 / 64 under strong scaling: 96-192 tiles, K up to 3072): with one
-        // workgroup per CU every K step is exposed DMA latency, so a plain bf16 result is K-split as well (f32 slabs, fixed-order
-        // reduce that writes bf16) when K is long enough to pay for the slab round trip
-        const bool plain_bf16 = !e.out_f32 && !e.bias && !e.act && !e.aux_out && !e.gate && !e.resid && !e.rowadd && e.beta == 0.f &&
-                                N % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C & 7) == 0;
-        if (split == 1 && plain_bf16 && !colsum_out && !rowsum_out && workspace && K >= 2048 && n_wg <= 256) {
-            int64_t sp = 512 / n_wg;
-            if (sp > K / 512) sp = K / 512;
-            if (sp > workspace_floats / (M * N)) sp = workspace_floats / (M * N);
-            if (sp > 8) sp = 8;
-            if (sp >= 2) split = (int)sp;
+        case VAW_GV_PERSISTENT: {
+            // default cache policy for the epilogue stores (nt costs 5-15 % on the f32 gated-residual and 192-column launches, and the
+            // next kernel re-reads the output from L2 / MALL); the aux_out stores alone are non-temporal (-0.5 % on the DiT-B/4 step)
+            EpiDev e8 = e;
+            e8.nt_off = !k.p8_nt, e8.nt_aux = k.nt_aux;
+            vaw_p8_launch(P8Plan{true, p.ntw, p.split, p.grid_x}, p.epi_kind, a_kmajor, b_kmajor, M, N, K, a, lda, b, ldb, e8, s);
+            break;
         }
-        if (colsum_out) e.colpart = colsum_dst;
-        if (split > 1) {   // no empty splits
-            const int per = (nk_total + split - 1) / split;
-            split = (nk_total + per - 1) / per;
-        }
-        float* rowpart = nullptr;
-        if (fused_rowsum) rowpart = e.rowpart = workspace + (split > 1 ? (int64_t)split * M * N : 0);
-        const bf16_t* a = (const bf16_t*)A;
-        const bf16_t* b = (const bf16_t*)B;
-        const int xparts = xcd_parts_for(split);
-        dim3 grid((unsigned)n_wg, (unsigned)split);
-        if (xparts) grid = dim3((unsigned)(8 * ((n_wg + xparts - 1) / xparts)), 1);
-#define LAUNCH_FAST(AKv, BKv, BKTv)                                                                                   \
-    do {                                                                                                              \
-        static bool attr_done = false;                                                                                \
-        const int lds = FastCfg<BKTv>::lds_bytes;                                                                     \
-        if (!attr_done) {                                                                                             \
-            (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<AKv, BKv, BKTv, 0>,                               \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);                               \
-            attr_done = true;                                                                                         \
-        }                                                                                                             \
-        gemm_bf16_kernel<AKv, BKv, BKTv, 0><<<grid, 256, lds, s>>>(a, lda, b, ldb, nk_total, tiles_n, (int)n_wg, split, e, \
-                                                                    ConvGeom{}, xparts);                             \
-    } while (0)
-#define LAUNCH_FAST_BK(BKTv)                                         \
-    do {                                                             \
-        if (a_kmajor && b_kmajor) LAUNCH_FAST(true, true, BKTv);     \
-        else if (a_kmajor && !b_kmajor) LAUNCH_FAST(true, false, BKTv); \
-        else if (!a_kmajor && b_kmajor) LAUNCH_FAST(false, true, BKTv); \
-        else LAUNCH_FAST(false, false, BKTv);                        \
-    } while (0)
-        if (g_gemm_tile == -2) { const char* v = getenv("VAW_GEMM_BIG"); g_gemm_tile = v ? atoi(v) : -1; }
-        {
-            // parked-drain kernel (gemm_pd_kernel.h): the un-split forward / input-gradient launches of the Linear layers whose
-            // epilogue it can hide under the next tile's K loop.  Measured level with or behind the 256-row
-            // kernel on every DiT-B/4 shape, so the automatic choice is OFF: VAW_GEMM_PD=1 switches it on by shape,
-            // vaw_debug_gemm_tile(9 / 10 / 11) forces it (tests, A/B runs).
-            static int pd_auto = -1;
-            if (pd_auto < 0) { const char* v = getenv("VAW_GEMM_PD"); pd_auto = v ? atoi(v) : 0; }
-            const bool ws_forced = g_gemm_tile >= 12 && g_gemm_tile <= 14;       // 12 / 13 / 14: the warp-specialised kernel (width by shape / 256 / 192)
-            static int ws_auto = -1;
-            if (ws_auto < 0) { const char* v = getenv("VAW_GEMM_WS"); ws_auto = v ? atoi(v) : 0; }
-            const bool pd_forced = (g_gemm_tile >= 9 && g_gemm_tile <= 11) || ws_forced;
-            const int64_t rows64 = (M + 63) / 64;
-            EpiDev epd = e;          // (e.colpart is set above when this launch carries column sums)
-            const int pd_kind = (pd_forced || ((pd_auto || ws_auto) && g_gemm_tile == -1)) && bk_env == 0 && !rowsum_out &&
-                                        (!colsum_out || colsum_part || workspace_floats >= rows64 * N)
-                                    ? vaw_pd_epi_kind(epd, a_kmajor != 0, b_kmajor != 0, M, N, K) : -1;
-            if (pd_kind >= 0) {
-                const int cus = vaw_p8_cus_available();
-                const int ntw = (g_gemm_tile == 10 || g_gemm_tile == 13) ? 4 : (g_gemm_tile == 11 || g_gemm_tile == 14) ? 3 : vaw_pd_pick_ntw(M, N, cus);
-                const int64_t items = ((M + 127) / 128) * ((N + 64 * ntw - 1) / (64 * ntw));
-                // by shape: at least two rounds of workgroups (the first tile of a workgroup has nothing to hide its epilogue
-                // under... the last one's leaves in the open), K of the blocks' Linear layers
-                const bool pd_shape = items >= 2 * cus && K >= 768 && K <= 4096;
-                if (pd_forced || pd_shape) {
-                    CS_CAP_CHECK(rows64);
-                    static int nt_aux = -1;
-                    if (nt_aux < 0) { const char* v = getenv("VAW_P8_NT_AUX"); nt_aux = (v && atoi(v) == 0) ? 0 : 1; }
-                    epd.nt_off = 1;
-                    epd.nt_aux = nt_aux;
-                    epd.colpart = colsum_out ? colsum_dst : nullptr;
-                    if (ws_forced || (ws_auto && !pd_forced)) vaw_ws_launch(ntw, pd_kind, b_kmajor, M, N, K, a, lda, b, ldb, epd, cus, s);
-                    else vaw_pd_launch(ntw, pd_kind, b_kmajor, M, N, K, a, lda, b, ldb, epd, cus, s);
-                    VAW_CHECK_LAUNCH("gemm_pd");
-                    if (colsum_out) return fold_colsum(rows64);
-                    return VAW_OK;
-                }
-            }
-        }
-        {
-            const int force = g_gemm_tile == -1 ? -1 : g_gemm_tile == 4 ? 1 : (g_gemm_tile == 2 || g_gemm_tile == 3) ? g_gemm_tile : 0;
-            const bool p8_epi_ok = !(e.act == 2 && e.gate) && !(e.resid && e.rowadd);     // gemm_epi.h: EpiOps has two slots
-            const P8Plan pl = (bk_env == 0 && !fused_rowsum && p8_epi_ok)
-                                  ? vaw_p8_plan(M, N, K, plain_f32 || (plain_bf16 && !rowsum_out && K >= 2048 && workspace != nullptr),
-                                                colsum_out, workspace_floats, force)
-                                  : P8Plan{false, 4, 1, 0};
-            // small M (strong-scaling batches): a persistent launch that gives only half the CUs an item loses to the 128 x 128
-            // kernel's 2-3 workgroups per CU (fc1 forward at 2048 rows: 28.7 vs 22.0 us, fc2's GELU' input gradient 29.7 vs 26.5)
-            const bool p8_half_empty = force < 0 && M <= 4096 && pl.use && pl.grid < 200 &&
-                                       ((M + 255) / 256) * ((N + 64 * pl.ntw - 1) / (64 * pl.ntw)) * pl.split < 200;
-            if (pl.use && !p8_half_empty) {
-                CS_CAP_CHECK((M + 127) / 128);
-                EpiDev ep8 = e;
-                static int nt_off = -1;
-                // default: epilogue stores with the default cache policy (measured: nt costs 5-15 % on the f32 gated-residual and
-                // the 192-column launches, whose row segments are not whole 128-byte lines, and the next kernel re-reads the
-                // output from L2 / MALL anyway); VAW_P8_NT=1 switches the non-temporal hint on
-                if (nt_off < 0) { const char* v = getenv("VAW_P8_NT"); nt_off = (v && atoi(v) == 1) ? 0 : 1; }
-                ep8.nt_off = nt_off;
-                static int nt_aux = -1;
-                if (nt_aux < 0) { const char* v = getenv("VAW_P8_NT_AUX"); nt_aux = (v && atoi(v) == 0) ? 0 : 1; }      // default on: -0.5 % on the DiT-B/4 step (13.89 -> 13.83, 13.95 -> 13.88 ms, one box)
-                ep8.nt_aux = nt_aux;
-                ep8.colpart = colsum_out ? colsum_dst : nullptr;
-                ep8.rowpart = nullptr;
-                vaw_p8_launch(pl, a_kmajor, b_kmajor, M, N, K, a, lda, b, ldb, ep8, s);
-                if (pl.split > 1 && !e.out_f32)      // plain bf16 result (input gradients of half-full launches): slabs -> bf16
-                    splitk_reduce_kernel<bf16_t><<<ceil_div(M * N / 4, 256) > 2048 ? 2048 : ceil_div(M * N / 4, 256), 256, 0, s>>>(
-                        workspace, pl.split, M, N, ldc, C, e.alpha, 0.f, 0);
-                else if (pl.split > 1)
-                    splitk_reduce_kernel<float><<<ceil_div(M * N / 4, 256) > 2048 ? 2048 : ceil_div(M * N / 4, 256), 256, 0, s>>>(
-                        workspace, pl.split, M, N, ldc, C, e.alpha, e.beta, 1);
-                VAW_CHECK_LAUNCH("gemm_p8");
-                if (rowsum_out) {
-                    const int rc = rowsum_a_separate(dt, a_kmajor, M, K, A, lda, rowsum_out, rowsum_beta, workspace, workspace_floats, stream);
-                    if (rc != VAW_OK) return rc;
-                }
-                if (colsum_out) return fold_colsum((M + 127) / 128);
-                return VAW_OK;
-            }
-        }
-        const int64_t tiles_nb = (N + BIG_BN - 1) / BIG_BN, n_wgb = ((M + BIG_BM - 1) / BIG_BM) * tiles_nb;
-        const bool use_big = bk_env == 0 && !fused_rowsum && (g_gemm_tile == 1 || (g_gemm_tile == -1 && big_tile_pays(M, N, K, n_wgb)));
-        if (use_big) {
-            CS_CAP_CHECK((M + BIG_BM - 1) / BIG_BM);
-            const int nkb = (int)(K / 32);
-            int splitb = colsum_out ? 1 : pick_split(n_wgb * 2, K, M * N, workspace_floats, plain_f32);
-            if (splitb > 1) {
-                const int per = (nkb + splitb - 1) / splitb;
-                splitb = (nkb + per - 1) / per;
-            }
-            dim3 gridb((unsigned)n_wgb, (unsigned)splitb);
-#define LAUNCH_BIG(AKv, BKv)                                                                                             \
-    do {                                                                                                                 \
-        static bool attr_done = false;                                                                                   \
-        if (!attr_done) {                                                                                                \
-            (void)hipFuncSetAttribute((const void*)gemm_bf16_big_kernel<AKv, BKv>,                                       \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BIG_LDS);                              \
-            attr_done = true;                                                                                            \
-        }                                                                                                                \
-        gemm_bf16_big_kernel<AKv, BKv><<<gridb, 512, BIG_LDS, s>>>(a, lda, b, ldb, nkb, (int)tiles_nb, (int)n_wgb, splitb, e); \
-    } while (0)
-            if (a_kmajor && b_kmajor) LAUNCH_BIG(true, true);
-            else if (a_kmajor && !b_kmajor) LAUNCH_BIG(true, false);
-            else if (!a_kmajor && b_kmajor) LAUNCH_BIG(false, true);
-            else LAUNCH_BIG(false, false);
-            if (splitb > 1)
-                splitk_reduce_kernel<float><<<ceil_div(M * N / 4, 256) > 2048 ? 2048 : ceil_div(M * N / 4, 256), 256, 0, s>>>(
-                    workspace, splitb, M, N, ldc, C, e.alpha, e.beta, 1);
-            VAW_CHECK_LAUNCH("gemm_bf16_big");
-            if (rowsum_out) {
-                const int rc = rowsum_a_separate(dt, a_kmajor, M, K, A, lda, rowsum_out, rowsum_beta, workspace, workspace_floats, stream);
-                if (rc != VAW_OK) return rc;
-            }
-            if (colsum_out) return fold_colsum((M + BIG_BM - 1) / BIG_BM);
-            return VAW_OK;
-        }
-        CS_CAP_CHECK((M + BM - 1) / BM);
-        if (bkt == 32) LAUNCH_FAST_BK(32);
-        else LAUNCH_FAST_BK(64);
-        if (split > 1 && !e.out_f32)
-            splitk_reduce_kernel<bf16_t><<<ceil_div(M * N / 4, 256) > 2048 ? 2048 : ceil_div(M * N / 4, 256), 256, 0, s>>>(
-                workspace, split, M, N, ldc, C, e.alpha, 0.f, 0);
-        else if (split > 1)
-            splitk_reduce_kernel<float><<<ceil_div(M * N / 4, 256) > 2048 ? 2048 : ceil_div(M * N / 4, 256), 256, 0, s>>>(
-                workspace, split, M, N, ldc, C, e.alpha, e.beta, 1, rowpart, rowsum_out, rowsum_beta);
-        VAW_CHECK_LAUNCH("gemm_bf16");
-        if (fused_rowsum && split == 1) {
-            const int rc = vaw_reduce_rows(rowpart, split, M, rowsum_out, rowsum_beta, stream);
-            if (rc != VAW_OK) return rc;
-        } else if (rowsum_out && !fused_rowsum) {
-            const int rc = rowsum_a_separate(dt, a_kmajor, M, K, A, lda, rowsum_out, rowsum_beta, workspace, workspace_floats, stream);
-            if (rc != VAW_OK) return rc;
-        }
-        if (colsum_out) return fold_colsum((M + BM - 1) / BM);
-        return VAW_OK;
+        case VAW_GV_RING256: launch_ring256(p, a_kmajor, b_kmajor, M, N, K, a, lda, b, ldb, e, s); break;
+        case VAW_GV_T128_BK32: launch_t128<32>(p, a_kmajor, b_kmajor, M, N, K, a, lda, b, ldb, e, s); break;
+        case VAW_GV_T128_BK64: launch_t128<64>(p, a_kmajor, b_kmajor, M, N, K, a, lda, b, ldb, e, s); break;
+        default:
+            if (dt == VAW_F32) launch_generic<float>(p, a_kmajor, b_kmajor, K, A, lda, B, ldb, e, s);
+            else launch_generic<bf16_t>(p, a_kmajor, b_kmajor, K, A, lda, B, ldb, e, s);
+            break;
     }
-    const int64_t tiles = (int64_t)ceil_div(N, GBN) * ceil_div(M, GBM);
-    int split = colsum_out ? 1 : pick_split(tiles, K, M * N, workspace_floats, plain_f32);
-    int64_t kchunk = K;
-    if (split > 1) {
-        kchunk = ((K + split - 1) / split + GBK - 1) / GBK * GBK;
-        split = (int)((K + kchunk - 1) / kchunk);
+    float* const rowsum_out = ep ? ep->rowsum_a_out : nullptr;
+    if (p.reduce != VAW_GR_NONE)
+        splitk_reduce(p.reduce, workspace, p.split, M, N, ldc, C, e.alpha, e.beta, s, e.rowpart, rowsum_out, ep ? ep->rowsum_a_beta : 0.f);
+    VAW_CHECK_LAUNCH("gemm");
+    // the fold of the column-sum rows goes first: a separate row-sum pass reuses the workspace they lie in
+    if (p.colsum_mode == VAW_GC_FOLD && (rc = vaw_reduce_rows(workspace, p.colsum_rows, N, ep->colsum_out, ep->colsum_beta, stream))) return rc;
+    // row sums of A: the MFMA kernel's partials (folded by the reduce when there was one), or, A being stored [K][M], a column sum over its K rows
+    if (p.rowsum_mode == VAW_GS_FUSED && p.reduce == VAW_GR_NONE) rc = vaw_reduce_rows(e.rowpart, 1, M, rowsum_out, ep->rowsum_a_beta, stream);
+    else if (p.rowsum_mode == VAW_GS_SEPARATE) rc = vaw_colsum(dt, A, K, M, lda, rowsum_out, ep->rowsum_a_beta, workspace, workspace_floats, stream);
+    if (rc) return rc;
+    switch (p.colsum_mode) {
+        case VAW_GC_DEFERRED: *ep->colsum_rows_out = p.colsum_rows; return VAW_OK;
+        case VAW_GC_SEPARATE:      // a pass over the output just written; deferred: its one complete row is the only "partial" row
+            if (ep->colsum_partial_out) *ep->colsum_rows_out = p.colsum_rows;
+            return vaw_colsum(e.out_f32 ? VAW_F32 : dt, C, M, N, ldc, ep->colsum_partial_out ? ep->colsum_partial_out : ep->colsum_out,
+                              ep->colsum_partial_out ? 0.f : ep->colsum_beta, workspace, workspace_floats, stream);
+        default: return VAW_OK;
     }
-    CS_CAP_CHECK(1);
-    dim3 grid(ceil_div(N, GBN), ceil_div(M, GBM), split);
-#define LAUNCH_GEN(T, AKv, BKv) \
-    gemm_generic_kernel<T, AKv, BKv><<<grid, 256, 0, s>>>((const T*)A, lda, (const T*)B, ldb, K, kchunk, e)
-#define LAUNCH_GEN_T(T)                                          \
-    do {                                                         \
-        if (a_kmajor && b_kmajor) LAUNCH_GEN(T, true, true);     \
-        else if (a_kmajor && !b_kmajor) LAUNCH_GEN(T, true, false); \
-        else if (!a_kmajor && b_kmajor) LAUNCH_GEN(T, false, true); \
-        else LAUNCH_GEN(T, false, false);                        \
-    } while (0)
-    if (dt == VAW_F32) LAUNCH_GEN_T(float);
-    else LAUNCH_GEN_T(bf16_t);
-    if (split > 1)
-        splitk_reduce_kernel<float><<<ceil_div(M * N / 4, 256) > 2048 ? 2048 : ceil_div(M * N / 4, 256), 256, 0, s>>>(
-            workspace, split, M, N, ldc, C, e.alpha, e.beta, 1);
-    VAW_CHECK_LAUNCH("gemm_generic");
-    if (rowsum_out) {
-        const int rc = rowsum_a_separate(dt, a_kmajor, M, K, A, lda, rowsum_out, rowsum_beta, workspace, workspace_floats, stream);
-        if (rc != VAW_OK) return rc;
-    }
-    if (colsum_part) {   // generic path, deferred fold: one complete row of column sums as the only "partial" row
-        VAW_CHECK_ARG(workspace && workspace_floats >= vaw_colsum_workspace_floats(M, N), "gemm: colsum_partial_out on the generic path needs the workspace");
-        *ep->colsum_rows_out = 1;
-        return vaw_colsum(e.out_f32 ? VAW_F32 : dt, C, M, N, ldc, colsum_part, 0.f, workspace, workspace_floats, stream);
-    }
-    if (colsum_out)   // generic path: a separate pass over the output just written
-        return vaw_colsum(e.out_f32 ? VAW_F32 : dt, C, M, N, ldc, colsum_final, colsum_beta, workspace, workspace_floats, stream);
-    return VAW_OK;
 }
 
 
@@ -1148,7 +871,7 @@ extern "C" int vaw_conv3x3(vaw_dtype dt, int mode, const void* act, const void* 
                            vaw_stream stream) {
     VAW_CHECK_ARG(mode >= 0 && mode <= 2 && act && (w || mode == 2) && out && B > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0,
                   "conv3x3: bad arguments");
-    if (dt != VAW_BF16 || g_force_generic) return VAW_ERR_UNSUPPORTED;
+    if (dt != VAW_BF16 || vaw_gemm_knobs_state().force_generic) return VAW_ERR_UNSUPPORTED;
     const int64_t Mpix = (int64_t)B * H * W;
     int64_t M, N, K;
     if (mode == 0) { M = Mpix; N = Co; K = 9LL * Ci; if (Ci % 64) return VAW_ERR_UNSUPPORTED; }
@@ -1156,19 +879,9 @@ extern "C" int vaw_conv3x3(vaw_dtype dt, int mode, const void* act, const void* 
     else { M = Co; N = 9LL * Ci; K = Mpix; if (Ci % 8 || Mpix % 64 || Co % 8 || !act2) return VAW_ERR_UNSUPPORTED; }
     if (N % 8 || M < 16 || N < 16 || Mpix >= (1LL << 31)) return VAW_ERR_UNSUPPORTED;
     if ((((uintptr_t)act | (uintptr_t)act2 | (uintptr_t)w | (uintptr_t)out) & 15) != 0) return VAW_ERR_UNSUPPORTED;
-    EpiDev e{};
-    e.alpha = 1.f;
-    if (ep) {
-        e.bias = ep->bias; e.act = ep->act; e.aux_in = ep->aux_in; e.aux_out = ep->aux_out; e.gate = ep->gate;
-        e.gate_ld = ep->gate_ld; e.resid = ep->resid; e.rowadd = ep->rowadd; e.rpb = ep->rows_per_batch;
-        e.alpha = ep->alpha; e.beta = ep->beta; e.out_f32 = ep->out_f32; e.resid_act = ep->resid_is_act;
-    }
-    if (e.rpb <= 0) e.rpb = 1;
-    {
-        static int depi = -1;
-        if (depi < 0) { const char* v = getenv("VAW_GEMM_EPI"); depi = v ? atoi(v) : 1; }
-        e.direct_epi = depi;
-    }
+    const GemmKnobs& k = vaw_gemm_knobs_state();
+    EpiDev e = vaw_epi_dev(ep, k);
+    e.debug = 0;            // (the ablation switch of VAW_GEMM_DEBUG belongs to vaw_gemm's launches)
     if (mode == 2) e.out_f32 = 1;
     VAW_CHECK_ARG(e.beta == 0.f || e.out_f32, "conv3x3: beta needs f32 output");
     float* colsum_out = ep ? ep->colsum_out : nullptr;
@@ -1181,8 +894,7 @@ extern "C" int vaw_conv3x3(vaw_dtype dt, int mode, const void* act, const void* 
     VAW_CHECK_ARG(!colsum_out || (workspace && workspace_floats >= ((M + 127) / 128) * N), "conv3x3: colsum_out needs a workspace");
     hipStream_t s = (hipStream_t)stream;
     {   // the persistent 256-row-tile kernel first (gemm_p8_conv.hip); shapes it declines stay on the 128 x 128 kernel below
-        if (g_gemm_tile == -2) { const char* v = getenv("VAW_GEMM_BIG"); g_gemm_tile = v ? atoi(v) : -1; }
-        const int force = g_gemm_tile == -1 ? -1 : g_gemm_tile == 4 ? 1 : (g_gemm_tile == 2 || g_gemm_tile == 3) ? g_gemm_tile : 0;
+        const int force = k.tile == -1 ? -1 : k.tile == 4 ? 1 : (k.tile == 2 || k.tile == 3) ? k.tile : 0;
         float* rowsum_out8 = ep ? ep->rowsum_a_out : nullptr;
         int bias_done = 0;
         if (!colsum_out && (mode != 2 || act2) && force != 0 &&
@@ -1205,16 +917,13 @@ extern "C" int vaw_conv3x3(vaw_dtype dt, int mode, const void* act, const void* 
     const bool bias_grad = rowsum_out != nullptr;        // sum over pixels of dy (row sums of A = dy^T)
     int split = (colsum_out && !bias_grad) ? 1 : pick_split(n_wg, K, M * N, workspace_floats - (bias_grad ? 64 * M : 0), plain_f32);
     if (colsum_out && !bias_grad) e.colpart = workspace;
-    if (split > 1) {
-        const int per = (nk_total + split - 1) / split;
-        split = (nk_total + per - 1) / per;
-    }
+    split = no_empty_split(nk_total, split);
     float* rowpart = nullptr;
     if (bias_grad) {
         VAW_CHECK_ARG(workspace && workspace_floats >= (split > 1 ? split * M * N : 0) + split * M, "conv3x3: bias gradient needs a workspace");
         rowpart = e.rowpart = workspace + (split > 1 ? split * M * N : 0);
     }
-    const int xparts = xcd_parts_for(split);
+    const int xparts = xcd_parts_for(k, split);
     dim3 grid((unsigned)n_wg, (unsigned)split);
     if (xparts) grid = dim3((unsigned)(8 * ((n_wg + xparts - 1) / xparts)), 1);
     const ConvGeom cg{H, W, Ci, Co};
@@ -1233,9 +942,7 @@ extern "C" int vaw_conv3x3(vaw_dtype dt, int mode, const void* act, const void* 
     if (mode == 0) LAUNCH_CONV(true, true, 1, act, (int64_t)Ci, w, 9LL * Ci);
     else if (mode == 1) LAUNCH_CONV(true, false, 2, act, (int64_t)Co, w, 9LL * Ci);
     else LAUNCH_CONV(false, false, 3, act, (int64_t)Co, act2, (int64_t)Ci);
-    if (split > 1)
-        splitk_reduce_kernel<float><<<ceil_div(M * N / 4, 256) > 2048 ? 2048 : ceil_div(M * N / 4, 256), 256, 0, s>>>(
-            workspace, split, M, N, ldc, out, e.alpha, e.beta, 1, rowpart, rowsum_out, rowsum_beta);
+    if (split > 1) splitk_reduce(VAW_GR_F32, workspace, split, M, N, ldc, out, e.alpha, e.beta, s, rowpart, rowsum_out, rowsum_beta);
     VAW_CHECK_LAUNCH("conv3x3");
     if (bias_grad && split == 1) return vaw_reduce_rows(rowpart, split, M, rowsum_out, rowsum_beta, stream);
     if (colsum_out) return vaw_reduce_rows(workspace, (M + BM - 1) / BM, N, colsum_out, colsum_beta, stream);

@@ -1,6 +1,8 @@
 // Persistent 256-row-tile bf16 MFMA GEMM: shape planning and dispatch.  The kernel is in gemm_p8_kernel.h; its
 // instantiations live in one translation unit per operand layout (gemm_p8_fwd / _dgrad / _wgrad .hip) so they build in parallel.
 #include "gemm_p8_kernel.h"
+#include "gemm_plan.h"
+static_assert(P8Cfg<3>::lds_bytes == vaw_lds_p8(3) && P8Cfg<4>::lds_bytes == vaw_lds_p8(4), "gemm_plan.h: LDS size of the persistent kernel");
 
 void p8_launch_fwd(const P8Launch& L, const EpiDev& e, hipStream_t s);      // A [M][K], B [N][K]
 void p8_launch_dgrad(const P8Launch& L, const EpiDev& e, hipStream_t s);    // A [M][K], B [K][N]
@@ -8,12 +10,6 @@ void p8_launch_wgrad(const P8Launch& L, const EpiDev& e, hipStream_t s);    // A
 void p8_launch_tn(const P8Launch& L, const EpiDev& e, hipStream_t s);       // A [K][M], B [N][K]
 
 // ---- host side ----------------------------------------------------------------------------------------------
-// Tile width and split count for a shape, or use = false when the 128 x 128 kernel of gemm.hip should keep it.
-struct P8Plan {
-    bool use;
-    int ntw, split, grid;
-};
-
 // Workgroups a persistent launch may use = CUs - reserved.  A workgroup of this kernel owns a CU's whole register file and LDS
 // and the items are partitioned statically, so a kernel of another stream that holds even 8 CUs (RCCL's all-reduce during a
 // data-parallel backward) makes a full-width persistent grid run its last workgroups in a second pass: measured with a stand-in
@@ -49,10 +45,10 @@ static double p8_cost(int64_t M, int64_t N, int ntw, int split, int cus) {
     return (double)rounds * (ntw == 4 ? 1.0 : 0.85) / split;
 }
 
-P8Plan vaw_p8_plan(int64_t M, int64_t N, int64_t K, bool plain_f32, bool want_colsum, int64_t ws_floats, int force) {
+// (cus: the CUs the grid may use -- vaw_p8_cus_available() for a launch, stated by the caller so that the plan is a pure function)
+P8Plan vaw_p8_plan(int64_t M, int64_t N, int64_t K, bool plain_f32, bool want_colsum, int64_t ws_floats, int force, int cus) {
     P8Plan pl{false, 4, 1, 0};
     if (force == 0) return pl;
-    const int cus = p8_num_cus();
     const int nk = (int)(K / 64);
     double best = 1e30;
     for (int ntw = 4; ntw >= 3; --ntw) {
@@ -93,7 +89,8 @@ P8Plan vaw_p8_plan(int64_t M, int64_t N, int64_t K, bool plain_f32, bool want_co
     return pl;
 }
 
-void vaw_p8_launch(const P8Plan& pl, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda,
+// pl and epi (the P8_* epilogue kind) come from vaw_gemm_plan
+void vaw_p8_launch(const P8Plan& pl, int epi, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda,
                    const bf16_t* b, int64_t ldb, const EpiDev& e, hipStream_t s) {
     const int bn = 64 * pl.ntw;
     const int tiles_m = (int)((M + 255) / 256), tiles_n = (int)((N + bn - 1) / bn), nk = (int)(K / 64);
@@ -104,18 +101,7 @@ void vaw_p8_launch(const P8Plan& pl, int a_kmajor, int b_kmajor, int64_t M, int6
     const int64_t items = (int64_t)tiles_m * tiles_n * pl.split;
     const int nk_item = (nk + pl.split - 1) / pl.split;
     const int team_delay = (team_pct > 0 && items >= 2 * pl.grid) ? (int)(nk_item * 160LL * pl.ntw / 4 * team_pct / 100) : 0;
-    P8Launch L{a, b, lda, ldb, nk, tiles_m, tiles_n, pl.split, pl.grid, pl.ntw, 0, team_delay};
-    // epilogue kind (gemm_epi.h): the specialised kernels cover the launches of the training step, P8_ANY the rest
-    const bool bf16_out = !e.out_f32;
-    if (pl.split > 1) L.epi = P8_SLAB;
-    else if (e.act == 1 && e.aux_out && !e.gate && !e.resid && !e.rowadd && bf16_out && !e.colpart) L.epi = P8_GELU;
-    else if (e.act == 2 && !e.bias && !e.aux_out && !e.gate && !e.resid && !e.rowadd && bf16_out && e.alpha == 1.f) L.epi = P8_DGELU;
-    else if (e.act == 0 && e.gate && e.resid && !e.resid_act && e.aux_out && !e.rowadd && e.out_f32 && e.beta == 0.f && !e.colpart)
-        L.epi = P8_GATE;
-    else if (e.act == 0 && !e.aux_out && !e.gate && !e.resid && !e.rowadd && e.beta == 0.f) L.epi = P8_STORE;
-    else if (a_kmajor && b_kmajor && e.act == 0 && !e.aux_out && !e.gate && e.resid && e.resid_act && !e.rowadd && bf16_out && e.beta == 0.f && !e.colpart)
-        L.epi = P8_RESID;           // 1x1 convs with a fused skip add (UNet attention proj_out): P8_ANY ran them at 2.6x the time of the plain store
-    else L.epi = P8_ANY;
+    P8Launch L{a, b, lda, ldb, nk, tiles_m, tiles_n, pl.split, pl.grid, pl.ntw, epi, team_delay};
     if (a_kmajor && b_kmajor) p8_launch_fwd(L, e, s);
     else if (a_kmajor && !b_kmajor) p8_launch_dgrad(L, e, s);
     else if (!a_kmajor && !b_kmajor) p8_launch_wgrad(L, e, s);

@@ -1,12 +1,8 @@
 // Implicit-GEMM conv3x3 on the persistent kernel (gemm_p8_kernel.h, CONV modes): instantiations and the host entry that
 // vaw_conv3x3 (gemm.hip) tries first.  Reference: the 3x3 convolutions of ResBlock / stem / head, models/unet.py:182-213,492,625.
 #include "gemm_p8_kernel.h"
+#include "gemm_plan.h"
 
-struct P8Plan {
-    bool use;
-    int ntw, split, grid;
-};
-P8Plan vaw_p8_plan(int64_t M, int64_t N, int64_t K, bool plain_f32, bool want_colsum, int64_t ws_floats, int force);
 
 // out[n][m] = beta * out[n][m] + sum_s slab[s][m][n]: the slab reduce of the transposed weight-gradient problem
 // (slab rows = (tap, ci), columns = co; out = dW [Co][9*Ci]).  32 (m) x 64 (n) tiles: 16-byte slab reads (16 lanes per 256-byte row
@@ -67,7 +63,7 @@ bool vaw_p8_conv(int mode, const bf16_t* act, const bf16_t* act2, const bf16_t* 
     if (N % 8 || N < 64) return false;
     if (mode != 2 && (e.act || e.aux_out || e.gate || e.rowadd || e.out_f32 || e.beta != 0.f || e.colpart)) return false;
     if (mode != 2 && e.resid && !e.resid_act) return false;
-    const P8Plan pl = vaw_p8_plan(M, N, K, mode == 2, false, workspace_floats, force);
+    const P8Plan pl = vaw_p8_plan(M, N, K, mode == 2, false, workspace_floats, force, vaw_p8_cus_available());
     if (!pl.use) return false;
     if (mode == 2 && pl.split < 2) return false;                    // (always K-split in practice: K = pixels, few tiles)
     const int bn = 64 * pl.ntw, tiles_m = (int)((M + 255) / 256), tiles_n = (int)((N + bn - 1) / bn), nk = (int)(K / 64);

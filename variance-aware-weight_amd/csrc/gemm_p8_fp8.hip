@@ -9,12 +9,8 @@
 //                      epilogues (bias / GELU / GELU' / gated residual / column sums), f32 accumulation, bf16 or f32 output.
 //   (vaw_wgrad_grouped with dt = VAW_FP8 runs the deferred weight gradients on the transposed copies.)
 #include "gemm_p8_kernel.h"
+#include "gemm_plan.h"
 
-struct P8Plan {
-    bool use;
-    int ntw, split, grid;
-};
-P8Plan vaw_p8_plan(int64_t M, int64_t N, int64_t K, bool plain_f32, bool want_colsum, int64_t ws_floats, int force);
 extern "C" int vaw_reduce_rows(const float* partial, int64_t R, int64_t N, float* out, float beta, vaw_stream stream);
 
 // a_e5m2: the dy operand is e5m2 (vaw_wgrad_grouped with dt = VAW_BF8); x is e4m3 either way
@@ -527,7 +523,7 @@ extern "C" int vaw_gemm_fp8(vaw_dtype a_format, int64_t M, int64_t N, int64_t K,
     e.colpart = colsum_part ? colsum_part : colsum_final ? workspace : nullptr;
     // plan in units of the kernel's K tiles: 128 fp8 elements = one K tile = what 64 bf16 elements are to vaw_p8_plan
     // (plain_f32 = false: no K split -- the long-K launches of the step are the weight gradients, served by vaw_wgrad_grouped)
-    const P8Plan pl = vaw_p8_plan(M, N, K / 2, false, colsum_out, workspace_floats, 1);
+    const P8Plan pl = vaw_p8_plan(M, N, K / 2, false, colsum_out, workspace_floats, 1, vaw_p8_cus_available());
     hipStream_t s = (hipStream_t)stream;
     const int bn = 64 * pl.ntw, tiles_m = (int)((M + 255) / 256), tiles_n = (int)((N + bn - 1) / bn), nk = (int)(K / 128);
     int epi;

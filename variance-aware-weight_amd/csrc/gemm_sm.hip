@@ -14,6 +14,7 @@
 // Layouts: A k-major ([M][K]); B k-major ([N][K], forward) or mn-major ([K][N], input gradients).  Weight gradients keep the
 // grouped persistent launch (K = tokens is long there and all layers together fill the chip).
 #include "gemm_p8_kernel.h"
+#include "gemm_plan.h"
 
 template <int NB, int MB = 1> struct SmCfg {
     static constexpr int BM = 64 * MB;
@@ -178,6 +179,7 @@ static void sm_launch_one(const bf16_t* a, int64_t lda, const bf16_t* b, int64_t
                           hipStream_t s) {
     static bool attr_done = false;
     const int lds = STAGES * SmCfg<NB, MB>::stage_bytes;
+    static_assert(STAGES * SmCfg<NB, MB>::stage_bytes == vaw_lds_sm(MB, NB, STAGES), "gemm_plan.h: LDS size of the small-M kernel");
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)gemm_sm_kernel<BKM, NB, STAGES, MB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_done = true;

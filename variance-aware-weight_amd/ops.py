@@ -252,6 +252,37 @@ def gemm(dt, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, Cp, ldc, *, bias=None,
         tr.add(L.lib().vaw_gemm_uses_bf16_mfma(dt, M, N, K, A, lda, B, ldb), bool(a_kmajor), bool(b_kmajor), M, N, K, e0, e1, float(nb))
 
 
+def default_gemm_knobs(**kw):
+    """vaw_gemm_knobs with every knob at its default and 256 CUs (no environment), then the given fields."""
+    k = L.GemmKnobs()
+    L.lib().vaw_gemm_default_knobs(C.byref(k))
+    for name, v in kw.items():
+        setattr(k, name, v)
+    return k
+
+
+def gemm_plan(dt, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, Cp, ldc, *, workspace_floats=0, knobs=None, colsum_partial_rows=None,
+              check_status=True, **epi):
+    """The launch vaw_gemm makes for this call (vaw_gemm_plan: host arithmetic, no GPU).  Arguments as for gemm(), the addresses used
+    for null-ness and alignment only; colsum_partial_rows = capacity of a colsum_partial buffer (any non-zero address stands for
+    it); knobs = None: the process's own, else a GemmKnobs (default_gemm_knobs).  check_status = False returns the plan of a
+    refused call (status != 0) instead of raising."""
+    e = Epilogue(epi.get("bias") or None, epi.get("act", 0), epi.get("aux_in") or None, epi.get("aux_out") or None, epi.get("gate") or None,
+                 epi.get("gate_ld", 0), epi.get("resid") or None, epi.get("rowadd") or None, epi.get("rows_per_batch", 0),
+                 epi.get("alpha", 1.0), epi.get("beta", 0.0), 1 if epi.get("out_f32") else 0, epi.get("colsum_out") or None,
+                 epi.get("colsum_beta", 0.0), 1 if epi.get("resid_is_act") else 0, epi.get("rowsum_a_out") or None,
+                 epi.get("rowsum_a_beta", 0.0))
+    rows = C.c_int64(colsum_partial_rows or 0)
+    if colsum_partial_rows is not None:
+        e.colsum_partial_out, e.colsum_rows_out = epi.get("colsum_partial_out", 16), C.pointer(rows)
+    p = L.GemmLaunch()
+    rc = L.lib().vaw_gemm_plan(dt, 1 if a_kmajor else 0, 1 if b_kmajor else 0, M, N, K, lda, ldb, ldc, A, B, Cp, C.byref(e),
+                               workspace_floats, C.byref(knobs) if knobs is not None else None, C.byref(p))
+    if check_status:
+        check(rc, "vaw_gemm_plan")
+    return p
+
+
 # ---- fp8 operands ------------------------------------------------------------------------------------
 def fp8_quantize(src_dt, src, R, C_, ld, q, qt, scale, fmt=L.FP8, device=None):
     """Raw-pointer vaw_fp8_quantize: src [R][C] (row stride ld) -> q [R][C] bytes, qt [C][R] bytes (0 = not wanted), scale."""

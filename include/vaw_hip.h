@@ -510,6 +510,12 @@ int64_t vaw_groupnorm_workspace_floats(int B, int HW, int C);
 int vaw_groupnorm_fwd(vaw_dtype dt, const void* x, const float* gamma, const float* beta, const float* scale,
                       const float* shift, int64_t film_ld, int silu, void* y, float* mean, float* rstd, int B, int HW,
                       int C, int G, float eps, float* workspace, vaw_stream stream);
+/* The apply pass of vaw_groupnorm_fwd alone, on GIVEN statistics (mean/rstd: f32 [B*G], as vaw_groupnorm_fwd saved them):
+ * the same kernel under the same dispatch (flat 16-byte bf16 mapping / channel-quad mapping), so for the same x, statistics and
+ * parameters y is bitwise vaw_groupnorm_fwd's.  One pass over x instead of three: activation recomputation (UNet use_checkpoint). */
+int vaw_groupnorm_apply(vaw_dtype dt, const void* x, const float* mean, const float* rstd, const float* gamma,
+                        const float* beta, const float* scale, const float* shift, int64_t film_ld, int silu, void* y, int B,
+                        int HW, int C, int G, vaw_stream stream);
 /* dx = GN'(...) (+ dx_add, act dtype, may be NULL); dgamma/dbeta = grad_beta*old + sum; dscale/dshift rows (stride
  * dfilm_ld) when FiLM.  Fixed-order reductions. */
 int vaw_groupnorm_bwd(vaw_dtype dt, const void* dout, const void* x, const float* mean, const float* rstd,
@@ -552,6 +558,17 @@ int vaw_add_inplace(vaw_dtype dt, void* dst, const void* src, int64_t n, vaw_str
  *   vaw_rowvec_sum  de[b,:] = beta*de[b,:] + sum_p dh[b,p,:]: its backward (fixed-order reduction) */
 int vaw_mul(vaw_dtype dt, const void* a, const void* b, void* out, int64_t n, vaw_stream stream);
 int vaw_subsample2(vaw_dtype dt, const void* in, void* out, int B, int Ho, int Wo, int C, int mode, vaw_stream stream);
+/* nn.Dropout's keep mask at 1 bit per element (what a checkpointed ResBlock keeps: C/8 bytes per pixel instead of 2 C).
+ *   vaw_dropout_pack      mask [M][C] act dtype (keep ? 1/(1-p) : 0, as drawn for vaw_mul) -> bits: element i is bit i % 32 of the
+ *                         32-bit word i / 32 (1 = kept).  bits holds vaw_dropout_bits_words(M * C) words; the unused high bits of the
+ *                         last word are written as 0.  C % 8 != 0: VAW_ERR_INVALID (keep the unpacked mask).
+ *   vaw_dropout_bits_fwd  y  = x  * (bit ? keep_scale : 0)   keep_scale = the mask's non-zero value (1/(1-p) rounded to the act
+ *   vaw_dropout_bits_bwd  dx = dy * (bit ? keep_scale : 0)   dtype): the f32 product and rounding of vaw_mul, so bitwise its result.
+ *                         n % 8 == 0, 16-byte aligned x / y. */
+int64_t vaw_dropout_bits_words(int64_t n);
+int vaw_dropout_pack(vaw_dtype dt, const void* mask, void* bits, int64_t M, int C, vaw_stream stream);
+int vaw_dropout_bits_fwd(vaw_dtype dt, const void* x, const void* bits, float keep_scale, void* y, int64_t n, vaw_stream stream);
+int vaw_dropout_bits_bwd(vaw_dtype dt, const void* dy, const void* bits, float keep_scale, void* dx, int64_t n, vaw_stream stream);
 int vaw_rowvec_add(vaw_dtype dt, void* h, const float* e, int64_t ld, int B, int HW, int C, vaw_stream stream);
 int vaw_rowvec_sum(vaw_dtype dt, const void* dh, float* de, int64_t ld, int B, int HW, int C, float beta, vaw_stream stream);
 int vaw_nchw_to_nhwc(vaw_dtype dt, const float* nchw, void* nhwc, int B, int C, int HW, vaw_stream stream);

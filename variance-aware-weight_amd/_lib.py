@@ -113,6 +113,7 @@ _PROTOS = {
     "vaw_allgather_bucket_start": [_p, _l, _i, _p],
     "vaw_allreduce_bucket_wait": [_p],
     "vaw_groupnorm_fwd": [_i, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p],
+    "vaw_groupnorm_apply": [_i, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p, _i, _i, _i, _i, _p],
     "vaw_groupnorm_bwd": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p, _p, _f, _p, _p, _l, _i, _i, _i, _i, _p, _p],
     "vaw_im2col3x3": [_i, _p, _p, _i, _i, _i, _i, _p],
     "vaw_col2im3x3": [_i, _p, _p, _i, _i, _i, _i, _p],
@@ -130,6 +131,9 @@ _PROTOS = {
     "vaw_add_inplace": [_i, _p, _p, _l, _p],
     "vaw_mul": [_i, _p, _p, _p, _l, _p],
     "vaw_subsample2": [_i, _p, _p, _i, _i, _i, _i, _i, _p],
+    "vaw_dropout_pack": [_i, _p, _p, _l, _i, _p],
+    "vaw_dropout_bits_fwd": [_i, _p, _p, _f, _p, _l, _p],
+    "vaw_dropout_bits_bwd": [_i, _p, _p, _f, _p, _l, _p],
     "vaw_rowvec_add": [_i, _p, _p, _l, _i, _i, _i, _p],
     "vaw_rowvec_sum": [_i, _p, _p, _l, _i, _i, _i, _f, _p],
     "vaw_nchw_to_nhwc": [_i, _p, _p, _i, _i, _i, _p],
@@ -186,6 +190,9 @@ def lib():
         L.vaw_conv3x3_wgrad_small_workspace_floats.restype = _l
         L.vaw_groupnorm_workspace_floats.argtypes = [_i, _i, _i]
         L.vaw_groupnorm_workspace_floats.restype = _l
+        if hasattr(L, "vaw_dropout_bits_words"):
+            L.vaw_dropout_bits_words.argtypes = [_l]
+            L.vaw_dropout_bits_words.restype = _l
         L.vaw_wgrad_grouped_desc_bytes.argtypes = [_i]
         L.vaw_wgrad_grouped_desc_bytes.restype = _l
         L.vaw_reduce_rows_batched_desc_bytes.argtypes = [_i]
@@ -222,7 +229,7 @@ def exported_symbols():
                                    "vaw_sumsq_workspace_floats", "vaw_groupnorm_workspace_floats", "vaw_wgrad_grouped_desc_bytes",
                                    "vaw_conv3x3_wgrad_small_workspace_floats", "vaw_row_bwd_workspace_floats",
                                    "vaw_fp8_quantize_workspace_floats", "vaw_p8_set_reserved_cus", "vaw_reduce_rows_batched_desc_bytes", "vaw_fp8_quantize_batched_desc_bytes",
-                                   "vaw_gemm_default_knobs"])
+                                   "vaw_gemm_default_knobs", "vaw_dropout_bits_words"])
 
 
 def check(rc, what):

@@ -1203,6 +1203,30 @@ static int gnc_try_bwd(vaw_dtype dt, const void* dout, const void* x, const floa
     return 1;
 }
 
+// The apply pass on given statistics, under the dispatch of the streaming forward: the flat 16-byte mapping where gns_ok(), the
+// channel-quad mapping otherwise.  vaw_groupnorm_fwd's last launch and all of vaw_groupnorm_apply.
+static void gn_apply_launch(vaw_dtype dt, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                            const float* scale, const float* shift, int64_t film_ld, int silu, void* y, int B, int HW, int C, int G,
+                            hipStream_t s) {
+    if (gns_ok(dt, B, HW, C, G)) {
+        const GnsGeom gm = gns_geom(C, gns_rows(B, HW));
+        const int nch = ceil_div(HW, gm.rows);
+        const bf16_t* xb = (const bf16_t*)x;
+        bf16_t* yb = (bf16_t*)y;
+#define GNS_APPLY(S, F)                                                                                                              \
+    if ((silu != 0) == S && (scale != nullptr) == F)                                                                                 \
+        gns_apply_kernel<4, S, F><<<B * nch, GNS_NT, 0, s>>>(xb, mean, rstd, gamma, beta, scale, shift, film_ld, yb, HW, C, G, nch, gm);
+        GNS_APPLY(true, true)
+        GNS_APPLY(true, false)
+        GNS_APPLY(false, true)
+        GNS_APPLY(false, false)
+#undef GNS_APPLY
+        return;
+    }
+    dim3 grid(ceil_div(C, 64), B, gn_chunks(HW));
+    BY_DTYPE(dt, (gn_apply_kernel<T><<<grid, 256, 0, s>>>((const T*)x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, (T*)y, HW, C, G)));
+}
+
 extern "C" int vaw_groupnorm_fwd(vaw_dtype dt, const void* x, const float* gamma, const float* beta, const float* scale,
                                  const float* shift, int64_t film_ld, int silu, void* y, float* mean, float* rstd, int B,
                                  int HW, int C, int G, float eps, float* workspace, vaw_stream stream) {
@@ -1221,17 +1245,9 @@ extern "C" int vaw_groupnorm_fwd(vaw_dtype dt, const void* x, const float* gamma
         const GnsGeom gm = gns_geom(C, gns_rows(B, HW));
         const int nch = ceil_div(HW, gm.rows);
         const bf16_t* xb = (const bf16_t*)x;
-        bf16_t* yb = (bf16_t*)y;
         gns_fwd_sums_kernel<8><<<B * nch, GNS_NT, 0, s>>>(xb, HW, C, B, nch, gm, workspace);
         gn_group_stats_kernel<<<ceil_div(B * G, 128), 128, 0, s>>>(workspace, nch, B, C, G, HW, eps, mean, rstd);
-#define GNS_APPLY(S, F)                                                                                                              \
-    if ((silu != 0) == S && (scale != nullptr) == F)                                                                                 \
-        gns_apply_kernel<4, S, F><<<B * nch, GNS_NT, 0, s>>>(xb, mean, rstd, gamma, beta, scale, shift, film_ld, yb, HW, C, G, nch, gm);
-        GNS_APPLY(true, true)
-        GNS_APPLY(true, false)
-        GNS_APPLY(false, true)
-        GNS_APPLY(false, false)
-#undef GNS_APPLY
+        gn_apply_launch(dt, x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, y, B, HW, C, G, s);
         VAW_CHECK_LAUNCH("groupnorm_fwd");
         return VAW_OK;
     }
@@ -1239,8 +1255,22 @@ extern "C" int vaw_groupnorm_fwd(vaw_dtype dt, const void* x, const float* gamma
     dim3 grid(ceil_div(C, 64), B, nch);
     BY_DTYPE(dt, (gn_fwd_sums_kernel<T><<<grid, 256, 0, s>>>((const T*)x, HW, C, B, nch, workspace)));
     gn_group_stats_kernel<<<ceil_div(B * G, 128), 128, 0, s>>>(workspace, nch, B, C, G, HW, eps, mean, rstd);
-    BY_DTYPE(dt, (gn_apply_kernel<T><<<grid, 256, 0, s>>>((const T*)x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, (T*)y, HW, C, G)));
+    gn_apply_launch(dt, x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, y, B, HW, C, G, s);
     VAW_CHECK_LAUNCH("groupnorm_fwd");
+    return VAW_OK;
+}
+
+extern "C" int vaw_groupnorm_apply(vaw_dtype dt, const void* x, const float* mean, const float* rstd, const float* gamma,
+                                   const float* beta, const float* scale, const float* shift, int64_t film_ld, int silu, void* y,
+                                   int B, int HW, int C, int G, vaw_stream stream) {
+    VAW_CHECK_ARG(x && y && mean && rstd && gamma && beta, "groupnorm_apply: null pointer");
+    VAW_CHECK_ARG(dt == VAW_F32 || dt == VAW_BF16, "groupnorm_apply: dtype must be f32 or bf16");
+    VAW_CHECK_ARG(B > 0 && HW > 0 && C > 0 && G > 0 && G <= 64 && C % G == 0 && C % 4 == 0 && B < 65536,
+                  "groupnorm_apply: bad sizes (C=%d G=%d)", C, G);
+    VAW_CHECK_ARG((scale == nullptr) == (shift == nullptr), "groupnorm_apply: scale and shift go together");
+    VAW_CHECK_ARG(!scale || film_ld % 4 == 0, "groupnorm_apply: film_ld must be a multiple of 4");
+    gn_apply_launch(dt, x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, y, B, HW, C, G, (hipStream_t)stream);
+    VAW_CHECK_LAUNCH("groupnorm_apply");
     return VAW_OK;
 }
 
@@ -1396,6 +1426,78 @@ extern "C" int vaw_mul(vaw_dtype dt, const void* a, const void* b, void* out, in
     BY_DTYPE(dt, (mul_kernel<T><<<sgrid(n / 4, 256), 256, 0, (hipStream_t)stream>>>((const T*)a, (const T*)b, (T*)out, n / 4)));
     VAW_CHECK_LAUNCH("mul");
     return VAW_OK;
+}
+
+// nn.Dropout's keep mask at 1 bit per element (what a checkpointed ResBlock keeps).  Pack: a lane owns one 32-bit word = 32 mask
+// elements, read with 16-byte loads (4 for bf16, 8 for f32), and writes it with one plain dword store.  Apply: a lane owns one mask
+// BYTE = 8 elements (one 16-byte access of bf16, two of f32); the product is the f32 multiply and rounding of mul_kernel, with
+// b = keep_scale or 0, so the result is bitwise vaw_mul's with the unpacked mask.
+template <typename T> struct Vec16;
+template <> struct Vec16<bf16_t> { typedef bf16x8 type; static constexpr int N = 8; };
+template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4; };
+template <typename T>
+__global__ void __launch_bounds__(256)
+dropout_pack_kernel(const T* __restrict__ mask, unsigned* __restrict__ bits, int64_t n, int64_t nwords) {
+    typedef typename Vec16<T>::type vec_t;
+    constexpr int V = Vec16<T>::N;
+    for (int64_t w = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; w < nwords; w += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t e0 = 32 * w;
+        unsigned word = 0;
+#pragma unroll
+        for (int g = 0; g < 32 / V; ++g) {
+            if (e0 + g * V < n) {                      // n % 8 == 0: a 16-byte group lies wholly inside or wholly outside
+                const vec_t v = *reinterpret_cast<const vec_t*>(mask + e0 + g * V);
+#pragma unroll
+                for (int j = 0; j < V; ++j) word |= ((float)v[j] != 0.f ? 1u : 0u) << (g * V + j);
+            }
+        }
+        bits[w] = word;
+    }
+}
+template <typename T>
+__global__ void __launch_bounds__(256)
+dropout_bits_kernel(const T* __restrict__ x, const unsigned char* __restrict__ bits, float keep_scale, T* __restrict__ y, int64_t n8) {
+    typedef typename Vec16<T>::type vec_t;
+    constexpr int V = Vec16<T>::N;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned m = bits[i];
+#pragma unroll
+        for (int g = 0; g < 8 / V; ++g) {
+            const vec_t v = *reinterpret_cast<const vec_t*>(x + 8 * i + g * V);
+            vec_t o;
+#pragma unroll
+            for (int j = 0; j < V; ++j) o[j] = from_f32<T>(to_f32(v[j]) * (((m >> (g * V + j)) & 1u) ? keep_scale : 0.f));
+            *reinterpret_cast<vec_t*>(y + 8 * i + g * V) = o;
+        }
+    }
+}
+extern "C" int64_t vaw_dropout_bits_words(int64_t n) { return n > 0 ? (n + 31) / 32 : 0; }
+extern "C" int vaw_dropout_pack(vaw_dtype dt, const void* mask, void* bits, int64_t M, int C, vaw_stream stream) {
+    VAW_CHECK_ARG(mask && bits, "dropout_pack: null pointer");
+    VAW_CHECK_ARG(dt == VAW_F32 || dt == VAW_BF16, "dropout_pack: dtype must be f32 or bf16");
+    VAW_CHECK_ARG(M > 0 && C > 0 && C % 8 == 0, "dropout_pack: C must be a positive multiple of 8 (C=%d)", C);
+    VAW_CHECK_ARG((uintptr_t)mask % 16 == 0 && (uintptr_t)bits % 4 == 0, "dropout_pack: mask must be 16-byte aligned, bits 4-byte");
+    const int64_t n = M * C, nwords = vaw_dropout_bits_words(n);
+    BY_DTYPE(dt, (dropout_pack_kernel<T><<<sgrid(nwords, 256), 256, 0, (hipStream_t)stream>>>((const T*)mask, (unsigned*)bits, n, nwords)));
+    VAW_CHECK_LAUNCH("dropout_pack");
+    return VAW_OK;
+}
+static int dropout_bits_apply(const char* what, vaw_dtype dt, const void* x, const void* bits, float keep_scale, void* y, int64_t n,
+                              vaw_stream stream) {
+    VAW_CHECK_ARG(x && bits && y, "%s: null pointer", what);
+    VAW_CHECK_ARG(dt == VAW_F32 || dt == VAW_BF16, "%s: dtype must be f32 or bf16", what);
+    VAW_CHECK_ARG(n > 0 && n % 8 == 0, "%s: n must be a positive multiple of 8", what);
+    VAW_CHECK_ARG(((uintptr_t)x | (uintptr_t)y) % 16 == 0, "%s: x and y must be 16-byte aligned", what);
+    BY_DTYPE(dt, (dropout_bits_kernel<T><<<sgrid(n / 8, 256), 256, 0, (hipStream_t)stream>>>((const T*)x, (const unsigned char*)bits,
+                                                                                             keep_scale, (T*)y, n / 8)));
+    VAW_CHECK_LAUNCH(what);
+    return VAW_OK;
+}
+extern "C" int vaw_dropout_bits_fwd(vaw_dtype dt, const void* x, const void* bits, float keep_scale, void* y, int64_t n, vaw_stream stream) {
+    return dropout_bits_apply("dropout_bits_fwd", dt, x, bits, keep_scale, y, n, stream);
+}
+extern "C" int vaw_dropout_bits_bwd(vaw_dtype dt, const void* dy, const void* bits, float keep_scale, void* dx, int64_t n, vaw_stream stream) {
+    return dropout_bits_apply("dropout_bits_bwd", dt, dy, bits, keep_scale, dx, n, stream);
 }
 
 // mode 0: out[b,i,j,:] = in[b,2i,2j,:]  (the even pixels: a stride-2 conv is the stride-1 conv sampled there)

@@ -784,3 +784,23 @@ def cast_bf16(src, dst):
 def uncast_bf16(src, dst, scale=1.0):
     """dst (f32) = scale * src (bf16), on the current stream."""
     check(L.lib().vaw_uncast_bf16(ptr(src), ptr(dst), src.numel(), float(scale), stream_ptr()), "vaw_uncast_bf16")
+
+
+# ---- UNet activation recomputation (unet.py: use_checkpoint) ------------------------------------------------
+def groupnorm_apply(dt, x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, y, B, HW, C, G=32):
+    """The apply pass of vaw_groupnorm_fwd on saved statistics (raw pointers; scale / shift 0 = no FiLM)."""
+    check(L.lib().vaw_groupnorm_apply(dt, x, mean, rstd, gamma, beta, scale or None, shift or None, film_ld, 1 if silu else 0, y,
+                                      B, HW, C, G, stream_ptr()), "vaw_groupnorm_apply")
+
+
+def dropout_pack(dt, mask, M, C):
+    """[M, C] act-dtype keep mask (keep ? 1/(1-p) : 0) -> int32 words, 1 bit per element."""
+    bits = torch.empty(L.lib().vaw_dropout_bits_words(M * C), device=mask.device, dtype=torch.int32)
+    check(L.lib().vaw_dropout_pack(dt, ptr(mask), ptr(bits), M, C, stream_ptr()), "vaw_dropout_pack")
+    return bits
+
+
+def dropout_bits(dt, x, bits, keep_scale, y, n, backward=False):
+    """y = x * (bit ? keep_scale : 0): bitwise vaw_mul with the unpacked mask (raw pointers for x / y)."""
+    fn = L.lib().vaw_dropout_bits_bwd if backward else L.lib().vaw_dropout_bits_fwd
+    check(fn(dt, x, ptr(bits), keep_scale, y, n, stream_ptr()), "vaw_dropout_bits_bwd" if backward else "vaw_dropout_bits_fwd")

@@ -68,14 +68,14 @@ class Trainer:
             if inner.compute_dtype != want:
                 inner.set_compute_dtype(want)
         # args.activation_checkpointing (optional, default off; an extension): the DiT recomputes each block's activations in
-        # backward instead of keeping them (dit.py).  The UNets' use_checkpoint stays a no-op, which is numerically what the
-        # reference's flag does
+        # backward instead of keeping them (dit.py); the UNets do the same per ResBlock / AttentionBlock, which is what the
+        # reference's use_checkpoint wraps (unet.py: _ckpt_unit).  Numerically the flag changes nothing
         ckpt = getattr(args, "activation_checkpointing", None)      # absent: the model stays as it was built (default: off)
         if ckpt is not None and hasattr(inner, "set_activation_checkpointing"):
             if inner.activation_checkpointing != bool(ckpt):
                 inner.set_activation_checkpointing(ckpt)
         elif ckpt:
-            raise ValueError(f"args.activation_checkpointing: {type(inner).__name__} has no activation recomputation (the DiT models do)")
+            raise ValueError(f"args.activation_checkpointing: {type(inner).__name__} has no activation recomputation (the DiT and UNet models do)")
         if hasattr(inner, "host_dropout_rng"):
             inner.host_dropout_rng = bool(getattr(args, "cpu_rng", False))      # dropout masks from the CPU stream in parity runs
         self._fused = isinstance(optimizer, FusedAdamW)

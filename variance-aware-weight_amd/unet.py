@@ -14,6 +14,10 @@ Data layout in HBM: activations are NHWC -- a [B*H*W, C] row-major matrix in the
 All ResBlocks' `emb_layers` Linear weights are packed into one matrix: one GEMM produces every block's FiLM
 (scale, shift) from SiLU(emb).  Forward builds a short tape of coarse ops; backward walks it in reverse (no
 torch autograd graph inside the model).
+
+`use_checkpoint=True` (the reference's flag, tools/nn.py::checkpoint around every ResBlock._forward / AttentionBlock._forward) =
+`activation_checkpointing`: each ResBlock and AttentionBlock becomes ONE tape entry that keeps its input, its output, the
+GroupNorm statistics and the dropout mask at 1 bit per element, and re-runs the unit onto a private tape in backward (_ckpt_unit).
 """
 
 import torch
@@ -136,6 +140,27 @@ class _Act:
         return self.B * self.H * self.W
 
 
+class _CkptState:
+    """What a checkpointed unit keeps besides its input and output: per GroupNorm the [B*32] statistics, per dropout the mask
+    (packed to 1 bit per element where C % 8 == 0) and whether the unit ran in training mode.  The first forward appends, the
+    recomputation reads in the same order."""
+    __slots__ = ("gn", "drop", "training", "replay", "_i", "_j")
+
+    def __init__(self, training):
+        self.gn, self.drop, self.training, self.replay, self._i, self._j = [], [], training, False, 0, 0
+
+    def rewind(self):
+        self.replay, self._i, self._j = True, 0, 0
+
+    def next_gn(self):
+        self._i += 1
+        return self.gn[self._i - 1]
+
+    def next_drop(self):
+        self._j += 1
+        return self.drop[self._j - 1]
+
+
 class UNetModel(FlatModule):
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions,
                  dropout=0, channel_mult=(1, 2, 4, 8), conv_resample=True, dims=2, num_classes=0, use_checkpoint=False,
@@ -154,6 +179,7 @@ class UNetModel(FlatModule):
         self.out_channels, self.num_classes, self.drop_label_prob = out_channels, num_classes, drop_label_prob
         self.num_res_blocks, self.attention_resolutions, self.channel_mult = num_res_blocks, attention_resolutions, channel_mult
         self.dropout = dropout
+        self.use_checkpoint = self.activation_checkpointing = bool(use_checkpoint)
         ted = 512 if in_channels == 4 else model_channels * 4
         self.time_embed_dim = ted
         self.time_embed = nn.Sequential(nn.Linear(model_channels, ted), nn.SiLU(), nn.Linear(ted, ted))
@@ -207,6 +233,7 @@ class UNetModel(FlatModule):
         self.set_compute_dtype(compute_dtype)
         self._anchor = torch.zeros(1, requires_grad=True)
         self._tape, self._tape_gen, self._rec, self._record_next = [], 0, True, True
+        self._ck, self._ckpt_fwd, self._keep_scales = None, False, {}
         # nn.Dropout inside the ResBlocks (--dropout, reference main.py:99): True = the keep masks come from the CPU generator, in the
         # order and shapes the reference's CPU run draws them (parity runs; set by Trainer from args.cpu_rng); False = device RNG
         self.host_dropout_rng = False
@@ -234,6 +261,12 @@ class UNetModel(FlatModule):
             self.require_fresh_masters("set_compute_dtype()")
         self.compute_dtype = name
         self._dt = BF16 if name == "bf16" else F32
+
+    def set_activation_checkpointing(self, on):
+        """Activation recomputation (the reference's use_checkpoint): every ResBlock / AttentionBlock keeps its input, its output,
+        its GroupNorm statistics and its dropout bits; backward re-runs the unit right before back-propagating through it.  Same
+        output and gradients, bit for bit.  Takes effect at the next forward."""
+        self.use_checkpoint = self.activation_checkpointing = bool(on)
 
     def _apply(self, fn, recurse=True):
         r = super()._apply(fn, recurse)
@@ -298,13 +331,21 @@ class UNetModel(FlatModule):
         name = mod._vaw_name
         B, HW, C, dt, lib = a.B, a.H * a.W, a.C, self._dt, L.lib()
         y = _Act(self._new(a.M, C), B, a.H, a.W, C)
-        mean, rstd = self._new(B * 32, dtype=torch.float32), self._new(B * 32, dtype=torch.float32)
         gam, bet = self._p32(name + ".weight"), self._p32(name + ".bias")
         sc = film
         sh = film + 4 * C if film else 0
-        ws = ops.scratch_f32(self._flat.device, lib.vaw_groupnorm_workspace_floats(B, HW, C))
-        L.check(lib.vaw_groupnorm_fwd(dt, ptr(a.t), gam, bet, sc or None, sh or None, self.emb_cols, 1 if silu else 0,
-                                      ptr(y.t), ptr(mean), ptr(rstd), B, HW, C, 32, 1e-5, ptr(ws), L.stream_ptr()), "groupnorm_fwd")
+        ck = self._ck
+        if ck is not None and ck.replay:
+            # recomputation: the statistics of the first forward, one apply pass instead of sums + group + apply
+            mean, rstd = ck.next_gn()
+            ops.groupnorm_apply(dt, ptr(a.t), ptr(mean), ptr(rstd), gam, bet, sc, sh, self.emb_cols, silu, ptr(y.t), B, HW, C)
+        else:
+            mean, rstd = self._new(B * 32, dtype=torch.float32), self._new(B * 32, dtype=torch.float32)
+            ws = ops.scratch_f32(self._flat.device, lib.vaw_groupnorm_workspace_floats(B, HW, C))
+            L.check(lib.vaw_groupnorm_fwd(dt, ptr(a.t), gam, bet, sc or None, sh or None, self.emb_cols, 1 if silu else 0,
+                                          ptr(y.t), ptr(mean), ptr(rstd), B, HW, C, 32, 1e-5, ptr(ws), L.stream_ptr()), "groupnorm_fwd")
+            if ck is not None:
+                ck.gn.append((mean, rstd))
 
         def bw():
             dx = self._new(a.M, C)
@@ -466,21 +507,46 @@ class UNetModel(FlatModule):
     def _dropout(self, a, p):
         """nn.Dropout(p) in training mode: a * keep / (1 - p).  The mask is drawn like at::dropout draws it,
         empty_like(input).bernoulli_(1 - p) over the NCHW tensor, from the CPU generator in parity runs."""
-        if self.host_dropout_rng:
-            keep = torch.empty(a.B, a.C, a.H, a.W).bernoulli_(1 - p).div_(1 - p)
-            mask = keep.permute(0, 2, 3, 1).reshape(a.M, a.C).to(self._flat.device, self._adt)
+        ck, n = self._ck, a.M * a.C
+        if ck is not None and ck.replay:
+            mask, bits, ks = ck.next_drop()          # the first forward's draw is replayed, never re-drawn: the RNG stream does not move
         else:
-            mask = (torch.rand(a.M, a.C, device=self._flat.device) < (1 - p)).to(self._adt).mul_(1.0 / (1 - p))
+            if self.host_dropout_rng:
+                keep = torch.empty(a.B, a.C, a.H, a.W).bernoulli_(1 - p).div_(1 - p)
+                mask = keep.permute(0, 2, 3, 1).reshape(a.M, a.C).to(self._flat.device, self._adt)
+            else:
+                mask = (torch.rand(a.M, a.C, device=self._flat.device) < (1 - p)).to(self._adt).mul_(1.0 / (1 - p))
+            bits = ks = None
+            if ck is not None:
+                if a.C % 8 == 0:                     # a checkpointed unit keeps C/8 bytes per pixel instead of the act-dtype mask
+                    bits, ks, mask = ops.dropout_pack(self._dt, mask, a.M, a.C), self._keep_scale(p), None
+                ck.drop.append((mask, bits, ks))
         y = _Act(self._new(a.M, a.C), a.B, a.H, a.W, a.C)
-        L.check(L.lib().vaw_mul(self._dt, ptr(a.t), ptr(mask), ptr(y.t), a.M * a.C, L.stream_ptr()), "mul")
+        if bits is not None:
+            ops.dropout_bits(self._dt, ptr(a.t), bits, ks, ptr(y.t), n)
+        else:
+            L.check(L.lib().vaw_mul(self._dt, ptr(a.t), ptr(mask), ptr(y.t), n, L.stream_ptr()), "mul")
 
         def bw():
             dx = self._new(a.M, a.C)
-            L.check(L.lib().vaw_mul(self._dt, ptr(y.grad), ptr(mask), ptr(dx), a.M * a.C, L.stream_ptr()), "mul")
+            if bits is not None:
+                ops.dropout_bits(self._dt, ptr(y.grad), bits, ks, ptr(dx), n, backward=True)
+            else:
+                L.check(L.lib().vaw_mul(self._dt, ptr(y.grad), ptr(mask), ptr(dx), n, L.stream_ptr()), "mul")
             self._acc(a, dx)
             y.grad = None
         self._push(bw)
         return y
+
+    def _keep_scale(self, p):
+        """The non-zero value of _dropout's mask, made by the same torch operations on one element (host: f32 1 / (1 - p) cast to
+        the act dtype; device: act-dtype 1 times the scalar 1 / (1 - p)), so that the packed path multiplies by the same number."""
+        key = (p, self.host_dropout_rng, self._adt)
+        ks = self._keep_scales.get(key)
+        if ks is None:
+            one = torch.ones(1).div_(1 - p).to(self._adt) if self.host_dropout_rng else torch.ones(1, dtype=self._adt).mul_(1.0 / (1 - p))
+            ks = self._keep_scales[key] = float(one)
+        return ks
 
     def _add_emb(self, a, off):
         """h + emb_out (use_scale_shift_norm=False, reference :250-252): the block's row of the packed emb_layers output is added
@@ -522,7 +588,8 @@ class UNetModel(FlatModule):
             h = self._gn(h, rb.out_layers[0], silu=True, film=self._emb_base + 4 * rb.emb_off)
         else:
             h = self._gn(self._add_emb(h, rb.emb_off), rb.out_layers[0], silu=True)
-        if rb.dropout > 0 and self.training:
+        ck = self._ck
+        if rb.dropout > 0 and (ck.training if ck is not None else self.training):
             h = self._dropout(h, rb.dropout)
         if isinstance(rb.skip_connection, nn.Identity):
             skip = x
@@ -535,9 +602,9 @@ class UNetModel(FlatModule):
     def _run(self, seq, h):
         for layer in seq:
             if isinstance(layer, ResBlock):
-                h = self._resblock(h, layer)
+                h = self._ckpt_unit(self._resblock, h, layer)
             elif isinstance(layer, AttentionBlock):
-                h = self._attention(h, layer)
+                h = self._ckpt_unit(self._attention, h, layer)
             elif isinstance(layer, nn.Conv2d):
                 h = self._conv3(h, layer)
             elif isinstance(layer, Downsample):
@@ -553,6 +620,38 @@ class UNetModel(FlatModule):
             else:
                 raise TypeError(type(layer))
         return h
+
+    def _ckpt_unit(self, fn, x, layer):
+        """One ResBlock / AttentionBlock (the reference's checkpoint units).  Flag off, or a forward that records nothing: the plain
+        op-by-op tape.  Flag on: the unit runs without a tape, so its intermediates go back to the allocator as they fall out of
+        scope, and ONE closure is pushed; it re-runs the unit from its input onto a private tape (GroupNorm on the saved statistics,
+        dropout from the saved bits), hands the output's gradient to the recomputed output -- a fresh tensor, the first forward's
+        output is still read by later closures -- and pops the private tape.  The backward launches are those of the plain tape in
+        the same order; only the deferred weight gradients are grouped per unit (a grouped problem's result does not depend on its
+        group), flushed here so that the recomputed operands can go."""
+        if not (self._ckpt_fwd and self._rec):
+            return fn(x, layer)
+        st = _CkptState(self.training)
+        self._ck, self._rec = st, False
+        try:
+            y = fn(x, layer)
+        finally:
+            self._ck, self._rec = None, True
+
+        def bw():
+            outer, self._tape, self._ck = self._tape, [], st
+            st.rewind()
+            try:
+                y2 = fn(x, layer)
+                tape = self._tape
+            finally:
+                self._tape, self._ck = outer, None
+            y2.grad, y.grad = y.grad, None
+            for b in reversed(tape):
+                b()
+            self._flush_wgrads()
+        self._push(bw)
+        return y
 
     def _stage_done(self, stage):
         self._flush_wgrads()
@@ -628,6 +727,7 @@ class UNetModel(FlatModule):
                     setattr(self, k, v)
         self._rec = True
         self._tape_gen += 1
+        self._ckpt_fwd = bool(self.activation_checkpointing)
         return self._forward_body(x, t, y, need_dx)
 
     def _forward_body(self, x, t, y, need_dx):
@@ -762,6 +862,9 @@ class _UNetFn(torch.autograd.Function):
         if not m._tape or m._tape_gen != ctx.gen:
             raise L.VawError("UNet backward: the tape of this forward was already consumed, or a later forward of the same "
                              "module replaced it (run sampling / evaluation forwards under torch.no_grad())")
+        if m._ckpt_fwd != bool(m.activation_checkpointing):
+            raise L.VawError("UNet backward: activation_checkpointing was switched between this forward and its backward "
+                             "(the tape of the forward was built for the other mode)")
         dx = m._backward_impl(dout.contiguous())
         return torch.zeros_like(m._anchor), None, dx, None, None
 
@@ -783,7 +886,7 @@ def create_unet_model(image_size, num_channels, num_res_blocks, channel_mult="",
     return UNetModel(image_size=image_size, in_channels=in_channels, model_channels=num_channels,
                      out_channels=(2 * in_channels if learn_sigma else in_channels), num_res_blocks=num_res_blocks,
                      attention_resolutions=att, dropout=dropout, channel_mult=channel_mult,
-                     num_classes=(num_classes if class_cond else 0), num_heads=num_heads,
+                     num_classes=(num_classes if class_cond else 0), use_checkpoint=use_checkpoint, num_heads=num_heads,
                      num_head_channels=num_head_channels, num_heads_upsample=num_heads_upsample,
                      use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown,
                      use_new_attention_order=use_new_attention_order, drop_label_prob=drop_label_prob, **kw)

@@ -117,6 +117,34 @@ int vaw_ddim_reverse_step(const float* mean_out, int64_t model_ld, const float* 
                           float* sample, float* pred_xstart, int B, int64_t per_sample, vaw_stream stream);
 
 /* ---------------------------------------------------------------------------
+ * Loss-aware timestep sampling on the device  (tools/resample.py: LossSecondMomentResampler)
+ * ------------------------------------------------------------------------- */
+
+/* Most timesteps vaw_resampler_draw takes: its one workgroup keeps p and the CDF in LDS, 16 bytes per timestep. */
+#define VAW_RESAMPLER_MAX_T 4096
+
+/* update_with_all_losses :127-141 as the ring the package keeps: for i = 0 .. n-1 IN ORDER
+ *   ring[ts[i]][seen[ts[i]] % H] = (double)losses[i];  seen[ts[i]] += 1
+ * ring: f64 [T][H], seen: i64 [T].  One thread owns one timestep and walks the batch in order (no atomics), so entries of one
+ * call with the same t land in consecutive slots in batch order (wrapping inside a call included) and the result is bitwise
+ * reproducible whatever the launch shape.  An entry with t outside [0, T) is skipped and counted: bad[0] += 1. */
+int vaw_resampler_update(const int64_t* ts, const float* losses, int n, int T, int H, double* ring, int64_t* seen, int* bad,
+                         vaw_stream stream);
+
+/* weights() :116-125 + ScheduleSampler.sample :38-50 with the uniforms supplied (np.random.choice(p=...) is a right-sided
+ * search of the normalised running sum of p):
+ *   warm = all(seen >= H);   not warm: p[t] = 1 / T;
+ *   warm: w[t] = sqrt(mean_j ring[t][j]^2),  p[t] = w[t] / sum(w) * (1 - uniform_prob) + uniform_prob / T;
+ *   c = cumsum(p), c /= c[T-1];   out_t[b] = #{t : c[t] <= u[b]} (clamped to T-1);   out_w[b] = (float)(1 / (T * p[out_t[b]])).
+ * All arithmetic is IEEE f64, one rounding per operation (no contraction), in these fixed orders: the mean of squares adds
+ * j = 0 .. H-1 ascending into one accumulator, then divides by H; sum(w) forms 64 partial sums, partial l = w[l] + w[l+64] +
+ * w[l+128] + ... ascending, then adds the partials l = 0 .. 63 ascending; c is summed strictly left to right.
+ * u: f64 [B] uniforms of [0, 1); out_t: i64 [B]; out_w: f32 [B]; p: f64 [T], always written.  One workgroup:
+ * T > VAW_RESAMPLER_MAX_T is refused with VAW_ERR_INVALID. */
+int vaw_resampler_draw(const double* ring, const int64_t* seen, int T, int H, double uniform_prob, const double* u, int B,
+                       int64_t* out_t, float* out_w, double* p, vaw_stream stream);
+
+/* ---------------------------------------------------------------------------
  * Dense layers  (nn.Linear / Conv2d(k=p,s=p) / Conv1d(k=1) in models/dit.py, models/unet.py;
  * cuBLAS in the reference).  One GEMM entry point, MFMA inside.
  * ------------------------------------------------------------------------- */

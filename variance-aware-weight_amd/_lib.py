@@ -73,6 +73,8 @@ GC_NONE, GC_FOLD, GC_DEFERRED, GC_SEPARATE = range(4)
 P8_STORE, P8_GELU, P8_DGELU, P8_GATE, P8_SLAB, P8_ANY, P8_WGRAD, P8_RESID = range(8)
 
 # vaw_row_kind / vaw_row_variant
+RESAMPLER_MAX_T = 4096      # VAW_RESAMPLER_MAX_T
+
 ROW_LN_FWD, ROW_LN_FWD_FP8, ROW_LN_BWD, ROW_GATE_BWD, ROW_GATE_BWD_FP8, ROW_LN_BWD_GATE, ROW_LN_BWD_GATE_FP8, ROW_COLSUM = range(8)
 RV_LN_FWD, RV_ROW_BWD, RV_ROW_GATE, RV_ROW_FUSE, RV_ROW_FUSE8, RV_COLSUM_BF16X8, RV_COLSUM_VEC4, RV_COLSUM_SCALAR = range(8)
 
@@ -124,6 +126,8 @@ _PROTOS = {
     "vaw_bpd_terms": [_p, _p, _l, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _l, _i, _i, _l, _p],
     "vaw_prior_bpd": [_p, _f, _f, _p, _i, _l, _p],
     "vaw_ddim_reverse_step": [_p, _l, _p, _p, _i, _p, _p, _i, _l, _p],
+    "vaw_resampler_update": [_p, _p, _i, _i, _i, _p, _p, _p, _p],
+    "vaw_resampler_draw": [_p, _p, _i, _i, C.c_double, _p, _i, _p, _p, _p, _p],
     "vaw_conv3x3_narrow": [_i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "vaw_conv3x3_wgrad_small": [_i, _p, _p, _p, _f, _i, _i, _i, _i, _i, _p, _l, _p],
     "vaw_resample2": [_i, _p, _p, _i, _i, _i, _i, _i, _f, _p],

@@ -96,12 +96,15 @@ class Trainer:
         # optional importance sampling of t (resample.py exists in the reference but its Trainer never
         # calls it).  args.schedule_sampler = "loss-second-moment": t ~ sampler, loss = mean(w_t * loss_t) with the
         # sampler's 1/(T p_t) weights (guided-diffusion's TrainLoop), history updated from the per-sample losses
-        self.schedule_sampler = None
+        self.schedule_sampler, self._device_sampler = None, False
         name = getattr(args, "schedule_sampler", None)
         if name and name != "uniform":
             from .resample import create_named_schedule_sampler
-            self.schedule_sampler = create_named_schedule_sampler(name, diffusion)
-            if getattr(args, "hip_graph", False):
+            self.schedule_sampler = create_named_schedule_sampler(name, diffusion, device=device)
+            # "loss-second-moment-device" keeps the history in device memory: draw and update are two kernels of the step (no
+            # host synchronisation; captured with it under args.hip_graph).  The host sampler reads the losses back every step
+            self._device_sampler = hasattr(self.schedule_sampler, "ring")
+            if getattr(args, "hip_graph", False) and not self._device_sampler:
                 raise ValueError("args.schedule_sampler updates its history on the host every step: not with args.hip_graph")
         # hipGraph mode
         self._graph, self._graph_calls, self._gin, self._gout = None, 0, None, None
@@ -135,15 +138,17 @@ class Trainer:
 
     def _compute_loss(self, images, labels, features):
         model_kwargs = {"y": labels} if self.args.class_cond else {}
-        if self._cpu_rng:
+        if self._cpu_rng and not self._device_sampler:
             # parity runs: noise, then t, from the CPU generator, in the reference's order
             # (tools/gaussian_diffusion.py:849-852); both are accepted keyword arguments there too
             noise = torch.randn(images.shape).to(images.device)
             t = torch.randint(0, self.diffusion.num_timesteps, (images.shape[0],)).to(images.device)
             return self.diffusion.training_losses(self.model, images, features, t=t, model_kwargs=model_kwargs, noise=noise)
         if self.schedule_sampler is not None:
+            # (device sampler with args.cpu_rng: noise from the CPU generator, then the sampler's uniforms from numpy's)
+            noise = torch.randn(images.shape).to(images.device) if self._cpu_rng else None
             t, w = self.schedule_sampler.sample(images.shape[0], images.device)
-            terms = self.diffusion.training_losses(self.model, images, features, t=t, model_kwargs=model_kwargs)
+            terms = self.diffusion.training_losses(self.model, images, features, t=t, model_kwargs=model_kwargs, noise=noise)
             self.schedule_sampler.update_with_local_losses(t, terms["loss"].detach())
             terms = dict(terms)
             terms["loss"] = terms["loss"] * w

@@ -116,6 +116,37 @@ int vaw_prior_bpd(const float* x0, float sqrt_abar_last, float log_one_minus_aba
 int vaw_ddim_reverse_step(const float* mean_out, int64_t model_ld, const float* x, const float* coef, int clip_denoised,
                           float* sample, float* pred_xstart, int B, int64_t per_sample, vaw_stream stream);
 
+/* Sampler (tools/sampler.py): one reverse-process step with classifier-free guidance fused in.  The guided model call
+ * evaluates the batch stacked on itself (IntervalCFG.forward :41-48), so its [2N, 2C, H, W] output holds four quarters:
+ * conditional / unconditional half of the batch, mean / variance channels.  They are read in place: row b of each of
+ * mean_cond, mean_uncond, var_cond, var_uncond starts model_ld floats after row b-1 (model_ld >= per_sample).  Per element
+ *   m = mean_uncond + guidance_scale * (mean_cond - mean_uncond),   v likewise from the variance quarters
+ * in f32 with the difference, the product and the sum each rounded on its own (no fused multiply-add), i.e. bitwise the
+ * three tensor operations of :48, which guide every output channel.  Then exactly the per-element body of vaw_sample_step
+ * (one shared device function): kind, coef, mean_mode, var_mode, clip_denoised, eta and the optional outputs as there.
+ * mean_uncond == NULL: no guidance, the plain step reading the split halves of a [N, 2C, H, W] output in place
+ * (guidance_scale and var_uncond are ignored).  var_cond may be NULL with var_mode 0; var_uncond is needed only when both
+ * guided and var_mode != 0.  x, noise and the outputs are [B, per_sample] contiguous.  16-byte loads and stores when
+ * per_sample % 4 == 0, model_ld % 4 == 0 and every pointer is 16-byte aligned, scalar ones otherwise. */
+int vaw_guided_sample_step(int kind, const float* mean_cond, const float* mean_uncond, const float* var_cond,
+                           const float* var_uncond, int64_t model_ld, float guidance_scale, const float* x, const float* noise,
+                           const float* coef, int mean_mode, int var_mode, int clip_denoised, float eta, float* sample,
+                           float* pred_xstart, float* mean, float* log_variance, int B, int64_t per_sample, vaw_stream stream);
+
+/* The combination alone (guided EDM / flow samplers, whose update stays outside):
+ *   out[b,:] = uncond[b,:] + guidance_scale * (cond[b,:] - uncond[b,:])     with the rounding rule above.
+ * cond / uncond rows are model_ld floats apart, out is [B, per_sample] contiguous. */
+int vaw_cfg_combine(const float* cond, const float* uncond, int64_t model_ld, float guidance_scale, float* out, int B,
+                    int64_t per_sample, vaw_stream stream);
+
+/* _inverse_normalize :257-258:  ((x + 1) * 127.5).clamp(0, 255).to(uint8).permute(0, 2, 3, 1) in one pass.
+ * src: [B, C, H, W] contiguous, f32 (src_f64 = 0) or f64 (src_f64 = 1: EDM samples are finished in float64 as the
+ * reference does); dst: [B, H, W, C] contiguous bytes, any alignment.  v = (x + 1) * 127.5 is formed in the source precision,
+ * sum and product rounded separately, clamped to [0, 255] and truncated toward zero: for finite x bitwise the expression
+ * above.  NaN writes 0.  Any C >= 1.  Destination words that lie wholly inside dst are written as 32-bit words, the ragged
+ * first / last bytes singly; nothing outside [dst, dst + B*H*W*C) is touched. */
+int vaw_finish_images(const void* src, int src_f64, uint8_t* dst, int B, int C, int H, int W, vaw_stream stream);
+
 /* ---------------------------------------------------------------------------
  * Loss-aware timestep sampling on the device  (tools/resample.py: LossSecondMomentResampler)
  * ------------------------------------------------------------------------- */

@@ -1,0 +1,196 @@
+#!/usr/bin/env python3
+"""Sampler timings on one GPU (fixed work, warm-up first, device events or a host clock around a device synchronise).
+    python tools/sample_bench.py [--model UNet_32] [--batch 256] [--steps 50] [--iters 200] [--fp32]
+
+For a learn_sigma model under IntervalCFG (scale 2.5, active on part of the chain) over a respaced LEARNED_RANGE chain:
+ (a) one guided DDIM step, fused: the stacked model call + vaw_guided_sample_step, the interval decided on the host;
+ (b) the same step through the composition of existing pieces (what the step was before the fused kernel): the model call,
+     the mean timestep read back from the device, three torch ops, the split halves made contiguous, vaw_sample_step.
+     Both are also timed WITHOUT the model call (the step's tail alone over rotating buffers larger than the 256 MiB
+     Infinity Cache), which is where the byte arithmetic of DESIGN applies;
+ (c) vaw_finish_images against the torch expression, f32 and f64, rotating buffers;
+ (d) a full Sampler.sample of one batch (DDIM, `--steps` steps), fused and through the composition of (b).
+(a) / (b) and the two forms of (c) / (d) alternate inside one timed run.  One JSON line at the end."""
+import argparse
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import vaw_amd  # noqa: E402
+from vaw_amd import ops  # noqa: E402
+
+SCALE = 2.5
+
+
+class CompositionCFG(torch.nn.Module):
+    """IntervalCFG without guided_halves: the predicate read back from the device and three tensor operations."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+
+    def forward(self, x, t, **kw):
+        if not self.cfg.guidance_active(float(t.float().mean())):
+            return self.cfg.model(x, t, **kw)
+        n, y = x.shape[0], kw["y"]
+        out = self.cfg.model(x.repeat(2, 1, 1, 1), t.repeat(2), **{**kw, "y": torch.cat((y, y.new_full(y.shape, self.cfg.null_label)))})
+        out = out[0] if isinstance(out, tuple) else out
+        return out[n:] + self.cfg.guidance_scale * (out[:n] - out[n:])
+
+
+class CompositionSampler(vaw_amd.Sampler):
+    def _build_cfg_model(self, num_classes):
+        return CompositionCFG(super()._build_cfg_model(num_classes)).eval()
+
+    def _inverse_normalize(self, samples):
+        return ((samples + 1) * 127.5).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def events_us(fns, iters):
+    """Mean time per call in us: the callables alternate, warm-up of each first."""
+    for f in fns:
+        f()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for i in range(iters):
+        fns[i % len(fns)]()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / iters
+
+
+def wall_pair(fa, fb, repeats):
+    """Medians in seconds of two callables that end in a device synchronise, alternating."""
+    fa(), fb()
+    ta, tb = [], []
+    for _ in range(repeats):
+        for f, ts in ((fa, ta), (fb, tb)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+    return sorted(ta)[len(ta) // 2], sorted(tb)[len(tb) // 2]
+
+
+def build_model(a):
+    dt = "fp32" if a.fp32 else "bf16"
+    if a.model.startswith("DiT"):
+        model = vaw_amd.DiT_models[a.model.replace("_", "-")](image_size=a.image_size or 32, patch_size=a.patch, in_channels=4, class_dropout_prob=0.1,
+                                                              num_classes=a.num_classes, learn_sigma=True, compute_dtype=dt)
+        C, H = 4, a.image_size or 32
+    else:
+        model = getattr(vaw_amd, a.model)(num_classes=a.num_classes, class_cond=True, learn_sigma=True, drop_label_prob=0.1, compute_dtype=dt)
+        C, H = model.in_channels, model.image_size
+    model = model.to("cuda").eval()
+    with torch.no_grad():
+        for p in model.parameters():          # zero-initialised output layers would make every step trivial
+            if p.requires_grad:
+                p.add_(torch.randn_like(p) * 0.02)
+    if hasattr(model, "mark_weights_changed"):
+        model.mark_weights_changed()
+    return model, C, H
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="UNet_32")
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--image-size", type=int, default=0)
+    ap.add_argument("--patch", type=int, default=2)
+    ap.add_argument("--num-classes", type=int, default=10)
+    ap.add_argument("--fp32", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sample_bench.py measures on the GPU only")
+    torch.manual_seed(0)
+    model, C, H = build_model(a)
+    N, n = a.batch, C * H * H
+    args = SimpleNamespace(weight_type="lambda", gamma=0.0, learn_sigma=True, p2_gamma=1, p2_k=1, time_dist=["uniform"], cpu_rng=False,
+                           in_chans=3 if C == 3 else 4, class_cond=True, parallel=False, class_labels=None, amp=False, latent_scale=0.18215,
+                           guidance_scale=SCALE, interval=(100.0, 900.0), model_mode="diffusion", solver="ddim")
+    d = vaw_amd.SpacedDiffusion(use_timesteps=vaw_amd.space_timesteps(1000, str(a.steps)), args=args, betas=vaw_amd.get_named_beta_schedule("linear", 1000),
+                                model_mean_type=vaw_amd.ModelMeanType.EPSILON, model_var_type=vaw_amd.ModelVarType.LEARNED_RANGE,
+                                loss_type=vaw_amd.LossType.MSE, rescale_timesteps=True)
+    res = {"model": a.model, "dtype": "fp32" if a.fp32 else "bf16", "batch": N, "elements_per_sample": n, "chain_steps": a.steps}
+
+    with torch.no_grad():
+        # (a) / (b): the step's tail alone, rotating sets
+        i_mid = a.steps // 2
+        t = torch.full((N,), i_mid, device="cuda", dtype=torch.long)
+        coef = d._sample_rows(t)
+        nset = max(2, int(400e6 // (N * n * 4 * 8)) + 1)
+        sets = []
+        for _ in range(nset):
+            out = torch.randn(2 * N, 2 * C, H, H, device="cuda")
+            out[:, C:].clamp_(-1, 1)
+            sets.append((out, torch.randn(N, C, H, H, device="cuda"), torch.randn(N, C, H, H, device="cuda")))
+
+        def fused_tail(s):
+            out, x, nz = s
+            return lambda: ops.guided_sample_step(2, out[:N, :C], out[N:, :C], out[:N, C:], out[N:, C:], SCALE, x, nz, coef, 0, 2, True, 0.0)
+
+        def comp_tail(s):
+            out, x, nz = s
+
+            def run():
+                float(t.float().mean())                                    # the per-step read-back of the interval predicate
+                comb = out[N:] + SCALE * (out[:N] - out[N:])
+                m, v = torch.split(comb, C, dim=1)
+                return ops.sample_step(2, m.contiguous(), v.contiguous(), x, nz, coef, 0, 2, True, 0.0)
+            return run
+
+        got, ref = fused_tail(sets[0])(), comp_tail(sets[0])()
+        assert all(torch.equal(got[k], ref[k]) for k in ref), "fused step differs from the composition"
+        fs, cs = [fused_tail(s) for s in sets], [comp_tail(s) for s in sets]
+        both = [f for pair in zip(fs, cs) for f in pair]
+        events_us(both, 2 * len(both))                                       # warm-up of every set
+        res["a_tail_fused_us"] = events_us(fs, a.iters)
+        res["b_tail_composition_us"] = events_us(cs, a.iters)
+        res["tail_elements"] = N * n
+        res["a_tail_fused_algorithmic_TBps"] = 32.0 * N * n / res["a_tail_fused_us"] / 1e6
+
+        # (a) / (b): the whole guided step, model call included
+        y = torch.randint(0, a.num_classes, (N,), device="cuda")
+        cfg = vaw_amd.IntervalCFG(model, a.num_classes, SCALE, args.interval, True).eval()
+        comp_cfg = CompositionCFG(cfg).eval()
+        x = torch.randn(N, C, H, H, device="cuda")
+        assert cfg.guidance_active(d._host_model_time(i_mid))
+        step_f = lambda: d._reverse_step(2, cfg, x, t, True, None, None, {"y": y}, t_host=i_mid)
+        step_c = lambda: d._reverse_step(2, comp_cfg, x, t, True, None, None, {"y": y})
+        for _ in range(3):
+            step_f(), step_c()
+        it = max(10, a.iters // 10)
+        res["a_step_fused_us"] = events_us([step_f], it)
+        res["b_step_composition_us"] = events_us([step_c], it)
+        res["a_step_fused_us_again"] = events_us([step_f], it)
+
+        # (c) finish_images against the torch expression
+        torch_finish = lambda v: ((v + 1) * 127.5).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+        for dt, nm in ((torch.float32, "f32"), (torch.float64, "f64")):
+            imgs = [torch.rand(N, 3, H, H, device="cuda", dtype=dt) * 3 - 1.5 for _ in range(max(2, int(400e6 // (N * 3 * H * H * dt.itemsize)) + 1))]
+            assert torch.equal(ops.finish_images(imgs[0]), torch_finish(imgs[0]))
+            res[f"c_finish_{nm}_us"] = events_us([(lambda v=v: ops.finish_images(v)) for v in imgs], a.iters)
+            res[f"c_torch_{nm}_us"] = events_us([(lambda v=v: torch_finish(v)) for v in imgs], a.iters)
+            del imgs
+
+    # (d) a full Sampler.sample of one batch
+    kw = dict(decode_fn=(lambda z: z[:, :3])) if C == 4 else {}
+    fused = vaw_amd.Sampler(args, torch.device("cuda"), model, d, **kw)
+    comp = CompositionSampler(args, torch.device("cuda"), model, d, **kw)
+    run = lambda s: (lambda: (torch.manual_seed(1), s.sample(N, N, H, a.num_classes)))
+    res["d_sample_fused_s"], res["d_sample_composition_s"] = wall_pair(run(fused), run(comp), a.repeats)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -12,7 +12,7 @@ from .parallel import DistributedDataParallel  # noqa: F401
 from .data import DevicePrefetcher, LatentBatchLoader, LatentH5Dataset, ShardedSampler  # noqa: F401
 from .samplers import EDMDenoiser, edm_sample, flow_ode_sample, flow_sde_sample  # noqa: F401
 from .respace import SpacedDiffusion, space_timesteps  # noqa: F401
-from .sampler import IntervalCFG  # noqa: F401
+from .sampler import IntervalCFG, Sampler, sync_ema_model  # noqa: F401
 from .resample import (DeviceLossSecondMomentResampler, LossSecondMomentResampler, UniformSampler, create_named_schedule_sampler)  # noqa: F401
 from .trainer import Trainer, ema, sample_from_latent  # noqa: F401
 from .utils import get_lr_lambda, load_checkpoint, save_checkpoint, set_random_seed, warmup_cosine_lr  # noqa: F401

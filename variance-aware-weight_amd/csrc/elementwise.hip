@@ -261,37 +261,57 @@ extern "C" int vaw_vb_bwd(const float* mean_out, const float* var_out, const flo
 // kind 0: no sample (p_mean_variance only)   1: ancestral p_sample   2: ddim_sample.  Outputs may be NULL.
 // ---------------------------------------------------------------------------------------------
 #define SS_NCOEF 16
+// what a launch derives from one coefficient row before its element loop
+struct SsRow { float c[SS_NCOEF]; float mask, sigma, ddim_c; };
+__device__ __forceinline__ void ss_row(const float* __restrict__ coef, int b, float eta, SsRow& r) {
+#pragma unroll
+    for (int i = 0; i < SS_NCOEF; ++i) r.c[i] = coef[(int64_t)b * SS_NCOEF + i];
+    r.mask = r.c[11] != 0.f ? 0.f : 1.f;
+    r.sigma = (eta * r.c[9]) * r.c[12];
+    r.ddim_c = sqrtf(1.f - r.c[10] - r.sigma * r.sigma);
+}
+struct SsOut { float sample, pred, mean, lv; };
+// The per-element body of the step, shared by sample_step_kernel and guided_sample_step_kernel: m / v are the model's mean
+// output and variance value of the element (v is not read with a fixed variance), xv = x_t, nz the noise (not read by kind 0).
+__device__ __forceinline__ SsOut ss_elem(const SsRow& r, int kind, int mean_mode, int var_mode, int clip, float m, float v,
+                                         float xv, float nz) {
+    const float* c = r.c;
+    SsOut o;
+    float pred = c[0] * xv + c[1] * m;
+    if (clip) pred = fminf(fmaxf(pred, -1.f), 1.f);
+    float lv;
+    if (var_mode == 1) lv = v;
+    else if (var_mode == 2) { const float frac = (v + 1.f) / 2.f; lv = frac * c[5] + (1.f - frac) * c[4]; }
+    else lv = c[5];
+    o.pred = pred;
+    o.lv = lv;
+    o.mean = mean_mode == 1 ? m : c[2] * pred + c[3] * xv;
+    o.sample = 0.f;
+    if (kind == 1) {
+        o.sample = o.mean + (r.mask * expf(0.5f * lv)) * nz;
+    } else if (kind == 2) {
+        const float eps = (c[6] * xv - pred) / c[7];
+        const float mp = pred * c[8] + r.ddim_c * eps;
+        o.sample = mp + (r.mask * r.sigma) * nz;
+    }
+    return o;
+}
+
 __global__ void sample_step_kernel(const float* __restrict__ mean_out, const float* __restrict__ var_out, const float* __restrict__ x,
                                    const float* __restrict__ noise, const float* __restrict__ coef, int kind, int mean_mode,
                                    int var_mode, int clip, float eta, float* __restrict__ sample, float* __restrict__ pred_out,
                                    float* __restrict__ mean_o, float* __restrict__ logvar_o, int64_t n) {
     const int b = blockIdx.y;
-    float c[SS_NCOEF];
-#pragma unroll
-    for (int i = 0; i < SS_NCOEF; ++i) c[i] = coef[b * SS_NCOEF + i];
-    const float mask = c[11] != 0.f ? 0.f : 1.f;
-    const float sigma = (eta * c[9]) * c[12];
-    const float ddim_c = sqrtf(1.f - c[10] - sigma * sigma);
+    SsRow r;
+    ss_row(coef, b, eta, r);
     const int64_t base = (int64_t)b * n;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float xv = x[base + i], m = mean_out[base + i];
-        float pred = c[0] * xv + c[1] * m;
-        if (clip) pred = fminf(fmaxf(pred, -1.f), 1.f);
-        float lv;
-        if (var_mode == 1) lv = var_out[base + i];
-        else if (var_mode == 2) { const float frac = (var_out[base + i] + 1.f) / 2.f; lv = frac * c[5] + (1.f - frac) * c[4]; }
-        else lv = c[5];
-        const float mean = mean_mode == 1 ? m : c[2] * pred + c[3] * xv;
-        if (pred_out) pred_out[base + i] = pred;
-        if (mean_o) mean_o[base + i] = mean;
-        if (logvar_o) logvar_o[base + i] = lv;
-        if (kind == 1) {
-            sample[base + i] = mean + (mask * expf(0.5f * lv)) * noise[base + i];
-        } else if (kind == 2) {
-            const float eps = (c[6] * xv - pred) / c[7];
-            const float mp = pred * c[8] + ddim_c * eps;
-            sample[base + i] = mp + (mask * sigma) * noise[base + i];
-        }
+        const SsOut o = ss_elem(r, kind, mean_mode, var_mode, clip, mean_out[base + i], var_mode ? var_out[base + i] : 0.f,
+                                x[base + i], kind ? noise[base + i] : 0.f);
+        if (pred_out) pred_out[base + i] = o.pred;
+        if (mean_o) mean_o[base + i] = o.mean;
+        if (logvar_o) logvar_o[base + i] = o.lv;
+        if (kind) sample[base + i] = o.sample;
     }
 }
 
@@ -497,6 +517,238 @@ extern "C" int vaw_ddim_reverse_step(const float* mean_out, int64_t model_ld, co
         ddim_reverse_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(mean_out, model_ld, x, coef, clip_denoised, sample,
                                                                           pred_xstart, per_sample);
     VAW_CHECK_LAUNCH("ddim_reverse_step");
+    return VAW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sampler: classifier-free guidance fused into the reverse step, the combination alone, and the uint8 image finish.
+// ---------------------------------------------------------------------------------------------
+// u + s * (c - u): subtraction, product and sum each rounded on its own (this file is built with -ffp-contract=off), which
+// is what the three tensor operations of IntervalCFG.forward give.
+__device__ __forceinline__ float cfg_mix(float c, float u, float s) { return u + s * (c - u); }
+
+// The model output of the stacked [2N, ...] guided call is read in place: row b of each of the four quarters (conditional /
+// unconditional half of the batch, mean / variance channels) starts model_ld floats after row b-1.  mu == NULL: no guidance,
+// the plain step over split halves.  Everything else is [B, n] contiguous.  One grid row per sample, as sample_step_kernel.
+template <bool VEC>
+__global__ void guided_sample_step_kernel(const float* __restrict__ mc, const float* __restrict__ mu, const float* __restrict__ vc,
+                                          const float* __restrict__ vu, int64_t model_ld, float gs, const float* __restrict__ x,
+                                          const float* __restrict__ noise, const float* __restrict__ coef, int kind,
+                                          int mean_mode, int var_mode, int clip, float eta, float* __restrict__ sample,
+                                          float* __restrict__ pred_out, float* __restrict__ mean_o,
+                                          float* __restrict__ logvar_o, int64_t n) {
+    const int b = blockIdx.y;
+    SsRow r;
+    ss_row(coef, b, eta, r);
+    const int64_t base = (int64_t)b * n, mbase = (int64_t)b * model_ld;
+    const bool guided = mu != nullptr, var = var_mode != 0;
+    if (VEC) {
+        const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
+            f32x4 m = load4(mc + mbase + 4 * i), v = var ? load4(vc + mbase + 4 * i) : z4;
+            const f32x4 xv = load4(x + base + 4 * i), nz = kind ? load4(noise + base + 4 * i) : z4;
+            if (guided) {
+                const f32x4 m0 = load4(mu + mbase + 4 * i), v0 = var ? load4(vu + mbase + 4 * i) : z4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { m[j] = cfg_mix(m[j], m0[j], gs); if (var) v[j] = cfg_mix(v[j], v0[j], gs); }
+            }
+            f32x4 s, p, mo, lo;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const SsOut o = ss_elem(r, kind, mean_mode, var_mode, clip, m[j], v[j], xv[j], nz[j]);
+                s[j] = o.sample; p[j] = o.pred; mo[j] = o.mean; lo[j] = o.lv;
+            }
+            if (pred_out) store4(pred_out + base + 4 * i, p);
+            if (mean_o) store4(mean_o + base + 4 * i, mo);
+            if (logvar_o) store4(logvar_o + base + 4 * i, lo);
+            if (kind) store4(sample + base + 4 * i, s);
+        }
+    } else {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            float m = mc[mbase + i], v = var ? vc[mbase + i] : 0.f;
+            if (guided) {
+                m = cfg_mix(m, mu[mbase + i], gs);
+                if (var) v = cfg_mix(v, vu[mbase + i], gs);
+            }
+            const SsOut o = ss_elem(r, kind, mean_mode, var_mode, clip, m, v, x[base + i], kind ? noise[base + i] : 0.f);
+            if (pred_out) pred_out[base + i] = o.pred;
+            if (mean_o) mean_o[base + i] = o.mean;
+            if (logvar_o) logvar_o[base + i] = o.lv;
+            if (kind) sample[base + i] = o.sample;
+        }
+    }
+}
+
+extern "C" int vaw_guided_sample_step(int kind, const float* mean_cond, const float* mean_uncond, const float* var_cond,
+                                      const float* var_uncond, int64_t model_ld, float guidance_scale, const float* x,
+                                      const float* noise, const float* coef, int mean_mode, int var_mode, int clip_denoised,
+                                      float eta, float* sample, float* pred_xstart, float* mean, float* log_variance, int B,
+                                      int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "guided_sample_step: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(mean_cond && x && coef && kind >= 0 && kind <= 2, "guided_sample_step: null pointer or bad kind %d", kind);
+    VAW_CHECK_ARG(model_ld >= per_sample, "guided_sample_step: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
+    VAW_CHECK_ARG((mean_mode == 0 || mean_mode == 1) && var_mode >= 0 && var_mode <= 2 && (var_mode == 0 || var_cond) &&
+                      (var_mode == 0 || !mean_uncond || var_uncond),
+                  "guided_sample_step: bad modes (learned variance needs var_cond, and var_uncond when guided)");
+    VAW_CHECK_ARG(kind == 0 || (sample && noise), "guided_sample_step: kind 1/2 need noise and sample");
+    if (var_mode == 0) var_cond = var_uncond = nullptr;
+    if (!mean_uncond) var_uncond = nullptr;
+    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(mean_cond) && al16(mean_uncond) && al16(var_cond) &&
+                     al16(var_uncond) && al16(x) && al16(noise) && al16(sample) && al16(pred_xstart) && al16(mean) &&
+                     al16(log_variance);
+    int gx = stream_grid(vec ? per_sample / 4 : per_sample, 256);
+    dim3 grid(gx > 64 ? 64 : gx, B);
+    if (vec)
+        guided_sample_step_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(
+            mean_cond, mean_uncond, var_cond, var_uncond, model_ld, guidance_scale, x, noise, coef, kind, mean_mode, var_mode,
+            clip_denoised, eta, sample, pred_xstart, mean, log_variance, per_sample);
+    else
+        guided_sample_step_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(
+            mean_cond, mean_uncond, var_cond, var_uncond, model_ld, guidance_scale, x, noise, coef, kind, mean_mode, var_mode,
+            clip_denoised, eta, sample, pred_xstart, mean, log_variance, per_sample);
+    VAW_CHECK_LAUNCH("guided_sample_step");
+    return VAW_OK;
+}
+
+template <bool VEC>
+__global__ void cfg_combine_kernel(const float* __restrict__ cond, const float* __restrict__ uncond, int64_t model_ld, float gs,
+                                   float* __restrict__ out, int64_t n) {
+    const int b = blockIdx.y;
+    const int64_t base = (int64_t)b * n, mbase = (int64_t)b * model_ld;
+    if (VEC) {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
+            const f32x4 c = load4(cond + mbase + 4 * i), u = load4(uncond + mbase + 4 * i);
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = cfg_mix(c[j], u[j], gs);
+            store4(out + base + 4 * i, o);
+        }
+    } else {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+            out[base + i] = cfg_mix(cond[mbase + i], uncond[mbase + i], gs);
+    }
+}
+
+extern "C" int vaw_cfg_combine(const float* cond, const float* uncond, int64_t model_ld, float guidance_scale, float* out, int B,
+                               int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "cfg_combine: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(cond && uncond && out, "cfg_combine: null pointer");
+    VAW_CHECK_ARG(model_ld >= per_sample, "cfg_combine: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
+    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(cond) && al16(uncond) && al16(out);
+    int gx = stream_grid(vec ? per_sample / 4 : per_sample, 256);
+    dim3 grid(gx > 64 ? 64 : gx, B);
+    if (vec)
+        cfg_combine_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(cond, uncond, model_ld, guidance_scale, out, per_sample);
+    else
+        cfg_combine_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(cond, uncond, model_ld, guidance_scale, out, per_sample);
+    VAW_CHECK_LAUNCH("cfg_combine");
+    return VAW_OK;
+}
+
+// [B, C, H, W] samples in [-1, 1] -> [B, H, W, C] bytes:  v = (x + 1) * 127.5 in the source precision (sum and product each
+// rounded), clamped to [0, 255], truncated toward zero.  fmax(NaN, 0) is 0, so NaN writes 0.
+__device__ __forceinline__ unsigned quant_u8(float x) { return (unsigned)(int)fminf(fmaxf((x + 1.f) * 127.5f, 0.f), 255.f); }
+__device__ __forceinline__ unsigned quant_u8(double x) { return (unsigned)(int)fmin(fmax((x + 1.0) * 127.5, 0.0), 255.0); }
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void load_px4(const float* p, float* v) {
+    const f32x4 t = load4(p);
+    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+}
+__device__ __forceinline__ void load_px4(const double* p, double* v) {
+    const f64x2 a = *reinterpret_cast<const f64x2*>(p), b = *reinterpret_cast<const f64x2*>(p + 2);
+    v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
+}
+
+// Aligned form (HW % 4 == 0, src 16-byte and dst 4-byte aligned, C <= 4): a thread takes 4 neighbouring pixels of one image,
+// reads 16 (f32) or 32 (f64) contiguous bytes of each channel plane -- a wave reads 1 or 2 KiB of a plane per instruction --
+// and writes their 4*C interleaved bytes as C whole words; the lanes of a wave write one contiguous run.
+template <typename T, int C>
+__global__ void finish_images_vec_kernel(const T* __restrict__ src, uint32_t* __restrict__ dst, int64_t B, int64_t HW) {
+    const int64_t groups = HW / 4, total = B * groups;
+    for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = idx / groups, g = idx - b * groups;
+        uint32_t w[C];
+#pragma unroll
+        for (int k = 0; k < C; ++k) w[k] = 0u;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            T v[4];
+            load_px4(src + (b * C + c) * HW + 4 * g, v);
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                const int j = px * C + c;
+                w[j >> 2] |= quant_u8(v[px]) << (8 * (j & 3));
+            }
+        }
+        uint32_t* o = dst + idx * C;          // (b*HW + 4g) * C bytes = idx * C words
+#pragma unroll
+        for (int k = 0; k < C; ++k) o[k] = w[k];
+    }
+}
+
+// General form (any C, H, W, any alignment): a thread owns one 4-byte-aligned word of the destination.  A word that lies
+// wholly inside [dst, dst + total) is stored whole; the ragged first and last words are stored byte by byte, so nothing
+// outside the destination is written.  a0 = dst & 3; dst_al = dst - a0.
+template <typename T>
+__global__ void finish_images_gen_kernel(const T* __restrict__ src, uint8_t* __restrict__ dst_al, int a0, int64_t total, int64_t C,
+                                         int64_t HW) {
+    const int64_t words = (a0 + total + 3) / 4;
+    for (int64_t wi = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; wi < words; wi += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t w = 0u;
+        bool whole = true;
+        uint8_t q[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t k = 4 * wi + j - a0;          // flat index into [B, H, W, C]
+            q[j] = 0;
+            if (k < 0 || k >= total) { whole = false; continue; }
+            const int64_t pix = k / C, c = k - pix * C, b = pix / HW, p = pix - b * HW;
+            q[j] = (uint8_t)quant_u8(src[(b * C + c) * HW + p]);
+            w |= (uint32_t)q[j] << (8 * j);
+        }
+        if (whole) {
+            *reinterpret_cast<uint32_t*>(dst_al + 4 * wi) = w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t k = 4 * wi + j - a0;
+                if (k >= 0 && k < total) dst_al[4 * wi + j] = q[j];
+            }
+        }
+    }
+}
+
+template <typename T>
+static int finish_images_launch(const T* src, uint8_t* dst, int64_t B, int64_t C, int64_t HW, hipStream_t st) {
+    const int64_t total = B * C * HW;
+    const bool vec = HW % 4 == 0 && C <= 4 && al16(src) && ((uintptr_t)dst & 3) == 0;
+    if (vec) {
+        const int grid = stream_grid(B * (HW / 4), 256);
+        uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+        switch ((int)C) {
+            case 1: finish_images_vec_kernel<T, 1><<<grid, 256, 0, st>>>(src, d, B, HW); break;
+            case 2: finish_images_vec_kernel<T, 2><<<grid, 256, 0, st>>>(src, d, B, HW); break;
+            case 3: finish_images_vec_kernel<T, 3><<<grid, 256, 0, st>>>(src, d, B, HW); break;
+            default: finish_images_vec_kernel<T, 4><<<grid, 256, 0, st>>>(src, d, B, HW); break;
+        }
+    } else {
+        const int a0 = (int)((uintptr_t)dst & 3);
+        const int grid = stream_grid((a0 + total + 3) / 4, 256);
+        finish_images_gen_kernel<T><<<grid, 256, 0, st>>>(src, dst - a0, a0, total, C, HW);
+    }
+    return 0;
+}
+
+extern "C" int vaw_finish_images(const void* src, int src_f64, uint8_t* dst, int B, int C, int H, int W, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "finish_images: bad sizes B=%d C=%d H=%d W=%d", B, C, H, W);
+    VAW_CHECK_ARG(src && dst, "finish_images: null pointer");
+    VAW_CHECK_ARG(src_f64 == 0 || src_f64 == 1, "finish_images: src_f64 must be 0 (f32) or 1 (f64), got %d", src_f64);
+    VAW_CHECK_ARG(((uintptr_t)src & (src_f64 ? 7 : 3)) == 0, "finish_images: source not aligned to its element size");
+    const int64_t HW = (int64_t)H * W;
+    if (src_f64) finish_images_launch(static_cast<const double*>(src), dst, B, C, HW, (hipStream_t)stream);
+    else finish_images_launch(static_cast<const float*>(src), dst, B, C, HW, (hipStream_t)stream);
+    VAW_CHECK_LAUNCH("finish_images");
     return VAW_OK;
 }
 

@@ -11,6 +11,7 @@ What runs where
   vaw_wmse_bwd    d(out) in one pass                                                       (16 B/element)
   vaw_bpd_terms   calc_bpd_loop's per-timestep tail: bound with clip, x0 MSE, eps MSE, one pass      (20 B/element)
   vaw_prior_bpd / vaw_ddim_reverse_step   the prior KL of the bound; one step of the DDIM ODE towards noise
+  vaw_guided_sample_step   a reverse step under IntervalCFG: guidance combination + p_sample / ddim_sample, one pass  (32 B/element)
 Only the selected target is computed (the reference evaluates all four, :823-830).
 """
 import enum
@@ -252,7 +253,17 @@ class GaussianDiffusion:
                             f(self.alphas_cumprod_next), z, z],
                            dim=1).contiguous()
 
-    def _reverse_step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0, want_all=False):
+    def _host_model_time(self, i):
+        """What _scale_timesteps makes of a batch whose every timestep is the python int `i`, as a host float (same f32
+        product), so that a guidance interval can be decided without reading t back from the device."""
+        if self.rescale_timesteps:
+            return float(np.float32(i) * np.float32(1000.0 / self.num_timesteps))
+        return float(i)
+
+    def _reverse_step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0, want_all=False,
+                      t_host=None):
+        """t_host: the python int every entry of t equals, when the caller knows it (the sampling loops); only a model
+        that offers `guided_halves` (IntervalCFG) uses it."""
         if denoised_fn is not None or cond_fn is not None:
             raise NotImplementedError("denoised_fn / cond_fn (classifier guidance) are out of scope (SURVEY.md §2)")
         mt, vt = self.model_mean_type, self.model_var_type
@@ -262,28 +273,49 @@ class GaussianDiffusion:
             raise NotImplementedError(mt)
         B, C = x.shape[:2]
         assert t.shape == (B,)
-        out = model(x, self._scale_timesteps(t), **(model_kwargs or {}))
-        out = out[0] if isinstance(out, tuple) else out
-        var_out = None
-        if vt in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE):
-            assert out.shape == (B, C * 2, *x.shape[2:])
-            out, var_out = torch.split(out, C, dim=1)
-        assert out.shape == x.shape
+        model_kwargs = model_kwargs or {}
+        learned = vt in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE)
+        stacked = None
+        guided_halves = getattr(model, "guided_halves", None) if (kind != 3 and x.is_cuda) else None
+        if guided_halves is not None:
+            # classifier-free guidance: the stacked [2B, ...] output goes to the fused step uncombined
+            t_mean = None if t_host is None else self._host_model_time(t_host)
+            stacked = guided_halves(x, self._scale_timesteps(t), t_mean=t_mean, **model_kwargs)
+            if stacked is None:
+                out = model.unguided(x, self._scale_timesteps(t), **model_kwargs)
+            elif stacked.dtype != torch.float32:
+                out, stacked = model.combine(stacked), None
+        else:
+            out = model(x, self._scale_timesteps(t), **model_kwargs)
         key = "ss"
         tb = self._tables(x.device)
         if key not in tb:
             tb[key] = self._sample_table().to(x.device)
-        if kind == 3:                                                      # ddim_reverse_sample: deterministic, no noise draw
-            return ops.ddim_reverse_step(out, x, tb[key][t], clip_denoised)
+        mean_mode = 1 if mt == ModelMeanType.PREVIOUS_X else 0
+        var_mode = {ModelVarType.LEARNED: 1, ModelVarType.LEARNED_RANGE: 2}.get(vt, 0)
+        if stacked is None:
+            out = out[0] if isinstance(out, tuple) else out
+            var_out = None
+            if learned:
+                assert out.shape == (B, C * 2, *x.shape[2:])
+                out, var_out = torch.split(out, C, dim=1)
+            assert out.shape == x.shape
+            if kind == 3:                                                  # ddim_reverse_sample: deterministic, no noise draw
+                return ops.ddim_reverse_step(out, x, tb[key][t], clip_denoised)
+        else:
+            assert stacked.shape == (2 * B, C * 2 if learned else C, *x.shape[2:])
         noise = None
         if kind:
             if getattr(self.args, "cpu_rng", False):
                 noise = torch.randn(x.shape, dtype=torch.float32).to(x.device)     # the reference's CPU stream (parity runs)
             else:
                 noise = torch.randn_like(x)
-        var_mode = {ModelVarType.LEARNED: 1, ModelVarType.LEARNED_RANGE: 2}.get(vt, 0)
-        return ops.sample_step(kind, out, var_out, x, noise, tb[key][t], 1 if mt == ModelMeanType.PREVIOUS_X else 0, var_mode,
-                               clip_denoised, eta, want_all)
+        if stacked is not None:
+            cond, uncond = stacked[:B], stacked[B:]
+            return ops.guided_sample_step(kind, cond[:, :C], uncond[:, :C], cond[:, C:] if learned else None,
+                                          uncond[:, C:] if learned else None, model.guidance_scale, x, noise, tb[key][t],
+                                          mean_mode, var_mode, clip_denoised, eta, want_all)
+        return ops.sample_step(kind, out, var_out, x, noise, tb[key][t], mean_mode, var_mode, clip_denoised, eta, want_all)
 
     def _model_halves(self, model, x, t, model_kwargs):
         """Model call of p_mean_variance (:304-314): (mean output, variance values or None), the halves as views."""
@@ -325,7 +357,9 @@ class GaussianDiffusion:
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
         return self._reverse_step(2, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta)
 
-    def _loop(self, step, model, shape, noise, device, progress, **kw):
+    def _loop(self, kind, model, shape, noise, device, progress, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0):
+        """The reverse chain of p_sample (kind 1) / ddim_sample (kind 2).  The step index is a host integer here, and
+        _reverse_step gets it beside the device tensor: a guidance interval is decided from it, with no read-back per step."""
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
@@ -342,14 +376,13 @@ class GaussianDiffusion:
         for i in indices:
             t = torch.full((shape[0],), i, device=device, dtype=torch.long)
             with torch.no_grad():
-                out = step(model, img, t, **kw)
+                out = self._reverse_step(kind, model, img, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta, t_host=i)
                 yield out
                 img = out["sample"]
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                   model_kwargs=None, device=None, progress=False):
-        return self._loop(self.p_sample, model, shape, noise, device, progress, clip_denoised=clip_denoised,
-                          denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs)
+        return self._loop(1, model, shape, noise, device, progress, clip_denoised, denoised_fn, cond_fn, model_kwargs)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                       device=None, progress=False):
@@ -361,8 +394,7 @@ class GaussianDiffusion:
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0):
-        return self._loop(self.ddim_sample, model, shape, noise, device, progress, clip_denoised=clip_denoised,
-                          denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, eta=eta)
+        return self._loop(2, model, shape, noise, device, progress, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                          device=None, progress=False, eta=0.0):

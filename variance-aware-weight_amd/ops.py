@@ -116,25 +116,41 @@ def vb_terms(mean_out, var_out, x0, x_t, coef, mean_mode, var_mode, scale=1.0):
                           int(mean_mode), int(var_mode), float(scale))
 
 
-def sample_step(kind, mean_out, var_out, x, noise, coef, mean_mode, var_mode, clip_denoised, eta=0.0, want_all=False):
-    """One reverse-process step (vaw_sample_step): kind 0 = p_mean_variance only, 1 = p_sample, 2 = ddim_sample.
-    Returns {"sample", "pred_xstart"} (+ "mean", "log_variance" with want_all)."""
-    need_cuda(mean_out, x, coef)
-    mean_out, x = mean_out.contiguous().float(), x.contiguous().float()
-    var_out = None if var_out is None else var_out.contiguous().float()
-    noise = None if noise is None else noise.contiguous().float()
-    coef = coef.contiguous()
-    B = x.shape[0]
-    assert mean_out.shape == x.shape and coef.shape == (B, 16) and coef.dtype == torch.float32
+def _step_outputs(kind, x, want_all):
     res = {"pred_xstart": torch.empty_like(x)}
     if kind:
         res["sample"] = torch.empty_like(x)
     if want_all:
         res["mean"], res["log_variance"] = torch.empty_like(x), torch.empty_like(x)
-    check(L.lib().vaw_sample_step(kind, ptr(mean_out), ptr(var_out), ptr(x), ptr(noise), ptr(coef), int(mean_mode), int(var_mode),
-                                  1 if clip_denoised else 0, float(eta), ptr(res.get("sample")), ptr(res["pred_xstart"]),
-                                  ptr(res.get("mean")), ptr(res.get("log_variance")), B, x.numel() // B, stream_ptr()),
-          "vaw_sample_step")
+    return res
+
+
+def sample_step(kind, mean_out, var_out, x, noise, coef, mean_mode, var_mode, clip_denoised, eta=0.0, want_all=False):
+    """One reverse-process step (vaw_sample_step): kind 0 = p_mean_variance only, 1 = p_sample, 2 = ddim_sample.
+    Returns {"sample", "pred_xstart"} (+ "mean", "log_variance" with want_all).  The two halves of a [B, 2C, H, W] model
+    output split along dim 1 are read in place (the unguided form of vaw_guided_sample_step: same per-element body)."""
+    need_cuda(mean_out, x, coef)
+    x = x.contiguous().float()
+    noise = None if noise is None else noise.contiguous().float()
+    coef = coef.contiguous()
+    B = x.shape[0]
+    n = x.numel() // max(B, 1)
+    assert mean_out.shape == x.shape and coef.shape == (B, 16) and coef.dtype == torch.float32
+    if var_out is not None:
+        mean_out, var_out, ld = _model_halves(mean_out, var_out, n)
+    else:
+        mean_out, ld = mean_out.contiguous().float(), n
+    res = _step_outputs(kind, x, want_all)
+    if ld == n:
+        check(L.lib().vaw_sample_step(kind, ptr(mean_out), ptr(var_out), ptr(x), ptr(noise), ptr(coef), int(mean_mode), int(var_mode),
+                                      1 if clip_denoised else 0, float(eta), ptr(res.get("sample")), ptr(res["pred_xstart"]),
+                                      ptr(res.get("mean")), ptr(res.get("log_variance")), B, n, stream_ptr()),
+              "vaw_sample_step")
+    else:
+        check(L.lib().vaw_guided_sample_step(kind, ptr(mean_out), None, ptr(var_out), None, ld, 1.0, ptr(x), ptr(noise), ptr(coef),
+                                             int(mean_mode), int(var_mode), 1 if clip_denoised else 0, float(eta),
+                                             ptr(res.get("sample")), ptr(res["pred_xstart"]), ptr(res.get("mean")),
+                                             ptr(res.get("log_variance")), B, n, stream_ptr()), "vaw_guided_sample_step")
     return res
 
 
@@ -158,6 +174,80 @@ def _model_halves(mean_out, var_out, n):
         if ldv != ld:
             mean_out, var_out, ld = mean_out.contiguous(), var_out.contiguous(), n
     return mean_out, var_out, ld
+
+
+def _same_ld(ts, n):
+    """The given [B, ...] f32 tensors (None allowed) as in-place views sharing one row distance, or all as contiguous copies."""
+    rows = [None if t is None else _dense_rows(t, n) for t in ts]
+    lds = {r[1] for r in rows if r is not None}
+    if len(lds) > 1:
+        return [None if t is None else t.float().contiguous() for t in ts], n
+    return [None if r is None else r[0] for r in rows], (lds.pop() if lds else n)
+
+
+def guided_sample_step(kind, mean_cond, mean_uncond, var_cond, var_uncond, guidance_scale, x, noise, coef, mean_mode, var_mode,
+                       clip_denoised, eta=0.0, want_all=False):
+    """One reverse-process step with classifier-free guidance fused in (vaw_guided_sample_step): per element
+    m = mean_uncond + guidance_scale * (mean_cond - mean_uncond), the variance values likewise, then the step of sample_step.
+    The four tensors are x-shaped views of the stacked [2N, 2C, H, W] model output and are read in place.  mean_uncond=None:
+    the unguided step.  Returns what sample_step returns, bitwise what the three torch ops followed by sample_step give."""
+    need_cuda(mean_cond, mean_uncond, var_cond, var_uncond, x, noise, coef)
+    x = x.contiguous().float()
+    noise = None if noise is None else noise.contiguous().float()
+    coef = coef.contiguous()
+    B = x.shape[0]
+    n = x.numel() // max(B, 1)
+    if var_mode == 0:
+        var_cond = var_uncond = None
+    if mean_uncond is None:
+        var_uncond = None
+    for t in (mean_cond, mean_uncond, var_cond, var_uncond):
+        if t is not None and t.shape != x.shape:
+            raise L.VawError(f"guided_sample_step: model output part {tuple(t.shape)} != x {tuple(x.shape)}")
+    if not (coef.shape == (B, 16) and coef.dtype == torch.float32):
+        raise L.VawError(f"guided_sample_step: coef {tuple(coef.shape)} {coef.dtype} is not f32 [{B}, 16]")
+    if var_mode and (var_cond is None or (mean_uncond is not None and var_uncond is None)):
+        raise L.VawError("guided_sample_step: a learned variance needs the variance values of every half")
+    (mean_cond, mean_uncond, var_cond, var_uncond), ld = _same_ld((mean_cond, mean_uncond, var_cond, var_uncond), n)
+    res = _step_outputs(kind, x, want_all)
+    check(L.lib().vaw_guided_sample_step(kind, ptr(mean_cond), ptr(mean_uncond), ptr(var_cond), ptr(var_uncond), ld,
+                                         float(guidance_scale), ptr(x), ptr(noise), ptr(coef), int(mean_mode), int(var_mode),
+                                         1 if clip_denoised else 0, float(eta), ptr(res.get("sample")), ptr(res["pred_xstart"]),
+                                         ptr(res.get("mean")), ptr(res.get("log_variance")), B, n, stream_ptr()),
+          "vaw_guided_sample_step")
+    return res
+
+
+def cfg_combine(cond, uncond, guidance_scale):
+    """uncond + guidance_scale * (cond - uncond) in one pass (vaw_cfg_combine), bitwise the three torch ops.  cond / uncond:
+    f32 tensors of one shape, e.g. the two halves of the stacked [2N, ...] guided model output, read in place."""
+    need_cuda(cond, uncond)
+    if cond.shape != uncond.shape or cond.dtype != torch.float32 or uncond.dtype != torch.float32:
+        raise L.VawError(f"cfg_combine: {tuple(cond.shape)} {cond.dtype} vs {tuple(uncond.shape)} {uncond.dtype}")
+    B = cond.shape[0]
+    n = cond.numel() // max(B, 1)
+    (cond, uncond), ld = _same_ld((cond, uncond), n)
+    out = torch.empty(cond.shape, device=cond.device, dtype=torch.float32)
+    check(L.lib().vaw_cfg_combine(ptr(cond), ptr(uncond), ld, float(guidance_scale), ptr(out), B, n, stream_ptr()), "vaw_cfg_combine")
+    return out
+
+
+def finish_images(samples, out=None):
+    """[B, C, H, W] f32 / f64 samples in [-1, 1] -> [B, H, W, C] uint8 (vaw_finish_images): bitwise
+    ((x + 1) * 127.5).clamp(0, 255).to(uint8).permute(0, 2, 3, 1).contiguous() for finite x; NaN writes 0.
+    out: an optional contiguous uint8 [B, H, W, C] destination (any byte alignment)."""
+    need_cuda(samples, out)
+    if samples.dim() != 4 or samples.dtype not in (torch.float32, torch.float64):
+        raise L.VawError(f"finish_images: expected a [B, C, H, W] float32 / float64 tensor, got {tuple(samples.shape)} {samples.dtype}")
+    samples = samples.contiguous()
+    B, Cn, H, W = samples.shape
+    if out is None:
+        out = torch.empty((B, H, W, Cn), device=samples.device, dtype=torch.uint8)
+    elif not (out.dtype == torch.uint8 and out.shape == (B, H, W, Cn) and out.is_contiguous()):
+        raise L.VawError(f"finish_images: destination {tuple(out.shape)} {out.dtype} is not a contiguous uint8 {(B, H, W, Cn)}")
+    check(L.lib().vaw_finish_images(ptr(samples), 1 if samples.dtype == torch.float64 else 0, ptr(out), B, Cn, H, W, stream_ptr()),
+          "vaw_finish_images")
+    return out
 
 
 def bpd_terms(mean_out, var_out, x0, x_t, noise, coef, mean_mode, var_mode, clip_denoised, out=None, col=0, group=None):

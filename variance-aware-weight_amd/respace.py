@@ -68,6 +68,10 @@ class SpacedDiffusion(GaussianDiffusion):
     def _scale_timesteps(self, t):
         return t            # the respaced call (below) hands the model original, already rescaled timesteps
 
+    def _host_model_time(self, i):
+        k = self.timestep_map[i]
+        return float(np.float32(k) * np.float32(1000.0 / self.original_num_steps)) if self.rescale_timesteps else float(k)
+
     def _kept_steps_on(self, like):
         """The kept original timesteps k_j as a tensor living beside `like` (one upload per device / index dtype)."""
         cache = self.__dict__.setdefault("_kept_cache", {})
@@ -84,11 +88,18 @@ class SpacedDiffusion(GaussianDiffusion):
             return model
         factor = 1000.0 / self.original_num_steps if self.rescale_timesteps else None
 
-        def call(x, j, **kwargs):
+        def original(j):
             k = self._kept_steps_on(j).index_select(0, j.reshape(-1)).reshape(j.shape)
-            return model(x, k.float() * factor if factor is not None else k, **kwargs)
+            return k.float() * factor if factor is not None else k
+
+        def call(x, j, **kwargs):
+            return model(x, original(j), **kwargs)
 
         call._vaw_respaced_by = self
+        if hasattr(model, "guided_halves"):         # IntervalCFG: the fused guided step asks for the uncombined halves
+            call.guided_halves = lambda x, j, t_mean=None, **kwargs: model.guided_halves(x, original(j), t_mean=t_mean, **kwargs)
+            call.unguided = lambda x, j, **kwargs: model.unguided(x, original(j), **kwargs)
+            call.combine, call.guidance_scale = model.combine, model.guidance_scale
         if hasattr(model, "parameters"):
             call.parameters = model.parameters      # GaussianDiffusion asks the model for its device through this
         return call

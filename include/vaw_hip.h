@@ -148,6 +148,59 @@ int vaw_cfg_combine(const float* cond, const float* uncond, int64_t model_ld, fl
 int vaw_finish_images(const void* src, int src_f64, uint8_t* dst, int B, int C, int H, int W, vaw_stream stream);
 
 /* ---------------------------------------------------------------------------
+ * Solver steps of the EDM and flow-matching samplers  (tools/cfg_edm.py: ablation_sampler; tools/gaussian_diffusion.py:
+ * sde_sample / ode_sample).  Everything of a step that does not depend on x comes from a device table built once per grid
+ * (samplers.py) and is read by row index: nothing is uploaded per step.  Every operation is rounded on its own in the order
+ * of the tensor composition (no fused multiply-add, IEEE division and square root).  The model output is read in place:
+ * cond / uncond are the rows [:N] / [N:] of the stacked guided output (uncond == NULL: no guidance), row b starting
+ * model_ld floats after row b-1, so the [:, :C] slice of a learn_sigma output needs no copy; the guidance combination is
+ * that of vaw_cfg_combine.  All other tensors are [B, per_sample] contiguous.  16-byte loads and stores when
+ * per_sample % 4 == 0, model_ld % 4 == 0 and every pointer is 16-byte aligned, scalar ones otherwise.
+ * ------------------------------------------------------------------------- */
+
+/* Doubles per row of the EDM table, one row per solver step:
+ *   0 s(t_hat)/s(t_cur)   1 noise coefficient   2..9 evaluation at t_hat   10 h = t_next - t_hat   11 alpha*h
+ *   12 1 - 1/(2 alpha)   13 1/(2 alpha)   14..21 evaluation at t_mid = t_hat + alpha*h   22, 23 unused
+ * evaluation block: +0 s(t)  +1 sigma(t) as float32  +2 c_in  +3 c_in^2  +4 sigma*c_in  (the float32 scalars of the
+ * denoiser's preconditioning, stored widened)  +5 dsg/sg + ds/s  +6 dsg*s/sg  +7 chain index handed to the network. */
+#define VAW_EDM_COLS 24
+/* Floats per row of the flow table, one row per network evaluation at time t:
+ *   0 a  1 s  2 a'  3 s'  4 g2 = 2 s s'  5 g2/2  6 s^2  7 a^2 + s^2  8 s a' - a s'  9 sqrt(g2)
+ *   of the step that starts at t:  10 dt  11 sqrt(|dt|)  12 dt/2  13 t   14, 15 unused */
+#define VAW_FLOW_COLS 16
+
+/* Start of an EDM step:  x_hat = coef[0]*x (+ coef[1]*noise when noise != NULL), float64, and the float32 network input
+ * c_in * float(x_hat / s(t_hat)) written to model_in and, when model_in_dup != NULL, to the second half of the stacked
+ * guided input as well.  coef: [rows][VAW_EDM_COLS] float64, row < rows. */
+int vaw_edm_input(const double* x, const double* noise, const double* coef, int row, int rows, double* x_hat, float* model_in,
+                  float* model_in_dup, int B, int64_t per_sample, vaw_stream stream);
+
+/* After a network evaluation of an EDM step.  denoised (float32, as the denoiser forms it) from the network output o and
+ * x32 = float(x / s):  pred_type 0 EPSILON x32 - sigma*o,  1 START_X o,  2 VELOCITY c_in^2*x32 - (sigma*c_in)*o;  then in
+ * float64 d = k1*x - k2*denoised.
+ *   kind 0 Euler:         x_out = x_hat + h*d
+ *   kind 1 Heun predict:  d_cur = d (written), x_mid = x_hat + (alpha h)*d, network input of x_mid at t_mid -> model_in(_dup)
+ *   kind 2 Heun correct:  d_cur read, x_mid recomputed, d' at (x_mid, t_mid) from the second output,
+ *                         x_out = x_hat + h*(w1*d_cur + w2*d') */
+int vaw_edm_step(int kind, int pred_type, const float* cond, const float* uncond, int64_t model_ld, float guidance_scale,
+                 const double* x_hat, double* d_cur, const double* coef, int row, int rows, double* x_out, float* model_in,
+                 float* model_in_dup, int B, int64_t per_sample, vaw_stream stream);
+
+/* One step of the flow samplers after a network evaluation, float32.  Velocity and score of the output under mean_type
+ * 0 START_X, 1 EPSILON, 2 VELOCITY, 3 VECTOR (convert_model_output_to_vector / _to_score), drift f = v - (g2/2)*score for the
+ * SDE (sde = 1) and f = v for the ODE; row0 is the evaluation the step starts at, row1 the one at its end.
+ *   kind 0 Euler:         x_out = (x + f0*dt) + kick,  kick = (sqrt(g2)*noise)*sqrt|dt|  (noise == NULL: no kick -- the ODE and
+ *                         the SDE's last step)
+ *   kind 1 Heun predict:  the same, with f0 and kick written for the correction
+ *   kind 2 Heun correct:  f1 from the second output at x_pred;  SDE x_out = (x + (0.5*(f0 + f1))*dt) + kick,
+ *                         ODE x_out = x + (dt/2)*(f0 + f1)
+ * x_out_dup != NULL: x_out is written there too (second half of the stacked guided input). */
+int vaw_flow_step(int kind, int sde, int mean_type, const float* cond, const float* uncond, int64_t model_ld,
+                  float guidance_scale, const float* x, const float* noise, const float* x_pred, float* f0, float* kick,
+                  const float* coef, int row0, int row1, int rows, float* x_out, float* x_out_dup, int B, int64_t per_sample,
+                  vaw_stream stream);
+
+/* ---------------------------------------------------------------------------
  * Loss-aware timestep sampling on the device  (tools/resample.py: LossSecondMomentResampler)
  * ------------------------------------------------------------------------- */
 

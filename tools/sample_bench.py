@@ -10,7 +10,15 @@ For a learn_sigma model under IntervalCFG (scale 2.5, active on part of the chai
      Infinity Cache), which is where the byte arithmetic of DESIGN applies;
  (c) vaw_finish_images against the torch expression, f32 and f64, rotating buffers;
  (d) a full Sampler.sample of one batch (DDIM, `--steps` steps), fused and through the composition of (b).
-(a) / (b) and the two forms of (c) / (d) alternate inside one timed run.  One JSON line at the end."""
+(a) / (b) and the two forms of (c) / (d) alternate inside one timed run.  One JSON line at the end.
+
+With `--solver heun|euler` (EDM sampler) or `--mode flow` (flow SDE sampler, Heun unless `--solver euler`) the run is instead
+ (e) one Sampler.sample of `--batches` batches of `--batch` images, `--steps` solver steps, guidance `--guidance`: the time of
+     each batch on a host clock (every batch ends in the device-to-host copy of its images), the first `--skip` batches left
+     out (tables, workspaces and, with `--graph`, the capture), median / min / max of the rest in ms.  `--fused 0` runs the
+     tensor composition (`fused=False`), `--fused 1` the fused solver steps, `--graph` adds args.hip_graph=True.
+     `--tree DIR` imports the package from another checkout (built in place), e.g. the parent commit's, which knows
+     neither `fused` nor `hip_graph`: pass neither there."""
 import argparse
 import json
 import os
@@ -20,7 +28,8 @@ from types import SimpleNamespace
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+_tree = [a.split("=", 1)[1] if "=" in a else sys.argv[i + 1] for i, a in enumerate(sys.argv) if a == "--tree" or a.startswith("--tree=")]
+sys.path.insert(0, os.path.abspath(_tree[0]) if _tree else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import vaw_amd  # noqa: E402
 from vaw_amd import ops  # noqa: E402
 
@@ -79,14 +88,14 @@ def wall_pair(fa, fb, repeats):
     return sorted(ta)[len(ta) // 2], sorted(tb)[len(tb) // 2]
 
 
-def build_model(a):
+def build_model(a, learn_sigma=True):
     dt = "fp32" if a.fp32 else "bf16"
     if a.model.startswith("DiT"):
         model = vaw_amd.DiT_models[a.model.replace("_", "-")](image_size=a.image_size or 32, patch_size=a.patch, in_channels=4, class_dropout_prob=0.1,
-                                                              num_classes=a.num_classes, learn_sigma=True, compute_dtype=dt)
+                                                              num_classes=a.num_classes, learn_sigma=learn_sigma, compute_dtype=dt)
         C, H = 4, a.image_size or 32
     else:
-        model = getattr(vaw_amd, a.model)(num_classes=a.num_classes, class_cond=True, learn_sigma=True, drop_label_prob=0.1, compute_dtype=dt)
+        model = getattr(vaw_amd, a.model)(num_classes=a.num_classes, class_cond=True, learn_sigma=learn_sigma, drop_label_prob=0.1, compute_dtype=dt)
         C, H = model.in_channels, model.image_size
     model = model.to("cuda").eval()
     with torch.no_grad():
@@ -98,8 +107,53 @@ def build_model(a):
     return model, C, H
 
 
+def solver_bench(a):
+    """(e): per-batch time of Sampler.sample through the EDM / flow solvers."""
+    import functools
+    flow = a.mode == "flow"
+    solver = a.solver or "heun"
+    torch.manual_seed(0)
+    model, C, H = build_model(a, learn_sigma=not flow)
+    args = SimpleNamespace(weight_type="lambda", gamma=0.0, learn_sigma=not flow, p2_gamma=1, p2_k=1, time_dist=["uniform"], cpu_rng=False,
+                           in_chans=3 if C == 3 else 4, class_cond=True, parallel=False, class_labels=None, amp=False, latent_scale=0.18215,
+                           guidance_scale=a.guidance, interval=(-1.0, -1.0), model_mode="flow" if flow else "diffusion", solver=solver,
+                           sample_steps=a.steps, discretization="edm", schedule="linear", scaling="none", path_type="linear" if flow else "cosine",
+                           mean_type="VELOCITY" if flow else "EPSILON", sampler_type="sde")
+    if a.graph:
+        args.hip_graph = True
+    if a.fused is not None:
+        import vaw_amd.sampler as sm
+        for name in ("edm_sample", "flow_sde_sample", "flow_ode_sample"):
+            setattr(sm, name, functools.partial(getattr(sm, name), fused=bool(a.fused)))
+    diff = vaw_amd.FlowMatching(args=args, model_mean_type=vaw_amd.ModelMeanType.VELOCITY) if flow else None
+    s = vaw_amd.Sampler(args, torch.device("cuda"), model, diff, **(dict(decode_fn=(lambda z: z[:, :3])) if C == 4 else {}))
+    stamps, gather = [], s._gather_samples
+
+    def timed_gather(*g):
+        gather(*g)                          # ends in the images' copy to the host: the batch is done
+        stamps.append(time.perf_counter())
+    s._gather_samples = timed_gather
+    torch.cuda.synchronize()
+    stamps.append(time.perf_counter())
+    s.sample(a.batch * a.batches, a.batch, H, a.num_classes)
+    ms = sorted(1e3 * (t1 - t0) for t0, t1 in zip(stamps[a.skip:-1], stamps[a.skip + 1:]))
+    evals = (2 * a.steps - 1 if solver == "heun" else a.steps)
+    print(json.dumps({"part": "e", "model": a.model, "dtype": "fp32" if a.fp32 else "bf16", "mode": a.mode, "solver": solver, "steps": a.steps,
+                      "batch": a.batch, "guidance": a.guidance, "fused": a.fused, "graph": bool(a.graph), "tree": a.tree or ".",
+                      "evaluations_per_batch": evals, "batches_timed": len(ms), "ms_per_batch_median": ms[len(ms) // 2],
+                      "ms_per_batch_min": ms[0], "ms_per_batch_max": ms[-1]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--solver", choices=["heun", "euler"], default=None, help="(e): time Sampler.sample through this EDM / flow solver")
+    ap.add_argument("--mode", choices=["diffusion", "flow"], default="diffusion")
+    ap.add_argument("--fused", type=int, choices=[0, 1], default=None, help="(e): 0 = the tensor composition, 1 = the fused solver steps")
+    ap.add_argument("--graph", action="store_true", help="(e): args.hip_graph=True")
+    ap.add_argument("--guidance", type=float, default=1.0, help="(e): guidance scale (1.0, the reference's default: unguided)")
+    ap.add_argument("--batches", type=int, default=12)
+    ap.add_argument("--skip", type=int, default=2)
+    ap.add_argument("--tree", default=None, help="import vaw_amd from this checkout instead of the one the script lives in")
     ap.add_argument("--model", default="UNet_32")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=50)
@@ -112,6 +166,8 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_bench.py measures on the GPU only")
+    if a.solver or a.mode == "flow":
+        return solver_bench(a)
     torch.manual_seed(0)
     model, C, H = build_model(a)
     N, n = a.batch, C * H * H

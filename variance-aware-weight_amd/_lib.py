@@ -127,6 +127,9 @@ _PROTOS = {
     "vaw_guided_sample_step": [_i, _p, _p, _p, _p, _l, _f, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _i, _l, _p],
     "vaw_cfg_combine": [_p, _p, _l, _f, _p, _i, _l, _p],
     "vaw_finish_images": [_p, _i, _p, _i, _i, _i, _i, _p],
+    "vaw_edm_input": [_p, _p, _p, _i, _i, _p, _p, _p, _i, _l, _p],
+    "vaw_edm_step": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _i, _i, _p, _p, _p, _i, _l, _p],
+    "vaw_flow_step": [_i, _i, _i, _p, _p, _l, _f, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _l, _p],
     "vaw_prior_bpd": [_p, _f, _f, _p, _i, _l, _p],
     "vaw_ddim_reverse_step": [_p, _l, _p, _p, _i, _p, _p, _i, _l, _p],
     "vaw_resampler_update": [_p, _p, _i, _i, _i, _p, _p, _p, _p],

@@ -1,0 +1,367 @@
+// Solver steps of the EDM (Euler / Heun, float64) and flow-matching (SDE / ODE, float32) samplers: one streaming pass each
+// around the denoiser call.  The coefficients of a step do not depend on x; they come from a device table built once per
+// grid (samplers.py) and are read by row index.  Every operation is rounded on its own, in the order of the tensor
+// composition these kernels replace (this file is built with -ffp-contract=off; divisions and square roots are IEEE).
+// The model output of a guided call is the stacked [2N, ...] tensor read in place: rows model_ld floats apart.
+#include "common.h"
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// One grid row per sample, at most 64 blocks of 256 threads along it (grid-stride beyond): B x 64 blocks cover the chip's
+// 256 CUs from B = 4 on, and the FID batch (64 x 3072 elements, 768 four-element items a row) is 192 blocks.
+static inline dim3 row_grid(int64_t items, int B) {
+    int64_t g = (items + 255) / 256;
+    return dim3((unsigned)(g < 1 ? 1 : (g > 64 ? 64 : g)), (unsigned)B);
+}
+
+__device__ __forceinline__ float cfg_mix(float c, float u, float s) { return u + s * (c - u); }
+
+__device__ __forceinline__ void load4d(const double* p, double* v) {
+    const f64x2 a = *reinterpret_cast<const f64x2*>(p), b = *reinterpret_cast<const f64x2*>(p + 2);
+    v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
+}
+__device__ __forceinline__ void store4d(double* p, const double* v) {
+    const f64x2 a = {v[0], v[1]}, b = {v[2], v[3]};
+    *reinterpret_cast<f64x2*>(p) = a;
+    *reinterpret_cast<f64x2*>(p + 2) = b;
+}
+__device__ __forceinline__ void load4f(const float* p, float* v) {
+    const f32x4 t = load4(p);
+    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+}
+__device__ __forceinline__ void store4f(float* p, const float* v) {
+    const f32x4 t = {v[0], v[1], v[2], v[3]};
+    store4(p, t);
+}
+
+// ---------------------------------------------------------------------------------------------
+// EDM.  Table row (VAW_EDM_COLS doubles) of step i:
+//   0 x_hat scale s(t_hat)/s(t_cur)   1 noise coefficient   2..9 evaluation at t_hat   10 h   11 alpha*h   12, 13 Heun weights
+//   14..21 evaluation at t_mid.  An evaluation block: s(t), sigma as the denoiser sees it (f32), c_in, c_in^2, sigma*c_in
+//   (the f32 scalars of EDMDenoiser.forward, stored widened), dsg/sg + ds/sc, dsg*sc/sg, chain index.
+// ---------------------------------------------------------------------------------------------
+struct EdmEval {
+    double s, k1, k2;
+    float sigma, cin, cin2, sc;
+};
+__device__ __forceinline__ EdmEval edm_eval(const double* r) {
+    EdmEval e;
+    e.s = r[0]; e.sigma = (float)r[1]; e.cin = (float)r[2]; e.cin2 = (float)r[3]; e.sc = (float)r[4]; e.k1 = r[5]; e.k2 = r[6];
+    return e;
+}
+// f32 model input of EDMDenoiser.forward for the f64 state x at an evaluation: c_in * f32(x / s)
+__device__ __forceinline__ float edm_model_in(const EdmEval& e, double x) { return e.cin * (float)(x / e.s); }
+// dx/dt of _Path.slope with the denoised image of EDMDenoiser.forward (pred: 0 EPSILON, 1 START_X, 2 VELOCITY) for model output o
+__device__ __forceinline__ double edm_slope(const EdmEval& e, int pred, double x, float o) {
+    const float x32 = (float)(x / e.s);
+    float den;
+    if (pred == 0) den = x32 - e.sigma * o;
+    else if (pred == 1) den = o;
+    else den = e.cin2 * x32 - e.sc * o;
+    return e.k1 * x - e.k2 * (double)den;
+}
+
+template <bool VEC>
+__global__ void edm_input_kernel(const double* __restrict__ x, const double* __restrict__ noise, const double* __restrict__ coef,
+                                 double* __restrict__ x_hat, float* __restrict__ min, float* __restrict__ min2, int64_t n) {
+    const double A = coef[0], nc = coef[1];
+    const EdmEval e = edm_eval(coef + 2);
+    const int64_t base = (int64_t)blockIdx.y * n;
+    if (VEC) {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t o = base + 4 * i;
+            double xv[4], nz[4];
+            float mi[4];
+            load4d(x + o, xv);
+            if (noise) load4d(noise + o, nz);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double h = A * xv[j];
+                if (noise) h = h + nc * nz[j];
+                xv[j] = h;
+                mi[j] = edm_model_in(e, h);
+            }
+            store4d(x_hat + o, xv);
+            store4f(min + o, mi);
+            if (min2) store4f(min2 + o, mi);
+        }
+    } else {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            double h = A * x[base + i];
+            if (noise) h = h + nc * noise[base + i];
+            x_hat[base + i] = h;
+            const float m = edm_model_in(e, h);
+            min[base + i] = m;
+            if (min2) min2[base + i] = m;
+        }
+    }
+}
+
+extern "C" int vaw_edm_input(const double* x, const double* noise, const double* coef, int row, int rows, double* x_hat,
+                             float* model_in, float* model_in_dup, int B, int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "edm_input: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(x && coef && x_hat && model_in, "edm_input: null pointer");
+    VAW_CHECK_ARG(row >= 0 && row < rows, "edm_input: row %d outside the table of %d rows", row, rows);
+    VAW_CHECK_ARG(((uintptr_t)x & 7) == 0 && ((uintptr_t)noise & 7) == 0 && ((uintptr_t)x_hat & 7) == 0 && ((uintptr_t)coef & 7) == 0,
+                  "edm_input: float64 pointer not aligned to 8 bytes");
+    const bool vec = per_sample % 4 == 0 && al16(x) && al16(noise) && al16(x_hat) && al16(model_in) && al16(model_in_dup);
+    const dim3 grid = row_grid(vec ? per_sample / 4 : per_sample, B);
+    const double* r = coef + (int64_t)row * VAW_EDM_COLS;
+    if (vec)
+        edm_input_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(x, noise, r, x_hat, model_in, model_in_dup, per_sample);
+    else
+        edm_input_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(x, noise, r, x_hat, model_in, model_in_dup, per_sample);
+    VAW_CHECK_LAUNCH("edm_input");
+    return VAW_OK;
+}
+
+// kind 0 Euler:         x_out = x_hat + h * d,                      d = slope(x_hat, t_hat)
+// kind 1 Heun predict:  d_cur = d;  x_mid = x_hat + (alpha h) * d;  model input of x_mid at t_mid
+// kind 2 Heun correct:  x_mid recomputed from x_hat and d_cur (the same two operations, so the same bits);
+//                       d' = slope(x_mid, t_mid);  x_out = x_hat + h * (w1 * d_cur + w2 * d')
+struct EdmStepArgs {
+    const float *cond, *uncond;
+    int64_t ld;
+    float gs;
+    const double *x_hat, *coef;
+    double *d_cur, *x_out;
+    float *min, *min2;
+    int64_t n;
+    int kind, pred;
+};
+
+__device__ __forceinline__ void edm_step_elem(int kind, int pred, const EdmEval& hat, const EdmEval& mid, double h, double ah, double w1,
+                                              double w2, double xh, float o, double& dc, double& xo, float& mi) {
+    if (kind == 2) {
+        const double xm = xh + ah * dc;
+        const double dm = edm_slope(mid, pred, xm, o);
+        xo = xh + h * (w1 * dc + w2 * dm);
+        return;
+    }
+    const double d = edm_slope(hat, pred, xh, o);
+    if (kind == 0) {
+        xo = xh + h * d;
+        return;
+    }
+    dc = d;
+    mi = edm_model_in(mid, xh + ah * d);
+}
+
+template <bool VEC>
+__global__ void edm_step_kernel(const EdmStepArgs a) {
+    const double* r = a.coef;
+    const EdmEval hat = edm_eval(r + 2), mid = edm_eval(r + 14);
+    const double h = r[10], ah = r[11], w1 = r[12], w2 = r[13];
+    const int kind = a.kind, pred = a.pred;
+    const int64_t n = a.n, base = (int64_t)blockIdx.y * n, mbase = (int64_t)blockIdx.y * a.ld;
+    if (VEC) {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t o = base + 4 * i;
+            double xh[4], dc[4], xo[4];
+            float c[4], u[4], mi[4];
+            load4d(a.x_hat + o, xh);
+            load4f(a.cond + mbase + 4 * i, c);
+            if (a.uncond) load4f(a.uncond + mbase + 4 * i, u);
+            if (kind == 2) load4d(a.d_cur + o, dc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float m = a.uncond ? cfg_mix(c[j], u[j], a.gs) : c[j];
+                edm_step_elem(kind, pred, hat, mid, h, ah, w1, w2, xh[j], m, dc[j], xo[j], mi[j]);
+            }
+            if (kind == 1) {
+                store4d(a.d_cur + o, dc);
+                store4f(a.min + o, mi);
+                if (a.min2) store4f(a.min2 + o, mi);
+            } else {
+                store4d(a.x_out + o, xo);
+            }
+        }
+    } else {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            float m = a.cond[mbase + i];
+            if (a.uncond) m = cfg_mix(m, a.uncond[mbase + i], a.gs);
+            double dc = kind == 2 ? a.d_cur[base + i] : 0.0, xo = 0.0;
+            float mi = 0.f;
+            edm_step_elem(kind, pred, hat, mid, h, ah, w1, w2, a.x_hat[base + i], m, dc, xo, mi);
+            if (kind == 1) {
+                a.d_cur[base + i] = dc;
+                a.min[base + i] = mi;
+                if (a.min2) a.min2[base + i] = mi;
+            } else {
+                a.x_out[base + i] = xo;
+            }
+        }
+    }
+}
+
+extern "C" int vaw_edm_step(int kind, int pred_type, const float* cond, const float* uncond, int64_t model_ld, float guidance_scale,
+                            const double* x_hat, double* d_cur, const double* coef, int row, int rows, double* x_out,
+                            float* model_in, float* model_in_dup, int B, int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "edm_step: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(kind >= 0 && kind <= 2 && pred_type >= 0 && pred_type <= 2, "edm_step: bad kind %d or pred_type %d", kind, pred_type);
+    VAW_CHECK_ARG(cond && x_hat && coef, "edm_step: null pointer");
+    VAW_CHECK_ARG(kind == 1 ? (d_cur && model_in) : (x_out && (kind == 0 || d_cur)),
+                  "edm_step: kind 1 needs d_cur and model_in, kind 0 x_out, kind 2 d_cur and x_out");
+    VAW_CHECK_ARG(model_ld >= per_sample, "edm_step: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
+    VAW_CHECK_ARG(row >= 0 && row < rows, "edm_step: row %d outside the table of %d rows", row, rows);
+    VAW_CHECK_ARG(((uintptr_t)x_hat & 7) == 0 && ((uintptr_t)d_cur & 7) == 0 && ((uintptr_t)x_out & 7) == 0 && ((uintptr_t)coef & 7) == 0,
+                  "edm_step: float64 pointer not aligned to 8 bytes");
+    if (kind == 0) d_cur = nullptr;
+    if (kind == 1) x_out = nullptr;
+    else model_in = model_in_dup = nullptr;
+    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(cond) && al16(uncond) && al16(x_hat) && al16(d_cur) &&
+                     al16(x_out) && al16(model_in) && al16(model_in_dup);
+    const dim3 grid = row_grid(vec ? per_sample / 4 : per_sample, B);
+    const EdmStepArgs a = {cond, uncond, model_ld, guidance_scale, x_hat, coef + (int64_t)row * VAW_EDM_COLS, d_cur, x_out,
+                           model_in, model_in_dup, per_sample, kind, pred_type};
+    if (vec) edm_step_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else edm_step_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    VAW_CHECK_LAUNCH("edm_step");
+    return VAW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Flow matching.  Table row (VAW_FLOW_COLS floats) of one evaluation at time t:
+//   0 a  1 s  2 a'  3 s'  4 g2 = 2 s s'  5 g2/2  6 s^2  7 a^2 + s^2  8 s a' - a s'  9 sqrt(g2)
+//   and of the step that starts there:  10 dt  11 sqrt(|dt|)  12 dt/2  (13 t).
+// ---------------------------------------------------------------------------------------------
+struct FlowRow {
+    float a, s, da, ds, hg2, s2, den, vden;
+};
+__device__ __forceinline__ FlowRow flow_row(const float* r) {
+    FlowRow f;
+    f.a = r[0]; f.s = r[1]; f.da = r[2]; f.ds = r[3]; f.hg2 = r[5]; f.s2 = r[6]; f.den = r[7]; f.vden = r[8];
+    return f;
+}
+// _flow_fields + the drift: mean_type 0 START_X, 1 EPSILON, 2 VELOCITY, 3 VECTOR; sde: v - (g2/2) * score, else v.
+__device__ __forceinline__ float flow_drift(const FlowRow& f, int mt, bool sde, float o, float xt) {
+    float v, score = 0.f;
+    if (mt == 0) {
+        const float r = xt - f.a * o;
+        const float eps = r / f.s;
+        if (sde) score = (-r) / f.s2;
+        v = f.da * o + f.ds * eps;
+    } else if (mt == 1) {
+        const float x0 = (xt - f.s * o) / f.a;
+        if (sde) score = (-o) / f.s;
+        v = f.da * x0 + f.ds * o;
+    } else if (mt == 2) {
+        const float x0 = (f.a * xt - f.s * o) / f.den;
+        const float eps = (f.s * xt + f.a * o) / f.den;
+        if (sde) score = (-eps) / f.s;
+        v = f.da * x0 + f.ds * eps;
+    } else {
+        if (sde) score = (-((f.da * xt - f.a * o) / f.vden)) / f.s;
+        v = o;
+    }
+    return sde ? v - f.hg2 * score : v;
+}
+
+// kind 0 Euler:         x_out = (x + f0 dt) + kick           (kick = (sqrt(g2) noise) sqrt|dt|; none without noise, none for the ODE)
+// kind 1 Heun predict:  f0, kick stored;  x_out = the Euler step (the input of the second evaluation)
+// kind 2 Heun correct:  f1 = drift(x_pred, row1);  SDE x_out = (x + (0.5 (f0 + f1)) dt) + kick,  ODE x_out = x + (dt/2)(f0 + f1)
+struct FlowStepArgs {
+    const float *cond, *uncond;
+    int64_t ld;
+    float gs;
+    const float *x, *noise, *x_pred, *r0, *r1;
+    float *f0, *kick, *x_out, *x_out2;
+    int64_t n;
+    int kind, sde, mt;
+};
+
+__device__ __forceinline__ float flow_step_elem(const FlowStepArgs& a, const FlowRow& e0, const FlowRow& e1, float sg2, float dt, float sdt,
+                                                float hdt, float o, float x, float nz, float xp, float& f0, float& kick) {
+    const bool sde = a.sde != 0;
+    if (a.kind == 2) {
+        const float f1 = flow_drift(e1, a.mt, sde, o, xp);
+        if (sde) {
+            const float y = x + (0.5f * (f0 + f1)) * dt;
+            return a.kick ? y + kick : y;
+        }
+        return x + hdt * (f0 + f1);
+    }
+    f0 = flow_drift(e0, a.mt, sde, o, x);
+    const float y = x + f0 * dt;
+    if (!a.noise) return y;
+    kick = (sg2 * nz) * sdt;
+    return y + kick;
+}
+
+template <bool VEC>
+__global__ void flow_step_kernel(const FlowStepArgs a) {
+    const FlowRow e0 = flow_row(a.r0), e1 = flow_row(a.r1);
+    const float sg2 = a.r0[9], dt = a.r0[10], sdt = a.r0[11], hdt = a.r0[12];
+    const int64_t n = a.n, base = (int64_t)blockIdx.y * n, mbase = (int64_t)blockIdx.y * a.ld;
+    const bool corr = a.kind == 2, pred = a.kind == 1;
+    if (VEC) {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t o = base + 4 * i;
+            float c[4], u[4], x[4], nz[4] = {0.f, 0.f, 0.f, 0.f}, xp[4] = {0.f, 0.f, 0.f, 0.f}, f0[4], kk[4] = {0.f, 0.f, 0.f, 0.f}, y[4];
+            load4f(a.cond + mbase + 4 * i, c);
+            if (a.uncond) load4f(a.uncond + mbase + 4 * i, u);
+            load4f(a.x + o, x);
+            if (!corr && a.noise) load4f(a.noise + o, nz);
+            if (corr) {
+                load4f(a.x_pred + o, xp);
+                load4f(a.f0 + o, f0);
+                if (a.kick) load4f(a.kick + o, kk);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float m = a.uncond ? cfg_mix(c[j], u[j], a.gs) : c[j];
+                y[j] = flow_step_elem(a, e0, e1, sg2, dt, sdt, hdt, m, x[j], nz[j], xp[j], f0[j], kk[j]);
+            }
+            if (pred) {
+                store4f(a.f0 + o, f0);
+                if (a.kick) store4f(a.kick + o, kk);
+            }
+            store4f(a.x_out + o, y);
+            if (a.x_out2) store4f(a.x_out2 + o, y);
+        }
+    } else {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            float m = a.cond[mbase + i];
+            if (a.uncond) m = cfg_mix(m, a.uncond[mbase + i], a.gs);
+            float f0 = corr ? a.f0[base + i] : 0.f, kk = (corr && a.kick) ? a.kick[base + i] : 0.f;
+            const float y = flow_step_elem(a, e0, e1, sg2, dt, sdt, hdt, m, a.x[base + i], (!corr && a.noise) ? a.noise[base + i] : 0.f,
+                                           corr ? a.x_pred[base + i] : 0.f, f0, kk);
+            if (pred) {
+                a.f0[base + i] = f0;
+                if (a.kick) a.kick[base + i] = kk;
+            }
+            a.x_out[base + i] = y;
+            if (a.x_out2) a.x_out2[base + i] = y;
+        }
+    }
+}
+
+extern "C" int vaw_flow_step(int kind, int sde, int mean_type, const float* cond, const float* uncond, int64_t model_ld,
+                             float guidance_scale, const float* x, const float* noise, const float* x_pred, float* f0, float* kick,
+                             const float* coef, int row0, int row1, int rows, float* x_out, float* x_out_dup, int B,
+                             int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "flow_step: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(kind >= 0 && kind <= 2 && mean_type >= 0 && mean_type <= 3 && (sde == 0 || sde == 1),
+                  "flow_step: bad kind %d, mean_type %d or sde %d", kind, mean_type, sde);
+    VAW_CHECK_ARG(cond && x && coef && x_out, "flow_step: null pointer");
+    VAW_CHECK_ARG(kind == 0 || f0, "flow_step: Heun steps need f0");
+    VAW_CHECK_ARG(kind != 2 || x_pred, "flow_step: the Heun correction needs x_pred");
+    VAW_CHECK_ARG(sde || !(noise || kick), "flow_step: the ODE takes no noise");
+    VAW_CHECK_ARG(kind != 1 || !sde || (!noise == !kick), "flow_step: an SDE Heun prediction stores the kick of its noise");
+    VAW_CHECK_ARG(model_ld >= per_sample, "flow_step: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
+    VAW_CHECK_ARG(row0 >= 0 && row0 < rows && row1 >= 0 && row1 < rows, "flow_step: rows %d, %d outside the table of %d rows", row0, row1,
+                  rows);
+    if (kind == 0) f0 = kick = nullptr;
+    if (kind == 2) noise = nullptr;
+    else x_pred = nullptr;
+    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(cond) && al16(uncond) && al16(x) && al16(noise) && al16(x_pred) &&
+                     al16(f0) && al16(kick) && al16(x_out) && al16(x_out_dup);
+    const dim3 grid = row_grid(vec ? per_sample / 4 : per_sample, B);
+    const FlowStepArgs a = {cond, uncond, model_ld, guidance_scale, x, noise, x_pred, coef + (int64_t)row0 * VAW_FLOW_COLS,
+                            coef + (int64_t)row1 * VAW_FLOW_COLS, f0, kick, x_out, x_out_dup, per_sample, kind, sde, mean_type};
+    if (vec) flow_step_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else flow_step_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    VAW_CHECK_LAUNCH("flow_step");
+    return VAW_OK;
+}

@@ -232,6 +232,78 @@ def cfg_combine(cond, uncond, guidance_scale):
     return out
 
 
+EDM_COLS, FLOW_COLS = 24, 16          # VAW_EDM_COLS, VAW_FLOW_COLS
+EDM_PRED = {"EPSILON": 0, "START_X": 1, "VELOCITY": 2}
+FLOW_MEAN = {"START_X": 0, "EPSILON": 1, "VELOCITY": 2, "VECTOR": 3}
+STEP_EULER, STEP_PREDICT, STEP_CORRECT = range(3)
+
+
+def _dense(what, dtype, shape, *ts):
+    for t in ts:
+        if t is not None and not (t.dtype == dtype and t.shape == shape and t.is_contiguous()):
+            raise L.VawError(f"{what}: expected a contiguous {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)} "
+                             f"contiguous={t.is_contiguous()}")
+
+
+def _table(what, coef, dtype, cols, *rows):
+    if not (coef.dtype == dtype and coef.dim() == 2 and coef.shape[1] == cols and coef.is_contiguous()):
+        raise L.VawError(f"{what}: the table is not a contiguous {dtype} [rows, {cols}]: {coef.dtype} {tuple(coef.shape)}")
+    for r in rows:
+        if not 0 <= int(r) < coef.shape[0]:
+            raise L.VawError(f"{what}: row {r} outside the table of {coef.shape[0]} rows")
+
+
+def _model_halves_in_place(what, cond, uncond, x):
+    for t in (cond, uncond):
+        if t is not None and (t.shape != x.shape or t.dtype != torch.float32):
+            raise L.VawError(f"{what}: model output part {tuple(t.shape)} {t.dtype} is not float32 {tuple(x.shape)}")
+    return _same_ld((cond, uncond), x.numel() // max(x.shape[0], 1))
+
+
+def edm_input(x, noise, coef, row, x_hat, model_in, model_in_dup=None):
+    """Start of an EDM step (vaw_edm_input): x_hat = coef[row, 0] * x (+ coef[row, 1] * noise), float64, and the denoiser's
+    float32 network input c_in * float(x_hat / s) into model_in (and model_in_dup, the second half of a stacked guided input).
+    Bitwise the tensor operations of edm_sample / EDMDenoiser.forward.  Returns x_hat."""
+    need_cuda(x, noise, coef, x_hat, model_in, model_in_dup)
+    _dense("edm_input", torch.float64, x.shape, x, noise, x_hat)
+    _dense("edm_input", torch.float32, x.shape, model_in, model_in_dup)
+    _table("edm_input", coef, torch.float64, EDM_COLS, row)
+    B = x.shape[0]
+    check(L.lib().vaw_edm_input(ptr(x), ptr(noise), ptr(coef), int(row), coef.shape[0], ptr(x_hat), ptr(model_in), ptr(model_in_dup),
+                                B, x.numel() // max(B, 1), stream_ptr()), "vaw_edm_input")
+    return x_hat
+
+
+def edm_step(kind, pred_type, cond, uncond, guidance_scale, x_hat, d_cur, coef, row, x_out=None, model_in=None, model_in_dup=None):
+    """After a network evaluation of an EDM step (vaw_edm_step): kind STEP_EULER / STEP_CORRECT write and return x_out,
+    STEP_PREDICT writes d_cur and the network input of the midpoint (model_in, model_in_dup) and returns d_cur.  cond / uncond:
+    x-shaped float32 views of the network output (uncond=None: no guidance), read in place; pred_type: a key of EDM_PRED."""
+    need_cuda(cond, uncond, x_hat, d_cur, coef, x_out, model_in, model_in_dup)
+    _dense("edm_step", torch.float64, x_hat.shape, x_hat, d_cur, x_out)
+    _dense("edm_step", torch.float32, x_hat.shape, model_in, model_in_dup)
+    _table("edm_step", coef, torch.float64, EDM_COLS, row)
+    (cond, uncond), ld = _model_halves_in_place("edm_step", cond, uncond, x_hat)
+    B = x_hat.shape[0]
+    check(L.lib().vaw_edm_step(int(kind), EDM_PRED[pred_type], ptr(cond), ptr(uncond), ld, float(guidance_scale), ptr(x_hat), ptr(d_cur),
+                               ptr(coef), int(row), coef.shape[0], ptr(x_out), ptr(model_in), ptr(model_in_dup), B,
+                               x_hat.numel() // max(B, 1), stream_ptr()), "vaw_edm_step")
+    return d_cur if kind == STEP_PREDICT else x_out
+
+
+def flow_step(kind, sde, mean_type, cond, uncond, guidance_scale, x, noise, x_pred, f0, kick, coef, row0, row1, x_out, x_out_dup=None):
+    """One step of the flow samplers after a network evaluation (vaw_flow_step), float32: see include/vaw_hip.h.  Returns x_out.
+    mean_type: a key of FLOW_MEAN; cond / uncond as in edm_step."""
+    need_cuda(cond, uncond, x, noise, x_pred, f0, kick, coef, x_out, x_out_dup)
+    _dense("flow_step", torch.float32, x.shape, x, noise, x_pred, f0, kick, x_out, x_out_dup)
+    _table("flow_step", coef, torch.float32, FLOW_COLS, row0, row1)
+    (cond, uncond), ld = _model_halves_in_place("flow_step", cond, uncond, x)
+    B = x.shape[0]
+    check(L.lib().vaw_flow_step(int(kind), 1 if sde else 0, FLOW_MEAN[mean_type], ptr(cond), ptr(uncond), ld, float(guidance_scale),
+                                ptr(x), ptr(noise), ptr(x_pred), ptr(f0), ptr(kick), ptr(coef), int(row0), int(row1), coef.shape[0],
+                                ptr(x_out), ptr(x_out_dup), B, x.numel() // max(B, 1), stream_ptr()), "vaw_flow_step")
+    return x_out
+
+
 def finish_images(samples, out=None):
     """[B, C, H, W] f32 / f64 samples in [-1, 1] -> [B, H, W, C] uint8 (vaw_finish_images): bitwise
     ((x + 1) * 127.5).clamp(0, 255).to(uint8).permute(0, 2, 3, 1).contiguous() for finite x; NaN writes 0.

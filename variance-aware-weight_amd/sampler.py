@@ -93,7 +93,10 @@ class Sampler:
 
     Extensions: `decode_fn(latents) -> images in [-1, 1]` stands where the reference loads a diffusers VAE
     (args.in_chans == 4; the latents are handed over already divided by args.latent_scale); with args.cpu_rng the labels
-    and every noise draw come from the CPU generator in the reference's order, which reproduces its CPU stream."""
+    and every noise draw come from the CPU generator in the reference's order, which reproduces its CPU stream.
+    args.hip_graph=True (EDM and flow generators, whose loops do not synchronise with the host): the first batch runs eagerly,
+    the second is captured into one graph on static label and output buffers, later batches replay it; the labels are drawn
+    outside the graph in the same order, so images and labels are those of the eager run.  "auto" or absent: eager."""
 
     def __init__(self, args, device, eval_model, diffusion, classifier=None, decode_fn=None):
         if classifier is not None:
@@ -167,10 +170,23 @@ class Sampler:
         return self._inverse_normalize(samples), class_labels
 
     # ---- the three generators -----------------------------------------------------------------------------------
-    def _run(self, draw_batch, num_samples, sample_size, num_classes, progress_bar, desc):
+    def _use_graph(self):
+        if getattr(self.args, "hip_graph", None) is not True:
+            return False
+        why = ("not with args.cpu_rng (the noise would come from the host every step)" if self._cpu_rng() else
+               "not with args.parallel" if self.args.parallel else
+               "the model's forward is not capturable" if getattr(self.model, "graph_capturable", True) is False else
+               "needs a CUDA device" if torch.device(self.device).type != "cuda" else None)
+        if why:
+            raise ValueError(f"args.hip_graph: {why}")
+        return True
+
+    def _run(self, draw_batch, num_samples, sample_size, num_classes, progress_bar, desc, graph=False):
         """The loop the reference's three samplers share: sync the EMA weights, then batches of draw_batch(labels) until
-        num_samples are there (counted per rank, as the reference does)."""
+        num_samples are there (counted per rank, as the reference does).  graph: from the second batch on draw_batch runs
+        as one captured graph."""
         self.model.eval()
+        captured = None          # (graph, static labels, static samples)
         all_samples, all_labels = [], []
         world_size = dist.get_world_size() if self.args.parallel else 1
         if self.args.parallel:
@@ -183,7 +199,23 @@ class Sampler:
         while len(all_samples) * sample_size < num_samples:
             class_labels = self._get_y_cond(sample_size, num_classes)
             with torch.no_grad():
-                samples = draw_batch(class_labels)
+                if not graph or not all_samples:
+                    samples = draw_batch(class_labels)          # eager; with graph: the batch that builds the tables and workspaces
+                else:
+                    if captured is None:
+                        static_labels = None if class_labels is None else class_labels.clone()
+                        torch.cuda.synchronize()
+                        g = torch.cuda.CUDAGraph()
+                        try:
+                            with torch.cuda.graph(g):
+                                static_samples = draw_batch(static_labels)
+                        except RuntimeError as e:
+                            raise ValueError(f"args.hip_graph: the model's forward is not capturable ({e})") from e
+                        captured = (g, static_labels, static_samples)
+                    elif class_labels is not None:
+                        captured[1].copy_(class_labels)
+                    captured[0].replay()
+                    samples = captured[2]
             samples, class_labels = self._process_sample_label(samples, class_labels)
             self._gather_samples(all_samples, all_labels, samples, class_labels, world_size)
             if pbar is not None:
@@ -210,7 +242,8 @@ class Sampler:
             return edm_sample(net, latents, class_labels=class_labels, randn_like=self._randn_like, num_steps=a.sample_steps,
                               solver=a.solver, discretization=a.discretization, schedule=a.schedule, scaling=a.scaling)
 
-        return self._run(draw, num_samples, sample_size, num_classes, progress_bar, f"Generating Samples ({a.solver.capitalize()})")
+        return self._run(draw, num_samples, sample_size, num_classes, progress_bar, f"Generating Samples ({a.solver.capitalize()})",
+                         graph=self._use_graph())
 
     def flow_matching_sampler(self, num_samples, sample_size, image_size, num_classes, progress_bar=False):
         a = self.args
@@ -227,7 +260,8 @@ class Sampler:
             return flow_ode_sample(self.diffusion, cfg_model, noise, self.device, num_steps=a.sample_steps, solver=a.solver,
                                    y=class_labels)
 
-        return self._run(draw, num_samples, sample_size, num_classes, progress_bar, f"Generating Samples ({a.solver.capitalize()})")
+        return self._run(draw, num_samples, sample_size, num_classes, progress_bar, f"Generating Samples ({a.solver.capitalize()})",
+                         graph=self._use_graph())
 
     def sample(self, num_samples, sample_size, image_size, num_classes, progress_bar=False):
         if self.args.model_mode == "flow":

@@ -8,12 +8,19 @@
     solvers euler / midpoint / heun / rk4 are provided on the same time grid, and `dopri5` is refused -- parity unpinned
     for that one entry point.  The SDE sampler is self-contained in the reference and pinned by tests/golden/samplers.pt.
 
-The denoiser call is the hot part and runs on the HIP kernels; the per-step update is a handful of elementwise torch ops
-on [B, C, H, W] (float64 for EDM, as in the reference)."""
+The denoiser call is the hot part and runs on the HIP kernels.  On the GPU the update around it is fused too (`fused=None`):
+everything of a step that does not depend on x is computed once per grid into a device table, cached on the denoiser / flow
+object (`_edm_tables`, `_flow_tables`), and the Euler / Heun steps are single streaming kernels (vaw_edm_input, vaw_edm_step,
+vaw_flow_step; float64 for EDM, as in the reference) that read the table by row, fold the classifier-free guidance
+combination in and write the next network input: bitwise the tensor composition (`fused=False`), with no host
+synchronisation once the tables are cached, so a whole call can be captured into a graph."""
+
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
+from . import ops
 from .gaussian_diffusion import ModelMeanType
 
 __all__ = ["EDMDenoiser", "edm_sample", "flow_sde_sample", "flow_ode_sample"]
@@ -151,24 +158,166 @@ def _noise_levels(net, discretization, num_steps, sigma_min, sigma_max, rho, eps
     raise ValueError(f"discretization {discretization!r}")
 
 
-@torch.no_grad()
-def edm_sample(net, latents, class_labels=None, randn_like=torch.randn_like, num_steps=18, sigma_min=None, sigma_max=None, rho=7,
-               solver="heun", discretization="edm", schedule="linear", scaling="none", epsilon_s=1e-3, alpha=1, S_churn=0,
-               S_min=0, S_max=float("inf"), S_noise=1, **model_kwargs):
-    """x_0 from `latents` ~ N(0, I): `num_steps` Euler / Heun (2nd-order, `alpha` = 1) steps of the EDM sampler, with the
-    optional "churn" noise injection (S_churn, S_min, S_max, S_noise).  Every noise level handed to the network is first
-    snapped to its chain (net.round_sigma)."""
-    if solver not in ("euler", "heun"):
-        raise ValueError(f"solver {solver!r}")
+def _want_fused(fused, x, what, unsupported):
+    """Resolve the `fused` keyword of the samplers: None = fused where it is supported (GPU tensors), False = the tensor
+    composition, True = fused or an error."""
+    if fused is False:
+        return False
+    if not x.is_cuda:
+        unsupported = "tensors on the CPU (the fused steps are HIP kernels)"
+    if unsupported is None:
+        return True
+    if fused:
+        raise ValueError(f"{what}: fused=True is not supported for {unsupported}")
+    return False
+
+
+def _row(values, dtype, device, cols):
+    """A table row from the scalars the loops compute (0-dim / one-element tensors or Python numbers), widened exactly."""
+    vals = [(v.to(dtype) if torch.is_tensor(v) else torch.tensor(v, dtype=dtype, device=device)).reshape(()) for v in values]
+    return torch.stack(vals + [torch.zeros((), dtype=dtype, device=device)] * (cols - len(vals)))
+
+
+def _guidance(model, y, t_mean, model_kwargs):
+    """What the fused loops need to know of an IntervalCFG model: the wrapper (None for any other model), which evaluations
+    are guided (the host-side predicate on the mean timestep of each, None = not evaluated), the scale, the stacked labels."""
+    cfg = model if hasattr(model, "guided_halves") else None
+    can = cfg is not None and cfg.class_cond and y is not None
+    guided = [can and tm is not None and cfg.guidance_active(tm) for tm in t_mean]
+    y2 = None
+    if any(guided):
+        y2 = {**model_kwargs, "y": torch.cat((y, y.new_full(y.shape, cfg.null_label)))}
+    return cfg, guided, (cfg.guidance_scale if cfg is not None else 1.0), y2
+
+
+def _evaluate(model, cfg, guided, stacked_kwargs, buf, n, t_rows, e, channels, model_kwargs):
+    """One network evaluation of a fused loop on the input buffer `buf` ([2n, ...] when any evaluation of the grid is
+    guided): the (conditional, unconditional or None) x-shaped float32 views of its output, left where the network wrote it."""
+    if guided[e]:
+        out = cfg.model(buf, t_rows[e], **stacked_kwargs)
+    elif cfg is not None:
+        out = cfg.unguided(buf[:n], t_rows[e, :n], **model_kwargs)
+    else:
+        out = model(buf[:n], t_rows[e, :n], **model_kwargs)
+    out = _unwrap(out)
+    if channels is not None:
+        out = out[:, :channels]
+    if out.dtype != torch.float32:
+        out = out.to(torch.float32)
+    return (out[:n], out[n:]) if guided[e] else (out, None)
+
+
+def _edm_sigma_range(net, discretization, sigma_min, sigma_max, epsilon_s):
     vp0 = lambda t: (np.e ** (0.5 * 19.9 * (t ** 2) + 0.1 * t) - 1) ** 0.5
     lo = {"vp": vp0(epsilon_s), "ve": 0.02, "iddpm": 0.002, "edm": 0.002}[discretization] if sigma_min is None else sigma_min
     hi = {"vp": vp0(1), "ve": 100, "iddpm": 81, "edm": 80}[discretization] if sigma_max is None else sigma_max
-    lo, hi = max(lo, net.sigma_min), min(hi, net.sigma_max)
+    return max(lo, net.sigma_min), min(hi, net.sigma_max)
+
+
+def _edm_time_grid(net, device, num_steps, lo, hi, rho, discretization, schedule, scaling, epsilon_s):
     bd = 2 * (np.log(lo ** 2 + 1) / epsilon_s - np.log(hi ** 2 + 1)) / (epsilon_s - 1)
     path = _Path(schedule, scaling, bd, np.log(hi ** 2 + 1) - 0.5 * bd)
-    levels = _noise_levels(net, discretization, num_steps, lo, hi, rho, epsilon_s, latents.device)
+    levels = _noise_levels(net, discretization, num_steps, lo, hi, rho, epsilon_s, device)
     t_grid = path.sigma_inv(net.round_sigma(levels))
-    t_grid = torch.cat([t_grid, torch.zeros_like(t_grid[:1])])
+    return path, torch.cat([t_grid, torch.zeros_like(t_grid[:1])])
+
+
+def _edm_tables(net, device, batch, num_steps, lo, hi, rho, solver, discretization, schedule, scaling, epsilon_s, alpha, S_churn,
+                S_min, S_max, S_noise):
+    """Everything of edm_sample's loop that does not depend on x, computed once per grid with the loop's own expressions on
+    `device` (so each entry has the bits of the scalar the composition computes at that step) and cached on the denoiser:
+      coef    [num_steps, ops.EDM_COLS] float64 on the device: the rows vaw_edm_input / vaw_edm_step read (include/vaw_hip.h)
+      steps   [2 * num_steps, 2 * batch] int32 on the device: the chain index handed to the network at t_hat (row 2i) and
+              t_mid (row 2i + 1); a guided call takes a whole row, any other its first half
+      scale0  sigma(t_0) * s(t_0), as the loop forms it
+      noise_on, t_mean   host lists: does step i add noise, and the mean timestep as the network sees it at each evaluation
+              (None where the solver does not evaluate) -- the argument of the guidance predicate
+      host    the rows of coef on the host (one read-back together with t_mean)."""
+    key = (solver, num_steps, discretization, schedule, scaling, float(lo), float(hi), rho, epsilon_s, alpha, S_churn, S_min, S_max,
+           S_noise, int(batch), str(device))
+    cache = net.__dict__.setdefault("_solver_tables", {})
+    if key in cache:
+        return cache[key]
+    path, t_grid = _edm_time_grid(net, device, num_steps, lo, hi, rho, discretization, schedule, scaling, epsilon_s)
+
+    def evaluation(t):
+        sigma = path.sigma(t).to(torch.float32).reshape(-1, 1, 1, 1)          # EDMDenoiser.forward
+        c_in = 1 / (sigma ** 2 + 1).sqrt()
+        step = (net.M - 1 - net.nearest_index(sigma).to(torch.float32)).flatten()
+        sg, dsg, sc = path.sigma(t), path.dsigma(t), path.s(t)                  # _Path.slope
+        return [sc, sigma, c_in, c_in ** 2, sigma * c_in, dsg / sg + path.ds(t) / sc, dsg * sc / sg, step], step
+
+    rows, steps, t_mean = [], [], []
+    none = torch.zeros(1, device=device)
+    for i in range(num_steps):
+        t_cur, t_next = t_grid[i], t_grid[i + 1]
+        sg_cur = path.sigma(t_cur)
+        gamma = min(S_churn / num_steps, np.sqrt(2) - 1) if S_min <= sg_cur <= S_max else 0
+        t_hat = path.sigma_inv(net.round_sigma(sg_cur + gamma * sg_cur))
+        h = t_next - t_hat
+        heun = solver == "heun" and i < num_steps - 1
+        hat, step_hat = evaluation(t_hat)
+        mid, step_mid = evaluation(t_hat + alpha * h) if heun else ([0.0] * 8, none)
+        rows.append(_row([path.s(t_hat) / path.s(t_cur),
+                          (path.sigma(t_hat) ** 2 - sg_cur ** 2).clip(min=0).sqrt() * path.s(t_hat) * S_noise, *hat, h, alpha * h,
+                          1 - 1 / (2 * alpha), 1 / (2 * alpha), *mid], torch.float64, device, ops.EDM_COLS))
+        for step, used in ((step_hat, True), (step_mid, heun)):
+            steps.append(step.repeat(2 * batch).int())
+            t_mean.append(steps[-1][:batch].float().mean() if used else none[0])          # IntervalCFG.forward's read-back
+    coef = torch.stack(rows).contiguous()
+    host = torch.cat([coef.flatten(), torch.stack(t_mean).to(torch.float64)]).tolist()
+    n = coef.numel()
+    used = [solver == "heun" and (e // 2) < num_steps - 1 if e % 2 else True for e in range(2 * num_steps)]
+    tab = SimpleNamespace(coef=coef, steps=torch.stack(steps).contiguous(), scale0=path.sigma(t_grid[0]) * path.s(t_grid[0]),
+                          host=[host[i * ops.EDM_COLS:(i + 1) * ops.EDM_COLS] for i in range(num_steps)],
+                          t_mean=[tm if u else None for tm, u in zip(host[n:], used)], solver=solver, num_steps=num_steps)
+    tab.noise_on = [r[1] != 0 for r in tab.host]
+    cache[key] = tab
+    return tab
+
+
+def _edm_sample_fused(net, latents, class_labels, randn_like, tab, model_kwargs):
+    """edm_sample's loop on the fused kernels: per step the noise draw, vaw_edm_input, the network, vaw_edm_step (and for a
+    Heun step the network and vaw_edm_step again).  No host synchronisation."""
+    n, shape = latents.shape[0], tuple(latents.shape)
+    kwargs = {**model_kwargs, "y": class_labels}
+    cfg, guided, scale, stacked = _guidance(net.model, class_labels, tab.t_mean, kwargs)
+    if stacked is not None and class_labels.shape[0] != n:
+        raise AssertionError(f"CFG expects label batch size {n}, but got {class_labels.shape[0]}.")
+    buf = torch.empty(((2 * n if stacked is not None else n), *shape[1:]), dtype=torch.float32, device=latents.device)
+    lo, hi = buf[:n], (buf[n:] if stacked is not None else None)
+    x = latents.to(torch.float64) * tab.scale0
+    x_hat, d_cur = torch.empty_like(x), torch.empty_like(x)
+    evaluate = lambda e: _evaluate(net.model, cfg, guided, stacked, buf, n, tab.steps, e, net.img_channels, kwargs)
+    for i in range(tab.num_steps):
+        noise = randn_like(x)                                   # drawn every step, as the composition does: the stream does not move
+        ops.edm_input(x, noise if tab.noise_on[i] else None, tab.coef, i, x_hat, lo, hi)
+        cond, uncond = evaluate(2 * i)
+        if tab.solver == "euler" or i == tab.num_steps - 1:
+            ops.edm_step(ops.STEP_EULER, net.pred_type, cond, uncond, scale, x_hat, None, tab.coef, i, x_out=x)
+            continue
+        ops.edm_step(ops.STEP_PREDICT, net.pred_type, cond, uncond, scale, x_hat, d_cur, tab.coef, i, model_in=lo, model_in_dup=hi)
+        cond, uncond = evaluate(2 * i + 1)
+        ops.edm_step(ops.STEP_CORRECT, net.pred_type, cond, uncond, scale, x_hat, d_cur, tab.coef, i, x_out=x)
+    return x
+
+
+@torch.no_grad()
+def edm_sample(net, latents, class_labels=None, randn_like=torch.randn_like, num_steps=18, sigma_min=None, sigma_max=None, rho=7,
+               solver="heun", discretization="edm", schedule="linear", scaling="none", epsilon_s=1e-3, alpha=1, S_churn=0,
+               S_min=0, S_max=float("inf"), S_noise=1, fused=None, **model_kwargs):
+    """x_0 from `latents` ~ N(0, I): `num_steps` Euler / Heun (2nd-order, `alpha` = 1) steps of the EDM sampler, with the
+    optional "churn" noise injection (S_churn, S_min, S_max, S_noise).  Every noise level handed to the network is first
+    snapped to its chain (net.round_sigma).  fused: None = the fused kernels on the GPU, False = the tensor composition
+    below, True = fused or an error; same values, dtype and noise draws either way."""
+    if solver not in ("euler", "heun"):
+        raise ValueError(f"solver {solver!r}")
+    lo, hi = _edm_sigma_range(net, discretization, sigma_min, sigma_max, epsilon_s)
+    if _want_fused(fused, latents, "edm_sample", None if net.pred_type in ops.EDM_PRED else f"pred_type {net.pred_type!r}"):
+        tab = _edm_tables(net, latents.device, latents.shape[0], num_steps, lo, hi, rho, solver, discretization, schedule, scaling,
+                          epsilon_s, alpha, S_churn, S_min, S_max, S_noise)
+        return _edm_sample_fused(net, latents, class_labels, randn_like, tab, model_kwargs)
+    path, t_grid = _edm_time_grid(net, latents.device, num_steps, lo, hi, rho, discretization, schedule, scaling, epsilon_s)
     x = latents.to(torch.float64) * (path.sigma(t_grid[0]) * path.s(t_grid[0]))
     for i in range(num_steps):
         t_cur, t_next = t_grid[i], t_grid[i + 1]
@@ -226,13 +375,108 @@ def _flow_eval(fm, model, x, t_scalar, model_kwargs):
     return t, out
 
 
+def _flow_tables(fm, kind, solver, num_steps, batch, device):
+    """What the flow loops compute per evaluation that does not depend on x, with their own expressions, cached on `fm`:
+      coef   [evaluations, ops.FLOW_COLS] float32 on the device (include/vaw_hip.h): the interpolant at t and what
+             _flow_fields / the drift derive from it, and dt, sqrt|dt|, dt/2 of the step that starts there
+      times  [evaluations, 2 * batch] float32 on the device: t as the network gets it (a guided call takes a whole row)
+      t_mean host list: the mean of the first half of each row, the argument of the guidance predicate.
+    kind "sde": per step the evaluation at t_k (and t_{k+1} for Heun), then the last noise-free step; "ode": the same
+    without the last one."""
+    key = (kind, solver, num_steps, fm.path_type, int(batch), str(device))
+    cache = fm.__dict__.setdefault("_solver_tables", {})
+    if key in cache:
+        return cache[key]
+    if kind == "sde":
+        grid = torch.cat([torch.linspace(1.0, 0.04, num_steps, dtype=torch.float64, device=device),
+                          torch.zeros(1, dtype=torch.float64, device=device)])
+    else:
+        grid = torch.linspace(1.0, 0.0, num_steps, device=device)
+    like = torch.empty((batch, 1, 1, 1), dtype=torch.float32, device=device)
+    rows, times, t_mean = [], [], []
+
+    def evaluation(t_scalar, dt):
+        tb = fm.expand_t_like_x(t_scalar, like)                    # _flow_eval
+        t = tb[:1]
+        a, s, da, ds = fm.interpolant(t)
+        g2 = 2 * s * ds
+        step = [0.0, 0.0, 0.0] if dt is None else [dt, torch.sqrt(torch.abs(dt)), 0.5 * dt]
+        rows.append(_row([a, s, da, ds, g2, 0.5 * g2, s ** 2, a ** 2 + s ** 2, s * da - a * ds, torch.sqrt(g2), *step, t],
+                         torch.float32, device, ops.FLOW_COLS))
+        times.append(tb.view(batch).repeat(2))
+        t_mean.append(tb.view(batch).float().mean())              # IntervalCFG.forward's read-back
+
+    for k in range(num_steps - 1):
+        evaluation(grid[k], grid[k + 1] - grid[k])
+        if solver == "heun":
+            evaluation(grid[k + 1], None)
+    if kind == "sde":
+        evaluation(grid[-2], grid[-1] - grid[-2])
+    tab = SimpleNamespace(coef=torch.stack(rows).contiguous(), times=torch.stack(times).contiguous(),
+                          t_mean=torch.stack(t_mean).tolist(), solver=solver, num_steps=num_steps)
+    cache[key] = tab
+    return tab
+
+
+def _flow_sample_fused(fm, model, noise, randn_like, tab, sde, model_kwargs):
+    """The Euler / Heun loops of flow_sde_sample and flow_ode_sample on vaw_flow_step.  x lives in the first half of one of
+    three network-input buffers (current, Heun prediction, next), so every step writes the next network input directly."""
+    n, shape = noise.shape[0], tuple(noise.shape)
+    y = model_kwargs.get("y")
+    cfg, guided, scale, stacked = _guidance(model, y, tab.t_mean, model_kwargs)
+    if stacked is not None and y.shape[0] != n:
+        raise AssertionError(f"CFG expects label batch size {n}, but got {y.shape[0]}.")
+    rows = 2 * n if stacked is not None else n
+    cur, pred, nxt = (torch.empty((rows, *shape[1:]), dtype=torch.float32, device=noise.device) for _ in range(3))
+    half = lambda b: (b[:n], b[n:] if stacked is not None else None)
+    for part in half(cur):
+        if part is not None:
+            part.copy_(noise)
+    f0 = torch.empty(shape, dtype=torch.float32, device=noise.device)
+    kick = torch.empty_like(f0) if sde else None
+    mean_type = fm.model_mean_type.name
+    evaluate = lambda e, buf: _evaluate(model, cfg, guided, stacked, buf, n, tab.times, e, None, model_kwargs)
+    e = 0
+    for _ in range(tab.num_steps - 1):
+        cond, uncond = evaluate(e, cur)
+        z = randn_like(cur[:n]) if sde else None
+        if tab.solver == "euler":
+            ops.flow_step(ops.STEP_EULER, sde, mean_type, cond, uncond, scale, cur[:n], z, None, None, None, tab.coef, e, e, *half(nxt))
+            e += 1
+        else:
+            ops.flow_step(ops.STEP_PREDICT, sde, mean_type, cond, uncond, scale, cur[:n], z, None, f0, kick, tab.coef, e, e + 1, *half(pred))
+            cond, uncond = evaluate(e + 1, pred)
+            ops.flow_step(ops.STEP_CORRECT, sde, mean_type, cond, uncond, scale, cur[:n], None, pred[:n], f0, kick, tab.coef, e, e + 1,
+                          *half(nxt))
+            e += 2
+        cur, nxt = nxt, cur
+    if sde:
+        cond, uncond = evaluate(e, cur)
+        ops.flow_step(ops.STEP_EULER, sde, mean_type, cond, uncond, scale, cur[:n], None, None, None, None, tab.coef, e, e, nxt[:n])
+        cur = nxt
+    return cur[:n]
+
+
+def _flow_unsupported(fm, noise, solver):
+    if fm.model_mean_type.name not in ops.FLOW_MEAN:
+        return f"model_mean_type {fm.model_mean_type}"
+    if solver not in ("euler", "heun"):
+        return f"solver {solver!r} (euler and heun are fused)"
+    if noise.dtype != torch.float32:
+        return f"{noise.dtype} noise"
+    return None
+
+
 @torch.no_grad()
-def flow_sde_sample(fm, model, noise, device=None, num_steps=50, solver="heun", randn_like=torch.randn_like, **model_kwargs):
+def flow_sde_sample(fm, model, noise, device=None, num_steps=50, solver="heun", randn_like=torch.randn_like, fused=None, **model_kwargs):
     """Reverse-time SDE of the flow (reference sde_sample :1374-1409): drift = v - (1/2) g^2 score with g^2 = 2 sigma_t sigma_t',
     Euler-Maruyama or its Heun (trapezoidal drift) variant on t = linspace(1, 0.04, num_steps) in float64, and one final
-    noise-free Euler step from 0.04 to 0."""
+    noise-free Euler step from 0.04 to 0.  fused: as in edm_sample (None = vaw_flow_step on the GPU, bitwise this composition)."""
     if solver not in ("euler", "heun"):
         raise ValueError(f"Unknown solver: {solver}")
+    if _want_fused(fused, noise, "flow_sde_sample", _flow_unsupported(fm, noise, solver)):
+        return _flow_sample_fused(fm, model, noise, randn_like, _flow_tables(fm, "sde", solver, num_steps, noise.shape[0], noise.device),
+                                  True, model_kwargs)
     dev = noise.device
     grid = torch.cat([torch.linspace(1.0, 0.04, num_steps, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)])
 
@@ -259,15 +503,19 @@ def flow_sde_sample(fm, model, noise, device=None, num_steps=50, solver="heun", 
 
 
 @torch.no_grad()
-def flow_ode_sample(fm, model, noise, device=None, num_steps=50, solver="heun", **model_kwargs):
+def flow_ode_sample(fm, model, noise, device=None, num_steps=50, solver="heun", fused=None, **model_kwargs):
     """Probability-flow ODE dx/dt = v(x, t) from t = 1 to 0 on the reference's grid linspace(1, 0, num_steps) (ode_sample
     :1355-1366) with a FIXED-grid solver: euler | midpoint | heun | rk4.  The reference hands the same drift to
-    torchdiffeq.odeint (dopri5 by default); that adaptive integrator is not restated here."""
+    torchdiffeq.odeint (dopri5 by default); that adaptive integrator is not restated here.  fused: as in edm_sample, for
+    euler and heun (midpoint and rk4 stay the tensor composition; fused=True refuses them)."""
     if solver == "dopri5":
         raise NotImplementedError("flow_ode_sample: the adaptive dopri5 of torchdiffeq (not installed; parity unpinned) is not "
                                   "restated; use euler | midpoint | heun | rk4 on the same grid")
     if solver not in ("euler", "midpoint", "heun", "rk4"):
         raise ValueError(f"Unknown solver: {solver}")
+    if _want_fused(fused, noise, "flow_ode_sample", _flow_unsupported(fm, noise, solver)):
+        return _flow_sample_fused(fm, model, noise, None, _flow_tables(fm, "ode", solver, num_steps, noise.shape[0], noise.device),
+                                  False, model_kwargs)
     grid = torch.linspace(1.0, 0.0, num_steps, device=noise.device)
 
     def v(x, t_scalar):

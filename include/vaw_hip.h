@@ -57,6 +57,27 @@ int vaw_wmse_fwd(const float* model_out, const float* x0, const float* noise, co
 int vaw_wmse_bwd(const float* model_out, const float* x0, const float* noise, const float* ca, const float* cb,
                  const float* w, const float* gmse, float* dout, int B, int64_t per_sample, vaw_stream stream);
 
+/* The step's passes around the model, each one launch for a chain of tensor operations and bitwise the chain's values
+ * (Trainer with VAW_STEP_FUSED unset or 1).
+ * latent [B][2][per_sample]: mean and std planes of the VAE posterior of every sample.
+ *   x0  = (mean + std * eps) * latent_scale                (tools/trainer.py:21-25)
+ *   x_t = tab_a[t] * x0 + tab_s[t] * noise                 (q_sample, as vaw_qsample_fwd)
+ *   t_float[b] = float(t[b]) * t_scale                     (_scale_timesteps :1055-1058; t_float may be NULL) */
+int vaw_latent_qsample(const float* latent, const float* eps, const float* noise, const int64_t* t, const float* tab_a,
+                       const float* tab_s, int num_timesteps, float latent_scale, float t_scale, float* x0, float* x_t,
+                       float* t_float, int B, int64_t per_sample, vaw_stream stream);
+/* vaw_wmse_fwd / vaw_wmse_bwd with the coefficient gather inside: row b takes ca, cb, w at t[b] (f32[num_timesteps] tables; t out
+ * of range poisons the row with NaN), or at b when t is NULL (per-row vectors: the flow-matching objective).
+ * mean_out (may be NULL) = sum_b mse[b] / B / accum from a second, single-workgroup launch with a fixed summation order.
+ * bwd: d(model_out) of g[0] * inv_count * sum_b mse[b]; g is a device scalar (the gradient of the batch mean), inv_count =
+ * 1 / (B * accum) -- what the backward of mean() / accum expands into a vector. */
+int vaw_wmse_fwd_t(const float* model_out, const float* x0, const float* noise, const int64_t* t, const float* ca, const float* cb,
+                   const float* w, int num_timesteps, float* mse, float* mean_out, float accum, int B, int64_t per_sample,
+                   vaw_stream stream);
+int vaw_wmse_bwd_t(const float* model_out, const float* x0, const float* noise, const int64_t* t, const float* ca, const float* cb,
+                   const float* w, int num_timesteps, const float* g, float inv_count, float* dout, int B, int64_t per_sample,
+                   vaw_stream stream);
+
 /* Variational-bound term of the learned-variance objective and the KL losses: _vb_terms_bpd
  * (gaussian_diffusion.py:775-808) = q_posterior_mean_variance :254-276 + the training side of p_mean_variance
  * :278-384 + normal_kl / discretized_gaussian_log_likelihood (tools/losses.py:12-76) + mean_flat / ln 2, fused.
@@ -457,6 +478,12 @@ int vaw_ln_modulate_bwd(vaw_dtype dt, const void* dout, const float* x, const fl
                         const float* scale, int64_t mod_ld, const float* dres_in, float* dx, float* dshift,
                         float* dscale, int64_t dmod_ld, int B, int T, int D, float* workspace, int64_t workspace_floats,
                         vaw_stream stream);
+/* The same launch with dx_act (may be NULL) = dx rounded to the act dtype, written beside dx: the GEMM operand a cast pass over
+ * dx would make (the last LayerNorm backward of a DiT step feeds the patch embedding's weight gradient). */
+int vaw_ln_modulate_bwd_cast(vaw_dtype dt, const void* dout, const float* x, const float* mean, const float* rstd,
+                             const float* scale, int64_t mod_ld, const float* dres_in, float* dx, float* dshift,
+                             float* dscale, int64_t dmod_ld, int B, int T, int D, float* workspace, int64_t workspace_floats,
+                             void* dx_act, vaw_stream stream);
 /* fp8 mode of the DiT blocks (delayed scaling): the same two kernels with their activation output written as fp8 BYTES [B*T][D]
  * -- the bf16 rounding of each value divided by q_state[0], saturated: what vaw_fp8_quantize_delayed makes of the bf16 tensor,
  * which then is never written -- and the tensor's max |x| folded into q_state[1]; vaw_fp8_transpose supplies the transposed copy. */
@@ -534,6 +561,8 @@ int vaw_timestep_embedding(vaw_dtype dt, const float* t, void* out, int B, int d
 /* SiLU on f32 input; out act dtype.  bwd: dx(f32) += / = dy * silu'(x). */
 int vaw_silu_fwd(vaw_dtype dt, const float* x, void* out, int64_t n, vaw_stream stream);
 int vaw_silu_bwd(const float* x, const float* dy, float* dx, int64_t n, vaw_stream stream);
+/* vaw_silu_bwd that also leaves dx_bf16 (may be NULL) = bf16(dx): the operand of the weight gradient that follows */
+int vaw_silu_bwd_cast(const float* x, const float* dy, float* dx, void* dx_bf16, int64_t n, vaw_stream stream);
 /* out[b,:] = a[b,:] + table[idx[b],:]  (c = t_emb + y_emb, dit.py:267-269 / unet.py:676) */
 int vaw_add_embedding(const float* a, const float* table, const int64_t* idx, float* out, int B, int D,
                       int num_rows, vaw_stream stream);
@@ -716,6 +745,19 @@ int vaw_adamw_ema_step_dev(float* p, float* g, float* m, float* v, float* ema, v
 int vaw_ema_update(float* ema, const float* src, int64_t n, float decay, vaw_stream stream);
 /* dst(bf16) = src(f32) */
 int vaw_cast_bf16(const float* src, void* dst, int64_t n, vaw_stream stream);
+/* dst (bf16 [M][N], row stride ld_dst) = src (f32, row stride ld_src) and colsum[n] = beta * colsum[n] + sum_m float(dst[m][n])
+ * in ONE pass: bitwise what vaw_cast_bf16 followed by vaw_colsum over dst gives.  Covers M <= 512 (one row block of the column
+ * sums' tree), N, ld_src, ld_dst multiples of 4, src and dst 16-byte aligned; anything else is refused with VAW_ERR_INVALID before
+ * anything is launched, and the caller keeps the two-step sequence.  vaw_cast_colsum_plan is the host side alone. */
+typedef struct {
+    int grid_x, block;          /* one workgroup per 256 columns */
+    int rows_per_lane;          /* rows a lane walks: ceil(M / 4) */
+    int64_t bytes_read, bytes_written;
+} vaw_cast_colsum_launch;
+int vaw_cast_colsum_plan(int64_t M, int64_t N, int64_t ld_src, int64_t ld_dst, int64_t src_addr, int64_t dst_addr,
+                         int64_t colsum_addr, vaw_cast_colsum_launch* out);
+int vaw_cast_colsum_bf16(const float* src, int64_t ld_src, void* dst, int64_t ld_dst, int64_t M, int64_t N, float* colsum,
+                         float beta, vaw_stream stream);
 /* dst[i] = scale * float(src[i]), src bf16: the way back of a gradient bucket that was all-reduced in bf16 over xGMI
  * (the reference's DDP reduces f32 buckets, main.py:347-348; bf16 halves the bytes on the wire); scale = 1/world when the
  * collective summed.  src and dst 16-byte aligned. */

@@ -58,6 +58,11 @@ class DitWsPlan(C.Structure):
                 ("shared_bytes", _l), ("colsum_bytes", _l), ("scratch_bytes", _l), ("cond_bytes", _l), ("total", _l)]
 
 
+class CastColsumLaunch(C.Structure):
+    """vaw_cast_colsum_launch of include/vaw_hip.h: the launch vaw_cast_colsum_bf16 makes."""
+    _fields_ = [("grid_x", _i), ("block", _i), ("rows_per_lane", _i), ("bytes_read", _l), ("bytes_written", _l)]
+
+
 # vaw_attn_dir / vaw_attn_variant
 ATTN_FWD, ATTN_BWD, ATTN_BWD_COLSUM = range(3)
 (AV_ROWWISE, AV_FWD_T64, AV_FWD_G1, AV_FWD_G2, AV_FWD_BIG, AV_BWD_T64, AV_BWD_G1, AV_BWD_G2, AV_BWD_BIG_NT2,
@@ -167,6 +172,13 @@ _PROTOS = {
     "vaw_attn_plan": [_i, _i, C.POINTER(AttnDesc), _l, _l, _l, _l, _l, _l, _l, C.POINTER(AttnLaunch)],
     "vaw_gemm_plan": [_i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _l, _l, C.POINTER(Epilogue), _l, C.POINTER(GemmKnobs), C.POINTER(GemmLaunch)],
     "vaw_dit_ws_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(DitWsPlan)],
+    "vaw_latent_qsample": [_p, _p, _p, _p, _p, _p, _i, _f, _f, _p, _p, _p, _i, _l, _p],
+    "vaw_wmse_fwd_t": [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _f, _i, _l, _p],
+    "vaw_wmse_bwd_t": [_p, _p, _p, _p, _p, _p, _p, _i, _p, _f, _p, _i, _l, _p],
+    "vaw_ln_modulate_bwd_cast": [_i, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _l, _i, _i, _i, _p, _l, _p, _p],
+    "vaw_silu_bwd_cast": [_p, _p, _p, _p, _l, _p],
+    "vaw_cast_colsum_plan": [_l, _l, _l, _l, _l, _l, _l, C.POINTER(CastColsumLaunch)],
+    "vaw_cast_colsum_bf16": [_p, _l, _p, _l, _l, _l, _p, _f, _p],
 }
 
 _lib = None
@@ -240,6 +252,11 @@ def exported_symbols():
                                    "vaw_conv3x3_wgrad_small_workspace_floats", "vaw_row_bwd_workspace_floats",
                                    "vaw_fp8_quantize_workspace_floats", "vaw_p8_set_reserved_cus", "vaw_reduce_rows_batched_desc_bytes", "vaw_fp8_quantize_batched_desc_bytes",
                                    "vaw_gemm_default_knobs", "vaw_dropout_bits_words"])
+
+
+# VAW_STEP_FUSED (read once): 0 restores the step's unfused sequence of launches everywhere -- separate cast / column-sum
+# passes in the DiT backward, tensor operations for the latent sample, the coefficient gathers and the batch means of the loss
+STEP_FUSED = os.environ.get("VAW_STEP_FUSED", "1") != "0"
 
 
 def check(rc, what):

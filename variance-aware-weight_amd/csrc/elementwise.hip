@@ -12,6 +12,15 @@ static inline int stream_grid(int64_t work_items, int block) {
 // ---------------------------------------------------------------------------------------------
 // out[b,:] = ca[b]*x[b,:] + cb[b]*y[b,:]; coefficients either given per row or gathered from tables.
 // ---------------------------------------------------------------------------------------------
+// the two coefficients of row b gathered from their tables at t[b]; t out of [0, T) poisons the row with NaN
+__device__ __forceinline__ void gather_mix_coef(const float* __restrict__ ca, const float* __restrict__ cb, const int64_t* __restrict__ t,
+                                                int T, int b, float& a, float& c) {
+    const int64_t tt = t[b];
+    const bool ok = tt >= 0 && tt < T;
+    a = ok ? ca[tt] : __builtin_nanf("");
+    c = ok ? cb[tt] : __builtin_nanf("");
+}
+
 template <bool GATHER>
 __global__ void mix_rows_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ ca,
                                 const float* __restrict__ cb, const int64_t* __restrict__ t, int T,
@@ -19,10 +28,7 @@ __global__ void mix_rows_kernel(const float* __restrict__ x, const float* __rest
     const int b = blockIdx.y;
     float a, c;
     if (GATHER) {
-        const int64_t tt = t[b];
-        const bool ok = tt >= 0 && tt < T;
-        a = ok ? ca[tt] : __builtin_nanf("");
-        c = ok ? cb[tt] : __builtin_nanf("");
+        gather_mix_coef(ca, cb, t, T, b, a, c);
     } else {
         a = ca[b];
         c = cb[b];
@@ -61,14 +67,25 @@ extern "C" int vaw_mix_rows(const float* x, const float* y, const float* ca, con
 }
 
 // ---------------------------------------------------------------------------------------------
-// Weighted MSE: one block per sample; wave shuffles + one LDS hop for the reduction.
+// Weighted MSE: one block per sample; wave shuffles + one LDS hop for the reduction.  One pair of kernels serves the per-row
+// coefficient vectors of vaw_wmse_fwd / _bwd and the in-kernel table gather of vaw_wmse_fwd_t / _bwd_t.
 // ---------------------------------------------------------------------------------------------
-__global__ void wmse_fwd_kernel(const float* __restrict__ o, const float* __restrict__ x0, const float* __restrict__ nz,
-                                const float* __restrict__ ca, const float* __restrict__ cb, const float* __restrict__ w,
-                                float* __restrict__ mse, int64_t n) {
+// Weighted MSE with its coefficients gathered inside: row b reads ca / cb / w at t[b] (t == NULL: at b, the per-row vectors of
+// vaw_wmse_fwd -- the flow-matching objective has no tables).  t out of [0, T) poisons the row with NaN, as vaw_qsample_fwd does.
+struct WmseCoef { float a, c, w; };
+__device__ __forceinline__ WmseCoef wmse_coef(const float* ca, const float* cb, const float* w, const int64_t* t, int T, int b) {
+    if (!t) return WmseCoef{ca[b], cb[b], w[b]};
+    const int64_t tt = t[b];
+    const float nan = __builtin_nanf("");
+    return (tt >= 0 && tt < T) ? WmseCoef{ca[tt], cb[tt], w[tt]} : WmseCoef{nan, nan, nan};
+}
+__global__ void wmse_fwd_t_kernel(const float* __restrict__ o, const float* __restrict__ x0, const float* __restrict__ nz,
+                                  const float* __restrict__ ca, const float* __restrict__ cb, const float* __restrict__ w,
+                                  const int64_t* __restrict__ t, int T, float* __restrict__ mse, int64_t n) {
     __shared__ float scratch[16];
     const int b = blockIdx.x;
-    const float a = ca[b], c = cb[b];
+    const WmseCoef k = wmse_coef(ca, cb, w, t, T, b);
+    const float a = k.a, c = k.c;
     const float* orow = o + (int64_t)b * n;
     const float* xr = x0 + (int64_t)b * n;
     const float* nr = nz + (int64_t)b * n;
@@ -83,15 +100,20 @@ __global__ void wmse_fwd_kernel(const float* __restrict__ o, const float* __rest
         acc += d * d;
     }
     float tot = block_sum(acc, scratch);
-    if (threadIdx.x == 0) mse[b] = w[b] * (tot / (float)n);
+    if (threadIdx.x == 0) mse[b] = k.w * (tot / (float)n);
 }
-
-__global__ void wmse_bwd_kernel(const float* __restrict__ o, const float* __restrict__ x0, const float* __restrict__ nz,
-                                const float* __restrict__ ca, const float* __restrict__ cb, const float* __restrict__ w,
-                                const float* __restrict__ gmse, float* __restrict__ dout, int64_t n) {
+// the gradient of sum_b gm[b] * mse[b].  g_per_row: gm = g[b], the vector autograd hands vaw_wmse_bwd.  Otherwise g is the device
+// scalar handed down for the batch mean (1 for the loss itself) and inv_count = 1 / (B * accumulation steps): g * inv_count is the
+// gmse[b] the mean's backward would have expanded
+__global__ void wmse_bwd_t_kernel(const float* __restrict__ o, const float* __restrict__ x0, const float* __restrict__ nz,
+                                  const float* __restrict__ ca, const float* __restrict__ cb, const float* __restrict__ w,
+                                  const int64_t* __restrict__ t, int T, const float* __restrict__ g, int g_per_row, float inv_count,
+                                  float* __restrict__ dout, int64_t n) {
     const int b = blockIdx.y;
-    const float a = ca[b], c = cb[b];
-    const float k = gmse[b] * w[b] * 2.f / (float)n;
+    const WmseCoef kc = wmse_coef(ca, cb, w, t, T, b);
+    const float a = kc.a, c = kc.c;
+    const float gm = g_per_row ? g[b] : g[0] * inv_count;
+    const float k = gm * kc.w * 2.f / (float)n;
     const float* orow = o + (int64_t)b * n;
     const float* xr = x0 + (int64_t)b * n;
     const float* nr = nz + (int64_t)b * n;
@@ -102,12 +124,20 @@ __global__ void wmse_bwd_kernel(const float* __restrict__ o, const float* __rest
     for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         dr[i] = k * (orow[i] - a * xr[i] - c * nr[i]);
 }
+// out[0] = (sum_b v[b]) / B / accum in one fixed order: thread j adds v[j], v[j + 256], ... ascending, then block_sum's tree
+__global__ void __launch_bounds__(256) batch_mean_kernel(const float* __restrict__ v, int B, float accum, float* __restrict__ out) {
+    __shared__ float scratch[4];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) acc += v[i];
+    const float tot = block_sum(acc, scratch);
+    if (threadIdx.x == 0) out[0] = (tot / (float)B) / accum;
+}
 
 extern "C" int vaw_wmse_fwd(const float* model_out, const float* x0, const float* noise, const float* ca,
                             const float* cb, const float* w, float* mse, int B, int64_t per_sample,
                             vaw_stream stream) {
     VAW_CHECK_ARG(B > 0 && per_sample > 0, "wmse_fwd: bad sizes");
-    wmse_fwd_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, mse, per_sample);
+    wmse_fwd_t_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, nullptr, 0, mse, per_sample);
     VAW_CHECK_LAUNCH("wmse_fwd");
     return VAW_OK;
 }
@@ -118,7 +148,7 @@ extern "C" int vaw_wmse_bwd(const float* model_out, const float* x0, const float
     VAW_CHECK_ARG(B > 0 && per_sample > 0, "wmse_bwd: bad sizes");
     int gx = stream_grid(per_sample / 4 + 1, 256);
     dim3 grid(gx > 64 ? 64 : gx, B);
-    wmse_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, gmse, dout, per_sample);
+    wmse_bwd_t_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, nullptr, 0, gmse, 1, 1.f, dout, per_sample);
     VAW_CHECK_LAUNCH("wmse_bwd");
     return VAW_OK;
 }
@@ -796,6 +826,16 @@ __global__ void silu_bwd_kernel(const float* __restrict__ x, const float* __rest
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         dx[i] = dy[i] * silu_grad_f(x[i]);
 }
+// the same pass, leaving the bf16 rounding of dx beside it: the operand of the weight-gradient GEMM that follows (what
+// cast_bf16_kernel makes of dx in a launch of its own)
+__global__ void silu_bwd_cast_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dx,
+                                     bf16_t* __restrict__ dx_act, int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v = dy[i] * silu_grad_f(x[i]);
+        dx[i] = v;
+        dx_act[i] = (bf16_t)v;
+    }
+}
 extern "C" int vaw_silu_fwd(vaw_dtype dt, const float* x, void* out, int64_t n, vaw_stream stream) {
     VAW_CHECK_ARG(n > 0, "silu_fwd: n<=0");
     int grid = stream_grid(n, 256);
@@ -820,13 +860,16 @@ __global__ void add_embedding_kernel(const float* __restrict__ a, const float* _
     }
 }
 // dtable[r,:] = beta*dtable[r,:] + sum over {b : idx[b]==r} dc[b,:], b ascending.  One workgroup per table row: the index vector
-// goes through LDS in chunks of 1024 (every thread reads the same word: a broadcast), a thread owns columns t, t + 256, ... and adds
-// the matching rows in batch order.  Deterministic, no pre-zeroing pass over the table.  (Round 3 had one thread per table ELEMENT
-// scanning the whole index vector from global memory: 53 us for a 1001 x 768 table at batch 256; this form takes ~5.)
+// is compared with r 1024 entries at a time, one entry per thread and round, and every wave leaves the 64-bit mask of its matches
+// in LDS; a thread owns columns t, t + 256, ... and adds the matching rows by walking the set bits of those masks in batch order.
+// Deterministic, no pre-zeroing pass over the table.  (Round 3 had one thread per table ELEMENT scanning the whole index vector
+// from global memory: 53 us for a 1001 x 768 table at batch 256.  Round 4 staged the indices in LDS and let every thread test all
+// of them one after the other, a dependent LDS read and a branch per entry: 24 us, nearly all of it in rows nobody indexed.  With
+// the compare done once per entry a row without matches costs one round.)
 __global__ void __launch_bounds__(256)
 embedding_bwd_kernel(const float* __restrict__ dc, const int64_t* __restrict__ idx, float* __restrict__ dtable, int B, int D,
                      int rows, float beta) {
-    __shared__ int s_idx[1024];
+    __shared__ unsigned long long s_mask[16];                 // matches of entries b0 + 64 w .. b0 + 64 w + 63
     const int r = blockIdx.x;
     constexpr int MAXC = 8;                                   // columns per thread held in registers (D <= 2048); wider tables loop
     for (int d0 = 0; d0 < D; d0 += 256 * MAXC) {
@@ -836,15 +879,24 @@ embedding_bwd_kernel(const float* __restrict__ dc, const int64_t* __restrict__ i
         for (int b0 = 0; b0 < B; b0 += 1024) {
             const int nb = B - b0 < 1024 ? B - b0 : 1024;
             __syncthreads();
-            for (int i = threadIdx.x; i < nb; i += 256) s_idx[i] = (int)idx[b0 + i];
-            __syncthreads();
-            for (int i = 0; i < nb; ++i) {
-                if (s_idx[i] != r) continue;                  // uniform branch
-                const float* src = dc + (int64_t)(b0 + i) * D + d0;
 #pragma unroll
-                for (int j = 0; j < MAXC; ++j) {
-                    const int d = threadIdx.x + 256 * j;
-                    if (d0 + d < D) acc[j] += src[d];
+            for (int k = 0; k < 4; ++k) {
+                const int i = threadIdx.x + 256 * k;          // wave w of round k covers entries 64 (4 k + w) ..
+                const unsigned long long m = __ballot(i < nb && idx[b0 + (i < nb ? i : 0)] == (int64_t)r);
+                if ((threadIdx.x & 63) == 0) s_mask[4 * k + (threadIdx.x >> 6)] = m;
+            }
+            __syncthreads();
+            for (int w = 0; w < 16; ++w) {
+                unsigned long long m = s_mask[w];             // uniform: every thread walks the same bits
+                while (m) {
+                    const int i = 64 * w + __builtin_ctzll(m);
+                    m &= m - 1;
+                    const float* src = dc + (int64_t)(b0 + i) * D + d0;
+#pragma unroll
+                    for (int j = 0; j < MAXC; ++j) {
+                        const int d = threadIdx.x + 256 * j;
+                        if (d0 + d < D) acc[j] += src[d];
+                    }
                 }
             }
         }
@@ -858,6 +910,14 @@ embedding_bwd_kernel(const float* __restrict__ dc, const int64_t* __restrict__ i
         }
     }
 }
+extern "C" int vaw_silu_bwd_cast(const float* x, const float* dy, float* dx, void* dx_bf16, int64_t n, vaw_stream stream) {
+    if (!dx_bf16) return vaw_silu_bwd(x, dy, dx, n, stream);
+    VAW_CHECK_ARG(n > 0, "silu_bwd_cast: n<=0");
+    silu_bwd_cast_kernel<<<stream_grid(n, 256), 256, 0, (hipStream_t)stream>>>(x, dy, dx, (bf16_t*)dx_bf16, n);
+    VAW_CHECK_LAUNCH("silu_bwd_cast");
+    return VAW_OK;
+}
+
 extern "C" int vaw_add_embedding(const float* a, const float* table, const int64_t* idx, float* out, int B, int D,
                                  int num_rows, vaw_stream stream) {
     VAW_CHECK_ARG(B > 0 && D > 0 && num_rows > 0, "add_embedding: bad sizes");
@@ -1145,5 +1205,158 @@ extern "C" int vaw_uncast_bf16(const void* src, float* dst, int64_t n, float sca
     VAW_CHECK_ARG(n > 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 15) == 0, "uncast_bf16: n<=0 or unaligned");
     uncast_bf16_kernel<<<stream_grid(n / 8 + 1, 256), 256, 0, (hipStream_t)stream>>>((const bf16_t*)src, dst, n, scale);
     VAW_CHECK_LAUNCH("uncast_bf16");
+    return VAW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Passes of the training step that replace a chain of tensor operations around the model (VAW_STEP_FUSED).  Every
+// value is the one the chain produces: the same operations in the same order, each rounded on its own (-ffp-contract=off).
+// ---------------------------------------------------------------------------------------------
+// latent [B][2][n] = the VAE posterior's mean and std planes of a sample ->
+//   x0  = (mean + std * eps) * scale                       (sample_from_latent: product, sum, product)
+//   x_t = tab_a[t] * x0 + tab_s[t] * noise                  (mix_rows_kernel<true>)
+//   tf[b] = float(t[b]) * t_scale                           (_scale_timesteps; optional)
+__global__ void latent_qsample_kernel(const float* __restrict__ latent, const float* __restrict__ eps, const float* __restrict__ noise,
+                                      const int64_t* __restrict__ t, const float* __restrict__ tab_a, const float* __restrict__ tab_s,
+                                      int T, float scale, float t_scale, float* __restrict__ x0, float* __restrict__ x_t,
+                                      float* __restrict__ tf, int64_t n) {
+    const int b = blockIdx.y;
+    float a, c;
+    gather_mix_coef(tab_a, tab_s, t, T, b, a, c);
+    if (tf && blockIdx.x == 0 && threadIdx.x == 0) tf[b] = (float)t[b] * t_scale;
+    const float* mr = latent + (int64_t)b * 2 * n;
+    const float* sr = mr + n;
+    const float* er = eps + (int64_t)b * n;
+    const float* nr = noise + (int64_t)b * n;
+    float* xr = x0 + (int64_t)b * n;
+    float* orow = x_t + (int64_t)b * n;
+    const int64_t n4 = ((n & 3) == 0) ? n / 4 : 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const f32x4 x = (load4(mr + 4 * i) + load4(sr + 4 * i) * load4(er + 4 * i)) * scale;
+        store4(xr + 4 * i, x);
+        store4(orow + 4 * i, a * x + c * load4(nr + 4 * i));
+    }
+    for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float x = (mr[i] + sr[i] * er[i]) * scale;
+        xr[i] = x;
+        orow[i] = a * x + c * nr[i];
+    }
+}
+
+extern "C" int vaw_latent_qsample(const float* latent, const float* eps, const float* noise, const int64_t* t, const float* tab_a,
+                                  const float* tab_s, int num_timesteps, float latent_scale, float t_scale, float* x0, float* x_t,
+                                  float* t_float, int B, int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && B <= 65535 && per_sample > 0 && num_timesteps > 0, "latent_qsample: bad sizes B=%d n=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(latent && eps && noise && t && tab_a && tab_s && x0 && x_t, "latent_qsample: null pointer");
+    VAW_CHECK_ARG(per_sample % 4 != 0 || ((((uintptr_t)latent | (uintptr_t)eps | (uintptr_t)noise | (uintptr_t)x0 | (uintptr_t)x_t) & 15) == 0),
+                  "latent_qsample: tensors must be 16-byte aligned");
+    int gx = stream_grid(per_sample / 4 + 1, 256);
+    dim3 grid(gx > 64 ? 64 : gx, B);
+    latent_qsample_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(latent, eps, noise, t, tab_a, tab_s, num_timesteps, latent_scale, t_scale,
+                                                                x0, x_t, t_float, per_sample);
+    VAW_CHECK_LAUNCH("latent_qsample");
+    return VAW_OK;
+}
+
+extern "C" int vaw_wmse_fwd_t(const float* model_out, const float* x0, const float* noise, const int64_t* t, const float* ca,
+                              const float* cb, const float* w, int num_timesteps, float* mse, float* mean_out, float accum, int B,
+                              int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0 && (!t || num_timesteps > 0) && accum >= 1.f, "wmse_fwd_t: bad sizes");
+    VAW_CHECK_ARG(model_out && x0 && noise && ca && cb && w && mse, "wmse_fwd_t: null pointer");
+    wmse_fwd_t_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, t, num_timesteps, mse, per_sample);
+    if (mean_out) batch_mean_kernel<<<1, 256, 0, (hipStream_t)stream>>>(mse, B, accum, mean_out);
+    VAW_CHECK_LAUNCH("wmse_fwd_t");
+    return VAW_OK;
+}
+
+extern "C" int vaw_wmse_bwd_t(const float* model_out, const float* x0, const float* noise, const int64_t* t, const float* ca,
+                              const float* cb, const float* w, int num_timesteps, const float* g, float inv_count, float* dout, int B,
+                              int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && B <= 65535 && per_sample > 0 && (!t || num_timesteps > 0), "wmse_bwd_t: bad sizes");
+    VAW_CHECK_ARG(model_out && x0 && noise && ca && cb && w && g && dout, "wmse_bwd_t: null pointer");
+    int gx = stream_grid(per_sample / 4 + 1, 256);
+    dim3 grid(gx > 64 ? 64 : gx, B);
+    wmse_bwd_t_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, t, num_timesteps, g, 0, inv_count, dout,
+                                                            per_sample);
+    VAW_CHECK_LAUNCH("wmse_bwd_t");
+    return VAW_OK;
+}
+
+// dst (bf16, row stride ld_dst) = src (f32 [M][N], row stride ld_src) and, in the same pass, colsum[n] = beta * colsum[n] +
+// sum_m float(dst[m][n]): the sums of the values as stored, in the order vaw_colsum(VAW_BF16, dst, ...) adds them for M <= 512
+// (colsum_partial_kernel<bf16_t>: four interleaved row groups, rows ascending inside a group, ((g0 + g1) + g2) + g3; then
+// colsum_final_kernel over that one partial row: 0 + p, then beta * out + it) -- bitwise its result.  256 columns per workgroup,
+// every lane CC_U independent 16-byte loads in flight.  The adaLN modulation gradient of dit.py: the cast feeds two GEMMs, the
+// column sums are the bias gradient; separately they were three launches reading the tensor twice.
+#define CC_U 16
+__global__ void __launch_bounds__(256)
+cast_colsum_kernel(const float* __restrict__ X, int64_t ldx, bf16_t* __restrict__ Y, int64_t ldy, int64_t M, int64_t N,
+                   float* __restrict__ out, float beta) {
+    __shared__ __attribute__((aligned(16))) float part[4][256];
+    const int cg = threadIdx.x & 63, rg = threadIdx.x >> 6;
+    const int64_t col = (int64_t)blockIdx.x * 256 + cg * 4;
+    f32x4 acc = {0, 0, 0, 0};
+    if (col < N) {          // N % 4 == 0: a group of 4 columns is in or out as a whole
+        int64_t r = rg;
+        for (; r + 4 * (CC_U - 1) < M; r += 4 * CC_U) {
+            f32x4 v[CC_U];
+#pragma unroll
+            for (int u = 0; u < CC_U; ++u) v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(X + (r + 4 * u) * ldx + col));
+#pragma unroll
+            for (int u = 0; u < CC_U; ++u) {          // rows ascending: fixed order
+                bf16_t* y = Y + (r + 4 * u) * ldy + col;
+                store4(y, v[u]);
+                const bf16x4 q = {(bf16_t)v[u][0], (bf16_t)v[u][1], (bf16_t)v[u][2], (bf16_t)v[u][3]};
+                acc += f32x4{(float)q[0], (float)q[1], (float)q[2], (float)q[3]};
+            }
+        }
+        for (; r < M; r += 4) {
+            const f32x4 v = load4(X + r * ldx + col);
+            store4(Y + r * ldy + col, v);
+            const bf16x4 q = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+            acc += f32x4{(float)q[0], (float)q[1], (float)q[2], (float)q[3]};
+        }
+    }
+    store4(&part[rg][cg * 4], acc);
+    __syncthreads();
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c < N) {
+        const float p = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+        float tsum = 0.f;
+        tsum += p;
+        out[c] = (beta != 0.f ? beta * out[c] : 0.f) + tsum;
+    }
+}
+
+// host arithmetic only: the launch vaw_cast_colsum_bf16 makes, or why it makes none
+extern "C" int vaw_cast_colsum_plan(int64_t M, int64_t N, int64_t ld_src, int64_t ld_dst, int64_t src_addr, int64_t dst_addr,
+                                    int64_t colsum_addr, vaw_cast_colsum_launch* out) {
+    VAW_CHECK_ARG(out != nullptr, "cast_colsum_plan: out is NULL");
+    vaw_cast_colsum_launch p = {};
+    *out = p;
+    VAW_CHECK_ARG(M > 0 && N > 0 && ld_src >= N && ld_dst >= N, "cast_colsum: bad sizes M=%ld N=%ld ld_src=%ld ld_dst=%ld", (long)M, (long)N,
+                  (long)ld_src, (long)ld_dst);
+    // beyond 512 rows vaw_colsum cuts the rows into blocks (and takes another kernel for bf16 from 1024 on): another summation order
+    VAW_CHECK_ARG(M <= 512, "cast_colsum: M=%ld > 512 rows is left to vaw_cast_bf16 + vaw_colsum", (long)M);
+    VAW_CHECK_ARG(N % 4 == 0 && ld_src % 4 == 0 && ld_dst % 4 == 0, "cast_colsum: N, ld_src and ld_dst must be multiples of 4");
+    VAW_CHECK_ARG((src_addr & 15) == 0 && (dst_addr & 15) == 0 && (colsum_addr & 3) == 0 && src_addr && dst_addr && colsum_addr,
+                  "cast_colsum: src and dst must be 16-byte aligned");
+    VAW_CHECK_ARG((N + 255) / 256 < (1LL << 31), "cast_colsum: N too large");
+    p.grid_x = (int)((N + 255) / 256);
+    p.block = 256;
+    p.rows_per_lane = (int)((M + 3) / 4);
+    p.bytes_read = M * N * 4;
+    p.bytes_written = M * N * 2 + N * 4;
+    *out = p;
+    return VAW_OK;
+}
+
+extern "C" int vaw_cast_colsum_bf16(const float* src, int64_t ld_src, void* dst, int64_t ld_dst, int64_t M, int64_t N, float* colsum,
+                                    float beta, vaw_stream stream) {
+    vaw_cast_colsum_launch p;
+    const int rc = vaw_cast_colsum_plan(M, N, ld_src, ld_dst, (int64_t)(uintptr_t)src, (int64_t)(uintptr_t)dst, (int64_t)(uintptr_t)colsum, &p);
+    if (rc != VAW_OK) return rc;
+    cast_colsum_kernel<<<p.grid_x, p.block, 0, (hipStream_t)stream>>>(src, ld_src, (bf16_t*)dst, ld_dst, M, N, colsum, beta);
+    VAW_CHECK_LAUNCH("cast_colsum_bf16");
     return VAW_OK;
 }

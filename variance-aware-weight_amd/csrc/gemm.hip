@@ -599,16 +599,26 @@ gemm_bf16_big_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __
 }
 
 // out = beta*C + alpha * sum_s slab[s], fixed order (deterministic split-K).  N % 4 == 0.
-// The LAST workgroup also folds the [S][M] partial row sums of A (bias gradient), when given: one launch fewer.
+// The grid also folds the [S][M] partial row sums of A (bias gradient), when given: one launch fewer.
 template <typename TO>
 __global__ void splitk_reduce_kernel(const float* __restrict__ slab, int S, int64_t M, int64_t N, int64_t ldc,
                                      void* __restrict__ C, float alpha, float beta, int out_f32,
                                      const float* __restrict__ rowpart = nullptr, float* __restrict__ rowsum_out = nullptr,
                                      float rowsum_beta = 0.f) {
-    if (rowpart && blockIdx.x == gridDim.x - 1) {
-        for (int64_t m = threadIdx.x; m < M; m += blockDim.x) {
+    if (rowpart) {
+        // one row sum per thread of the whole grid, eight slabs requested at once and added in slab order (round 4 left all M rows
+        // to the last workgroup, one dependent load at a time: 51 us for the patch embedding's 768 rows x 64 slabs)
+        for (int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; m < M; m += (int64_t)gridDim.x * blockDim.x) {
             float t = 0.f;
-            for (int sidx = 0; sidx < S; ++sidx) t += rowpart[(int64_t)sidx * M + m];
+            int sidx = 0;
+            for (; sidx + 8 <= S; sidx += 8) {
+                float v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = rowpart[(int64_t)(sidx + u) * M + m];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) t += v[u];
+            }
+            for (; sidx < S; ++sidx) t += rowpart[(int64_t)sidx * M + m];
             rowsum_out[m] = (rowsum_beta != 0.f ? rowsum_beta * rowsum_out[m] : 0.f) + t;
         }
     }

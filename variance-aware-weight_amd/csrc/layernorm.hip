@@ -116,7 +116,9 @@ row_bwd_kernel(const T* __restrict__ dout, const float* __restrict__ x, const fl
                // column sums then go to part[chunk][b][2][D] and row_bwd_finish_kernel folds the chunks in order
                int rows_per_chunk, float* __restrict__ part,
                // GATE_ONLY, fp8 mode: dy goes out as fp8 bytes of its bf16 rounding instead (q_state: its delayed-scaling state)
-               unsigned char* __restrict__ q_out = nullptr, float* __restrict__ q_state = nullptr, int q_e5m2 = 0) {
+               unsigned char* __restrict__ q_out = nullptr, float* __restrict__ q_state = nullptr, int q_e5m2 = 0,
+               // LayerNorm mode, optional: the rounding of dx to the act dtype beside it (the GEMM operand a cast pass would make)
+               T* __restrict__ dx_act = nullptr) {
     static_assert(!(FUSE && GATE_ONLY), "FUSE extends the LayerNorm mode");
     constexpr int NQ = FUSE ? 4 : 2;                               // per-sample column sums carried
     extern __shared__ __attribute__((aligned(16))) float lds[];   // [NQ][D]
@@ -193,6 +195,7 @@ row_bwd_kernel(const T* __restrict__ dout, const float* __restrict__ x, const fl
                     f32x4 r = (g[i] - c1 - xh[i] * c2) * rs;
                     if (dres_in) r += load4(dres_in + row * D + c);
                     store4(dx + row * D + c, r);
+                    if (dx_act) store4(dx_act + row * D + c, r);
                     if (FUSE) {      // the gate backward of vaw_gate_bwd, on the row just produced
                         const f32x4 yv = load4(y + row * D + c);
                         const f32x4 d = r * load4(gsc_lds + c);
@@ -577,12 +580,13 @@ extern "C" int vaw_ln_modulate_fwd_fp8(const float* x, const float* shift, const
     return VAW_OK;
 }
 
-extern "C" int vaw_ln_modulate_bwd(vaw_dtype dt, const void* dout, const float* x, const float* mean, const float* rstd,
-                                   const float* scale, int64_t mod_ld, const float* dres_in, float* dx, float* dshift,
-                                   float* dscale, int64_t dmod_ld, int B, int T, int D, float* workspace,
-                                   int64_t workspace_floats, vaw_stream stream) {
+// the launch of vaw_ln_modulate_bwd and vaw_ln_modulate_bwd_cast (`who` names the entry point in error messages)
+static int ln_modulate_bwd_launch(const char* who, vaw_dtype dt, const void* dout, const float* x, const float* mean, const float* rstd,
+                                  const float* scale, int64_t mod_ld, const float* dres_in, float* dx, float* dshift, float* dscale,
+                                  int64_t dmod_ld, int B, int T, int D, float* workspace, int64_t workspace_floats, void* dx_act,
+                                  vaw_stream stream) {
     VAW_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 2048 && mod_ld % 4 == 0,
-                  "ln_modulate_bwd: need D%%4==0, D<=2048, mod_ld%%4==0 (D=%d)", D);
+                  "%s: need D%%4==0, D<=2048, mod_ld%%4==0 (D=%d)", who, D);
     ROW_PLAN(VAW_ROW_LN_BWD, dt, B, T, D, 0, 0, workspace ? workspace_floats : 0);
     hipStream_t s = (hipStream_t)stream;
     const int nc = plan.nc, rpc = plan.rows_per_chunk, block = plan.block;
@@ -590,13 +594,29 @@ extern "C" int vaw_ln_modulate_bwd(vaw_dtype dt, const void* dout, const float* 
     const size_t lds = plan.lds_bytes;
     dim3 grid(B, nc);
     if (dt == VAW_F32) {
-        DISPATCH_NV(plan.nv, (row_bwd_kernel<float, NV, false><<<grid, block, lds, s>>>((const float*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rpc, part)));
+        DISPATCH_NV(plan.nv, (row_bwd_kernel<float, NV, false><<<grid, block, lds, s>>>((const float*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rpc, part, nullptr, nullptr, 0, (float*)dx_act)));
     } else {
-        DISPATCH_NV(plan.nv, (row_bwd_kernel<bf16_t, NV, false><<<grid, block, lds, s>>>((const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rpc, part)));
+        DISPATCH_NV(plan.nv, (row_bwd_kernel<bf16_t, NV, false><<<grid, block, lds, s>>>((const bf16_t*)dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, T, D, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, rpc, part, nullptr, nullptr, 0, (bf16_t*)dx_act)));
     }
     if (nc > 1) row_bwd_finish_kernel<<<ceil_div((int64_t)B * D, 256), 256, 0, s>>>(part, nc, B, D, dshift, dmod_ld, dscale, dmod_ld);
-    VAW_CHECK_LAUNCH("ln_modulate_bwd");
+    VAW_CHECK_LAUNCH(who);
     return VAW_OK;
+}
+
+extern "C" int vaw_ln_modulate_bwd(vaw_dtype dt, const void* dout, const float* x, const float* mean, const float* rstd,
+                                   const float* scale, int64_t mod_ld, const float* dres_in, float* dx, float* dshift,
+                                   float* dscale, int64_t dmod_ld, int B, int T, int D, float* workspace,
+                                   int64_t workspace_floats, vaw_stream stream) {
+    return ln_modulate_bwd_launch("ln_modulate_bwd", dt, dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, B, T, D,
+                                  workspace, workspace_floats, nullptr, stream);
+}
+
+extern "C" int vaw_ln_modulate_bwd_cast(vaw_dtype dt, const void* dout, const float* x, const float* mean, const float* rstd,
+                                        const float* scale, int64_t mod_ld, const float* dres_in, float* dx, float* dshift,
+                                        float* dscale, int64_t dmod_ld, int B, int T, int D, float* workspace,
+                                        int64_t workspace_floats, void* dx_act, vaw_stream stream) {
+    return ln_modulate_bwd_launch("ln_modulate_bwd_cast", dt, dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, B, T,
+                                  D, workspace, workspace_floats, dx_act, stream);
 }
 
 // vaw_ln_modulate_bwd followed by vaw_gate_bwd of the branch in front of this LayerNorm, as ONE pass (row_bwd_fuse8_kernel for bf16

@@ -232,7 +232,9 @@ class _DiTFn(torch.autograd.Function):
             raise L.VawError("DiT backward: activation_checkpointing was switched between this forward and its backward "
                              "(the workspace of the forward was laid out for the other mode)")
         dx = m._backward_impl(dout.contiguous(), ctx.need_dx)
-        return torch.zeros_like(m._anchor), None, dx, None, None
+        # the anchor only ties this node into the graph: nobody reads its gradient, and a defined one costs a fill and, from the
+        # second step on, an accumulate launch per backward
+        return (None if L.STEP_FUSED else torch.zeros_like(m._anchor)), None, dx, None, None
 
 
 class DiT(FlatModule):
@@ -594,14 +596,23 @@ class DiT(FlatModule):
         """Weight and bias gradient of rows [r0, r0 + nrows) of the packed adaLN matrix: dW = dmod[:, rows]^T cs, db = colsum.
         Returns the address of dmod in the GEMM operand dtype (whole buffer)."""
         D, ld = self.D, self.mod_cols
+        gw, gb = self._g("blocks.0.adaLN_modulation.1.weight") + 4 * r0 * D, self._g("blocks.0.adaLN_modulation.1.bias") + 4 * r0
+        fused = False
         if dt == BF16:
-            ops.cast_bf16(ws.dmod, ws.dmod_a)
             dmod_a, es = ptr(ws.dmod_a), 2
+            # one pass: the bf16 operand of these columns and their column sums (the columns of an earlier bucket are final and were
+            # cast then).  Where the pass does not cover the operands, the whole-buffer cast and the separate column sums as before
+            fused = L.STEP_FUSED and ops.cast_colsum_plan(B, nrows, ld, ld, ptr(ws.dmod) + 4 * r0, dmod_a + es * r0, gb) is not None
+            if fused:
+                ops.cast_colsum(ptr(ws.dmod) + 4 * r0, ld, dmod_a + es * r0, ld, B, nrows, gb, beta)
+            else:
+                ops.cast_bf16(ws.dmod, ws.dmod_a)
         else:
             dmod_a, es = ptr(ws.dmod), 4
-        ops.gemm(dt, 0, 0, nrows, D, ws.Bk, dmod_a + es * r0, ld, ptr(ws.cs), D, self._g("blocks.0.adaLN_modulation.1.weight") + 4 * r0 * D,
-                 D, beta=beta, out_f32=True)                 # K = the batch, zero rows up to ws.Bk (see _Workspace)
-        ops.colsum(dt, dmod_a + es * r0, B, nrows, ld, self._g("blocks.0.adaLN_modulation.1.bias") + 4 * r0, beta)
+        ops.gemm(dt, 0, 0, nrows, D, ws.Bk, dmod_a + es * r0, ld, ptr(ws.cs), D, gw, D, beta=beta, out_f32=True)
+        # (K = the batch, zero rows up to ws.Bk: see _Workspace)
+        if not fused:
+            ops.colsum(dt, dmod_a + es * r0, B, nrows, ld, gb, beta)
         return dmod_a
 
     def _backward_impl(self, dout, need_dx):
@@ -630,13 +641,14 @@ class DiT(FlatModule):
         ckpt = ws.ckpt
         # fp8, delayed scaling: the row kernels write dy as fp8 themselves
         fuse_rows = fp8 and ws.d_bwd and self.fp8_fuse_epilogue and self.fp8_fuse_rows and M % 64 == 0 and D % 128 == 0
+        fuse_tail = L.STEP_FUSED and dt == BF16      # the conversions of the conditioning path and of d(x0) ride on their producers
 
-        def ln_bwd_and_gate(dout_p, x_p, mean_p, rstd_p, scale_p, dres_in, dsh, dsc, nxt):
+        def ln_bwd_and_gate(dout_p, x_p, mean_p, rstd_p, scale_p, dres_in, dsh, dsc, nxt, dx_act=0):
             """Backward of one LayerNorm+modulate (d of its output -> residual-stream gradient, dshift, dscale) and, in the same
             pass over the rows, the gate backward of the branch in FRONT of it (nxt = (block index, "mlp" | "attn") or None):
             dy of that branch, its dgate and the per-sample column sums of dy (the bias gradient of fc2 / proj)."""
             if nxt is None:
-                ops.ln_modulate_bwd(dt, dout_p, x_p, mean_p, rstd_p, scale_p, ld, dres_in, dres, dsh, dsc, ld, B, T, D)
+                ops.ln_modulate_bwd(dt, dout_p, x_p, mean_p, rstd_p, scale_p, ld, dres_in, dres, dsh, dsc, ld, B, T, D, dx_act=dx_act)
                 return
             l2, which = nxt
             nb = ws.blk[l2]
@@ -751,8 +763,12 @@ class DiT(FlatModule):
                 else:      # (the per-layer launch takes the bias gradient from its staged dy tiles)
                     self._wgrad(dt, pre + "attn.qkv.", dq, ptr(b["xm"]), 3 * D, D, M, beta)
             self._linear_dgrad(ws, b, "f_dqkv", dq, pre + "attn.qkv.", M, 3 * D, D, dD)
+            # block 0's LayerNorm backward ends the residual stream: its dx is the patch embedding's output gradient, and the bf16
+            # operand of that layer's two GEMMs leaves the same launch, in ws.dao (free since this block's attention backward; dD
+            # is the launch's own input), instead of a cast pass over dres
+            last_cast = fuse_tail and l == 0
             ln_bwd_and_gate(dD, xin, ptr(b["mean1"]), ptr(b["rstd1"]), mo + 4 * D, dres, dmo, dmo + 4 * D,
-                            (l - 1, "mlp") if (l and not ckpt) else None)
+                            (l - 1, "mlp") if (l and not ckpt) else None, dx_act=ptr(ws.dao) if last_cast else 0)
             if defer:
                 pending.append(l)
                 if ckpt or l == group_cut:      # (recomputation: the operands are gone once the next block is re-run)
@@ -772,7 +788,9 @@ class DiT(FlatModule):
         pending.reverse()
         flush()
         # patch embedding: d(x0) = dres
-        if dt == BF16:
+        if dt == BF16 and fuse_tail and Lyr:
+            dx0 = ptr(ws.dao)
+        elif dt == BF16:
             ops.cast_bf16(ws.dres, ws.dD)
             dx0 = dD
         else:
@@ -787,23 +805,19 @@ class DiT(FlatModule):
         rows = ld if ada_half is None else 6 * ada_half * D
         dmod_a = self._adaln_wgrad(dt, ws, 0, rows, B, beta)
         ops.gemm(dt, 1, 0, B, D, ld, dmod_a, ld, self._w("blocks.0.adaLN_modulation.1.weight"), D, ptr(ws.dcs), D, out_f32=True)
-        L.check(lib.vaw_silu_bwd(ptr(ws.c), ptr(ws.dcs), ptr(ws.dc), B * D, st), "silu_bwd")
+        ops.silu_bwd(ws.c, ws.dcs, ws.dc, ws.dc_a[:B] if fuse_tail else None)
         ye = self.y_embedder.embedding_table
         L.check(lib.vaw_embedding_bwd(ptr(ws.dc), ptr(ws.y), self._g("y_embedder.embedding_table.weight"), B, D,
                                       ye.num_embeddings, beta, st), "embedding_bwd")
-        if dt == BF16:
+        if dt == BF16 and not fuse_tail:
             ops.cast_bf16(ws.dc, ws.dc_a)
-            dc_a = ptr(ws.dc_a)
-        else:
-            dc_a = ptr(ws.dc)
+        dc_a = ptr(ws.dc_a) if dt == BF16 else ptr(ws.dc)
         self._wgrad(dt, "t_embedder.mlp.2.", dc_a, ptr(ws.h1s), D, D, ws.Bk, beta)
         ops.gemm(dt, 1, 0, B, D, D, dc_a, D, self._w("t_embedder.mlp.2.weight"), D, ptr(ws.dh1s), D, out_f32=True)
-        L.check(lib.vaw_silu_bwd(ptr(ws.h1), ptr(ws.dh1s), ptr(ws.dh1), B * D, st), "silu_bwd")
-        if dt == BF16:
+        ops.silu_bwd(ws.h1, ws.dh1s, ws.dh1, ws.dh1_a[:B] if fuse_tail else None)
+        if dt == BF16 and not fuse_tail:
             ops.cast_bf16(ws.dh1, ws.dh1_a)
-            dh1_a = ptr(ws.dh1_a)
-        else:
-            dh1_a = ptr(ws.dh1)
+        dh1_a = ptr(ws.dh1_a) if dt == BF16 else ptr(ws.dh1)
         self._wgrad(dt, "t_embedder.mlp.0.", dh1_a, ptr(ws.tfreq), D, 256, ws.Bk, beta)
         self.attach_grads()
         if fp8:

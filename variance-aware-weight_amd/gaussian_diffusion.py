@@ -539,23 +539,55 @@ class GaussianDiffusion:
             return noise
         return ops.mix_rows(x_start.contiguous(), noise.contiguous(), tb["ca"][t], tb["cb"][t])
 
-    def training_losses(self, model, x_start, features=None, t=None, model_kwargs=None, noise=None):
+    def _check_objective(self):
+        kl_loss = self.loss_type in (LossType.KL, LossType.RESCALED_KL)
+        if not kl_loss and self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE):
+            raise NotImplementedError(self.loss_type)
+        if getattr(self.args, "learn_align", False):
+            raise NotImplementedError("learn_align: feature-alignment teachers are out of scope (SURVEY.md §2.1 row 12)")
+        return kl_loss
+
+    def training_losses(self, model, x_start, features=None, t=None, model_kwargs=None, noise=None, accum=None):
+        """accum (an extension; the Trainer's fused step passes its gradient-accumulation count): with the MSE objective and a fixed
+        variance the terms also carry "loss_mean" = mean(loss) / accum as a differentiable device scalar and "mse_mean", both from
+        the loss kernels themselves (ops.weighted_mse_mean) instead of tensor operations on the per-sample vector."""
         if model_kwargs is None:
             model_kwargs = {}
         if noise is None:
             noise = torch.randn_like(x_start)       # drawn BEFORE t, as the reference (:849-852)
         if t is None:
             t = self.sample_t(x_start)
-        kl_loss = self.loss_type in (LossType.KL, LossType.RESCALED_KL)
-        if not kl_loss and self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE):
-            raise NotImplementedError(self.loss_type)
-        if getattr(self.args, "learn_align", False):
-            raise NotImplementedError("learn_align: feature-alignment teachers are out of scope (SURVEY.md §2.1 row 12)")
+        kl_loss = self._check_objective()
         x_start = x_start.contiguous()
         noise = noise.contiguous()
         tb = self._tables(x_start.device)
         x_t = ops.qsample(x_start, noise, t, tb["a"], tb["s"])
-        raw_output = model(x_t, self._scale_timesteps(t), **model_kwargs)
+        return self._losses_after_qsample(model, x_start, x_t, self._scale_timesteps(t), noise, t, model_kwargs, kl_loss, accum)
+
+    def training_losses_fused(self, model, latent, latent_scale, eps, t=None, model_kwargs=None, noise=None, accum=1):
+        """training_losses on sample_from_latent(latent) with the sample, q_sample and the timestep scaling in one launch
+        (ops.latent_qsample): latent = cat[mean, std] of the VAE posterior, eps the normal draw of the sample (drawn by the caller,
+        BEFORE noise and t: the order of the unfused step).  Same values as the unfused sequence, bit for bit."""
+        if model_kwargs is None:
+            model_kwargs = {}
+        if noise is None:
+            noise = torch.randn_like(eps)
+        if t is None:
+            t = self.sample_t(eps)
+        kl_loss = self._check_objective()
+        tb = self._tables(latent.device)
+        # the kernel scales t only where _scale_timesteps would: a respaced chain maps indices itself, and without rescale_timesteps
+        # the model is handed the int64 t as always
+        own_scale = type(self)._scale_timesteps is GaussianDiffusion._scale_timesteps and bool(self.rescale_timesteps)
+        t_scale = 1000.0 / self.num_timesteps if own_scale else None
+        out = ops.latent_qsample(latent.contiguous(), eps.contiguous(), noise.contiguous(), t.contiguous(), tb["a"], tb["s"],
+                                 latent_scale, t_scale)
+        t_model = out[2] if own_scale else self._scale_timesteps(t)
+        return self._losses_after_qsample(model, out[0], out[1], t_model, noise.contiguous(), t, model_kwargs, kl_loss, accum)
+
+    def _losses_after_qsample(self, model, x_start, x_t, t_model, noise, t, model_kwargs, kl_loss, accum):
+        tb = self._tables(x_start.device)
+        raw_output = model(x_t, t_model, **model_kwargs)
         model_output = raw_output[0] if isinstance(raw_output, tuple) else raw_output
         learned = self.model_var_type in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE)
         var_values = None
@@ -572,6 +604,9 @@ class GaussianDiffusion:
             scale = self.num_timesteps / 1000.0 if self.loss_type == LossType.RESCALED_MSE else 1.0
             terms["vb"] = self._vb_terms_bpd(model_output.detach(), var_values, x_start, x_t, t, scale)
         assert model_output.shape == x_start.shape
+        if accum is not None and not learned:
+            mse, mean = ops.weighted_mse_mean(model_output, x_start, noise, t.contiguous(), tb["ca"], tb["cb"], tb["w"], accum)
+            return {"mse": mse, "loss": mse, "loss_mean": mean, "mse_mean": mean.detach()}
         terms["mse"] = ops.weighted_mse(model_output, x_start, noise, tb["ca"][t], tb["cb"][t], tb["w"][t])
         terms["loss"] = terms["mse"] + terms["vb"] if "vb" in terms else terms["mse"]
         return terms
@@ -644,7 +679,8 @@ class FlowMatching:
         ca, cb = self._target_coefs(alpha_t, sigma_t, d_alpha_t, d_sigma_t)
         return ops.mix_rows(x_start.contiguous(), noise.contiguous(), ca.float().contiguous(), cb.float().contiguous())
 
-    def training_losses(self, model, x_start, features=None, t=None, model_kwargs=None, noise=None):
+    def training_losses(self, model, x_start, features=None, t=None, model_kwargs=None, noise=None, accum=None):
+        """accum: as GaussianDiffusion.training_losses (the batch means come from the loss kernels; per-row coefficients)."""
         if model_kwargs is None:
             model_kwargs = {}
         if noise is None:
@@ -663,6 +699,10 @@ class FlowMatching:
         raw_output = model(x_t, t, **model_kwargs)
         model_output = raw_output[0] if isinstance(raw_output, tuple) else raw_output
         assert model_output.shape == x_start.shape
+        if accum is not None:
+            mse, mean = ops.weighted_mse_mean(model_output, x_start, noise, None, ca.float().contiguous(), cb.float().contiguous(),
+                                              w.float().contiguous(), accum)
+            return {"mse": mse, "loss": mse, "loss_mean": mean, "mse_mean": mean.detach()}
         terms = {"mse": ops.weighted_mse(model_output, x_start, noise, ca.float().contiguous(), cb.float().contiguous(),
                                          w.float().contiguous())}
         terms["loss"] = terms["mse"]

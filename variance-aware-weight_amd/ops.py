@@ -74,6 +74,79 @@ def weighted_mse(model_out, x0, noise, ca, cb, w):
     return _WeightedMSE.apply(model_out, x0, noise, ca, cb, w)
 
 
+def latent_qsample(latent, eps, noise, t, tab_a, tab_s, latent_scale, t_scale=None):
+    """sample_from_latent and qsample in one launch: latent [B, 2C, H, W] (mean | std planes), eps and noise [B, C, H, W] ->
+    (x0, x_t[, float(t) * t_scale]), each bitwise what the tensor operations and vaw_qsample_fwd give."""
+    need_cuda(latent, eps, noise, t, tab_a, tab_s)
+    _f32c(latent, eps, noise, tab_a, tab_s)
+    B = latent.shape[0]
+    assert latent.shape[1] % 2 == 0 and eps.shape == noise.shape == (B, latent.shape[1] // 2, *latent.shape[2:])
+    assert t.dtype == torch.int64 and t.shape == (B,) and t.is_contiguous()
+    x0, x_t = torch.empty_like(eps), torch.empty_like(eps)
+    tf = torch.empty(B, device=eps.device, dtype=torch.float32) if t_scale is not None else None
+    check(L.lib().vaw_latent_qsample(ptr(latent), ptr(eps), ptr(noise), ptr(t), ptr(tab_a), ptr(tab_s), tab_a.numel(),
+                                     float(latent_scale), float(t_scale or 0.0), ptr(x0), ptr(x_t), ptr(tf), B, eps.numel() // B,
+                                     stream_ptr()), "vaw_latent_qsample")
+    return (x0, x_t, tf) if t_scale is not None else (x0, x_t)
+
+
+class _WeightedMSEMean(torch.autograd.Function):
+    """(per-sample mse [B], mean(mse) / accum) of the weighted MSE with the coefficient gather inside (vaw_wmse_fwd_t); the scalar is
+    the differentiable output, and its backward hands g / (B * accum) to the kernel directly -- no ones_like / expand / div / mul."""
+
+    @staticmethod
+    def forward(ctx, model_out, x0, noise, t, ca, cb, w, accum):
+        need_cuda(model_out, x0, noise, t, ca, cb, w)
+        model_out = model_out.contiguous()
+        _f32c(model_out, x0, noise, ca, cb, w)
+        B = x0.shape[0]
+        assert model_out.shape == x0.shape == noise.shape
+        if t is None:
+            assert ca.shape == cb.shape == w.shape == (B,)
+        else:
+            assert t.dtype == torch.int64 and t.shape == (B,) and t.is_contiguous() and ca.shape == cb.shape == w.shape
+        mse = torch.empty(B, device=x0.device, dtype=torch.float32)
+        mean = torch.empty((), device=x0.device, dtype=torch.float32)
+        check(L.lib().vaw_wmse_fwd_t(ptr(model_out), ptr(x0), ptr(noise), ptr(t), ptr(ca), ptr(cb), ptr(w), ca.numel(), ptr(mse),
+                                     ptr(mean), float(accum), B, x0.numel() // B, stream_ptr()), "vaw_wmse_fwd_t")
+        ctx.save_for_backward(model_out, x0, noise, t, ca, cb, w)
+        # 1 / (B * accum) as the two f32 divisions of the chain round it: (1 / accum) / B
+        ctx.inv_count = float((torch.tensor(1.0) / float(accum)) / float(B))
+        ctx.mark_non_differentiable(mse)
+        ctx.set_materialize_grads(False)      # no zeros [B] for the per-sample output's absent gradient
+        return mse, mean
+
+    @staticmethod
+    def backward(ctx, _gmse, gmean):
+        if gmean is None:
+            return (None,) * 8
+        model_out, x0, noise, t, ca, cb, w = ctx.saved_tensors
+        need_cuda(gmean)
+        gmean = gmean.contiguous().float()
+        dout = torch.empty_like(model_out)
+        B = x0.shape[0]
+        check(L.lib().vaw_wmse_bwd_t(ptr(model_out), ptr(x0), ptr(noise), ptr(t), ptr(ca), ptr(cb), ptr(w), ca.numel(), ptr(gmean),
+                                     ctx.inv_count, ptr(dout), B, x0.numel() // B, stream_ptr()), "vaw_wmse_bwd_t")
+        return dout, None, None, None, None, None, None, None
+
+
+def weighted_mse_mean(model_out, x0, noise, t, ca, cb, w, accum=1):
+    """(mse[b] = w * mean((ca * x0 + cb * noise - model_out)^2) per sample, detached; mean_b(mse) / accum, differentiable in model_out).
+    ca / cb / w are tables gathered at t[b] inside the kernel, or per-sample vectors with t = None."""
+    return _WeightedMSEMean.apply(model_out, x0, noise, t, ca, cb, w, accum)
+
+
+_ones = {}
+
+
+def one_like(x):
+    """A resident 0-dim 1.0 on x's device: the seed gradient of a scalar loss without the ones_like fill launch of backward()."""
+    t = _ones.get(x.device)
+    if t is None:
+        t = _ones[x.device] = torch.ones((), device=x.device, dtype=torch.float32)
+    return t
+
+
 class _VbTerms(torch.autograd.Function):
     """vb[b] of reference _vb_terms_bpd (gaussian_diffusion.py:775-808), one fused pass; d/d(var values) and, when the
     mean prediction is not detached (pure KL losses), d/d(mean output)."""
@@ -775,8 +848,13 @@ def _row_ws(B, T, D):
     return scratch_f32(torch.device("cuda", torch.cuda.current_device()), L.lib().vaw_row_bwd_workspace_floats(B, T, D))
 
 
-def ln_modulate_bwd(dt, dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, B, T, D):
+def ln_modulate_bwd(dt, dout, x, mean, rstd, scale, mod_ld, dres_in, dx, dshift, dscale, dmod_ld, B, T, D, dx_act=0):
+    """dx_act: address of an act-dtype copy of dx the same launch leaves (0: none)."""
     ws = _row_ws(B, T, D)
+    if dx_act:
+        check(L.lib().vaw_ln_modulate_bwd_cast(dt, dout, x, mean, rstd, scale, mod_ld, dres_in or None, dx, dshift, dscale,
+                                               dmod_ld, B, T, D, ws.data_ptr(), ws.numel(), dx_act, stream_ptr()), "vaw_ln_modulate_bwd_cast")
+        return
     check(L.lib().vaw_ln_modulate_bwd(dt, dout, x, mean, rstd, scale, mod_ld, dres_in or None, dx, dshift, dscale,
                                       dmod_ld, B, T, D, ws.data_ptr(), ws.numel(), stream_ptr()), "vaw_ln_modulate_bwd")
 
@@ -941,6 +1019,24 @@ def ema_update(ema, src, decay):
 
 def cast_bf16(src, dst):
     check(L.lib().vaw_cast_bf16(ptr(src), ptr(dst), src.numel(), stream_ptr()), "vaw_cast_bf16")
+
+
+def cast_colsum_plan(M, N, ld_src, ld_dst, src_addr, dst_addr, colsum_addr):
+    """The launch vaw_cast_colsum_bf16 makes for these operands, or None where it refuses them (host arithmetic, no GPU)."""
+    p = L.CastColsumLaunch()
+    rc = L.lib().vaw_cast_colsum_plan(M, N, ld_src, ld_dst, src_addr, dst_addr, colsum_addr, C.byref(p))
+    return p if rc == 0 else None
+
+
+def cast_colsum(src, ld_src, dst, ld_dst, M, N, colsum_out, beta=0.0):
+    """dst (bf16) = src (f32) over [M][N] (raw addresses, row strides in elements) and colsum_out = beta * colsum_out + the column
+    sums of dst, one launch; bitwise cast_bf16 followed by colsum.  Raises where vaw_cast_colsum_plan refuses."""
+    check(L.lib().vaw_cast_colsum_bf16(src, ld_src, dst, ld_dst, M, N, colsum_out, beta, stream_ptr()), "vaw_cast_colsum_bf16")
+
+
+def silu_bwd(x, dy, dx, dx_bf16=None):
+    """dx = dy * silu'(x) (f32 tensors) and, when given, dx_bf16 = bf16(dx) from the same launch."""
+    check(L.lib().vaw_silu_bwd_cast(ptr(x), ptr(dy), ptr(dx), ptr(dx_bf16), dx.numel(), stream_ptr()), "vaw_silu_bwd_cast")
 
 
 def uncast_bf16(src, dst, scale=1.0):

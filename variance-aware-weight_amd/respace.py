@@ -62,6 +62,9 @@ class SpacedDiffusion(GaussianDiffusion):
     def training_losses(self, model, *args, **kwargs):
         return super().training_losses(self._respaced(model), *args, **kwargs)
 
+    def training_losses_fused(self, model, *args, **kwargs):
+        return super().training_losses_fused(self._respaced(model), *args, **kwargs)
+
     def calc_bpd_loop(self, model, *args, **kwargs):              # ddim_reverse_sample comes through _reverse_step
         return super().calc_bpd_loop(self._respaced(model), *args, **kwargs)
 

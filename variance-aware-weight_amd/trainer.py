@@ -18,7 +18,7 @@ from contextlib import nullcontext
 import torch
 import torch.nn as nn
 
-from . import dist_util, ops
+from . import _lib, dist_util, ops
 from .flat import FlatModule
 from .optim import FusedAdamW
 
@@ -93,6 +93,17 @@ class Trainer:
             optimizer.attach_ema(ema_model, args.ema_decay)
         self.last_mse = None
         self._cpu_rng = bool(getattr(args, "cpu_rng", False))
+        # VAW_STEP_FUSED (default on): the latent sample, q_sample and the timestep scaling are one launch, the loss kernels gather
+        # their coefficients and produce the batch means, and backward is seeded with a resident 1.0 -- same draws in the same order
+        self._step_fused = _lib.STEP_FUSED and torch.device(device).type == "cuda"
+        # ... for the objectives of this package as they stand: a subclass that overrides training_losses (to pin the draws, to add
+        # a term) is called the way it always was
+        from .gaussian_diffusion import FlowMatching, GaussianDiffusion
+        from .respace import SpacedDiffusion
+        own = getattr(type(diffusion), "training_losses", None) in (GaussianDiffusion.training_losses, SpacedDiffusion.training_losses,
+                                                                   FlowMatching.training_losses)
+        self._fused_means = self._step_fused and own
+        self._fused_latent = self._fused_means and hasattr(diffusion, "training_losses_fused")
         # optional importance sampling of t (resample.py exists in the reference but its Trainer never
         # calls it).  args.schedule_sampler = "loss-second-moment": t ~ sampler, loss = mean(w_t * loss_t) with the
         # sampler's 1/(T p_t) weights (guided-diffusion's TrainLoop), history updated from the per-sample losses
@@ -136,14 +147,16 @@ class Trainer:
         return (images.to(self.device, non_blocking=True),
                 labels.to(self.device, non_blocking=True) if self.args.class_cond else None)
 
-    def _compute_loss(self, images, labels, features):
+    def _compute_loss(self, images, labels, features, accum=None):
+        """accum (fused step only): asks the objective for the batch means as well (terms["loss_mean"], see training_losses)."""
         model_kwargs = {"y": labels} if self.args.class_cond else {}
+        extra = {"accum": accum} if accum is not None and self._fused_means else {}
         if self._cpu_rng and not self._device_sampler:
             # parity runs: noise, then t, from the CPU generator, in the reference's order
             # (tools/gaussian_diffusion.py:849-852); both are accepted keyword arguments there too
             noise = torch.randn(images.shape).to(images.device)
             t = torch.randint(0, self.diffusion.num_timesteps, (images.shape[0],)).to(images.device)
-            return self.diffusion.training_losses(self.model, images, features, t=t, model_kwargs=model_kwargs, noise=noise)
+            return self.diffusion.training_losses(self.model, images, features, t=t, model_kwargs=model_kwargs, noise=noise, **extra)
         if self.schedule_sampler is not None:
             # (device sampler with args.cpu_rng: noise from the CPU generator, then the sampler's uniforms from numpy's)
             noise = torch.randn(images.shape).to(images.device) if self._cpu_rng else None
@@ -153,7 +166,43 @@ class Trainer:
             terms = dict(terms)
             terms["loss"] = terms["loss"] * w
             return terms
-        return self.diffusion.training_losses(self.model, images, features, model_kwargs=model_kwargs)
+        return self.diffusion.training_losses(self.model, images, features, model_kwargs=model_kwargs, **extra)
+
+    def _micro_step(self, images, labels, accum, cpu_rng, divide):
+        """Loss and backward of one micro-batch; returns (loss, mse) as detached device scalars, both already divided by `accum`
+        (`divide` False: the captured body, which never accumulates, leaves the division out as it always has)."""
+        a = self.args
+        fused = self._step_fused and images.is_cuda
+        if fused and a.in_chans == 4 and self.schedule_sampler is None and self._fused_latent:
+            # sample_from_latent's draw, then (parity runs) noise and t from the CPU generator: today's draws in today's order
+            mean, _ = torch.chunk(images, 2, dim=1)
+            model_kwargs = {"y": labels} if a.class_cond else {}
+            if cpu_rng:
+                eps = torch.randn(mean.shape).to(mean.device)
+                model_kwargs = dict(model_kwargs=model_kwargs, noise=torch.randn(mean.shape).to(mean.device),
+                                    t=torch.randint(0, self.diffusion.num_timesteps, (mean.shape[0],)).to(mean.device))
+            else:
+                eps = torch.randn_like(mean)
+                model_kwargs = dict(model_kwargs=model_kwargs)
+            loss_dict = self.diffusion.training_losses_fused(self.model, images, a.latent_scale, eps, accum=accum, **model_kwargs)
+        else:
+            if a.in_chans == 4:
+                images = sample_from_latent(images, a.latent_scale, cpu_rng)
+            loss_dict = self._compute_loss(images, labels, None, accum if fused else None)
+        if "loss_mean" in loss_dict:
+            loss = loss_dict["loss_mean"]
+            torch.autograd.backward(loss, ops.one_like(loss))
+            return loss.detach(), loss_dict["mse_mean"]
+        loss = loss_dict["loss"].mean()
+        if divide:
+            loss = loss / accum
+        loss.backward()
+        ld = loss.detach()
+        # pure KL / RESCALED_KL objectives carry no "mse" term (reference tools/trainer.py:116 guards the same way)
+        if "mse" not in loss_dict:
+            return ld, torch.zeros_like(ld)
+        md = loss_dict["mse"].detach().mean()
+        return ld, (md / accum if divide else md)
 
     def _apply_gradient_clipping(self):
         if self.args.grad_clip:
@@ -180,17 +229,11 @@ class Trainer:
 
     def _graph_body(self, images, labels):
         """Everything of one step that runs on the GPU, on static inputs; returns (loss, mse) device scalars."""
-        a = self.args
-        if a.in_chans == 4:
-            images = sample_from_latent(images, a.latent_scale, False)
-        loss_dict = self._compute_loss(images, labels, None)
-        loss = loss_dict["loss"].mean()
-        loss.backward()
+        loss, mse = self._micro_step(images, labels, 1, False, False)
         self._apply_gradient_clipping()
         self.optimizer.step()
         self.optimizer.zero_grad()
-        # pure KL / RESCALED_KL objectives carry no "mse" term (reference tools/trainer.py:116 guards the same way)
-        return loss.detach(), (loss_dict["mse"].detach().mean() if "mse" in loss_dict else torch.zeros_like(loss.detach()))
+        return loss, mse
 
     def eager_from_now_on(self):
         """Drop a captured graph: later steps launch their kernels one by one again (bench.py brackets them with HIP events)."""
@@ -261,18 +304,12 @@ class Trainer:
         total, mse_avg = None, None
         for i in range(accum):
             images, labels = self._get_next_batch()
-            if a.in_chans == 4:
-                images = sample_from_latent(images, a.latent_scale, self._cpu_rng)
             if a.parallel and accum > 1 and i < accum - 1:
                 ctx = self.model.no_sync()
             else:
                 ctx = nullcontext()
             with ctx:
-                loss_dict = self._compute_loss(images, labels, None)
-                loss = loss_dict["loss"].mean() / accum
-                loss.backward()
-            ld = loss.detach()
-            md = loss_dict["mse"].detach().mean() / accum if "mse" in loss_dict else torch.zeros_like(ld)
+                ld, md = self._micro_step(images, labels, accum, self._cpu_rng, True)
             total = ld if total is None else total + ld
             mse_avg = md if mse_avg is None else mse_avg + md
             if (i + 1) % accum == 0:

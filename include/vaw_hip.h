@@ -82,9 +82,8 @@ int vaw_wmse_bwd_t(const float* model_out, const float* x0, const float* noise, 
  * (gaussian_diffusion.py:775-808) = q_posterior_mean_variance :254-276 + the training side of p_mean_variance
  * :278-384 + normal_kl / discretized_gaussian_log_likelihood (tools/losses.py:12-76) + mean_flat / ln 2, fused.
  *   vb[b] = scale * mean_flat(t[b]==0 ? decoder NLL : KL(q(x_{t-1}|x_t,x_0) || p(x_{t-1}|x_t))) / ln 2
- * coef: f32 [B][8] per-sample table rows {posterior_mean_coef1, posterior_mean_coef2, posterior_log_variance_clipped,
- * log(beta_t) (LEARNED_RANGE upper end) or the fixed model log variance, pa, pb (pred_xstart = pa*x_t + pb*mean_out),
- * t==0 ? 1 : 0, unused}.  mean_mode 0: model mean = posterior mean of pred_xstart, 1: mean_out itself (PREVIOUS_X).
+ * coef: f32 [B][16], the per-sample rows of the one per-timestep table (vaw_guided_sample_step below; column layout in
+ * csrc/elementwise.hip above SS_NCOEF).  mean_mode 0: model mean = posterior mean of pred_xstart, 1: mean_out itself (PREVIOUS_X).
  * var_mode 0: fixed, 1: LEARNED (var_out = log variance), 2: LEARNED_RANGE (var_out in [-1,1]).  All tensors f32,
  * [B, per_sample] contiguous.  bwd: d_var / d_mean (either may be NULL: the MSE+vb objective detaches the mean). */
 int vaw_vb_fwd(const float* mean_out, const float* var_out, const float* x0, const float* x_t, const float* coef,
@@ -93,24 +92,15 @@ int vaw_vb_bwd(const float* mean_out, const float* var_out, const float* x0, con
                int mean_mode, int var_mode, float scale, const float* gvb, float* d_mean, float* d_var, int B,
                int64_t per_sample, vaw_stream stream);
 
-/* One reverse-process step of the sampling side, fused: p_mean_variance (gaussian_diffusion.py:278-384, no
- * denoised_fn / cond_fn) followed by p_sample (:461-505, kind 1) or ddim_sample (:603-651, kind 2); kind 0 only
- * fills pred_xstart / mean / log_variance.  coef: f32 [B][16] per-sample rows of the timestep tables (layout in
- * csrc/elementwise.hip; built by vaw_amd.GaussianDiffusion._sample_table with the reference's f64 -> f32 casts).
- * noise: the randn_like(x) draw of the step (caller's RNG).  Outputs may be NULL.  All f32 [B, per_sample]. */
-int vaw_sample_step(int kind, const float* mean_out, const float* var_out, const float* x, const float* noise,
-                    const float* coef, int mean_mode, int var_mode, int clip_denoised, float eta, float* sample,
-                    float* pred_xstart, float* mean, float* log_variance, int B, int64_t per_sample, vaw_stream stream);
-
 /* Likelihood evaluation, one timestep of calc_bpd_loop (gaussian_diffusion.py:950-1005) after the model call, fused:
  * _vb_terms_bpd :775-808 WITH clip_denoised (p_mean_variance :343-368; the training-side kernel above has no clip) and
  * the two report metrics of :989-991.  Per row b, with pred_xstart / model mean / log variance formed per element as
- * in the sampling step above and never stored:
+ * in the reverse step below (one shared device function) and never stored:
  *   vb         = mean_flat(t[b]==0 ? decoder NLL : KL(q(x_{t-1}|x_t,x_0) || p(x_{t-1}|x_t))) / ln 2
  *   xstart_mse = mean_flat((pred_xstart - x0)^2)
  *   mse        = mean_flat((eps - noise)^2),  eps = (sqrt_recip_abar*x_t - pred_xstart) / sqrt_recipm1_abar  (:411-415,
  *                evaluated in f32 in exactly this order: the difference cancels heavily at small t)
- * coef: f32 [B][16], the rows of the sampling step.  mean_out / var_out: row b starts model_ld floats after row b-1
+ * coef: f32 [B][16], the rows of the reverse step.  mean_out / var_out: row b starts model_ld floats after row b-1
  * (model_ld = per_sample when contiguous, 2*per_sample for the halves of a [B, 2C, H, W] output read in place);
  * x0, x_t, noise are [B, per_sample] contiguous.  mean_mode / var_mode as above.  The three scalars of row b go to
  * out[(b % group)*out_ld + b / group] of each output: with B = K*group rows (K timesteps of `group` samples stacked)
@@ -128,27 +118,28 @@ int vaw_bpd_terms(const float* mean_out, const float* var_out, int64_t model_ld,
 int vaw_prior_bpd(const float* x0, float sqrt_abar_last, float log_one_minus_abar_last, float* prior_bpd, int B,
                   int64_t per_sample, vaw_stream stream);
 
-/* ddim_reverse_sample :653-689 after the model call (eta = 0, the DDIM ODE run from data towards noise):
- *   pred_xstart as in the sampling step (clip included), eps = (sqrt_recip_abar*x - pred_xstart) / sqrt_recipm1_abar,
- *   sample = pred_xstart*sqrt(abar_next) + sqrt(1 - abar_next)*eps.
- * coef: the [B][16] rows of the sampling step, column 13 = alphas_cumprod_next; columns 0-1 already encode the mean
- * type (EPSILON / START_X / PREVIOUS_X) and the model variance does not enter, so there are no mode arguments.
- * mean_out rows are model_ld floats apart.  pred_xstart may be NULL. */
-int vaw_ddim_reverse_step(const float* mean_out, int64_t model_ld, const float* x, const float* coef, int clip_denoised,
-                          float* sample, float* pred_xstart, int B, int64_t per_sample, vaw_stream stream);
-
-/* Sampler (tools/sampler.py): one reverse-process step with classifier-free guidance fused in.  The guided model call
+/* The one reverse-process step of the sampling side, fused: classifier-free guidance (tools/sampler.py), p_mean_variance
+ * (gaussian_diffusion.py:278-384, no denoised_fn / cond_fn) and the update of the sampler:
+ *   kind 0  none: only pred_xstart / mean / log_variance are filled
+ *   kind 1  p_sample :461-505        kind 2  ddim_sample :603-651 (eta)
+ *   kind 3  ddim_reverse_sample :653-689 (eta = 0, the DDIM ODE run from data towards noise):
+ *           eps = (sqrt_recip_abar*x - pred_xstart) / sqrt_recipm1_abar,  sample = pred_xstart*sqrt(abar_next) + sqrt(1 - abar_next)*eps;
+ *           takes no noise and no variance (noise and var_* NULL, var_mode 0) and writes sample and pred_xstart (mean and
+ *           log_variance NULL)
+ * coef: f32 [B][16] per-sample rows of the per-timestep table (column layout in csrc/elementwise.hip above SS_NCOEF; built by
+ * vaw_amd.GaussianDiffusion._sample_table with the reference's f64 -> f32 casts; columns 0-1 encode the mean type).
+ * noise: the randn_like(x) draw of the step (caller's RNG; kinds 1 and 2).  Outputs may be NULL.  The guided model call
  * evaluates the batch stacked on itself (IntervalCFG.forward :41-48), so its [2N, 2C, H, W] output holds four quarters:
  * conditional / unconditional half of the batch, mean / variance channels.  They are read in place: row b of each of
  * mean_cond, mean_uncond, var_cond, var_uncond starts model_ld floats after row b-1 (model_ld >= per_sample).  Per element
  *   m = mean_uncond + guidance_scale * (mean_cond - mean_uncond),   v likewise from the variance quarters
  * in f32 with the difference, the product and the sum each rounded on its own (no fused multiply-add), i.e. bitwise the
- * three tensor operations of :48, which guide every output channel.  Then exactly the per-element body of vaw_sample_step
- * (one shared device function): kind, coef, mean_mode, var_mode, clip_denoised, eta and the optional outputs as there.
+ * three tensor operations of :48, which guide every output channel.  Then the per-element step above.
  * mean_uncond == NULL: no guidance, the plain step reading the split halves of a [N, 2C, H, W] output in place
  * (guidance_scale and var_uncond are ignored).  var_cond may be NULL with var_mode 0; var_uncond is needed only when both
  * guided and var_mode != 0.  x, noise and the outputs are [B, per_sample] contiguous.  16-byte loads and stores when
- * per_sample % 4 == 0, model_ld % 4 == 0 and every pointer is 16-byte aligned, scalar ones otherwise. */
+ * per_sample % 4 == 0, model_ld % 4 == 0 and every pointer is 16-byte aligned, scalar ones otherwise: one loop body at either
+ * width, the same bits. */
 int vaw_guided_sample_step(int kind, const float* mean_cond, const float* mean_uncond, const float* var_cond,
                            const float* var_uncond, int64_t model_ld, float guidance_scale, const float* x, const float* noise,
                            const float* coef, int mean_mode, int var_mode, int clip_denoised, float eta, float* sample,

@@ -206,7 +206,7 @@ def test_refusals():
 
 def test_new_entry_points_are_bound():
     lib = vaw_amd.lib()
-    for name in ("vaw_bpd_terms", "vaw_prior_bpd", "vaw_ddim_reverse_step"):
+    for name in ("vaw_bpd_terms", "vaw_prior_bpd", "vaw_guided_sample_step"):
         assert name in vaw_amd.exported_symbols() and hasattr(lib, name)
 
 
@@ -228,6 +228,10 @@ def test_c_abi_refuses_bad_arguments_before_any_launch():
         assert word in lib.vaw_last_error_string().decode(), (kw, lib.vaw_last_error_string())
     assert lib.vaw_prior_bpd(P, 0.1, -0.1, P, 2, 0, None) == -1 and "sizes" in lib.vaw_last_error_string().decode()
     assert lib.vaw_prior_bpd(None, 0.1, -0.1, P, 2, 64, None) == -1 and "null" in lib.vaw_last_error_string().decode()
-    assert lib.vaw_ddim_reverse_step(P, 64, P, P, 1, P, P, 2, 0, None) == -1 and "sizes" in lib.vaw_last_error_string().decode()
-    assert lib.vaw_ddim_reverse_step(P, 64, None, P, 1, P, P, 2, 64, None) == -1 and "null" in lib.vaw_last_error_string().decode()
-    assert lib.vaw_ddim_reverse_step(P, 32, P, P, 1, P, P, 2, 64, None) == -1 and "model_ld" in lib.vaw_last_error_string().decode()
+
+    def ddim_reverse(mean=P, ld=64, x=P, n=64):          # kind 3 of the one reverse-step entry: no guidance, noise or variance
+        return lib.vaw_guided_sample_step(3, mean, None, None, None, ld, 1.0, x, None, P, 0, 0, 1, 0.0, P, P, None, None, 2, n, None)
+
+    assert ddim_reverse(n=0) == -1 and "sizes" in lib.vaw_last_error_string().decode()
+    assert ddim_reverse(x=None) == -1 and "null" in lib.vaw_last_error_string().decode()
+    assert ddim_reverse(ld=32) == -1 and "model_ld" in lib.vaw_last_error_string().decode()

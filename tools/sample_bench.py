@@ -5,7 +5,7 @@
 For a learn_sigma model under IntervalCFG (scale 2.5, active on part of the chain) over a respaced LEARNED_RANGE chain:
  (a) one guided DDIM step, fused: the stacked model call + vaw_guided_sample_step, the interval decided on the host;
  (b) the same step through the composition of existing pieces (what the step was before the fused kernel): the model call,
-     the mean timestep read back from the device, three torch ops, the split halves made contiguous, vaw_sample_step.
+     the mean timestep read back from the device, three torch ops, the split halves made contiguous, ops.sample_step.
      Both are also timed WITHOUT the model call (the step's tail alone over rotating buffers larger than the 256 MiB
      Infinity Cache), which is where the byte arithmetic of DESIGN applies;
  (c) vaw_finish_images against the torch expression, f32 and f64, rotating buffers;

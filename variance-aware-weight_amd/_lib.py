@@ -127,7 +127,6 @@ _PROTOS = {
     "vaw_conv3x3": [_i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, C.POINTER(Epilogue), _p, _l, _p],
     "vaw_vb_fwd": [_p, _p, _p, _p, _p, _i, _i, _f, _p, _i, _l, _p],
     "vaw_vb_bwd": [_p, _p, _p, _p, _p, _i, _i, _f, _p, _p, _p, _i, _l, _p],
-    "vaw_sample_step": [_i, _p, _p, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _i, _l, _p],
     "vaw_bpd_terms": [_p, _p, _l, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _l, _i, _i, _l, _p],
     "vaw_guided_sample_step": [_i, _p, _p, _p, _p, _l, _f, _p, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _i, _l, _p],
     "vaw_cfg_combine": [_p, _p, _l, _f, _p, _i, _l, _p],
@@ -136,7 +135,6 @@ _PROTOS = {
     "vaw_edm_step": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _i, _i, _p, _p, _p, _i, _l, _p],
     "vaw_flow_step": [_i, _i, _i, _p, _p, _l, _f, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _l, _p],
     "vaw_prior_bpd": [_p, _f, _f, _p, _i, _l, _p],
-    "vaw_ddim_reverse_step": [_p, _l, _p, _p, _i, _p, _p, _i, _l, _p],
     "vaw_resampler_update": [_p, _p, _i, _i, _i, _p, _p, _p, _p],
     "vaw_resampler_draw": [_p, _p, _i, _i, C.c_double, _p, _i, _p, _p, _p, _p],
     "vaw_conv3x3_narrow": [_i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/vaw_hip.h"
 
 typedef __bf16 bf16_t;
@@ -53,6 +55,68 @@ __device__ __forceinline__ void store4(bf16_t* p, f32x4 v) {
     bf16x4 r = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
     *reinterpret_cast<bf16x4*>(p) = r;
 }
+
+// W-wide fill / drain of T v[W] for the streaming kernels that run one loop body at W = 4 (16-byte accesses: one f32x4, two
+// f64x2) and at W = 1 (any alignment, any length)
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+template <int W> __device__ __forceinline__ void loadw(const float* p, float* v) {
+    if constexpr (W == 4) {
+        const f32x4 t = load4(p);
+        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+    } else {
+        v[0] = p[0];
+    }
+}
+template <int W> __device__ __forceinline__ void loadw(const double* p, double* v) {
+    if constexpr (W == 4) {
+        const f64x2 a = *reinterpret_cast<const f64x2*>(p), b = *reinterpret_cast<const f64x2*>(p + 2);
+        v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
+    } else {
+        v[0] = p[0];
+    }
+}
+template <int W> __device__ __forceinline__ void storew(float* p, const float* v) {
+    if constexpr (W == 4) {
+        const f32x4 t = {v[0], v[1], v[2], v[3]};
+        store4(p, t);
+    } else {
+        p[0] = v[0];
+    }
+}
+template <int W> __device__ __forceinline__ void storew(double* p, const double* v) {
+    if constexpr (W == 4) {
+        const f64x2 a = {v[0], v[1]}, b = {v[2], v[3]};
+        *reinterpret_cast<f64x2*>(p) = a;
+        *reinterpret_cast<f64x2*>(p + 2) = b;
+    } else {
+        p[0] = v[0];
+    }
+}
+
+// classifier-free guidance, u + s * (c - u): subtraction, product and sum each rounded on its own where the file is built with
+// -ffp-contract=off, which is what the three tensor operations of IntervalCFG.forward give
+__device__ __forceinline__ float cfg_mix(float c, float u, float s) { return u + s * (c - u); }
+
+// ---- launch plumbing of the row-streaming kernels (host) ------------------------------------------------------------------
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// One grid row per sample, at most 64 blocks of 256 threads along it (grid-stride beyond): B x 64 blocks cover the chip's
+// 256 CUs from B = 4 on, and the FID batch (64 x 3072 elements, 768 four-element items a row) is 192 blocks.
+static inline dim3 row_grid(int64_t items, int B) {
+    int64_t g = (items + 255) / 256;
+    return dim3((unsigned)(g < 1 ? 1 : (g > 64 ? 64 : g)), (unsigned)B);
+}
+// The one place that decides vectorisation: rows of per_sample elements, model_ld apart where they are read in place, both
+// multiples of 4, and every non-null pointer 16-byte aligned.  VAW_LAUNCH_W then launches KERNEL<4> or KERNEL<1>.
+static inline bool vec4_ok(int64_t per_sample, int64_t model_ld, std::initializer_list<const void*> ptrs) {
+    bool ok = per_sample % 4 == 0 && model_ld % 4 == 0;
+    for (const void* p : ptrs) ok = ok && al16(p);
+    return ok;
+}
+#define VAW_LAUNCH_W(KERNEL, vec, grid, block, stream, ...)                                   \
+    do {                                                                                      \
+        if (vec) KERNEL<4><<<grid, block, 0, (hipStream_t)(stream)>>>(__VA_ARGS__);           \
+        else KERNEL<1><<<grid, block, 0, (hipStream_t)(stream)>>>(__VA_ARGS__);               \
+    } while (0)
 
 // ---- wave / block reductions -------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {

@@ -154,14 +154,39 @@ extern "C" int vaw_wmse_bwd(const float* model_out, const float* x0, const float
 }
 
 // ---------------------------------------------------------------------------------------------
-// Variational-bound term (learned variance / KL losses): one pass over (x0, x_t, model mean, model var values) per
-// sample, bits per dim.  coef[b][8] = {c1, c2, plv, lv_aux, pa, pb, is_t0, -}: posterior mean coefficients, the
-// clipped posterior log variance (true log variance and the lower end of the learned range), log(beta_t) (upper end
-// of the range) or the fixed model log variance, pred_xstart = pa*x_t + pb*mean_out, and the t == 0 flag.
-//   mean_mode 0: model mean = c1*pred_xstart + c2*x_t      1: model mean = mean_out (PREVIOUS_X)
+// The per-timestep table of the reverse process and its per-element p_mean_variance (reference :278-384), shared by the
+// variational-bound term of the training loss, the likelihood evaluation and the reverse step.
+// One row of SS_NCOEF floats per timestep (GaussianDiffusion._sample_table: the reference's f64 tables cast to f32):
+//    0 pa, 1 pb     pred_xstart = pa*x_t + pb*mean_out (clamped to [-1,1] if clip)
+//    2 c1, 3 c2     posterior mean coefficients: q mean = c1*x0 + c2*x_t, model mean = c1*pred + c2*x_t
+//    4 plv          clipped posterior log variance (true log variance; lower end of the learned range)
+//    5 lv_aux       the fixed model log variance, or log(beta_t), the upper end of the learned range
+//    6 ra, 7 rm1    eps = (ra*x_t - pred)/rm1
+//    8 sqrt_abp, 9 s1, 10 abp, 12 s2    ddim: sigma = (eta*s1)*s2, mean = pred*sqrt_abp + sqrt(1 - abp - sigma^2)*eps
+//   11 is_t0        t == 0: no noise added; decoder NLL instead of the KL
+//   13 abn          alphas_cumprod_next (DDIM reverse step)        14, 15 unused
+//   mean_mode 0: model mean = c1*pred + c2*x_t      1: model mean = mean_out (PREVIOUS_X)
 //   var_mode  0: log variance = lv_aux (fixed)   1: = var values (LEARNED)   2: interpolated (LEARNED_RANGE)
 // ---------------------------------------------------------------------------------------------
-#define VB_NCOEF 8
+#define SS_NCOEF 16
+struct Pmv { float pred, mean, lv; };
+// m / v: the model's mean output and variance value of the element (v is not read with a fixed variance), x_t the noised image
+__device__ __forceinline__ Pmv p_mean_variance(const float* c, int mean_mode, int var_mode, int clip, float m, float v, float x_t) {
+    Pmv o;
+    float pred = c[0] * x_t + c[1] * m;
+    if (clip) pred = fminf(fmaxf(pred, -1.f), 1.f);
+    if (var_mode == 1) o.lv = v;
+    else if (var_mode == 2) { const float frac = (v + 1.f) / 2.f; o.lv = frac * c[5] + (1.f - frac) * c[4]; }
+    else o.lv = c[5];
+    o.pred = pred;
+    o.mean = mean_mode == 1 ? m : c[2] * pred + c[3] * x_t;
+    return o;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Variational-bound term (learned variance / KL losses): one pass over (x0, x_t, model mean, model var values) per
+// sample, bits per dim.  coef[b] is the table row of t[b]; no clipping.
+// ---------------------------------------------------------------------------------------------
 struct VbElem {
     float val;      // KL or decoder NLL of this element, nats
     float d_lv;     // d val / d model log variance
@@ -205,30 +230,22 @@ __device__ __forceinline__ VbElem vb_elem(float x0, float true_mean, float true_
     r.d_mean = inv * (g_pin + g_min);                           // d plus_in / d mean = -inv_stdv
     return r;
 }
-__device__ __forceinline__ void vb_model(const float* c, int mean_mode, int var_mode, float xt, float m, float v, float& mean,
-                                         float& lv) {
-    mean = mean_mode == 1 ? m : c[0] * (c[4] * xt + c[5] * m) + c[1] * xt;
-    if (var_mode == 1) lv = v;
-    else if (var_mode == 2) { const float frac = (v + 1.f) / 2.f; lv = frac * c[3] + (1.f - frac) * c[2]; }
-    else lv = c[3];
-}
 
 __global__ void vb_fwd_kernel(const float* __restrict__ mean_out, const float* __restrict__ var_out, const float* __restrict__ x0,
                               const float* __restrict__ xt, const float* __restrict__ coef, int mean_mode, int var_mode,
                               float scale, float* __restrict__ vb, int64_t n) {
     __shared__ float scratch[16];
     const int b = blockIdx.x;
-    float c[VB_NCOEF];
+    float c[SS_NCOEF];
 #pragma unroll
-    for (int i = 0; i < VB_NCOEF; ++i) c[i] = coef[b * VB_NCOEF + i];
-    const bool t0 = c[6] != 0.f;
+    for (int i = 0; i < SS_NCOEF; ++i) c[i] = coef[(int64_t)b * SS_NCOEF + i];
+    const bool t0 = c[11] != 0.f;
     const int64_t base = (int64_t)b * n;
     float acc = 0.f;
     for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
         const float x = x0[base + i], z = xt[base + i];
-        float mean, lv;
-        vb_model(c, mean_mode, var_mode, z, mean_out[base + i], var_out ? var_out[base + i] : 0.f, mean, lv);
-        acc += vb_elem(x, c[0] * x + c[1] * z, c[2], mean, lv, t0).val;
+        const Pmv p = p_mean_variance(c, mean_mode, var_mode, 0, mean_out[base + i], var_out ? var_out[base + i] : 0.f, z);
+        acc += vb_elem(x, c[2] * x + c[3] * z, c[4], p.mean, p.lv, t0).val;
     }
     const float tot = block_sum(acc, scratch);
     if (threadIdx.x == 0) vb[b] = scale * ((tot / (float)n) / 0.6931471805599453f);
@@ -239,19 +256,18 @@ __global__ void vb_bwd_kernel(const float* __restrict__ mean_out, const float* _
                               float scale, const float* __restrict__ gvb, float* __restrict__ d_mean, float* __restrict__ d_var,
                               int64_t n) {
     const int b = blockIdx.y;
-    float c[VB_NCOEF];
+    float c[SS_NCOEF];
 #pragma unroll
-    for (int i = 0; i < VB_NCOEF; ++i) c[i] = coef[b * VB_NCOEF + i];
-    const bool t0 = c[6] != 0.f;
+    for (int i = 0; i < SS_NCOEF; ++i) c[i] = coef[(int64_t)b * SS_NCOEF + i];
+    const bool t0 = c[11] != 0.f;
     const float g = gvb[b] * scale / ((float)n * 0.6931471805599453f);
-    const float dlv_dv = var_mode == 2 ? 0.5f * (c[3] - c[2]) : 1.f;
-    const float dmean_dm = mean_mode == 1 ? 1.f : c[0] * c[5];
+    const float dlv_dv = var_mode == 2 ? 0.5f * (c[5] - c[4]) : 1.f;
+    const float dmean_dm = mean_mode == 1 ? 1.f : c[2] * c[1];
     const int64_t base = (int64_t)b * n;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float x = x0[base + i], z = xt[base + i];
-        float mean, lv;
-        vb_model(c, mean_mode, var_mode, z, mean_out[base + i], var_out ? var_out[base + i] : 0.f, mean, lv);
-        const VbElem e = vb_elem(x, c[0] * x + c[1] * z, c[2], mean, lv, t0);
+        const Pmv p = p_mean_variance(c, mean_mode, var_mode, 0, mean_out[base + i], var_out ? var_out[base + i] : 0.f, z);
+        const VbElem e = vb_elem(x, c[2] * x + c[3] * z, c[4], p.mean, p.lv, t0);
         if (d_var) d_var[base + i] = g * e.d_lv * dlv_dv;
         if (d_mean) d_mean[base + i] = g * e.d_mean * dmean_dm;
     }
@@ -274,125 +290,38 @@ extern "C" int vaw_vb_bwd(const float* mean_out, const float* var_out, const flo
     VAW_CHECK_ARG((mean_mode == 0 || mean_mode == 1) && var_mode >= 0 && var_mode <= 2 && (var_mode == 0 || var_out) &&
                       (var_mode != 0 || !d_var),
                   "vb_bwd: bad modes");
-    int gx = stream_grid(per_sample, 256);
-    dim3 grid(gx > 64 ? 64 : gx, B);
-    vb_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(mean_out, var_out, x0, x_t, coef, mean_mode, var_mode, scale, gvb, d_mean,
-                                                         d_var, per_sample);
+    vb_bwd_kernel<<<row_grid(per_sample, B), 256, 0, (hipStream_t)stream>>>(mean_out, var_out, x0, x_t, coef, mean_mode, var_mode, scale,
+                                                                            gvb, d_mean, d_var, per_sample);
     VAW_CHECK_LAUNCH("vb_bwd");
-    return VAW_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// One reverse-process step (sampling side): p_mean_variance + p_sample / ddim_sample fused.
-// coef[b][16] = {pa, pb, c1, c2, plv, lv_aux, ra, rm1, sqrt_abp, s1, abp, is_t0, s2, abn, -, -}  (abn = alphas_cumprod_next: read by
-// ddim_reverse_kernel only):
-//   pred_xstart = pa*x + pb*mean_out (clamped to [-1,1] if clip), model mean = c1*pred + c2*x (or mean_out itself),
-//   eps = (ra*x - pred)/rm1, sigma = (eta*s1)*s2, ddim mean = pred*sqrt_abp + sqrt(1 - abp - sigma^2)*eps.
-// kind 0: no sample (p_mean_variance only)   1: ancestral p_sample   2: ddim_sample.  Outputs may be NULL.
-// ---------------------------------------------------------------------------------------------
-#define SS_NCOEF 16
-// what a launch derives from one coefficient row before its element loop
-struct SsRow { float c[SS_NCOEF]; float mask, sigma, ddim_c; };
-__device__ __forceinline__ void ss_row(const float* __restrict__ coef, int b, float eta, SsRow& r) {
-#pragma unroll
-    for (int i = 0; i < SS_NCOEF; ++i) r.c[i] = coef[(int64_t)b * SS_NCOEF + i];
-    r.mask = r.c[11] != 0.f ? 0.f : 1.f;
-    r.sigma = (eta * r.c[9]) * r.c[12];
-    r.ddim_c = sqrtf(1.f - r.c[10] - r.sigma * r.sigma);
-}
-struct SsOut { float sample, pred, mean, lv; };
-// The per-element body of the step, shared by sample_step_kernel and guided_sample_step_kernel: m / v are the model's mean
-// output and variance value of the element (v is not read with a fixed variance), xv = x_t, nz the noise (not read by kind 0).
-__device__ __forceinline__ SsOut ss_elem(const SsRow& r, int kind, int mean_mode, int var_mode, int clip, float m, float v,
-                                         float xv, float nz) {
-    const float* c = r.c;
-    SsOut o;
-    float pred = c[0] * xv + c[1] * m;
-    if (clip) pred = fminf(fmaxf(pred, -1.f), 1.f);
-    float lv;
-    if (var_mode == 1) lv = v;
-    else if (var_mode == 2) { const float frac = (v + 1.f) / 2.f; lv = frac * c[5] + (1.f - frac) * c[4]; }
-    else lv = c[5];
-    o.pred = pred;
-    o.lv = lv;
-    o.mean = mean_mode == 1 ? m : c[2] * pred + c[3] * xv;
-    o.sample = 0.f;
-    if (kind == 1) {
-        o.sample = o.mean + (r.mask * expf(0.5f * lv)) * nz;
-    } else if (kind == 2) {
-        const float eps = (c[6] * xv - pred) / c[7];
-        const float mp = pred * c[8] + r.ddim_c * eps;
-        o.sample = mp + (r.mask * r.sigma) * nz;
-    }
-    return o;
-}
-
-__global__ void sample_step_kernel(const float* __restrict__ mean_out, const float* __restrict__ var_out, const float* __restrict__ x,
-                                   const float* __restrict__ noise, const float* __restrict__ coef, int kind, int mean_mode,
-                                   int var_mode, int clip, float eta, float* __restrict__ sample, float* __restrict__ pred_out,
-                                   float* __restrict__ mean_o, float* __restrict__ logvar_o, int64_t n) {
-    const int b = blockIdx.y;
-    SsRow r;
-    ss_row(coef, b, eta, r);
-    const int64_t base = (int64_t)b * n;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const SsOut o = ss_elem(r, kind, mean_mode, var_mode, clip, mean_out[base + i], var_mode ? var_out[base + i] : 0.f,
-                                x[base + i], kind ? noise[base + i] : 0.f);
-        if (pred_out) pred_out[base + i] = o.pred;
-        if (mean_o) mean_o[base + i] = o.mean;
-        if (logvar_o) logvar_o[base + i] = o.lv;
-        if (kind) sample[base + i] = o.sample;
-    }
-}
-
-extern "C" int vaw_sample_step(int kind, const float* mean_out, const float* var_out, const float* x, const float* noise,
-                               const float* coef, int mean_mode, int var_mode, int clip_denoised, float eta, float* sample,
-                               float* pred_xstart, float* mean, float* log_variance, int B, int64_t per_sample,
-                               vaw_stream stream) {
-    VAW_CHECK_ARG(B > 0 && per_sample > 0 && mean_out && x && coef && kind >= 0 && kind <= 2, "sample_step: bad arguments");
-    VAW_CHECK_ARG((mean_mode == 0 || mean_mode == 1) && var_mode >= 0 && var_mode <= 2 && (var_mode == 0 || var_out),
-                  "sample_step: bad modes (learned variance needs var_out)");
-    VAW_CHECK_ARG(kind == 0 || (sample && noise), "sample_step: kind 1/2 need noise and sample");
-    int gx = stream_grid(per_sample, 256);
-    dim3 grid(gx > 64 ? 64 : gx, B);
-    sample_step_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(mean_out, var_out, x, noise, coef, kind, mean_mode, var_mode,
-                                                             clip_denoised, eta, sample, pred_xstart, mean, log_variance, per_sample);
-    VAW_CHECK_LAUNCH("sample_step");
     return VAW_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // Likelihood evaluation (calc_bpd_loop): the three per-sample scalars of one evaluated timestep in one pass over
 // (model mean output, model var values, x0, x_t, noise): 20 B/element read (16 with a fixed variance), nothing of
-// [B, per_sample] shape written.  coef rows are those of sample_step_kernel (SS_NCOEF, same columns).
-//   pred  = pa*x_t + pb*mean_out, clamped to [-1,1] if clip          (p_mean_variance :343-368)
+// [B, per_sample] shape written.
+//   pred  = p_mean_variance's, clamped to [-1,1] if clip               (p_mean_variance :343-368)
 //   vb    = mean(t==0 ? decoder NLL : KL(q(x_{t-1}|x_t,x0) || p(x_{t-1}|x_t))) / ln 2    (vb_elem, as vb_fwd_kernel)
 //   xmse  = mean((pred - x0)^2)                                       (:989)
 //   mse   = mean((eps - noise)^2),  eps = (ra*x_t - pred) / rm1       (:990-991, :411-415; not re-associated)
-// One workgroup per row; a thread sums its elements in index order, then wave shuffles + one LDS hop (block_sum): a fixed
-// order that depends on per_sample and the path (VEC) only, never on B.  Row b writes out[(b % group)*out_ld + b / group]:
-// a launch over K stacked timesteps of `group` samples fills K adjacent columns of the [N, T] outputs.
-// mean_out / var_out rows are model_ld elements apart (the two halves of one [B, 2C, H, W] model output are read in
-// place); every other tensor is [B, per_sample] contiguous.
+// One workgroup per row; a thread sums its elements in index order (W*i .. W*i + W-1 of each of its items), then wave
+// shuffles + one LDS hop (block_sum): a fixed order that depends on per_sample and W only, never on B.  Row b writes
+// out[(b % group)*out_ld + b / group]: a launch over K stacked timesteps of `group` samples fills K adjacent columns of the
+// [N, T] outputs.  mean_out / var_out rows are model_ld elements apart (the two halves of one [B, 2C, H, W] model output
+// are read in place); every other tensor is [B, per_sample] contiguous.
 // ---------------------------------------------------------------------------------------------
 struct BpdAcc { float vb, xm, ms; };
 __device__ __forceinline__ void bpd_elem(const float* c, int mean_mode, int var_mode, int clip, bool t0, float m, float v, float x,
                                          float z, float nz, BpdAcc& a) {
-    float pred = c[0] * z + c[1] * m;
-    if (clip) pred = fminf(fmaxf(pred, -1.f), 1.f);
-    float lv;
-    if (var_mode == 1) lv = v;
-    else if (var_mode == 2) { const float frac = (v + 1.f) / 2.f; lv = frac * c[5] + (1.f - frac) * c[4]; }
-    else lv = c[5];
-    const float mean = mean_mode == 1 ? m : c[2] * pred + c[3] * z;
-    a.vb += vb_elem(x, c[2] * x + c[3] * z, c[4], mean, lv, t0).val;
-    const float dx = pred - x;
+    const Pmv p = p_mean_variance(c, mean_mode, var_mode, clip, m, v, z);
+    a.vb += vb_elem(x, c[2] * x + c[3] * z, c[4], p.mean, p.lv, t0).val;
+    const float dx = p.pred - x;
     a.xm += dx * dx;
-    const float de = (c[6] * z - pred) / c[7] - nz;
+    const float de = (c[6] * z - p.pred) / c[7] - nz;
     a.ms += de * de;
 }
 
-template <bool VEC>
+template <int W>
 __global__ void __launch_bounds__(1024)
 bpd_terms_kernel(const float* __restrict__ mean_out, const float* __restrict__ var_out, int64_t model_ld,
                  const float* __restrict__ x0, const float* __restrict__ xt, const float* __restrict__ noise,
@@ -410,17 +339,15 @@ bpd_terms_kernel(const float* __restrict__ mean_out, const float* __restrict__ v
     const float* zr = xt + (int64_t)b * n;
     const float* nr = noise + (int64_t)b * n;
     BpdAcc a = {0.f, 0.f, 0.f};
-    if (VEC) {
-        const int64_t n4 = n / 4;
-        for (int64_t i = threadIdx.x; i < n4; i += blockDim.x) {
-            const f32x4 m = load4(mr + 4 * i), x = load4(xr + 4 * i), z = load4(zr + 4 * i), e = load4(nr + 4 * i);
-            const f32x4 v = vr ? load4(vr + 4 * i) : f32x4{0, 0, 0, 0};
+    for (int64_t i = threadIdx.x; i < n / W; i += blockDim.x) {
+        float m[W], x[W], z[W], e[W], v[W] = {};
+        loadw<W>(mr + W * i, m);
+        loadw<W>(xr + W * i, x);
+        loadw<W>(zr + W * i, z);
+        loadw<W>(nr + W * i, e);
+        if (vr) loadw<W>(vr + W * i, v);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bpd_elem(c, mean_mode, var_mode, clip, t0, m[j], v[j], x[j], z[j], e[j], a);
-        }
-    } else {
-        for (int64_t i = threadIdx.x; i < n; i += blockDim.x)
-            bpd_elem(c, mean_mode, var_mode, clip, t0, mr[i], vr ? vr[i] : 0.f, xr[i], zr[i], nr[i], a);
+        for (int j = 0; j < W; ++j) bpd_elem(c, mean_mode, var_mode, clip, t0, m[j], v[j], x[j], z[j], e[j], a);
     }
     const float tv = block_sum(a.vb, scratch), tx = block_sum(a.xm, scratch), tm = block_sum(a.ms, scratch);
     if (threadIdx.x == 0) {
@@ -430,8 +357,6 @@ bpd_terms_kernel(const float* __restrict__ mean_out, const float* __restrict__ v
         mse[o] = tm / (float)n;
     }
 }
-
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int vaw_bpd_terms(const float* mean_out, const float* var_out, int64_t model_ld, const float* x0, const float* x_t,
                              const float* noise, const float* coef, int mean_mode, int var_mode, int clip_denoised, float* vb,
@@ -444,16 +369,8 @@ extern "C" int vaw_bpd_terms(const float* mean_out, const float* var_out, int64_
                   "bpd_terms: bad modes (mean_mode %d, var_mode %d; learned variance needs var_out)", mean_mode, var_mode);
     VAW_CHECK_ARG(group > 0 && B % group == 0 && out_ld >= B / group, "bpd_terms: bad output layout (group %d, out_ld %ld, B %d)",
                   group, (long)out_ld, B);
-    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(mean_out) && al16(var_out) && al16(x0) && al16(x_t) &&
-                     al16(noise);
-    if (vec)
-        bpd_terms_kernel<true><<<B, 1024, 0, (hipStream_t)stream>>>(mean_out, var_out, model_ld, x0, x_t, noise, coef, mean_mode,
-                                                                    var_mode, clip_denoised, vb, xstart_mse, mse, out_ld, group,
-                                                                    per_sample);
-    else
-        bpd_terms_kernel<false><<<B, 1024, 0, (hipStream_t)stream>>>(mean_out, var_out, model_ld, x0, x_t, noise, coef, mean_mode,
-                                                                     var_mode, clip_denoised, vb, xstart_mse, mse, out_ld, group,
-                                                                     per_sample);
+    VAW_LAUNCH_W(bpd_terms_kernel, vec4_ok(per_sample, model_ld, {mean_out, var_out, x0, x_t, noise}), B, 1024, stream, mean_out, var_out,
+                 model_ld, x0, x_t, noise, coef, mean_mode, var_mode, clip_denoised, vb, xstart_mse, mse, out_ld, group, per_sample);
     VAW_CHECK_LAUNCH("bpd_terms");
     return VAW_OK;
 }
@@ -491,76 +408,51 @@ extern "C" int vaw_prior_bpd(const float* x0, float sqrt_abar_last, float log_on
     return VAW_OK;
 }
 
-// ddim_reverse_sample :653-689 after the model call (eta = 0: the deterministic DDIM ODE run towards noise).  Rows of
-// sample_step_kernel's table, column 13 = alphas_cumprod_next:
-//   pred = pa*x + pb*mean_out (clamped if clip),  eps = (ra*x - pred)/rm1,  sample = pred*sqrt(abn) + sqrt(1 - abn)*eps.
-// The model variance does not enter; mean_out rows are model_ld elements apart.
-__device__ __forceinline__ void ddim_rev_elem(const float* c, int clip, float sa, float sb, float m, float xv, float& s, float& p) {
-    float pred = c[0] * xv + c[1] * m;
-    if (clip) pred = fminf(fmaxf(pred, -1.f), 1.f);
-    const float eps = (c[6] * xv - pred) / c[7];
-    p = pred;
-    s = pred * sa + sb * eps;
-}
-template <bool VEC>
-__global__ void ddim_reverse_kernel(const float* __restrict__ mean_out, int64_t model_ld, const float* __restrict__ x,
-                                    const float* __restrict__ coef, int clip, float* __restrict__ sample,
-                                    float* __restrict__ pred_out, int64_t n) {
-    const int b = blockIdx.y;
-    float c[SS_NCOEF];
-#pragma unroll
-    for (int i = 0; i < SS_NCOEF; ++i) c[i] = coef[b * SS_NCOEF + i];
-    const float sa = sqrtf(c[13]), sb = sqrtf(1.f - c[13]);
-    const float* mr = mean_out + (int64_t)b * model_ld;
-    const int64_t base = (int64_t)b * n;
-    if (VEC) {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
-            const f32x4 m = load4(mr + 4 * i), xv = load4(x + base + 4 * i);
-            f32x4 s, p;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { float sj, pj; ddim_rev_elem(c, clip, sa, sb, m[j], xv[j], sj, pj); s[j] = sj; p[j] = pj; }
-            store4(sample + base + 4 * i, s);
-            if (pred_out) store4(pred_out + base + 4 * i, p);
-        }
-    } else {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-            float s, p;
-            ddim_rev_elem(c, clip, sa, sb, mr[i], x[base + i], s, p);
-            sample[base + i] = s;
-            if (pred_out) pred_out[base + i] = p;
-        }
-    }
-}
-
-extern "C" int vaw_ddim_reverse_step(const float* mean_out, int64_t model_ld, const float* x, const float* coef, int clip_denoised,
-                                     float* sample, float* pred_xstart, int B, int64_t per_sample, vaw_stream stream) {
-    VAW_CHECK_ARG(B > 0 && per_sample > 0, "ddim_reverse_step: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
-    VAW_CHECK_ARG(mean_out && x && coef && sample, "ddim_reverse_step: null pointer");
-    VAW_CHECK_ARG(model_ld >= per_sample, "ddim_reverse_step: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
-    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(mean_out) && al16(x) && al16(sample) && al16(pred_xstart);
-    int gx = stream_grid(vec ? per_sample / 4 : per_sample, 256);
-    dim3 grid(gx > 64 ? 64 : gx, B);
-    if (vec)
-        ddim_reverse_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(mean_out, model_ld, x, coef, clip_denoised, sample,
-                                                                         pred_xstart, per_sample);
-    else
-        ddim_reverse_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(mean_out, model_ld, x, coef, clip_denoised, sample,
-                                                                          pred_xstart, per_sample);
-    VAW_CHECK_LAUNCH("ddim_reverse_step");
-    return VAW_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
-// Sampler: classifier-free guidance fused into the reverse step, the combination alone, and the uint8 image finish.
-// ---------------------------------------------------------------------------------------------
-// u + s * (c - u): subtraction, product and sum each rounded on its own (this file is built with -ffp-contract=off), which
-// is what the three tensor operations of IntervalCFG.forward give.
-__device__ __forceinline__ float cfg_mix(float c, float u, float s) { return u + s * (c - u); }
-
+// One reverse-process step (sampling side): classifier-free guidance + p_mean_variance + the sampler's update, fused.
+//   kind 0: no sample (p_mean_variance only)
+//        1: ancestral p_sample:  sample = mean + (t != 0) * exp(lv/2) * noise
+//        2: ddim_sample:         eps = (ra*x - pred)/rm1, sigma = (eta*s1)*s2,
+//                                sample = pred*sqrt_abp + sqrt(1 - abp - sigma^2)*eps + (t != 0) * sigma * noise
+//        3: ddim_reverse_sample (:653-689, eta = 0, the DDIM ODE run towards noise): sample = pred*sqrt(abn) + sqrt(1 - abn)*eps;
+//           no noise, and the model variance does not enter
 // The model output of the stacked [2N, ...] guided call is read in place: row b of each of the four quarters (conditional /
 // unconditional half of the batch, mean / variance channels) starts model_ld floats after row b-1.  mu == NULL: no guidance,
-// the plain step over split halves.  Everything else is [B, n] contiguous.  One grid row per sample, as sample_step_kernel.
-template <bool VEC>
+// the plain step over split halves.  Everything else is [B, n] contiguous; outputs may be NULL.  One grid row per sample.
+// ---------------------------------------------------------------------------------------------
+// what a launch derives from one coefficient row before its element loop
+struct SsRow { float c[SS_NCOEF]; float mask, sigma, ddim_c, rev_a, rev_b; };
+__device__ __forceinline__ void ss_row(const float* __restrict__ coef, int b, float eta, SsRow& r) {
+#pragma unroll
+    for (int i = 0; i < SS_NCOEF; ++i) r.c[i] = coef[(int64_t)b * SS_NCOEF + i];
+    r.mask = r.c[11] != 0.f ? 0.f : 1.f;
+    r.sigma = (eta * r.c[9]) * r.c[12];
+    r.ddim_c = sqrtf(1.f - r.c[10] - r.sigma * r.sigma);
+    r.rev_a = sqrtf(r.c[13]);
+    r.rev_b = sqrtf(1.f - r.c[13]);
+}
+struct SsOut { float sample, pred, mean, lv; };
+// nz: the noise of the element (read by kinds 1 and 2 only)
+__device__ __forceinline__ SsOut ss_elem(const SsRow& r, int kind, int mean_mode, int var_mode, int clip, float m, float v,
+                                         float xv, float nz) {
+    const float* c = r.c;
+    const Pmv p = p_mean_variance(c, mean_mode, var_mode, clip, m, v, xv);
+    SsOut o = {0.f, p.pred, p.mean, p.lv};
+    if (kind == 1) {
+        o.sample = p.mean + (r.mask * expf(0.5f * p.lv)) * nz;
+    } else if (kind >= 2) {
+        const float eps = (c[6] * xv - p.pred) / c[7];
+        if (kind == 2) {
+            const float mp = p.pred * c[8] + r.ddim_c * eps;
+            o.sample = mp + (r.mask * r.sigma) * nz;
+        } else {
+            o.sample = p.pred * r.rev_a + r.rev_b * eps;
+        }
+    }
+    return o;
+}
+
+template <int W>
 __global__ void guided_sample_step_kernel(const float* __restrict__ mc, const float* __restrict__ mu, const float* __restrict__ vc,
                                           const float* __restrict__ vu, int64_t model_ld, float gs, const float* __restrict__ x,
                                           const float* __restrict__ noise, const float* __restrict__ coef, int kind,
@@ -572,40 +464,30 @@ __global__ void guided_sample_step_kernel(const float* __restrict__ mc, const fl
     ss_row(coef, b, eta, r);
     const int64_t base = (int64_t)b * n, mbase = (int64_t)b * model_ld;
     const bool guided = mu != nullptr, var = var_mode != 0;
-    if (VEC) {
-        const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
-            f32x4 m = load4(mc + mbase + 4 * i), v = var ? load4(vc + mbase + 4 * i) : z4;
-            const f32x4 xv = load4(x + base + 4 * i), nz = kind ? load4(noise + base + 4 * i) : z4;
-            if (guided) {
-                const f32x4 m0 = load4(mu + mbase + 4 * i), v0 = var ? load4(vu + mbase + 4 * i) : z4;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / W; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = base + W * i, mo = mbase + W * i;
+        float m[W], v[W] = {}, xv[W], nz[W] = {};
+        loadw<W>(mc + mo, m);
+        if (var) loadw<W>(vc + mo, v);
+        loadw<W>(x + o, xv);
+        if (noise) loadw<W>(noise + o, nz);
+        if (guided) {
+            float m0[W], v0[W] = {};
+            loadw<W>(mu + mo, m0);
+            if (var) loadw<W>(vu + mo, v0);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { m[j] = cfg_mix(m[j], m0[j], gs); if (var) v[j] = cfg_mix(v[j], v0[j], gs); }
-            }
-            f32x4 s, p, mo, lo;
+            for (int j = 0; j < W; ++j) { m[j] = cfg_mix(m[j], m0[j], gs); if (var) v[j] = cfg_mix(v[j], v0[j], gs); }
+        }
+        float s[W], p[W], mn[W], lv[W];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const SsOut o = ss_elem(r, kind, mean_mode, var_mode, clip, m[j], v[j], xv[j], nz[j]);
-                s[j] = o.sample; p[j] = o.pred; mo[j] = o.mean; lo[j] = o.lv;
-            }
-            if (pred_out) store4(pred_out + base + 4 * i, p);
-            if (mean_o) store4(mean_o + base + 4 * i, mo);
-            if (logvar_o) store4(logvar_o + base + 4 * i, lo);
-            if (kind) store4(sample + base + 4 * i, s);
+        for (int j = 0; j < W; ++j) {
+            const SsOut e = ss_elem(r, kind, mean_mode, var_mode, clip, m[j], v[j], xv[j], nz[j]);
+            s[j] = e.sample; p[j] = e.pred; mn[j] = e.mean; lv[j] = e.lv;
         }
-    } else {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-            float m = mc[mbase + i], v = var ? vc[mbase + i] : 0.f;
-            if (guided) {
-                m = cfg_mix(m, mu[mbase + i], gs);
-                if (var) v = cfg_mix(v, vu[mbase + i], gs);
-            }
-            const SsOut o = ss_elem(r, kind, mean_mode, var_mode, clip, m, v, x[base + i], kind ? noise[base + i] : 0.f);
-            if (pred_out) pred_out[base + i] = o.pred;
-            if (mean_o) mean_o[base + i] = o.mean;
-            if (logvar_o) logvar_o[base + i] = o.lv;
-            if (kind) sample[base + i] = o.sample;
-        }
+        if (pred_out) storew<W>(pred_out + o, p);
+        if (mean_o) storew<W>(mean_o + o, mn);
+        if (logvar_o) storew<W>(logvar_o + o, lv);
+        if (kind) storew<W>(sample + o, s);
     }
 }
 
@@ -615,47 +497,37 @@ extern "C" int vaw_guided_sample_step(int kind, const float* mean_cond, const fl
                                       float eta, float* sample, float* pred_xstart, float* mean, float* log_variance, int B,
                                       int64_t per_sample, vaw_stream stream) {
     VAW_CHECK_ARG(B > 0 && per_sample > 0, "guided_sample_step: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
-    VAW_CHECK_ARG(mean_cond && x && coef && kind >= 0 && kind <= 2, "guided_sample_step: null pointer or bad kind %d", kind);
+    VAW_CHECK_ARG(mean_cond && x && coef && kind >= 0 && kind <= 3, "guided_sample_step: null pointer or bad kind %d", kind);
     VAW_CHECK_ARG(model_ld >= per_sample, "guided_sample_step: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
+    VAW_CHECK_ARG(kind != 3 || (!noise && !var_cond && !var_uncond && var_mode == 0 && !mean && !log_variance),
+                  "guided_sample_step: kind 3 takes no noise and no variance (var_mode 0) and writes sample and pred_xstart only");
     VAW_CHECK_ARG((mean_mode == 0 || mean_mode == 1) && var_mode >= 0 && var_mode <= 2 && (var_mode == 0 || var_cond) &&
                       (var_mode == 0 || !mean_uncond || var_uncond),
                   "guided_sample_step: bad modes (learned variance needs var_cond, and var_uncond when guided)");
-    VAW_CHECK_ARG(kind == 0 || (sample && noise), "guided_sample_step: kind 1/2 need noise and sample");
+    VAW_CHECK_ARG(kind == 0 || (sample && (noise || kind == 3)), "guided_sample_step: kind 1/2 need noise and sample, kind 3 sample (null pointer)");
+    if (kind == 0) noise = nullptr;
     if (var_mode == 0) var_cond = var_uncond = nullptr;
     if (!mean_uncond) var_uncond = nullptr;
-    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(mean_cond) && al16(mean_uncond) && al16(var_cond) &&
-                     al16(var_uncond) && al16(x) && al16(noise) && al16(sample) && al16(pred_xstart) && al16(mean) &&
-                     al16(log_variance);
-    int gx = stream_grid(vec ? per_sample / 4 : per_sample, 256);
-    dim3 grid(gx > 64 ? 64 : gx, B);
-    if (vec)
-        guided_sample_step_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(
-            mean_cond, mean_uncond, var_cond, var_uncond, model_ld, guidance_scale, x, noise, coef, kind, mean_mode, var_mode,
-            clip_denoised, eta, sample, pred_xstart, mean, log_variance, per_sample);
-    else
-        guided_sample_step_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(
-            mean_cond, mean_uncond, var_cond, var_uncond, model_ld, guidance_scale, x, noise, coef, kind, mean_mode, var_mode,
-            clip_denoised, eta, sample, pred_xstart, mean, log_variance, per_sample);
+    const bool vec = vec4_ok(per_sample, model_ld, {mean_cond, mean_uncond, var_cond, var_uncond, x, noise, sample, pred_xstart, mean,
+                                                    log_variance});
+    VAW_LAUNCH_W(guided_sample_step_kernel, vec, row_grid(vec ? per_sample / 4 : per_sample, B), 256, stream, mean_cond, mean_uncond,
+                 var_cond, var_uncond, model_ld, guidance_scale, x, noise, coef, kind, mean_mode, var_mode, clip_denoised, eta, sample,
+                 pred_xstart, mean, log_variance, per_sample);
     VAW_CHECK_LAUNCH("guided_sample_step");
     return VAW_OK;
 }
 
-template <bool VEC>
+template <int W>
 __global__ void cfg_combine_kernel(const float* __restrict__ cond, const float* __restrict__ uncond, int64_t model_ld, float gs,
                                    float* __restrict__ out, int64_t n) {
-    const int b = blockIdx.y;
-    const int64_t base = (int64_t)b * n, mbase = (int64_t)b * model_ld;
-    if (VEC) {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
-            const f32x4 c = load4(cond + mbase + 4 * i), u = load4(uncond + mbase + 4 * i);
-            f32x4 o;
+    const int64_t base = (int64_t)blockIdx.y * n, mbase = (int64_t)blockIdx.y * model_ld;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / W; i += (int64_t)gridDim.x * blockDim.x) {
+        float c[W], u[W];
+        loadw<W>(cond + mbase + W * i, c);
+        loadw<W>(uncond + mbase + W * i, u);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = cfg_mix(c[j], u[j], gs);
-            store4(out + base + 4 * i, o);
-        }
-    } else {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-            out[base + i] = cfg_mix(cond[mbase + i], uncond[mbase + i], gs);
+        for (int j = 0; j < W; ++j) c[j] = cfg_mix(c[j], u[j], gs);
+        storew<W>(out + base + W * i, c);
     }
 }
 
@@ -664,13 +536,9 @@ extern "C" int vaw_cfg_combine(const float* cond, const float* uncond, int64_t m
     VAW_CHECK_ARG(B > 0 && per_sample > 0, "cfg_combine: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
     VAW_CHECK_ARG(cond && uncond && out, "cfg_combine: null pointer");
     VAW_CHECK_ARG(model_ld >= per_sample, "cfg_combine: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
-    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(cond) && al16(uncond) && al16(out);
-    int gx = stream_grid(vec ? per_sample / 4 : per_sample, 256);
-    dim3 grid(gx > 64 ? 64 : gx, B);
-    if (vec)
-        cfg_combine_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(cond, uncond, model_ld, guidance_scale, out, per_sample);
-    else
-        cfg_combine_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(cond, uncond, model_ld, guidance_scale, out, per_sample);
+    const bool vec = vec4_ok(per_sample, model_ld, {cond, uncond, out});
+    VAW_LAUNCH_W(cfg_combine_kernel, vec, row_grid(vec ? per_sample / 4 : per_sample, B), 256, stream, cond, uncond, model_ld,
+                 guidance_scale, out, per_sample);
     VAW_CHECK_LAUNCH("cfg_combine");
     return VAW_OK;
 }
@@ -679,16 +547,6 @@ extern "C" int vaw_cfg_combine(const float* cond, const float* uncond, int64_t m
 // rounded), clamped to [0, 255], truncated toward zero.  fmax(NaN, 0) is 0, so NaN writes 0.
 __device__ __forceinline__ unsigned quant_u8(float x) { return (unsigned)(int)fminf(fmaxf((x + 1.f) * 127.5f, 0.f), 255.f); }
 __device__ __forceinline__ unsigned quant_u8(double x) { return (unsigned)(int)fmin(fmax((x + 1.0) * 127.5, 0.0), 255.0); }
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void load_px4(const float* p, float* v) {
-    const f32x4 t = load4(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-}
-__device__ __forceinline__ void load_px4(const double* p, double* v) {
-    const f64x2 a = *reinterpret_cast<const f64x2*>(p), b = *reinterpret_cast<const f64x2*>(p + 2);
-    v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
-}
 
 // Aligned form (HW % 4 == 0, src 16-byte and dst 4-byte aligned, C <= 4): a thread takes 4 neighbouring pixels of one image,
 // reads 16 (f32) or 32 (f64) contiguous bytes of each channel plane -- a wave reads 1 or 2 KiB of a plane per instruction --
@@ -704,7 +562,7 @@ __global__ void finish_images_vec_kernel(const T* __restrict__ src, uint32_t* __
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             T v[4];
-            load_px4(src + (b * C + c) * HW + 4 * g, v);
+            loadw<4>(src + (b * C + c) * HW + 4 * g, v);
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
                 const int j = px * C + c;

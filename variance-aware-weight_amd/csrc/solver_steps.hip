@@ -3,37 +3,9 @@
 // grid (samplers.py) and are read by row index.  Every operation is rounded on its own, in the order of the tensor
 // composition these kernels replace (this file is built with -ffp-contract=off; divisions and square roots are IEEE).
 // The model output of a guided call is the stacked [2N, ...] tensor read in place: rows model_ld floats apart.
+// Each kernel has one loop body over per_sample / W items of W elements, W = 4 or 1 (common.h: loadw / storew, vec4_ok,
+// VAW_LAUNCH_W, row_grid); the per-element work is the same inlined function at either width, so the two give the same bits.
 #include "common.h"
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-// One grid row per sample, at most 64 blocks of 256 threads along it (grid-stride beyond): B x 64 blocks cover the chip's
-// 256 CUs from B = 4 on, and the FID batch (64 x 3072 elements, 768 four-element items a row) is 192 blocks.
-static inline dim3 row_grid(int64_t items, int B) {
-    int64_t g = (items + 255) / 256;
-    return dim3((unsigned)(g < 1 ? 1 : (g > 64 ? 64 : g)), (unsigned)B);
-}
-
-__device__ __forceinline__ float cfg_mix(float c, float u, float s) { return u + s * (c - u); }
-
-__device__ __forceinline__ void load4d(const double* p, double* v) {
-    const f64x2 a = *reinterpret_cast<const f64x2*>(p), b = *reinterpret_cast<const f64x2*>(p + 2);
-    v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
-}
-__device__ __forceinline__ void store4d(double* p, const double* v) {
-    const f64x2 a = {v[0], v[1]}, b = {v[2], v[3]};
-    *reinterpret_cast<f64x2*>(p) = a;
-    *reinterpret_cast<f64x2*>(p + 2) = b;
-}
-__device__ __forceinline__ void load4f(const float* p, float* v) {
-    const f32x4 t = load4(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-}
-__device__ __forceinline__ void store4f(float* p, const float* v) {
-    const f32x4 t = {v[0], v[1], v[2], v[3]};
-    store4(p, t);
-}
 
 // ---------------------------------------------------------------------------------------------
 // EDM.  Table row (VAW_EDM_COLS doubles) of step i:
@@ -62,39 +34,28 @@ __device__ __forceinline__ double edm_slope(const EdmEval& e, int pred, double x
     return e.k1 * x - e.k2 * (double)den;
 }
 
-template <bool VEC>
+template <int W>
 __global__ void edm_input_kernel(const double* __restrict__ x, const double* __restrict__ noise, const double* __restrict__ coef,
                                  double* __restrict__ x_hat, float* __restrict__ min, float* __restrict__ min2, int64_t n) {
     const double A = coef[0], nc = coef[1];
     const EdmEval e = edm_eval(coef + 2);
     const int64_t base = (int64_t)blockIdx.y * n;
-    if (VEC) {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t o = base + 4 * i;
-            double xv[4], nz[4];
-            float mi[4];
-            load4d(x + o, xv);
-            if (noise) load4d(noise + o, nz);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / W; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = base + W * i;
+        double xv[W], nz[W];
+        float mi[W];
+        loadw<W>(x + o, xv);
+        if (noise) loadw<W>(noise + o, nz);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                double h = A * xv[j];
-                if (noise) h = h + nc * nz[j];
-                xv[j] = h;
-                mi[j] = edm_model_in(e, h);
-            }
-            store4d(x_hat + o, xv);
-            store4f(min + o, mi);
-            if (min2) store4f(min2 + o, mi);
+        for (int j = 0; j < W; ++j) {
+            double h = A * xv[j];
+            if (noise) h = h + nc * nz[j];
+            xv[j] = h;
+            mi[j] = edm_model_in(e, h);
         }
-    } else {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-            double h = A * x[base + i];
-            if (noise) h = h + nc * noise[base + i];
-            x_hat[base + i] = h;
-            const float m = edm_model_in(e, h);
-            min[base + i] = m;
-            if (min2) min2[base + i] = m;
-        }
+        storew<W>(x_hat + o, xv);
+        storew<W>(min + o, mi);
+        if (min2) storew<W>(min2 + o, mi);
     }
 }
 
@@ -105,13 +66,9 @@ extern "C" int vaw_edm_input(const double* x, const double* noise, const double*
     VAW_CHECK_ARG(row >= 0 && row < rows, "edm_input: row %d outside the table of %d rows", row, rows);
     VAW_CHECK_ARG(((uintptr_t)x & 7) == 0 && ((uintptr_t)noise & 7) == 0 && ((uintptr_t)x_hat & 7) == 0 && ((uintptr_t)coef & 7) == 0,
                   "edm_input: float64 pointer not aligned to 8 bytes");
-    const bool vec = per_sample % 4 == 0 && al16(x) && al16(noise) && al16(x_hat) && al16(model_in) && al16(model_in_dup);
-    const dim3 grid = row_grid(vec ? per_sample / 4 : per_sample, B);
-    const double* r = coef + (int64_t)row * VAW_EDM_COLS;
-    if (vec)
-        edm_input_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(x, noise, r, x_hat, model_in, model_in_dup, per_sample);
-    else
-        edm_input_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(x, noise, r, x_hat, model_in, model_in_dup, per_sample);
+    const bool vec = vec4_ok(per_sample, 0, {x, noise, x_hat, model_in, model_in_dup});
+    VAW_LAUNCH_W(edm_input_kernel, vec, row_grid(vec ? per_sample / 4 : per_sample, B), 256, stream, x, noise,
+                 coef + (int64_t)row * VAW_EDM_COLS, x_hat, model_in, model_in_dup, per_sample);
     VAW_CHECK_LAUNCH("edm_input");
     return VAW_OK;
 }
@@ -148,49 +105,32 @@ __device__ __forceinline__ void edm_step_elem(int kind, int pred, const EdmEval&
     mi = edm_model_in(mid, xh + ah * d);
 }
 
-template <bool VEC>
+template <int W>
 __global__ void edm_step_kernel(const EdmStepArgs a) {
     const double* r = a.coef;
     const EdmEval hat = edm_eval(r + 2), mid = edm_eval(r + 14);
     const double h = r[10], ah = r[11], w1 = r[12], w2 = r[13];
     const int kind = a.kind, pred = a.pred;
     const int64_t n = a.n, base = (int64_t)blockIdx.y * n, mbase = (int64_t)blockIdx.y * a.ld;
-    if (VEC) {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t o = base + 4 * i;
-            double xh[4], dc[4], xo[4];
-            float c[4], u[4], mi[4];
-            load4d(a.x_hat + o, xh);
-            load4f(a.cond + mbase + 4 * i, c);
-            if (a.uncond) load4f(a.uncond + mbase + 4 * i, u);
-            if (kind == 2) load4d(a.d_cur + o, dc);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / W; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = base + W * i;
+        double xh[W], dc[W], xo[W];
+        float c[W], u[W], mi[W];
+        loadw<W>(a.x_hat + o, xh);
+        loadw<W>(a.cond + mbase + W * i, c);
+        if (a.uncond) loadw<W>(a.uncond + mbase + W * i, u);
+        if (kind == 2) loadw<W>(a.d_cur + o, dc);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float m = a.uncond ? cfg_mix(c[j], u[j], a.gs) : c[j];
-                edm_step_elem(kind, pred, hat, mid, h, ah, w1, w2, xh[j], m, dc[j], xo[j], mi[j]);
-            }
-            if (kind == 1) {
-                store4d(a.d_cur + o, dc);
-                store4f(a.min + o, mi);
-                if (a.min2) store4f(a.min2 + o, mi);
-            } else {
-                store4d(a.x_out + o, xo);
-            }
+        for (int j = 0; j < W; ++j) {
+            const float m = a.uncond ? cfg_mix(c[j], u[j], a.gs) : c[j];
+            edm_step_elem(kind, pred, hat, mid, h, ah, w1, w2, xh[j], m, dc[j], xo[j], mi[j]);
         }
-    } else {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-            float m = a.cond[mbase + i];
-            if (a.uncond) m = cfg_mix(m, a.uncond[mbase + i], a.gs);
-            double dc = kind == 2 ? a.d_cur[base + i] : 0.0, xo = 0.0;
-            float mi = 0.f;
-            edm_step_elem(kind, pred, hat, mid, h, ah, w1, w2, a.x_hat[base + i], m, dc, xo, mi);
-            if (kind == 1) {
-                a.d_cur[base + i] = dc;
-                a.min[base + i] = mi;
-                if (a.min2) a.min2[base + i] = mi;
-            } else {
-                a.x_out[base + i] = xo;
-            }
+        if (kind == 1) {
+            storew<W>(a.d_cur + o, dc);
+            storew<W>(a.min + o, mi);
+            if (a.min2) storew<W>(a.min2 + o, mi);
+        } else {
+            storew<W>(a.x_out + o, xo);
         }
     }
 }
@@ -210,13 +150,10 @@ extern "C" int vaw_edm_step(int kind, int pred_type, const float* cond, const fl
     if (kind == 0) d_cur = nullptr;
     if (kind == 1) x_out = nullptr;
     else model_in = model_in_dup = nullptr;
-    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(cond) && al16(uncond) && al16(x_hat) && al16(d_cur) &&
-                     al16(x_out) && al16(model_in) && al16(model_in_dup);
-    const dim3 grid = row_grid(vec ? per_sample / 4 : per_sample, B);
+    const bool vec = vec4_ok(per_sample, model_ld, {cond, uncond, x_hat, d_cur, x_out, model_in, model_in_dup});
     const EdmStepArgs a = {cond, uncond, model_ld, guidance_scale, x_hat, coef + (int64_t)row * VAW_EDM_COLS, d_cur, x_out,
                            model_in, model_in_dup, per_sample, kind, pred_type};
-    if (vec) edm_step_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    else edm_step_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    VAW_LAUNCH_W(edm_step_kernel, vec, row_grid(vec ? per_sample / 4 : per_sample, B), 256, stream, a);
     VAW_CHECK_LAUNCH("edm_step");
     return VAW_OK;
 }
@@ -289,51 +226,35 @@ __device__ __forceinline__ float flow_step_elem(const FlowStepArgs& a, const Flo
     return y + kick;
 }
 
-template <bool VEC>
+template <int W>
 __global__ void flow_step_kernel(const FlowStepArgs a) {
     const FlowRow e0 = flow_row(a.r0), e1 = flow_row(a.r1);
     const float sg2 = a.r0[9], dt = a.r0[10], sdt = a.r0[11], hdt = a.r0[12];
     const int64_t n = a.n, base = (int64_t)blockIdx.y * n, mbase = (int64_t)blockIdx.y * a.ld;
     const bool corr = a.kind == 2, pred = a.kind == 1;
-    if (VEC) {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / 4; i += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t o = base + 4 * i;
-            float c[4], u[4], x[4], nz[4] = {0.f, 0.f, 0.f, 0.f}, xp[4] = {0.f, 0.f, 0.f, 0.f}, f0[4], kk[4] = {0.f, 0.f, 0.f, 0.f}, y[4];
-            load4f(a.cond + mbase + 4 * i, c);
-            if (a.uncond) load4f(a.uncond + mbase + 4 * i, u);
-            load4f(a.x + o, x);
-            if (!corr && a.noise) load4f(a.noise + o, nz);
-            if (corr) {
-                load4f(a.x_pred + o, xp);
-                load4f(a.f0 + o, f0);
-                if (a.kick) load4f(a.kick + o, kk);
-            }
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / W; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = base + W * i;
+        float c[W], u[W], x[W], nz[W] = {}, xp[W] = {}, f0[W], kk[W] = {}, y[W];
+        loadw<W>(a.cond + mbase + W * i, c);
+        if (a.uncond) loadw<W>(a.uncond + mbase + W * i, u);
+        loadw<W>(a.x + o, x);
+        if (!corr && a.noise) loadw<W>(a.noise + o, nz);
+        if (corr) {
+            loadw<W>(a.x_pred + o, xp);
+            loadw<W>(a.f0 + o, f0);
+            if (a.kick) loadw<W>(a.kick + o, kk);
+        }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float m = a.uncond ? cfg_mix(c[j], u[j], a.gs) : c[j];
-                y[j] = flow_step_elem(a, e0, e1, sg2, dt, sdt, hdt, m, x[j], nz[j], xp[j], f0[j], kk[j]);
-            }
-            if (pred) {
-                store4f(a.f0 + o, f0);
-                if (a.kick) store4f(a.kick + o, kk);
-            }
-            store4f(a.x_out + o, y);
-            if (a.x_out2) store4f(a.x_out2 + o, y);
+        for (int j = 0; j < W; ++j) {
+            const float m = a.uncond ? cfg_mix(c[j], u[j], a.gs) : c[j];
+            y[j] = flow_step_elem(a, e0, e1, sg2, dt, sdt, hdt, m, x[j], nz[j], xp[j], f0[j], kk[j]);
         }
-    } else {
-        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-            float m = a.cond[mbase + i];
-            if (a.uncond) m = cfg_mix(m, a.uncond[mbase + i], a.gs);
-            float f0 = corr ? a.f0[base + i] : 0.f, kk = (corr && a.kick) ? a.kick[base + i] : 0.f;
-            const float y = flow_step_elem(a, e0, e1, sg2, dt, sdt, hdt, m, a.x[base + i], (!corr && a.noise) ? a.noise[base + i] : 0.f,
-                                           corr ? a.x_pred[base + i] : 0.f, f0, kk);
-            if (pred) {
-                a.f0[base + i] = f0;
-                if (a.kick) a.kick[base + i] = kk;
-            }
-            a.x_out[base + i] = y;
-            if (a.x_out2) a.x_out2[base + i] = y;
+        if (pred) {
+            storew<W>(a.f0 + o, f0);
+            if (a.kick) storew<W>(a.kick + o, kk);
         }
+        storew<W>(a.x_out + o, y);
+        if (a.x_out2) storew<W>(a.x_out2 + o, y);
     }
 }
 
@@ -355,13 +276,10 @@ extern "C" int vaw_flow_step(int kind, int sde, int mean_type, const float* cond
     if (kind == 0) f0 = kick = nullptr;
     if (kind == 2) noise = nullptr;
     else x_pred = nullptr;
-    const bool vec = per_sample % 4 == 0 && model_ld % 4 == 0 && al16(cond) && al16(uncond) && al16(x) && al16(noise) && al16(x_pred) &&
-                     al16(f0) && al16(kick) && al16(x_out) && al16(x_out_dup);
-    const dim3 grid = row_grid(vec ? per_sample / 4 : per_sample, B);
+    const bool vec = vec4_ok(per_sample, model_ld, {cond, uncond, x, noise, x_pred, f0, kick, x_out, x_out_dup});
     const FlowStepArgs a = {cond, uncond, model_ld, guidance_scale, x, noise, x_pred, coef + (int64_t)row0 * VAW_FLOW_COLS,
                             coef + (int64_t)row1 * VAW_FLOW_COLS, f0, kick, x_out, x_out_dup, per_sample, kind, sde, mean_type};
-    if (vec) flow_step_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    else flow_step_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    VAW_LAUNCH_W(flow_step_kernel, vec, row_grid(vec ? per_sample / 4 : per_sample, B), 256, stream, a);
     VAW_CHECK_LAUNCH("flow_step");
     return VAW_OK;
 }

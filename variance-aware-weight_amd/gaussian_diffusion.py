@@ -9,9 +9,12 @@ What runs where
   vaw_qsample_fwd x_t = sqrt(abar_t) x0 + sqrt(1-abar_t) eps, table gather fused        (12 B/element)
   vaw_wmse_fwd    target + (target-out)^2 + mean over CHW + per-sample weight, one pass  (12 B/element)
   vaw_wmse_bwd    d(out) in one pass                                                       (16 B/element)
+  vaw_vb_fwd/bwd  the variational-bound term of the learned-variance and KL objectives, one pass each
   vaw_bpd_terms   calc_bpd_loop's per-timestep tail: bound with clip, x0 MSE, eps MSE, one pass      (20 B/element)
-  vaw_prior_bpd / vaw_ddim_reverse_step   the prior KL of the bound; one step of the DDIM ODE towards noise
-  vaw_guided_sample_step   a reverse step under IntervalCFG: guidance combination + p_sample / ddim_sample, one pass  (32 B/element)
+  vaw_prior_bpd   the prior KL of the bound
+  vaw_guided_sample_step   the one reverse step: guidance combination (under IntervalCFG) + p_mean_variance + p_sample /
+                  ddim_sample / the DDIM step towards noise (kinds 0-3), one pass                    (32 B/element)
+The last four read the rows of ONE per-timestep table (_sample_table, [T, 16]) and share one per-element p_mean_variance.
 Only the selected target is computed (the reference evaluates all four, :823-830).
 """
 import enum
@@ -197,36 +200,16 @@ class GaussianDiffusion:
             else:
                 raise KeyError(mt)
             tb = {k: v.contiguous().to(device) for k, v in dict(a=a, s=s, w=w, ca=ca, cb=cb).items()}
-            tb["vb"] = self._vb_table().to(device)
+            tb["ss"] = self._sample_table().to(device)
             self._dev[key] = tb
         return tb
 
-    def _vb_table(self):
-        """[T, 8] f32 rows for vaw_vb_fwd: the float64 tables of q_posterior_mean_variance / p_mean_variance
-        (:254-276, :304-330, :386-392) cast to f32 exactly as _extract_into_tensor does."""
-        f = lambda arr: torch.from_numpy(np.asarray(arr, dtype=np.float64)).float()
-        T = self.num_timesteps
-        vt, mt = self.model_var_type, self.model_mean_type
-        if vt == ModelVarType.FIXED_LARGE:
-            lv_aux = f(np.log(np.append(self.posterior_variance[1], self.betas[1:])))
-        elif vt == ModelVarType.FIXED_SMALL:
-            lv_aux = f(self.posterior_log_variance_clipped)
-        else:
-            lv_aux = f(np.log(self.betas))
-        if mt == ModelMeanType.EPSILON:
-            pa, pb = f(self.sqrt_recip_alphas_cumprod), -f(self.sqrt_recipm1_alphas_cumprod)
-        else:                                   # START_X: pred = model output; PREVIOUS_X ignores pa/pb
-            pa, pb = torch.zeros(T), torch.ones(T)
-        t0 = torch.zeros(T)
-        t0[0] = 1.0
-        return torch.stack([f(self.posterior_mean_coef1), f(self.posterior_mean_coef2), f(self.posterior_log_variance_clipped),
-                            lv_aux, pa, pb, t0, torch.zeros(T)], dim=1).contiguous()
-
     # ---- sampling side (reference :278-384, :461-601, :603-790; no denoised_fn / cond_fn) ----------------------
     def _sample_table(self):
-        """[T, 16] f32 rows for vaw_sample_step, vaw_bpd_terms and vaw_ddim_reverse_step.  Every entry is the reference's
-        float64 table cast to f32 as _extract_into_tensor does; products of tables (ddim sigma) are formed in f32 in the
-        kernel, as the reference's tensor ops do.  Column 13 (alphas_cumprod_next) is read by the DDIM reverse step only."""
+        """The one per-timestep table, [T, 16] f32 rows for vaw_vb_fwd/bwd, vaw_bpd_terms and vaw_guided_sample_step (column
+        layout: csrc/elementwise.hip, above SS_NCOEF).  Every entry is the reference's float64 table (q_posterior_mean_variance /
+        p_mean_variance :254-276, :304-330, :386-392) cast to f32 as _extract_into_tensor does; products of tables (ddim
+        sigma) are formed in f32 in the kernel, as the reference's tensor ops do."""
         f = lambda arr: torch.from_numpy(np.asarray(arr, dtype=np.float64)).float()
         T = self.num_timesteps
         vt, mt = self.model_var_type, self.model_mean_type
@@ -287,10 +270,7 @@ class GaussianDiffusion:
                 out, stacked = model.combine(stacked), None
         else:
             out = model(x, self._scale_timesteps(t), **model_kwargs)
-        key = "ss"
-        tb = self._tables(x.device)
-        if key not in tb:
-            tb[key] = self._sample_table().to(x.device)
+        coef = self._tables(x.device)["ss"][t]
         mean_mode = 1 if mt == ModelMeanType.PREVIOUS_X else 0
         var_mode = {ModelVarType.LEARNED: 1, ModelVarType.LEARNED_RANGE: 2}.get(vt, 0)
         if stacked is None:
@@ -301,7 +281,7 @@ class GaussianDiffusion:
                 out, var_out = torch.split(out, C, dim=1)
             assert out.shape == x.shape
             if kind == 3:                                                  # ddim_reverse_sample: deterministic, no noise draw
-                return ops.ddim_reverse_step(out, x, tb[key][t], clip_denoised)
+                return ops.ddim_reverse_step(out, x, coef, clip_denoised)
         else:
             assert stacked.shape == (2 * B, C * 2 if learned else C, *x.shape[2:])
         noise = None
@@ -313,9 +293,9 @@ class GaussianDiffusion:
         if stacked is not None:
             cond, uncond = stacked[:B], stacked[B:]
             return ops.guided_sample_step(kind, cond[:, :C], uncond[:, :C], cond[:, C:] if learned else None,
-                                          uncond[:, C:] if learned else None, model.guidance_scale, x, noise, tb[key][t],
+                                          uncond[:, C:] if learned else None, model.guidance_scale, x, noise, coef,
                                           mean_mode, var_mode, clip_denoised, eta, want_all)
-        return ops.sample_step(kind, out, var_out, x, noise, tb[key][t], mean_mode, var_mode, clip_denoised, eta, want_all)
+        return ops.sample_step(kind, out, var_out, x, noise, coef, mean_mode, var_mode, clip_denoised, eta, want_all)
 
     def _model_halves(self, model, x, t, model_kwargs):
         """Model call of p_mean_variance (:304-314): (mean output, variance values or None), the halves as views."""
@@ -341,10 +321,7 @@ class GaussianDiffusion:
             raise NotImplementedError(mt)
 
     def _sample_rows(self, t):
-        tb = self._tables(t.device)
-        if "ss" not in tb:
-            tb["ss"] = self._sample_table().to(t.device)
-        return tb["ss"][t]
+        return self._tables(t.device)["ss"][t]
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         r = self._reverse_step(0, model, x, t, clip_denoised, denoised_fn, None, model_kwargs, want_all=True)
@@ -511,7 +488,7 @@ class GaussianDiffusion:
         self._refuse_unsupported_mean_type()
         mt, vt = self.model_mean_type, self.model_var_type
         var_mode = {ModelVarType.LEARNED: 1, ModelVarType.LEARNED_RANGE: 2}.get(vt, 0)
-        coef = self._tables(x_start.device)["vb"][t]
+        coef = self._tables(x_start.device)["ss"][t]
         return ops.vb_terms(mean_out, var_out, x_start, x_t, coef, 1 if mt == ModelMeanType.PREVIOUS_X else 0, var_mode, scale)
 
     def _scale_timesteps(self, t):

@@ -156,7 +156,7 @@ class _VbTerms(torch.autograd.Function):
         need_cuda(mean_out, x0, x_t, coef)
         _f32c(mean_out, x0, x_t, coef)
         B = x0.shape[0]
-        assert mean_out.shape == x0.shape == x_t.shape and coef.shape == (B, 8)
+        assert mean_out.shape == x0.shape == x_t.shape and coef.shape == (B, 16)
         if var_out is not None:
             need_cuda(var_out)
             _f32c(var_out)
@@ -198,78 +198,47 @@ def _step_outputs(kind, x, want_all):
     return res
 
 
-def sample_step(kind, mean_out, var_out, x, noise, coef, mean_mode, var_mode, clip_denoised, eta=0.0, want_all=False):
-    """One reverse-process step (vaw_sample_step): kind 0 = p_mean_variance only, 1 = p_sample, 2 = ddim_sample.
-    Returns {"sample", "pred_xstart"} (+ "mean", "log_variance" with want_all).  The two halves of a [B, 2C, H, W] model
-    output split along dim 1 are read in place (the unguided form of vaw_guided_sample_step: same per-element body)."""
-    need_cuda(mean_out, x, coef)
-    x = x.contiguous().float()
-    noise = None if noise is None else noise.contiguous().float()
-    coef = coef.contiguous()
-    B = x.shape[0]
-    n = x.numel() // max(B, 1)
-    assert mean_out.shape == x.shape and coef.shape == (B, 16) and coef.dtype == torch.float32
-    if var_out is not None:
-        mean_out, var_out, ld = _model_halves(mean_out, var_out, n)
-    else:
-        mean_out, ld = mean_out.contiguous().float(), n
-    res = _step_outputs(kind, x, want_all)
-    if ld == n:
-        check(L.lib().vaw_sample_step(kind, ptr(mean_out), ptr(var_out), ptr(x), ptr(noise), ptr(coef), int(mean_mode), int(var_mode),
-                                      1 if clip_denoised else 0, float(eta), ptr(res.get("sample")), ptr(res["pred_xstart"]),
-                                      ptr(res.get("mean")), ptr(res.get("log_variance")), B, n, stream_ptr()),
-              "vaw_sample_step")
-    else:
-        check(L.lib().vaw_guided_sample_step(kind, ptr(mean_out), None, ptr(var_out), None, ld, 1.0, ptr(x), ptr(noise), ptr(coef),
-                                             int(mean_mode), int(var_mode), 1 if clip_denoised else 0, float(eta),
-                                             ptr(res.get("sample")), ptr(res["pred_xstart"]), ptr(res.get("mean")),
-                                             ptr(res.get("log_variance")), B, n, stream_ptr()), "vaw_guided_sample_step")
-    return res
+def _rows_in_place(ts, n):
+    """The given [B, ...] tensors (None allowed) as float32 with one distance between row starts: (tensors, that distance).
+    A tensor whose rows are dense but further apart than their length n (a part of a [B, 2C, H, W] or stacked [2N, ...] model
+    output) is read in place; if any is laid out otherwise, or the distances differ, all are copied to contiguous."""
+    def view(t):
+        t = t if t.dtype == torch.float32 else t.float()
+        if t.shape[0] == 1 or t.is_contiguous():
+            return t.contiguous(), n
+        return (t, t.stride(0)) if t[0].is_contiguous() and t.stride(0) >= n else (t.contiguous(), n)
 
-
-def _dense_rows(t, n):
-    """f32 [B, ...] tensor -> (tensor, elements between row starts).  A tensor whose rows are dense but further apart
-    than their length (one half of a [B, 2C, H, W] model output split along dim 1) is read in place; anything else that
-    is not contiguous is copied."""
-    if t.dtype != torch.float32:
-        t = t.float()
-    if t.shape[0] == 1 or t.is_contiguous():
-        return t.contiguous(), n
-    if t[0].is_contiguous() and t.stride(0) >= n:
-        return t, t.stride(0)
-    return t.contiguous(), n
-
-
-def _model_halves(mean_out, var_out, n):
-    mean_out, ld = _dense_rows(mean_out, n)
-    if var_out is not None:
-        var_out, ldv = _dense_rows(var_out, n)
-        if ldv != ld:
-            mean_out, var_out, ld = mean_out.contiguous(), var_out.contiguous(), n
-    return mean_out, var_out, ld
-
-
-def _same_ld(ts, n):
-    """The given [B, ...] f32 tensors (None allowed) as in-place views sharing one row distance, or all as contiguous copies."""
-    rows = [None if t is None else _dense_rows(t, n) for t in ts]
+    rows = [None if t is None else view(t) for t in ts]
     lds = {r[1] for r in rows if r is not None}
     if len(lds) > 1:
-        return [None if t is None else t.float().contiguous() for t in ts], n
+        return [None if r is None else r[0].contiguous() for r in rows], n
     return [None if r is None else r[0] for r in rows], (lds.pop() if lds else n)
+
+
+def sample_step(kind, mean_out, var_out, x, noise, coef, mean_mode, var_mode, clip_denoised, eta=0.0, want_all=False):
+    """One reverse-process step without guidance: kind 0 = p_mean_variance only, 1 = p_sample, 2 = ddim_sample.
+    Returns {"sample", "pred_xstart"} (+ "mean", "log_variance" with want_all).  The two halves of a [B, 2C, H, W] model
+    output split along dim 1 are read in place."""
+    assert mean_out.shape == x.shape and coef.shape == (x.shape[0], 16) and coef.dtype == torch.float32
+    return guided_sample_step(kind, mean_out, None, var_out, None, 1.0, x, noise, coef, mean_mode, var_mode, clip_denoised, eta, want_all)
 
 
 def guided_sample_step(kind, mean_cond, mean_uncond, var_cond, var_uncond, guidance_scale, x, noise, coef, mean_mode, var_mode,
                        clip_denoised, eta=0.0, want_all=False):
     """One reverse-process step with classifier-free guidance fused in (vaw_guided_sample_step): per element
-    m = mean_uncond + guidance_scale * (mean_cond - mean_uncond), the variance values likewise, then the step of sample_step.
+    m = mean_uncond + guidance_scale * (mean_cond - mean_uncond), the variance values likewise, then p_mean_variance and the
+    update of `kind` (0 none, 1 p_sample, 2 ddim_sample, 3 the DDIM reverse step: no noise, no variance, no want_all).
     The four tensors are x-shaped views of the stacked [2N, 2C, H, W] model output and are read in place.  mean_uncond=None:
-    the unguided step.  Returns what sample_step returns, bitwise what the three torch ops followed by sample_step give."""
+    the unguided step.  Returns {"sample", "pred_xstart"} (+ "mean", "log_variance" with want_all), bitwise what the three
+    torch ops followed by the unguided step give."""
     need_cuda(mean_cond, mean_uncond, var_cond, var_uncond, x, noise, coef)
     x = x.contiguous().float()
     noise = None if noise is None else noise.contiguous().float()
     coef = coef.contiguous()
     B = x.shape[0]
     n = x.numel() // max(B, 1)
+    if kind == 3:
+        var_mode = 0
     if var_mode == 0:
         var_cond = var_uncond = None
     if mean_uncond is None:
@@ -281,8 +250,8 @@ def guided_sample_step(kind, mean_cond, mean_uncond, var_cond, var_uncond, guida
         raise L.VawError(f"guided_sample_step: coef {tuple(coef.shape)} {coef.dtype} is not f32 [{B}, 16]")
     if var_mode and (var_cond is None or (mean_uncond is not None and var_uncond is None)):
         raise L.VawError("guided_sample_step: a learned variance needs the variance values of every half")
-    (mean_cond, mean_uncond, var_cond, var_uncond), ld = _same_ld((mean_cond, mean_uncond, var_cond, var_uncond), n)
-    res = _step_outputs(kind, x, want_all)
+    (mean_cond, mean_uncond, var_cond, var_uncond), ld = _rows_in_place((mean_cond, mean_uncond, var_cond, var_uncond), n)
+    res = _step_outputs(kind, x, want_all and kind != 3)
     check(L.lib().vaw_guided_sample_step(kind, ptr(mean_cond), ptr(mean_uncond), ptr(var_cond), ptr(var_uncond), ld,
                                          float(guidance_scale), ptr(x), ptr(noise), ptr(coef), int(mean_mode), int(var_mode),
                                          1 if clip_denoised else 0, float(eta), ptr(res.get("sample")), ptr(res["pred_xstart"]),
@@ -299,7 +268,7 @@ def cfg_combine(cond, uncond, guidance_scale):
         raise L.VawError(f"cfg_combine: {tuple(cond.shape)} {cond.dtype} vs {tuple(uncond.shape)} {uncond.dtype}")
     B = cond.shape[0]
     n = cond.numel() // max(B, 1)
-    (cond, uncond), ld = _same_ld((cond, uncond), n)
+    (cond, uncond), ld = _rows_in_place((cond, uncond), n)
     out = torch.empty(cond.shape, device=cond.device, dtype=torch.float32)
     check(L.lib().vaw_cfg_combine(ptr(cond), ptr(uncond), ld, float(guidance_scale), ptr(out), B, n, stream_ptr()), "vaw_cfg_combine")
     return out
@@ -326,11 +295,10 @@ def _table(what, coef, dtype, cols, *rows):
             raise L.VawError(f"{what}: row {r} outside the table of {coef.shape[0]} rows")
 
 
-def _model_halves_in_place(what, cond, uncond, x):
-    for t in (cond, uncond):
+def _f32_parts(what, x, *ts):
+    for t in ts:
         if t is not None and (t.shape != x.shape or t.dtype != torch.float32):
             raise L.VawError(f"{what}: model output part {tuple(t.shape)} {t.dtype} is not float32 {tuple(x.shape)}")
-    return _same_ld((cond, uncond), x.numel() // max(x.shape[0], 1))
 
 
 def edm_input(x, noise, coef, row, x_hat, model_in, model_in_dup=None):
@@ -355,8 +323,9 @@ def edm_step(kind, pred_type, cond, uncond, guidance_scale, x_hat, d_cur, coef, 
     _dense("edm_step", torch.float64, x_hat.shape, x_hat, d_cur, x_out)
     _dense("edm_step", torch.float32, x_hat.shape, model_in, model_in_dup)
     _table("edm_step", coef, torch.float64, EDM_COLS, row)
-    (cond, uncond), ld = _model_halves_in_place("edm_step", cond, uncond, x_hat)
+    _f32_parts("edm_step", x_hat, cond, uncond)
     B = x_hat.shape[0]
+    (cond, uncond), ld = _rows_in_place((cond, uncond), x_hat.numel() // max(B, 1))
     check(L.lib().vaw_edm_step(int(kind), EDM_PRED[pred_type], ptr(cond), ptr(uncond), ld, float(guidance_scale), ptr(x_hat), ptr(d_cur),
                                ptr(coef), int(row), coef.shape[0], ptr(x_out), ptr(model_in), ptr(model_in_dup), B,
                                x_hat.numel() // max(B, 1), stream_ptr()), "vaw_edm_step")
@@ -369,8 +338,9 @@ def flow_step(kind, sde, mean_type, cond, uncond, guidance_scale, x, noise, x_pr
     need_cuda(cond, uncond, x, noise, x_pred, f0, kick, coef, x_out, x_out_dup)
     _dense("flow_step", torch.float32, x.shape, x, noise, x_pred, f0, kick, x_out, x_out_dup)
     _table("flow_step", coef, torch.float32, FLOW_COLS, row0, row1)
-    (cond, uncond), ld = _model_halves_in_place("flow_step", cond, uncond, x)
+    _f32_parts("flow_step", x, cond, uncond)
     B = x.shape[0]
+    (cond, uncond), ld = _rows_in_place((cond, uncond), x.numel() // max(B, 1))
     check(L.lib().vaw_flow_step(int(kind), 1 if sde else 0, FLOW_MEAN[mean_type], ptr(cond), ptr(uncond), ld, float(guidance_scale),
                                 ptr(x), ptr(noise), ptr(x_pred), ptr(f0), ptr(kick), ptr(coef), int(row0), int(row1), coef.shape[0],
                                 ptr(x_out), ptr(x_out_dup), B, x.numel() // max(B, 1), stream_ptr()), "vaw_flow_step")
@@ -408,7 +378,7 @@ def bpd_terms(mean_out, var_out, x0, x_t, noise, coef, mean_mode, var_mode, clip
                          f"coef {tuple(coef.shape)} do not agree")
     if var_out is not None and var_out.shape != x0.shape:
         raise L.VawError(f"bpd_terms: var_out shape {tuple(var_out.shape)} != {tuple(x0.shape)}")
-    mean_out, var_out, ld = _model_halves(mean_out, var_out, n)
+    (mean_out, var_out), ld = _rows_in_place((mean_out, var_out), n)
     if out is None:
         res = tuple(torch.empty(B, device=x0.device, dtype=torch.float32) for _ in range(3))
         ptrs, out_ld, group = [ptr(r) for r in res], 1, B
@@ -442,19 +412,10 @@ def prior_bpd(x0, sqrt_abar_last, log_one_minus_abar_last):
 
 
 def ddim_reverse_step(mean_out, x, coef, clip_denoised):
-    """One step of the DDIM ODE towards noise (vaw_ddim_reverse_step, eta = 0): {"sample", "pred_xstart"}."""
-    need_cuda(mean_out, x, coef)
-    x = x.contiguous().float()
-    coef = coef.contiguous()
-    B = x.shape[0]
-    n = x.numel() // max(B, 1)
-    if not (mean_out.shape == x.shape and coef.shape == (B, 16) and coef.dtype == torch.float32):
+    """One step of the DDIM ODE towards noise (kind 3 of vaw_guided_sample_step, eta = 0): {"sample", "pred_xstart"}."""
+    if not (mean_out.shape == x.shape and coef.shape == (x.shape[0], 16) and coef.dtype == torch.float32):
         raise L.VawError(f"ddim_reverse_step: shapes {tuple(mean_out.shape)} {tuple(x.shape)} coef {tuple(coef.shape)} do not agree")
-    mean_out, _, ld = _model_halves(mean_out, None, n)
-    res = {"sample": torch.empty_like(x), "pred_xstart": torch.empty_like(x)}
-    check(L.lib().vaw_ddim_reverse_step(ptr(mean_out), ld, ptr(x), ptr(coef), 1 if clip_denoised else 0, ptr(res["sample"]),
-                                        ptr(res["pred_xstart"]), B, n, stream_ptr()), "vaw_ddim_reverse_step")
-    return res
+    return guided_sample_step(3, mean_out, None, None, None, 1.0, x, None, coef, 0, 0, clip_denoised)
 
 
 # ---- dense -------------------------------------------------------------------------------------

@@ -241,6 +241,49 @@ int vaw_resampler_draw(const double* ring, const int64_t* seen, int T, int H, do
                        int64_t* out_t, float* out_w, double* p, vaw_stream stream);
 
 /* ---------------------------------------------------------------------------
+ * Evaluation metrics from activations  (evaluations/evaluator.py: ManifoldEstimator, DistanceBlock, Evaluator.compute_statistics)
+ * ------------------------------------------------------------------------- */
+
+/* out[i] = sum_k X[i][k]^2 in f32, X: f32 [n][D] row-major, any D >= 1 (rows need no alignment).  Fixed order: 64 partial sums,
+ * partial l = x[l]^2 + x[l+64]^2 + ... ascending, folded by the xor butterfly 32, 16, .. 1. */
+int vaw_row_sqnorms(const float* X, int64_t n, int D, float* out, vaw_stream stream);
+
+/* _batch_pairwise_distances :415-431 in f32 (the reference casts to fp16 first: a documented difference), never materialised:
+ *   d(i, j) = max((norm_u[i] - 2 * dot(U_i, V_j)) + norm_v[j], 0)
+ * U: f32 [nu][D], V: f32 [nv][D], norm_*: f32 row square norms (vaw_row_sqnorms).  dot is an f32 MFMA chain over k = 0 .. D-1 in
+ * order in one accumulator (K is never split), every operation outside it is rounded on its own, so d(i, j) has the same bits
+ * whatever launch computes it: results are independent of how a caller cuts U and V into calls.
+ *
+ * out[i][0 .. k1) = the k1 smallest d(i, j) over j, ascending (manifold_radii :249-282 takes columns of it).  1 <= k1 <= 16 and
+ * k1 <= nv, else VAW_ERR_INVALID.  ws: at least vaw_pairwise_workspace_bytes(nu, nv, k1) bytes (0 for sizes that are refused),
+ * which is nu * k1 * 4 bytes times twice the number of column ranges (at most 16) a row tile is cut into; no nu x nv buffer
+ * exists.  Partial lists are merged in a fixed order, no float atomics. */
+int64_t vaw_pairwise_workspace_bytes(int64_t nu, int64_t nv, int k1);
+int vaw_pairwise_ksmallest(const float* U, int64_t nu, const float* V, int64_t nv, int D, const float* norm_u, const float* norm_v,
+                           int k1, float* out, void* ws, int64_t ws_bytes, vaw_stream stream);
+
+/* out[i][0 .. k1) = the k1 smallest of the P * k1 values parts[i * row_stride + p * part_stride + q] (p < P, q < k1), ascending;
+ * +inf marks an empty slot.  The merge step of vaw_pairwise_ksmallest, exported for callers that cut V into several calls. */
+int vaw_ksmallest_merge(const float* parts, int64_t n, int P, int k1, int64_t part_stride, int64_t row_stride, float* out,
+                        vaw_stream stream);
+
+/* DistanceBlock.less_thans :403-412 for whole arrays, ORed into the flags (evaluate_pr :346-356 ORs its blocks the same way):
+ *   u_in[i][c] |= any_j d(i, j) <= radii_v[j][c]     u_in: uint8 [nu][Kv]
+ *   v_in[j][c] |= any_i d(i, j) <= radii_u[i][c]     v_in: uint8 [nv][Ku]
+ * radii_u: f32 [nu][Ku], radii_v: f32 [nv][Kv], 1 <= Ku, Kv <= 4.  The caller zeroes the flags before the first call; a flag
+ * byte only goes from 0 to 1 (a plain store of 1 by every block that finds a pair), so the result does not depend on any order. */
+int vaw_pairwise_within(const float* U, int64_t nu, const float* V, int64_t nv, int D, const float* norm_u, const float* norm_v,
+                        const float* radii_u, int Ku, const float* radii_v, int Kv, uint8_t* u_in, uint8_t* v_in, vaw_stream stream);
+
+/* np.mean(X, axis=0) and np.cov(X, rowvar=False) of Evaluator.compute_statistics :175-178 in f64 from f32 X [n][D] (widened
+ * exactly).  mu[c] = (sum_i X[i][c]) / n: 16 partial sums per column, partial p = rows p, p+16, ... ascending, added p ascending.
+ * sigma[a][b] = (sum_i (X[i][a] - mu[a]) * (X[i][b] - mu[b])) / (n - 1): two-pass and centred, one f64 fma chain over
+ * i = 0 .. n-1 ascending per element (f64 vector FMA), computed for a <= b and stored at both places: sigma [D][D] is written
+ * fully and is symmetric bit for bit.  n = 1 gives 0 / 0 = NaN as numpy does. */
+int vaw_col_mean_f64(const float* X, int64_t n, int D, double* mu, vaw_stream stream);
+int vaw_cov_f64(const float* X, int64_t n, int D, const double* mu, double* sigma, vaw_stream stream);
+
+/* ---------------------------------------------------------------------------
  * Dense layers  (nn.Linear / Conv2d(k=p,s=p) / Conv1d(k=1) in models/dit.py, models/unet.py;
  * cuBLAS in the reference).  One GEMM entry point, MFMA inside.
  * ------------------------------------------------------------------------- */

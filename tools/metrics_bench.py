@@ -1,0 +1,161 @@
+#!/usr/bin/env python3
+"""Times the evaluation metrics of vaw_amd.evaluator on synthetic activations.
+
+    python tools/metrics_bench.py [--sizes 10000 50000] [--out FILE.json]
+
+Activations are non-negative and of low rank plus noise, like pooled ReLU features: max(z P + off + 0.01 noise, 0) with rank 64,
+generated on the device from a seed; the sample set is drawn with z scaled by 0.8 and shifted by 0.5.  Per N it reports the median
+over the repeats (after one warm-up of the same shapes) of
+  * compute_prec_recall at D = 2048, device tensors in, two floats out (host clock around a call that ends in the read-back of the
+    flags), and of its three pairwise launches alone (device events): two k-smallest launches and one within-radius launch, with the
+    achieved f32 rate 2 N^2 D / t of each against the 157.3 TFLOP/s peak of the f32 matrix pipe;
+  * compute_statistics at D = 2048 and D = 2023 (host clock, the [D, D] float64 read-back included) and of its covariance kernel
+    alone (device events), with the f64 rate 2 N D^2 / t -- the FLOP of the full product, of which the kernel computes the upper
+    triangle;
+  * at N = 10000 only, the host baseline: the same arithmetic in numpy (float32 distances through the norm expansion in row blocks,
+    np.partition / comparisons; float64 np.mean / np.cov).  The reference's TensorFlow path cannot run without TensorFlow.
+One JSON object is printed (and written to --out).  It needs the GPU: there is no host path to time."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import vaw_amd  # noqa: E402
+from vaw_amd import evaluator as ev, ops  # noqa: E402
+
+PEAK_F32_TFLOPS = 157.3
+RANK = 64
+
+
+def features(n, d, seed, sample):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    proj = torch.randn(RANK, d, device="cuda", generator=g) / RANK ** 0.5
+    off = torch.rand(d, device="cuda", generator=g) + 0.5
+    g2 = torch.Generator(device="cuda").manual_seed(seed + 1 + int(sample))
+    z = torch.randn(n, RANK, device="cuda", generator=g2)
+    if sample:
+        z = 0.8 * z + 0.5
+    return torch.clamp_min(z @ proj + off + 0.01 * torch.randn(n, d, device="cuda", generator=g2), 0).contiguous()
+
+
+def host_clock(fn, warmup, repeats):
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    return times
+
+
+def device_clock(fn, warmup, repeats):
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e-3)
+    return times
+
+
+def summary(times):
+    return dict(median_s=statistics.median(times), min_s=min(times), max_s=max(times), repeats=len(times))
+
+
+def host_prec_recall(f1, f2, k=3, block=2000):
+    """float32 numpy restatement of compute_prec_recall (distances through the norm expansion, row blocks of `block`)."""
+    def dist(u, nu, v, nv):
+        return np.maximum(nu[:, None] - 2 * (u @ v.T) + nv[None, :], 0)
+
+    n1, n2 = (f1 * f1).sum(1), (f2 * f2).sum(1)
+
+    def radii(f, n):
+        out = np.empty(len(f), np.float32)
+        for i in range(0, len(f), block):
+            out[i:i + block] = np.partition(dist(f[i:i + block], n[i:i + block], f, n), k, axis=1)[:, k]
+        return out
+
+    r1, r2 = radii(f1, n1), radii(f2, n2)
+    in1, in2 = np.zeros(len(f1), bool), np.zeros(len(f2), bool)
+    for i in range(0, len(f1), block):
+        d = dist(f1[i:i + block], n1[i:i + block], f2, n2)
+        in1[i:i + block] = (d <= r2[None, :]).any(1)
+        in2 |= (d <= r1[i:i + block, None]).any(0)
+    return float(in2.mean()), float(in1.mean())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=int, nargs="+", default=[10000, 50000])
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--host-baseline-at", type=int, default=10000)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "metrics_bench needs the GPU: the metric kernels have no host path"
+    vaw_amd.lib()
+    result = dict(gpu=torch.cuda.get_device_name(0), date=time.strftime("%Y-%m-%d"), peak_f32_tflops=PEAK_F32_TFLOPS, sizes={})
+    for n in args.sizes:
+        reps = args.repeats if n <= 20000 else max(3, args.repeats // 2 + 1)
+        row = {}
+        ref, sample = features(n, 2048, 0, False), features(n, 2048, 0, True)
+        est = ev.ManifoldEstimator()
+        row["precision_recall"] = ev.compute_prec_recall(ref, sample)
+        row["compute_prec_recall"] = summary(host_clock(lambda: ev.compute_prec_recall(ref, sample), 1, reps))
+        n1, n2 = ops.row_sqnorms(ref), ops.row_sqnorms(sample)
+        r1 = torch.from_numpy(est.manifold_radii(ref)).cuda()
+        r2 = torch.from_numpy(est.manifold_radii(sample)).cuda()
+        u_in = torch.zeros(n, 1, device="cuda", dtype=torch.uint8)
+        v_in = torch.zeros(n, 1, device="cuda", dtype=torch.uint8)
+        flop = 2.0 * n * n * 2048
+        for name, fn in (("ksmallest_ref", lambda: ops.pairwise_ksmallest(ref, ref, 4, n1, n1)),
+                         ("ksmallest_sample", lambda: ops.pairwise_ksmallest(sample, sample, 4, n2, n2)),
+                         ("within", lambda: ops.pairwise_within(ref, sample, n1, n2, r1, r2, u_in, v_in))):
+            s = summary(device_clock(fn, 1, reps))
+            s["tflops_f32"] = flop / s["median_s"] * 1e-12
+            s["share_of_f32_peak"] = s["tflops_f32"] / PEAK_F32_TFLOPS
+            row[name] = s
+        for d in (2048, 2023):
+            x = ref if d == 2048 else features(n, d, 3, False)
+            row[f"compute_statistics_d{d}"] = summary(host_clock(lambda: ev.compute_statistics(x), 1, reps))
+            mu = ops.col_mean_f64(x)
+            row[f"col_mean_f64_d{d}"] = summary(device_clock(lambda: ops.col_mean_f64(x), 1, reps))
+            s = summary(device_clock(lambda: ops.cov_f64(x, mu), 1, reps))
+            s["tflops_f64_full_product"] = 2.0 * n * d * d / s["median_s"] * 1e-12
+            row[f"cov_f64_d{d}"] = s
+            if n == args.host_baseline_at:
+                xh = x.cpu().numpy()
+                t0 = time.perf_counter()
+                x64 = xh.astype(np.float64)
+                x64.mean(0), np.cov(x64, rowvar=False)
+                row[f"host_numpy_statistics_d{d}_s"] = time.perf_counter() - t0
+        if n == args.host_baseline_at:
+            f1, f2 = ref.cpu().numpy(), sample.cpu().numpy()
+            t0 = time.perf_counter()
+            row["host_numpy_precision_recall"] = host_prec_recall(f1, f2)
+            row["host_numpy_prec_recall_s"] = time.perf_counter() - t0
+            row["host_threads"] = torch.get_num_threads()
+        result["sizes"][str(n)] = row
+        del ref, sample
+        torch.cuda.empty_cache()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,5 +1,5 @@
 """Public names of vaw_amd."""
-from . import dist_util, gaussian_diffusion, ops, resample, respace, sampler, utils  # noqa: F401
+from . import dist_util, evaluator, gaussian_diffusion, ops, resample, respace, sampler, utils  # noqa: F401
 from ._lib import LIB_PATH, VawError, exported_symbols, lib  # noqa: F401
 from .dit import DiT, DiT_B, DiT_L, DiT_S, DiT_XL, DiT_models  # noqa: F401
 from .flat import FlatModule  # noqa: F401
@@ -16,3 +16,5 @@ from .sampler import IntervalCFG, Sampler, sync_ema_model  # noqa: F401
 from .resample import (DeviceLossSecondMomentResampler, LossSecondMomentResampler, UniformSampler, create_named_schedule_sampler)  # noqa: F401
 from .trainer import Trainer, ema, sample_from_latent  # noqa: F401
 from .utils import get_lr_lambda, load_checkpoint, save_checkpoint, set_random_seed, warmup_cosine_lr  # noqa: F401
+from .evaluator import (FIDStatistics, ManifoldEstimator, compute_prec_recall, compute_statistics,  # noqa: F401
+                        metrics_from_activations)

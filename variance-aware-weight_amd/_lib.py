@@ -177,6 +177,12 @@ _PROTOS = {
     "vaw_silu_bwd_cast": [_p, _p, _p, _p, _l, _p],
     "vaw_cast_colsum_plan": [_l, _l, _l, _l, _l, _l, _l, C.POINTER(CastColsumLaunch)],
     "vaw_cast_colsum_bf16": [_p, _l, _p, _l, _l, _l, _p, _f, _p],
+    "vaw_row_sqnorms": [_p, _l, _i, _p, _p],
+    "vaw_pairwise_ksmallest": [_p, _l, _p, _l, _i, _p, _p, _i, _p, _p, _l, _p],
+    "vaw_ksmallest_merge": [_p, _l, _i, _i, _l, _l, _p, _p],
+    "vaw_pairwise_within": [_p, _l, _p, _l, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p],
+    "vaw_col_mean_f64": [_p, _l, _i, _p, _p],
+    "vaw_cov_f64": [_p, _l, _i, _p, _p, _p],
 }
 
 _lib = None
@@ -221,6 +227,9 @@ def lib():
         L.vaw_fp8_quantize_batched_desc_bytes.restype = _l
         L.vaw_fp8_quantize_workspace_floats.argtypes = []
         L.vaw_fp8_quantize_workspace_floats.restype = _l
+        if hasattr(L, "vaw_pairwise_workspace_bytes"):
+            L.vaw_pairwise_workspace_bytes.argtypes = [_l, _l, _i]
+            L.vaw_pairwise_workspace_bytes.restype = _l
         L.vaw_sumsq_workspace_floats.argtypes = []
         L.vaw_sumsq_workspace_floats.restype = _l
         L.vaw_debug_force_rowwise_attention.argtypes = [_i]
@@ -249,7 +258,7 @@ def exported_symbols():
                                    "vaw_sumsq_workspace_floats", "vaw_groupnorm_workspace_floats", "vaw_wgrad_grouped_desc_bytes",
                                    "vaw_conv3x3_wgrad_small_workspace_floats", "vaw_row_bwd_workspace_floats",
                                    "vaw_fp8_quantize_workspace_floats", "vaw_p8_set_reserved_cus", "vaw_reduce_rows_batched_desc_bytes", "vaw_fp8_quantize_batched_desc_bytes",
-                                   "vaw_gemm_default_knobs", "vaw_dropout_bits_words"])
+                                   "vaw_gemm_default_knobs", "vaw_dropout_bits_words", "vaw_pairwise_workspace_bytes"])
 
 
 # VAW_STEP_FUSED (read once): 0 restores the step's unfused sequence of launches everywhere -- separate cast / column-sum

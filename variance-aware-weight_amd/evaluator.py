@@ -1,0 +1,217 @@
+"""FID statistics, Frechet distance and precision / recall from Inception activations: the part of the reference's
+evaluations/evaluator.py that follows `compute_activations`, with the reference's names and return types and no TensorFlow.
+
+The all-pairs distance work of `ManifoldEstimator` and the float64 mean / covariance of `compute_statistics` run as HIP kernels
+(csrc/metrics.hip); percentile clamping, the means of the flags and the matrix square root of the Frechet distance stay on the host
+in numpy / scipy as the reference has them.  Inputs are numpy arrays or torch tensors, on the CPU or on the device; they are
+uploaded once as float32 and a contiguous float32 device tensor is used in place.
+
+Deliberate difference: the reference computes distances in fp16 and falls back to f32 only when that overflows, so its radii and
+comparisons are quantised to fp16 (about 0.25 at typical pool-feature distances).  Here every distance is f32:
+max((|u|^2 - 2 u.v) + |v|^2, 0) with the dot product an ordered f32 fma chain.  Precision and recall can differ from a TensorFlow
+run in the third decimal.
+
+Not built: the Inception feature extractor and `compute_inception_score` (their weights are a download), and
+`ManifoldEstimator.evaluate` (realism scores)."""
+import warnings
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+class InvalidFIDException(Exception):
+    pass
+
+
+def _sqrtm(a):
+    from scipy import linalg          # lazy: only the Frechet distance needs scipy
+    try:
+        out = linalg.sqrtm(a, disp=False)
+    except TypeError:                 # a scipy without the keyword
+        out = linalg.sqrtm(a)
+    return out[0] if isinstance(out, tuple) else out
+
+
+class FIDStatistics:
+    def __init__(self, mu, sigma):
+        self.mu = mu
+        self.sigma = sigma
+
+    def frechet_distance(self, other, eps=1e-6):
+        """|mu1 - mu2|^2 + tr(s1) + tr(s2) - 2 tr(sqrtm(s1 s2)) in host float64; a non-finite square root is retried with eps
+        added to both diagonals (with a warning), a complex one is accepted when its diagonal is real to 1e-3."""
+        mu1, mu2 = np.atleast_1d(self.mu), np.atleast_1d(other.mu)
+        sigma1, sigma2 = np.atleast_2d(self.sigma), np.atleast_2d(other.sigma)
+        assert mu1.shape == mu2.shape, f"Training and test mean vectors have different lengths: {mu1.shape}, {mu2.shape}"
+        assert sigma1.shape == sigma2.shape, f"Training and test covariances have different dimensions: {sigma1.shape}, {sigma2.shape}"
+        diff = mu1 - mu2
+        covmean = _sqrtm(sigma1.dot(sigma2))
+        if not np.isfinite(covmean).all():
+            warnings.warn("fid calculation produces singular product; adding %s to diagonal of cov estimates" % eps)
+            offset = np.eye(sigma1.shape[0]) * eps
+            covmean = _sqrtm((sigma1 + offset).dot(sigma2 + offset))
+        if np.iscomplexobj(covmean):
+            if not np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3):
+                raise ValueError("Imaginary component {}".format(np.max(np.abs(covmean.imag))))
+            covmean = covmean.real
+        return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean)
+
+
+def _as_tensor(x, what):
+    """The input as a torch tensor where it lies, refused unless it is non-empty and 2-D (checked before anything is uploaded)."""
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(np.ascontiguousarray(x)) if x.flags.writeable else torch.tensor(x)      # torch warns on read-only arrays
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{what}: expected a numpy array or a torch tensor, got {type(x).__name__}")
+    if x.dim() != 2:
+        raise ValueError(f"{what}: expected 2-D [N, D] activations, got shape {tuple(x.shape)}")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{what}: empty activations of shape {tuple(x.shape)}")
+    return x
+
+
+def _same_width(what, a, b):
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"{what}: feature widths differ: {a.shape[1]} and {b.shape[1]}")
+
+
+def _device_features(x, what):
+    """float32 contiguous [N, D] on the GPU: one upload for host data, the tensor itself where it already is that."""
+    x = _as_tensor(x, what)
+    if not x.is_cuda:
+        x = x.to(torch.float32).cuda()       # no GPU: torch raises here, there is no host path
+    return x.to(torch.float32).contiguous()
+
+
+def _norms(x, what):
+    """Row square norms, and the one device reduction that refuses NaN / inf features (a non-finite feature, or a row whose
+    square norm overflows f32, makes its norm non-finite)."""
+    n = ops.row_sqnorms(x)
+    if not bool(torch.isfinite(n).all()):
+        raise ValueError(f"{what}: features hold NaN or inf (or a row's square norm overflows float32)")
+    return n
+
+
+def compute_statistics(activations):
+    """FIDStatistics(mu, sigma) of [N, D] activations: numpy float64 mean and covariance (np.cov(rowvar=False)), two kernels."""
+    x = _device_features(activations, "compute_statistics")
+    mu = ops.col_mean_f64(x)
+    if not bool(torch.isfinite(mu).all()):
+        raise ValueError("compute_statistics: activations hold NaN or inf")
+    sigma = ops.cov_f64(x, mu)
+    return FIDStatistics(mu.cpu().numpy(), sigma.cpu().numpy())
+
+
+class ManifoldEstimator:
+    """k-nearest-neighbour manifolds of feature sets (improved precision and recall).  The reference's constructor without its
+    TensorFlow session.  `row_batch_size` / `col_batch_size` cut the work into launches; no output bit depends on them."""
+
+    def __init__(self, row_batch_size=10000, col_batch_size=10000, nhood_sizes=(3,), clamp_to_percentile=None, eps=1e-5):
+        if row_batch_size < 1 or col_batch_size < 1:
+            raise ValueError(f"ManifoldEstimator: batch sizes must be positive, got {row_batch_size} x {col_batch_size}")
+        nhood_sizes = tuple(int(k) for k in nhood_sizes)
+        if not nhood_sizes or min(nhood_sizes) < 0 or max(nhood_sizes) + 1 > ops.KSMALLEST_MAX:
+            raise ValueError(f"ManifoldEstimator: nhood_sizes {nhood_sizes} outside 0 .. {ops.KSMALLEST_MAX - 1}")
+        if len(nhood_sizes) > ops.WITHIN_MAX_RADII:
+            raise ValueError(f"ManifoldEstimator: at most {ops.WITHIN_MAX_RADII} neighbourhood sizes, got {len(nhood_sizes)}")
+        self.row_batch_size = int(row_batch_size)
+        self.col_batch_size = int(col_batch_size)
+        self.nhood_sizes = nhood_sizes
+        self.num_nhoods = len(nhood_sizes)
+        self.clamp_to_percentile = clamp_to_percentile
+        self.eps = eps
+
+    def _ksmallest(self, x, norms, k1):
+        """[N, k1] ascending smallest distances of every row of x to all rows of x (itself included), cut into launches."""
+        n = x.shape[0]
+        out = torch.empty(n, k1, device=x.device, dtype=torch.float32)
+        cols = [(c0, min(c0 + self.col_batch_size, n)) for c0 in range(0, n, self.col_batch_size)]
+        for r0 in range(0, n, self.row_batch_size):
+            r1 = min(r0 + self.row_batch_size, n)
+            if len(cols) == 1:
+                out[r0:r1] = ops.pairwise_ksmallest(x[r0:r1], x, k1, norms[r0:r1], norms)
+                continue
+            parts = torch.full((len(cols), r1 - r0, k1), float("inf"), device=x.device, dtype=torch.float32)
+            for ci, (c0, c1) in enumerate(cols):
+                kc = min(k1, c1 - c0)
+                parts[ci, :, :kc] = ops.pairwise_ksmallest(x[r0:r1], x[c0:c1], kc, norms[r0:r1], norms[c0:c1])
+            out[r0:r1] = ops.ksmallest_merge(parts)
+        return out
+
+    def manifold_radii(self, features):
+        """float32 [N, len(nhood_sizes)]: the distance of every point to its k-th nearest neighbour, itself counted as the 0-th."""
+        features = _as_tensor(features, "manifold_radii")
+        kmax = max(self.nhood_sizes)
+        if features.shape[0] <= kmax:
+            raise ValueError(f"manifold_radii: N = {features.shape[0]} points, more than max(nhood_sizes) = {kmax} are needed")
+        x = _device_features(features, "manifold_radii")
+        norms = _norms(x, "manifold_radii")
+        small = self._ksmallest(x, norms, kmax + 1)
+        radii = np.ascontiguousarray(small.cpu().numpy()[:, list(self.nhood_sizes)], dtype=np.float32)
+        if self.clamp_to_percentile is not None:
+            max_distances = np.percentile(radii, self.clamp_to_percentile, axis=0)
+            radii[radii > max_distances] = 0
+        return radii
+
+    def evaluate(self, features, radii, eval_features):
+        raise NotImplementedError("ManifoldEstimator.evaluate (realism scores) is not built on the HIP path; evaluate_pr is")
+
+    def evaluate_pr(self, features_1, radii_1, features_2, radii_2):
+        """(precision [K1], recall [K2]) as float64 means: precision[c] is the share of features_2 within radii_1[:, c] of some
+        point of features_1, recall[c] the share of features_1 within radii_2[:, c] of some point of features_2."""
+        features_1, features_2 = _as_tensor(features_1, "evaluate_pr"), _as_tensor(features_2, "evaluate_pr")
+        _same_width("evaluate_pr", features_1, features_2)
+        r1, r2 = (torch.as_tensor(np.asarray(r), dtype=torch.float32) for r in (radii_1, radii_2))
+        for r, x, name in ((r1, features_1, "radii_1"), (r2, features_2, "radii_2")):
+            if r.dim() != 2 or r.shape[0] != x.shape[0] or not 1 <= r.shape[1] <= ops.WITHIN_MAX_RADII:
+                raise ValueError(f"evaluate_pr: {name} must be [{x.shape[0]}, 1 .. {ops.WITHIN_MAX_RADII}], got {tuple(r.shape)}")
+        x1, x2 = _device_features(features_1, "evaluate_pr"), _device_features(features_2, "evaluate_pr")
+        r1, r2 = r1.to(x1.device).contiguous(), r2.to(x1.device).contiguous()
+        n1, n2 = _norms(x1, "evaluate_pr"), _norms(x2, "evaluate_pr")
+        status_1 = torch.zeros(x1.shape[0], r2.shape[1], device=x1.device, dtype=torch.uint8)
+        status_2 = torch.zeros(x2.shape[0], r1.shape[1], device=x1.device, dtype=torch.uint8)
+        for b1 in range(0, x1.shape[0], self.row_batch_size):
+            e1 = min(b1 + self.row_batch_size, x1.shape[0])
+            for b2 in range(0, x2.shape[0], self.col_batch_size):
+                e2 = min(b2 + self.col_batch_size, x2.shape[0])
+                ops.pairwise_within(x1[b1:e1], x2[b2:e2], n1[b1:e1], n2[b2:e2], r1[b1:e1], r2[b2:e2], status_1[b1:e1], status_2[b2:e2])
+        self.last_status = (status_1.cpu().numpy().astype(bool), status_2.cpu().numpy().astype(bool))
+        return (np.mean(self.last_status[1].astype(np.float64), axis=0), np.mean(self.last_status[0].astype(np.float64), axis=0))
+
+
+def compute_prec_recall(activations_ref, activations_sample, manifold_estimator=None):
+    """(precision, recall) of the sample set against the reference set, neighbourhood size nhood_sizes[0]."""
+    est = manifold_estimator or ManifoldEstimator()
+    activations_ref, activations_sample = _as_tensor(activations_ref, "compute_prec_recall"), _as_tensor(activations_sample, "compute_prec_recall")
+    _same_width("compute_prec_recall", activations_ref, activations_sample)
+    if min(activations_ref.shape[0], activations_sample.shape[0]) <= max(est.nhood_sizes):
+        raise ValueError(f"compute_prec_recall: N = {activations_ref.shape[0]} and {activations_sample.shape[0]} points, more than "
+                         f"max(nhood_sizes) = {max(est.nhood_sizes)} are needed in each set")
+    ref = _device_features(activations_ref, "compute_prec_recall")
+    sample = _device_features(activations_sample, "compute_prec_recall")
+    radii_1 = est.manifold_radii(ref)
+    radii_2 = est.manifold_radii(sample)
+    pr = est.evaluate_pr(ref, radii_1, sample, radii_2)
+    return (float(pr[0][0]), float(pr[1][0]))
+
+
+def metrics_from_activations(ref_acts, sample_acts, ref_stats=None, ref_stats_spatial=None):
+    """What calculate_metrics does after compute_activations: ref_acts / sample_acts are (pool [N, 2048], spatial [N, 2023])
+    tuples; reference statistics that are given are used instead of being recomputed.  Returns dict(fid, sfid, precision, recall)."""
+    for name, acts in (("ref_acts", ref_acts), ("sample_acts", sample_acts)):
+        if not isinstance(acts, (tuple, list)) or len(acts) != 2:
+            raise ValueError(f"metrics_from_activations: {name} must be a (pool, spatial) pair")
+    what = "metrics_from_activations"
+    shapes = [[_as_tensor(a, what) for a in acts] for acts in (ref_acts, sample_acts)]
+    _same_width(what, shapes[0][0], shapes[1][0])
+    _same_width(what, shapes[0][1], shapes[1][1])
+    ref_pool = _device_features(ref_acts[0], "metrics_from_activations")
+    sample_pool = _device_features(sample_acts[0], "metrics_from_activations")
+    ref_stats = ref_stats if ref_stats is not None else compute_statistics(ref_pool)
+    ref_stats_spatial = ref_stats_spatial if ref_stats_spatial is not None else compute_statistics(ref_acts[1])
+    sample_stats, sample_stats_spatial = compute_statistics(sample_pool), compute_statistics(sample_acts[1])
+    prec, recall = compute_prec_recall(ref_pool, sample_pool)
+    return dict(fid=float(sample_stats.frechet_distance(ref_stats)), sfid=float(sample_stats_spatial.frechet_distance(ref_stats_spatial)),
+                precision=prec, recall=recall)

@@ -1023,3 +1023,98 @@ def dropout_bits(dt, x, bits, keep_scale, y, n, backward=False):
     """y = x * (bit ? keep_scale : 0): bitwise vaw_mul with the unpacked mask (raw pointers for x / y)."""
     fn = L.lib().vaw_dropout_bits_bwd if backward else L.lib().vaw_dropout_bits_fwd
     check(fn(dt, x, ptr(bits), keep_scale, y, n, stream_ptr()), "vaw_dropout_bits_bwd" if backward else "vaw_dropout_bits_fwd")
+
+
+# ---- evaluation metrics from activations (evaluator.py; csrc/metrics.hip) -----------------------------------------
+KSMALLEST_MAX = 16      # largest k1 of pairwise_ksmallest
+WITHIN_MAX_RADII = 4    # most radii per point of pairwise_within
+
+
+def _features(what, *ts):
+    """f32, 2-D, contiguous CUDA tensors of one feature width."""
+    need_cuda(*ts)
+    for t in ts:
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{what}: features must be non-empty contiguous float32 [N, D] tensors, got {t.dtype} {tuple(t.shape)}")
+        if t.shape[1] != ts[0].shape[1]:
+            raise ValueError(f"{what}: feature widths differ: {ts[0].shape[1]} and {t.shape[1]}")
+
+
+def _per_row(what, name, t, rows, cols=None, dtype=torch.float32):
+    need_cuda(t)
+    want = (rows,) if cols is None else (rows, cols)
+    if t.dtype != dtype or tuple(t.shape) != want or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor of shape {want}, got {t.dtype} {tuple(t.shape)}")
+
+
+def row_sqnorms(x):
+    """out[i] = sum_k x[i][k]^2 (f32, fixed order)."""
+    _features("row_sqnorms", x)
+    out = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
+    check(L.lib().vaw_row_sqnorms(ptr(x), x.shape[0], x.shape[1], ptr(out), stream_ptr()), "vaw_row_sqnorms")
+    return out
+
+
+def pairwise_ksmallest(u, v, k1, norm_u=None, norm_v=None):
+    """[nu, k1]: per row of u the k1 smallest squared distances max((|u|^2 - 2 u.v) + |v|^2, 0) to the rows of v, ascending."""
+    _features("pairwise_ksmallest", u, v)
+    nu, nv = u.shape[0], v.shape[0]
+    if not 1 <= k1 <= min(KSMALLEST_MAX, nv):
+        raise ValueError(f"pairwise_ksmallest: k1 = {k1} outside 1 .. min({KSMALLEST_MAX}, nv = {nv})")
+    norm_u = row_sqnorms(u) if norm_u is None else norm_u
+    norm_v = (norm_u if v is u else row_sqnorms(v)) if norm_v is None else norm_v
+    _per_row("pairwise_ksmallest", "norm_u", norm_u, nu)
+    _per_row("pairwise_ksmallest", "norm_v", norm_v, nv)
+    nbytes = L.lib().vaw_pairwise_workspace_bytes(nu, nv, k1)
+    ws = torch.empty(nbytes // 4, device=u.device, dtype=torch.float32)
+    out = torch.empty(nu, k1, device=u.device, dtype=torch.float32)
+    check(L.lib().vaw_pairwise_ksmallest(ptr(u), nu, ptr(v), nv, u.shape[1], ptr(norm_u), ptr(norm_v), k1, ptr(out), ptr(ws), nbytes,
+                                         stream_ptr()), "vaw_pairwise_ksmallest")
+    return out
+
+
+def ksmallest_merge(parts):
+    """parts [P, n, k1] (ascending or not, +inf = empty) -> [n, k1]: the k1 smallest of each row's P * k1 values, ascending."""
+    need_cuda(parts)
+    if parts.dtype != torch.float32 or parts.dim() != 3 or not parts.is_contiguous() or not 1 <= parts.shape[2] <= KSMALLEST_MAX:
+        raise ValueError(f"ksmallest_merge: parts must be contiguous float32 [P, n, k1 <= {KSMALLEST_MAX}], got {parts.dtype} {tuple(parts.shape)}")
+    P, n, k1 = parts.shape
+    out = torch.empty(n, k1, device=parts.device, dtype=torch.float32)
+    check(L.lib().vaw_ksmallest_merge(ptr(parts), n, P, k1, n * k1, k1, ptr(out), stream_ptr()), "vaw_ksmallest_merge")
+    return out
+
+
+def pairwise_within(u, v, norm_u, norm_v, radii_u, radii_v, u_in, v_in):
+    """u_in[i][c] |= any_j d(i, j) <= radii_v[j][c] and v_in[j][c] |= any_i d(i, j) <= radii_u[i][c] (uint8 flags, zeroed by the
+    caller before the first call)."""
+    _features("pairwise_within", u, v)
+    nu, nv = u.shape[0], v.shape[0]
+    for name, r in (("radii_u", radii_u), ("radii_v", radii_v)):
+        if r.dim() != 2 or not 1 <= r.shape[1] <= WITHIN_MAX_RADII:
+            raise ValueError(f"pairwise_within: {name} must be [N, 1 .. {WITHIN_MAX_RADII}], got {tuple(r.shape)}")
+    Ku, Kv = radii_u.shape[1], radii_v.shape[1]
+    _per_row("pairwise_within", "norm_u", norm_u, nu)
+    _per_row("pairwise_within", "norm_v", norm_v, nv)
+    _per_row("pairwise_within", "radii_u", radii_u, nu, Ku)
+    _per_row("pairwise_within", "radii_v", radii_v, nv, Kv)
+    _per_row("pairwise_within", "u_in", u_in, nu, Kv, torch.uint8)
+    _per_row("pairwise_within", "v_in", v_in, nv, Ku, torch.uint8)
+    check(L.lib().vaw_pairwise_within(ptr(u), nu, ptr(v), nv, u.shape[1], ptr(norm_u), ptr(norm_v), ptr(radii_u), Ku, ptr(radii_v), Kv,
+                                      ptr(u_in), ptr(v_in), stream_ptr()), "vaw_pairwise_within")
+
+
+def col_mean_f64(x):
+    """f64 [D]: the column means of f32 x [n, D]."""
+    _features("col_mean_f64", x)
+    mu = torch.empty(x.shape[1], device=x.device, dtype=torch.float64)
+    check(L.lib().vaw_col_mean_f64(ptr(x), x.shape[0], x.shape[1], ptr(mu), stream_ptr()), "vaw_col_mean_f64")
+    return mu
+
+
+def cov_f64(x, mu):
+    """f64 [D, D]: (x - mu)^T (x - mu) / (n - 1), centred and two-pass, symmetric bit for bit."""
+    _features("cov_f64", x)
+    _per_row("cov_f64", "mu", mu, x.shape[1], dtype=torch.float64)
+    sigma = torch.empty(x.shape[1], x.shape[1], device=x.device, dtype=torch.float64)
+    check(L.lib().vaw_cov_f64(ptr(x), x.shape[0], x.shape[1], ptr(mu), ptr(sigma), stream_ptr()), "vaw_cov_f64")
+    return sigma

@@ -686,8 +686,8 @@ int vaw_groupnorm_fwd(vaw_dtype dt, const void* x, const float* gamma, const flo
                       const float* shift, int64_t film_ld, int silu, void* y, float* mean, float* rstd, int B, int HW,
                       int C, int G, float eps, float* workspace, vaw_stream stream);
 /* The apply pass of vaw_groupnorm_fwd alone, on GIVEN statistics (mean/rstd: f32 [B*G], as vaw_groupnorm_fwd saved them):
- * the same kernel under the same dispatch (flat 16-byte bf16 mapping / channel-quad mapping), so for the same x, statistics and
- * parameters y is bitwise vaw_groupnorm_fwd's.  One pass over x instead of three: activation recomputation (UNet use_checkpoint). */
+ * the same kernel under the same plan (vaw_gn_plan, VAW_GN_APPLY), so for the same x, statistics and parameters y is bitwise
+ * vaw_groupnorm_fwd's.  One pass over x instead of three: activation recomputation (UNet use_checkpoint). */
 int vaw_groupnorm_apply(vaw_dtype dt, const void* x, const float* mean, const float* rstd, const float* gamma,
                         const float* beta, const float* scale, const float* shift, int64_t film_ld, int silu, void* y, int B,
                         int HW, int C, int G, vaw_stream stream);
@@ -697,6 +697,33 @@ int vaw_groupnorm_bwd(vaw_dtype dt, const void* dout, const void* x, const float
                       const float* gamma, const float* beta, const float* scale, const float* shift, int64_t film_ld,
                       int silu, const void* dx_add, void* dx, float* dgamma, float* dbeta, float grad_beta, float* dscale,
                       float* dshift, int64_t dfilm_ld, int B, int HW, int C, int G, float* workspace, vaw_stream stream);
+/* Launch plan of the GroupNorm entry points: the one host function vaw_groupnorm_fwd / _apply / _bwd take every launch choice
+ * from (pure arithmetic: no device call, so it can be asked without a GPU).  pass = one streaming launch: the forward is
+ * VAW_GN_FWD_SUMS then VAW_GN_APPLY (vaw_groupnorm_apply: that launch alone), the backward VAW_GN_BWD_SUMS then VAW_GN_BWD_APPLY
+ * (the small statistics / fold / group kernels between the two go with the sums pass).  Flat -- a thread owns a channel octet
+ * (16-byte accesses) of every rpi-th row -- needs: the switch not 0, bf16, C % 8 == 0, C / 8 <= 256, C <= 2048, B * HW < 2^30,
+ * HW * C < 2^31 and the largest chunk of 512 / 256 / 128 rows that gives B * ceil(HW / rows) >= 512 workgroups (switch 1: 128 rows
+ * where none does); everything else is quad -- a thread owns a channel quad -- on 512-row chunks.  Reads the vaw_debug_gn_flat
+ * switch (-1 by shape | 0 never | 1 wherever it can run) on every call.  VAW_ERR_INVALID: dt not f32 / bf16, a size <= 0,
+ * C % 4 != 0, C % G != 0, G > 64, B >= 65536, quad with more than 65535 chunks (grid.z). */
+typedef enum { VAW_GN_FWD_SUMS = 0, VAW_GN_APPLY = 1, VAW_GN_BWD_SUMS = 2, VAW_GN_BWD_APPLY = 3 } vaw_gn_pass;
+typedef enum {
+    VAW_GNV_QUAD = 0,           /* gn_fwd_sums / gn_apply / gn_bwd_sums / gn_bwd_apply _kernel<T> */
+    VAW_GNV_FLAT = 1            /* gns_fwd_sums / gns_apply / gns_bwd_sums / gns_bwd_apply _kernel */
+} vaw_gn_variant;
+typedef struct {
+    int variant;                /* vaw_gn_variant */
+    int rows, nch;              /* rows of a chunk, chunks per sample: nch = ceil(HW / rows) */
+    int nt, rpi;                /* flat: live lanes of a workgroup (a multiple of C / 8) and rows per step nt / (C / 8); quad: 0 */
+    int grid_x, grid_y, grid_z, block;   /* flat: B * nch workgroups; quad: (ceil(C / 64), B, nch) */
+    int64_t lds_bytes;          /* static LDS of the pass's streaming kernel */
+    int64_t workspace_floats;   /* f32 workspace the pass reads or writes, from its start (apply: 0);
+                                 * never more than vaw_groupnorm_workspace_floats(B, HW, C), whatever the switch */
+    int64_t off_part, off_sums, off_s1, off_s2;   /* f32 offsets of its regions, -1 = not used: chunk partials [2 | 4][nch][B][C],
+                                 * folded sums [4][B][C], S1 and S2 [B * G] */
+    int status;                 /* vaw_status: VAW_OK, or what the entry point returns before launching anything */
+} vaw_gn_launch;
+int vaw_gn_plan(int pass, vaw_dtype dt, int B, int HW, int C, int G, vaw_gn_launch* out);
 /* conv3x3 stride 1 pad 1 as GEMM (round 1: explicit patch matrix).  col[m, tap*C + c] = x[pixel(m)+tap offset, c];
  * vaw_col2im3x3 is the transposed map written as a gather (deterministic): the input gradient from d(col). */
 int vaw_im2col3x3(vaw_dtype dt, const void* x, void* col, int B, int H, int W, int C, vaw_stream stream);

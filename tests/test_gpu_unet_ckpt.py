@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 import vaw_amd
 from vaw_amd import ops
-from vaw_amd._lib import BF16, F32, lib, ptr, stream_ptr
+from vaw_amd._lib import BF16, F32, GN_APPLY, GN_FWD_SUMS, GNV_FLAT, GNV_QUAD, lib, ptr, stream_ptr
 
 DEV = "cuda"
 TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16}
@@ -185,10 +185,9 @@ def _gn_case(dt, B, HW, C, film, silu, seed):
 @pytest.mark.parametrize("path", ["f32_quad", "bf16_quad", "bf16_flat_forced", "bf16_flat_by_shape"])
 def test_groupnorm_apply_is_the_forward_apply_pass(path, film, silu):
     """vaw_groupnorm_apply on the statistics vaw_groupnorm_fwd wrote = vaw_groupnorm_fwd's output, bitwise, on every dispatch
-    path of the apply pass.  GroupNorm has no plan query, so the paths are picked by the dispatch conditions (unet_ops.hip: gns_ok /
-    gns_rows): f32 always takes the channel-quad kernel; bf16 takes the flat 16-byte kernel when B x ceil(HW / rows) >= 512 for
-    some rows in {512, 256, 128} -- never for B <= 3, HW <= 1024, where it is forced through vaw_debug_gn_flat(1) (128-row chunks:
-    HW = 16 and 64 are a short single chunk, HW = 1024 is 8 chunks) -- and by shape at B = 128, HW = 512 (4 chunks x 128 samples)."""
+    path of the apply pass; ops.gn_plan says that each `path` is the variant its name names.  The small shapes are flat only when
+    forced through vaw_debug_gn_flat(1) (128-row chunks: HW = 16 and 64 are a short single chunk, HW = 1024 is 8 chunks); B = 128,
+    HW = 512 is flat by shape (4 chunks x 128 samples)."""
     dt = F32 if path == "f32_quad" else BF16
     shapes = [(B, HW, C) for C in (32, 96, 192) for HW in (16, 64, 1024) for B in (1, 3)]
     if path == "bf16_flat_by_shape":
@@ -197,6 +196,7 @@ def test_groupnorm_apply_is_the_forward_apply_pass(path, film, silu):
         if path == "bf16_flat_forced":
             lib().vaw_debug_gn_flat(1)
         for i, (B, HW, C) in enumerate(shapes):
+            assert all(ops.gn_plan(p, dt, B, HW, C).variant == (GNV_FLAT if "flat" in path else GNV_QUAD) for p in (GN_FWD_SUMS, GN_APPLY)), (path, B, HW, C)
             _gn_case(dt, B, HW, C, film, silu, seed=100 + i)
     finally:
         lib().vaw_debug_gn_flat(-1)

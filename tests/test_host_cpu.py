@@ -1087,3 +1087,95 @@ def test_gemm_plan_refusals():
     refused("grid too large", M=(1 << 31) - 8, N=(1 << 31) - 8, K=64, lda=64, ldb=64, bias=a)
     # and a call that passes them all
     assert ops.gemm_plan(L.BF16, 1, 1, 256, 256, 256, a, 256, a, 256, a, 256, knobs=k).status == 0
+
+
+# ------------------------------------------------------------------------------------------------
+# Launch plan of GroupNorm (vaw_gn_plan: host arithmetic only, vaw_groupnorm_fwd / _apply / _bwd take every choice from it)
+# ------------------------------------------------------------------------------------------------
+_GN_FIELDS = "@9i6qi"          # vaw_gn_launch: variant rows nch nt rpi grid_x grid_y grid_z block | lds ws off_part off_sums off_s1 off_s2 | status
+
+
+def _gn_want(switch, dt, B, HW, C, G):
+    """The rule and the launch restated: the fields of vaw_gn_launch for each pass (_lib.GN_* = 0 .. 3), or None where the plan refuses."""
+    if dt not in (0, 1) or min(B, HW, C, G) <= 0 or C % 4 or C % G or G > 64 or B >= 65536:
+        return None
+    rows = 0
+    if switch != 0 and dt == 1 and C % 8 == 0 and C // 8 <= 256 and C <= 2048 and B * HW < 2 ** 30 and HW * C < 2 ** 31:
+        rows = next((r for r in (512, 256, 128) if B * -(-HW // r) >= 512), 128 if switch == 1 else 0)
+    flat, rows = rows > 0, rows or 512
+    nch = -(-HW // rows)
+    if not flat and nch > 65535:
+        return None
+    nt = 256 // (C // 8) * (C // 8) if flat else 0
+    geom = (int(flat), rows, nch, nt, nt // (C // 8) if flat else 0) + ((B * nch, 1, 1) if flat else (-(-C // 64), B, nch)) + (256,)
+    BC, BG, part = B * C, B * G, 4 * nch * B * C          # part: the backward's chunk partials, in front of its other regions
+    sums_lds = lambda planes: 4 * (2 * 256 * 8 + 2 * 2048 if flat else planes * 16 * 64)
+    bwd_ws = part + 4 * BC + 2 * BG
+    return [geom + (sums_lds(2), 2 * nch * BC, 0, -1, -1, -1, 0), geom + (0, 0, -1, -1, -1, -1, 0),
+            geom + (sums_lds(4), bwd_ws, 0, part, part + 4 * BC, part + 4 * BC + BG, 0),
+            geom + (0, bwd_ws, -1, -1, part + 4 * BC, part + 4 * BC + BG, 0)]
+
+
+def test_gn_plan_sweep_variant_geometry_and_workspace():
+    """Every field is the restated rule's (so a shape's four passes share one geometry: the apply pass is the forward's); chunks cover
+    HW, none empty; flat fits its workgroup and the LDS arrays of its sums kernels (red: 2 rpi C <= 4096 floats, chs: 2 C <= 4096);
+    quad fits grid.y / grid.z; every workspace fits vaw_groupnorm_workspace_floats under any switch, its regions do not overlap."""
+    import struct
+    from vaw_amd.ops import gn_plan
+    lib = vaw_amd.lib()
+    try:
+        for C in list(range(4, 2049, 4)) + [2052, 4096]:
+            groups = sorted({G for G in (1, 32, 64, C // 4) if C % G == 0})
+            for B in (1, 2, 3, 127, 128, 256, 511, 512, 4096):
+                for HW in (1, 16, 127, 128, 129, 512, 513, 1024, 4096, 16384):
+                    cap = lib.vaw_groupnorm_workspace_floats(B, HW, C)
+                    for switch, dt, G in ((s, d, g) for s in (-1, 0, 1) for d in (0, 1) for g in groups):
+                        lib.vaw_debug_gn_flat(switch)
+                        want, where = _gn_want(switch, dt, B, HW, C, G), f"switch={switch} dt={dt} B={B} HW={HW} C={C} G={G}"
+                        if want is None:
+                            assert G > 64, where
+                            for gn_pass in range(4):
+                                with pytest.raises(vaw_amd.VawError):
+                                    gn_plan(gn_pass, dt, B, HW, C, G)
+                            continue
+                        for gn_pass in range(4):
+                            got = struct.unpack_from(_GN_FIELDS, gn_plan(gn_pass, dt, B, HW, C, G))
+                            assert got == want[gn_pass], f"{where} pass={gn_pass}: {got} != {want[gn_pass]}"
+                        flat, rows, nch, nt, rpi, gx, gy, gz, block = want[0][:9]          # the properties, on the fields just compared
+                        assert nch * rows >= HW > (nch - 1) * rows and block == 256, where
+                        if flat:
+                            assert nt == 256 // (C // 8) * (C // 8) and 1 <= rpi == nt // (C // 8) and nt <= block and 2 * rpi * C <= 4096 \
+                                and 2 * C <= 4096 and (gx, gy, gz) == (B * nch, 1, 1), where
+                        else:
+                            assert (gx, gy, gz) == (-(-C // 64), B, nch) and gy <= 65535 and gz <= 65535, where
+                        assert want[0][10:12] == (2 * nch * B * C, 0) and want[0][10] <= cap and want[1][10:15] == (0, -1, -1, -1, -1), where
+                        ws, part, sums, s1, s2 = want[2][10:15]
+                        assert 0 == part and part + 4 * nch * B * C <= sums and sums + 4 * B * C <= s1 and s1 + B * G <= s2 and s2 + B * G <= ws <= cap, where
+                        assert want[3][10:15] == (ws, -1, -1, s1, s2), where
+    finally:
+        lib.vaw_debug_gn_flat(-1)
+
+
+def test_gn_plan_refusals_and_production_pins():
+    """Refused: a dtype that is neither f32 nor bf16 (the fp8 tags used to run as bf16), C % 4, C % G, G > 64, B >= 65536, a size <= 0,
+    a quad launch of more than 65535 chunks (grid.z).  Pinned: the five shapes of tools/gn_bench.py (UNet_64) at bf16 under the
+    default switch, worked out by hand from the rule before the plan existed."""
+    from vaw_amd import _lib as L
+    from vaw_amd.ops import gn_plan
+    ok = dict(dt=L.BF16, B=2, HW=64, C=64, G=32)
+    bad = [dict(dt=L.FP8), dict(dt=L.BF8), dict(dt=7), dict(C=66, G=1), dict(C=36, G=8), dict(C=520, G=130), dict(C=260, G=65),
+           dict(B=65536), dict(B=0), dict(HW=0), dict(C=0), dict(G=0), dict(B=-1), dict(HW=-5),
+           dict(dt=L.F32, B=1, HW=65536 * 512, C=4, G=1), dict(dt=L.BF16, B=1, HW=65535 * 512 + 1, C=4, G=1)]
+    pins = {(256, 4096, 192): (L.GNV_FLAT, 512), (256, 1024, 384): (L.GNV_FLAT, 512), (128, 4096, 192): (L.GNV_FLAT, 512),
+            (256, 256, 576): (L.GNV_FLAT, 128), (256, 64, 768): (L.GNV_QUAD, 512)}
+    for gn_pass in (L.GN_FWD_SUMS, L.GN_APPLY, L.GN_BWD_SUMS, L.GN_BWD_APPLY):
+        assert gn_plan(gn_pass, **ok).status == 0
+        assert gn_plan(gn_pass, L.F32, 1, 65535 * 512, 4, 1).grid_z == 65535          # the last HW the quad grid holds
+        for change in bad:
+            with pytest.raises(vaw_amd.VawError):
+                gn_plan(gn_pass, **{**ok, **change})
+        for (B, HW, C), want in pins.items():
+            p = gn_plan(gn_pass, L.BF16, B, HW, C)
+            assert (p.variant, p.rows) == want, (B, HW, C, gn_pass, p.variant, p.rows)
+    with pytest.raises(vaw_amd.VawError):
+        gn_plan(4, **ok)

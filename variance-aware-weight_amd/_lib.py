@@ -38,6 +38,13 @@ class AttnLaunch(C.Structure):
                 ("lds_cap_raised", _i), ("colsum_rows", _l), ("status", _i)]
 
 
+class GnLaunch(C.Structure):
+    """vaw_gn_launch of include/vaw_hip.h: the launch vaw_gn_plan picks for one streaming pass of a GroupNorm entry point."""
+    _fields_ = [("variant", _i), ("rows", _i), ("nch", _i), ("nt", _i), ("rpi", _i), ("grid_x", _i), ("grid_y", _i), ("grid_z", _i),
+                ("block", _i), ("lds_bytes", _l), ("workspace_floats", _l), ("off_part", _l), ("off_sums", _l), ("off_s1", _l),
+                ("off_s2", _l), ("status", _i)]
+
+
 class GemmKnobs(C.Structure):
     """vaw_gemm_knobs of include/vaw_hip.h: the switches and the CU count vaw_gemm_plan decides by (default_gemm_knobs())."""
     _fields_ = [(n, _i) for n in ("tile", "force_generic", "bk", "pd", "ws", "xcdsplit", "sm_max_m", "sm_wide_m", "sm_nb", "sm_stages",
@@ -82,6 +89,10 @@ RESAMPLER_MAX_T = 4096      # VAW_RESAMPLER_MAX_T
 
 ROW_LN_FWD, ROW_LN_FWD_FP8, ROW_LN_BWD, ROW_GATE_BWD, ROW_GATE_BWD_FP8, ROW_LN_BWD_GATE, ROW_LN_BWD_GATE_FP8, ROW_COLSUM = range(8)
 RV_LN_FWD, RV_ROW_BWD, RV_ROW_GATE, RV_ROW_FUSE, RV_ROW_FUSE8, RV_COLSUM_BF16X8, RV_COLSUM_VEC4, RV_COLSUM_SCALAR = range(8)
+
+# vaw_gn_pass / vaw_gn_variant
+GN_FWD_SUMS, GN_APPLY, GN_BWD_SUMS, GN_BWD_APPLY = range(4)
+GNV_QUAD, GNV_FLAT = range(2)
 
 # name -> argtypes (every function returns int status unless noted)
 _PROTOS = {
@@ -168,6 +179,7 @@ _PROTOS = {
     "vaw_gate_bwd_fp8": [_p, _p, _p, _l, _p, _p, _i, _p, _l, _p, _i, _i, _i, _p, _l, _p],
     "vaw_row_plan": [_i, _i, _l, _l, _l, _l, _l, _l, C.POINTER(RowLaunch)],
     "vaw_attn_plan": [_i, _i, C.POINTER(AttnDesc), _l, _l, _l, _l, _l, _l, _l, C.POINTER(AttnLaunch)],
+    "vaw_gn_plan": [_i, _i, _i, _i, _i, _i, C.POINTER(GnLaunch)],
     "vaw_gemm_plan": [_i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _l, _l, C.POINTER(Epilogue), _l, C.POINTER(GemmKnobs), C.POINTER(GemmLaunch)],
     "vaw_dit_ws_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(DitWsPlan)],
     "vaw_latent_qsample": [_p, _p, _p, _p, _p, _p, _i, _f, _f, _p, _p, _p, _i, _l, _p],
@@ -241,10 +253,9 @@ def lib():
         if hasattr(L, "vaw_gemm_default_knobs"):
             L.vaw_gemm_default_knobs.argtypes = [C.POINTER(GemmKnobs)]
             L.vaw_gemm_default_knobs.restype = None
-        for dbg in ("vaw_debug_gn_coop", "vaw_debug_gn_flat"):      # absent from older measurement builds loaded through VAW_HIP_LIB
-            if hasattr(L, dbg):
-                getattr(L, dbg).argtypes = [_i]
-                getattr(L, dbg).restype = None
+        if hasattr(L, "vaw_debug_gn_flat"):      # absent from older measurement builds loaded through VAW_HIP_LIB
+            L.vaw_debug_gn_flat.argtypes = [_i]
+            L.vaw_debug_gn_flat.restype = None
         L.vaw_p8_set_reserved_cus.argtypes = [_i]
         L.vaw_p8_set_reserved_cus.restype = None
         L.vaw_debug_cu_hog.argtypes = [_i, _i, _p]

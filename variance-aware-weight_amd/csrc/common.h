@@ -56,6 +56,19 @@ __device__ __forceinline__ void store4(bf16_t* p, f32x4 v) {
     *reinterpret_cast<bf16x4*>(p) = r;
 }
 
+// one bf16 octet (16 bytes) as four packed words: the accesses of the flat GroupNorm kernels (groupnorm.hip) and of the bf16
+// data-movement kernels (unet_ops.hip)
+typedef unsigned gns_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ gns_u32x4 gns_ld(const bf16_t* p) { return *reinterpret_cast<const gns_u32x4*>(p); }
+__device__ __forceinline__ gns_u32x4 gns_ld_nt(const bf16_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const gns_u32x4*>(p)); }
+__device__ __forceinline__ void gns_unpack(gns_u32x4 v, float (&f)[8]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        f[2 * k] = __uint_as_float(v[k] << 16);
+        f[2 * k + 1] = __uint_as_float(v[k] & 0xffff0000u);
+    }
+}
+
 // W-wide fill / drain of T v[W] for the streaming kernels that run one loop body at W = 4 (16-byte accesses: one f32x4, two
 // f64x2) and at W = 1 (any alignment, any length)
 typedef double f64x2 __attribute__((ext_vector_type(2)));

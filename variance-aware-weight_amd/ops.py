@@ -1006,6 +1006,14 @@ def uncast_bf16(src, dst, scale=1.0):
 
 
 # ---- UNet activation recomputation (unet.py: use_checkpoint) ------------------------------------------------
+def gn_plan(gn_pass, dt, B, HW, C, G=32):
+    """The launch the GroupNorm entry points make for the streaming pass `gn_pass` (_lib.GN_FWD_SUMS / GN_APPLY / GN_BWD_SUMS /
+    GN_BWD_APPLY) at these sizes, under the vaw_debug_gn_flat switch as it stands (vaw_gn_plan: host arithmetic, no GPU)."""
+    p = L.GnLaunch()
+    check(L.lib().vaw_gn_plan(gn_pass, dt, B, HW, C, G, L.C.byref(p)), "vaw_gn_plan")
+    return p
+
+
 def groupnorm_apply(dt, x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, y, B, HW, C, G=32):
     """The apply pass of vaw_groupnorm_fwd on saved statistics (raw pointers; scale / shift 0 = no FiLM)."""
     check(L.lib().vaw_groupnorm_apply(dt, x, mean, rstd, gamma, beta, scale or None, shift or None, film_ld, 1 if silu else 0, y,

@@ -213,6 +213,42 @@ int vaw_flow_step(int kind, int sde, int mean_type, const float* cond, const flo
                   vaw_stream stream);
 
 /* ---------------------------------------------------------------------------
+ * Adaptive explicit Runge-Kutta steps of the flow ODE  (flow_ode_sample(solver="rk45"): Dormand-Prince 5(4), the step
+ * controller on the host).  Same conventions as the solver steps above: float32, every operation rounded on its own, the
+ * model output read in place, 16-byte accesses when per_sample % 4 == 0, model_ld % 4 == 0 and every pointer is aligned.
+ * Sums leave the device as float64: one partial per workgroup (vaw_rk_partial_count of them, a function of the sizes alone)
+ * summed in a fixed order, then vaw_rk_sumsq_finish; bitwise reproducible from run to run, no atomics.
+ * ------------------------------------------------------------------------- */
+#define VAW_RK_STAGES 7       /* network evaluations of a step (the last one is the first of the next: FSAL), slots of k */
+#define VAW_RK_MAX_GRID_X 64  /* workgroups along a sample */
+int64_t vaw_rk_partial_count(int B, int64_t per_sample);
+
+/* The pass after the network evaluation of stage `stage` (0..6) of a step from x with signed step h:
+ *   cond != NULL:  k[slots[stage]] = v(output, x_stage) under mean_type (the ODE branch of vaw_flow_step, interpolant from
+ *                  coef[row], a [rows][VAW_FLOW_COLS] table at the stage times); x_stage == NULL: the stage state is x.
+ *   cond == NULL:  k[slots[stage]] is there already (a rejected step tried again with another h, or k1 <- k7 after an
+ *                  accepted one: the host swaps slots[0] and slots[6], nothing is copied).
+ *   dy = sum_{s < ncoef} a[s] * k[slots[s]]   ascending, zero coefficients skipped, left to right (a: host pointer)
+ *   x_out != NULL:     x_out (and x_out_dup) = x + h*dy, the next stage's state, written straight into the network input
+ *                      (x_out may be x_stage: every element is read before it is written)
+ *   partials != NULL:  partial sums of ((h*dy) / (atol + rtol*max(|x|, |x_new|)))^2, a = the error weights
+ *   ncoef == 0:        k only.
+ * k: [VAW_RK_STAGES][B*per_sample] float32; slots: VAW_RK_STAGES host ints in 0..6.  One coefficient vector per call, so
+ * the Euler trial of the first-step selection (a = {1}) and any other explicit tableau are the same kernel. */
+int vaw_rk_stage(int stage, int mean_type, const float* cond, const float* uncond, int64_t model_ld, float guidance_scale,
+                 const float* x, const float* x_stage, const float* coef, int row, int rows, float* k, const int* slots,
+                 const float* a, int ncoef, float h, float* x_out, float* x_out_dup, const float* x_new, float atol,
+                 float rtol, double* partials, int64_t partials_cap, int B, int64_t per_sample, vaw_stream stream);
+
+/* partials[workgroup] of  sum ((u - v) / (atol + rtol*max(|a|, |b|)))^2  over [B, per_sample] float32 tensors; v == NULL:
+ * u alone, b == NULL: |a| alone.  The quotient is float32 (IEEE division), its square and the sums float64. */
+int vaw_rk_scaled_sumsq(const float* u, const float* v, const float* a, const float* b, float atol, float rtol,
+                        double* partials, int64_t partials_cap, int B, int64_t per_sample, vaw_stream stream);
+
+/* out[0] = the `count` partial sums folded by one workgroup in a fixed order. */
+int vaw_rk_sumsq_finish(const double* partials, int64_t count, double* out, vaw_stream stream);
+
+/* ---------------------------------------------------------------------------
  * Loss-aware timestep sampling on the device  (tools/resample.py: LossSecondMomentResampler)
  * ------------------------------------------------------------------------- */
 

@@ -18,7 +18,13 @@ With `--solver heun|euler` (EDM sampler) or `--mode flow` (flow SDE sampler, Heu
      out (tables, workspaces and, with `--graph`, the capture), median / min / max of the rest in ms.  `--fused 0` runs the
      tensor composition (`fused=False`), `--fused 1` the fused solver steps, `--graph` adds args.hip_graph=True.
      `--tree DIR` imports the package from another checkout (built in place), e.g. the parent commit's, which knows
-     neither `fused` nor `hip_graph`: pass neither there."""
+     neither `fused` nor `hip_graph`: pass neither there.
+
+With `--solver rk45` the run is
+ (f) flow_ode_sample(solver="rk45") over a stand-in network (0.6 tanh(2x) + 0.5 sin(12 t) + 0.02 y: three tensor operations, so
+     the time is the solver's own) on `--batch` x 4 x S x S noise (S = `--image-size` or 32), linear path, VELOCITY,
+     `--rtol` / `--atol`: attempts, network evaluations and read-backs of a call, and the median ms per attempt of `--repeats`
+     calls, fused (vaw_rk_stage) and as the tensor composition (`fused=False`) alternating, each after a warm-up call."""
 import argparse
 import json
 import os
@@ -144,9 +150,41 @@ def solver_bench(a):
                       "ms_per_batch_min": ms[0], "ms_per_batch_max": ms[-1]}))
 
 
+def rk45_bench(a):
+    """(f): the adaptive flow-ODE solver around a stand-in network, fused against the tensor composition."""
+    S = a.image_size or 32
+    args = SimpleNamespace(weight_type="lambda", gamma=0.0, learn_sigma=False, p2_gamma=1, p2_k=1, path_type="linear")
+    fm = vaw_amd.FlowMatching(args=args, model_mean_type=vaw_amd.ModelMeanType.VELOCITY)
+    col = lambda v, x: v.reshape(-1, 1, 1, 1).to(x.dtype)
+    standin = lambda x, t, y=None, **kw: 0.6 * torch.tanh(2 * x) + 0.5 * torch.sin(12 * col(t, x)) + 0.02 * col(y, x)
+    torch.manual_seed(1)
+    x0 = torch.randn(a.batch, 4, S, S, device="cuda")
+    y = torch.arange(a.batch, device="cuda") % a.num_classes
+    res = {"part": "f", "solver": "rk45", "batch": a.batch, "elements_per_sample": 4 * S * S, "rtol": a.rtol, "atol": a.atol}
+    outs = {}
+
+    def run(fused):
+        outs[fused] = vaw_amd.flow_ode_sample(fm, standin, x0, solver="rk45", rtol=a.rtol, atol=a.atol, fused=fused, y=y)
+        return dict(fm.last_ode_stats)
+
+    stats = {fused: run(fused) for fused in (True, False)}          # warm-up
+    t_f, t_c = wall_pair(lambda: run(True), lambda: run(False), max(a.repeats, 5))
+    for name, fused, t in (("fused", True, t_f), ("composition", False, t_c)):
+        st = stats[fused]
+        attempts = st["accepted"] + st["rejected"]
+        res.update({f"{name}_attempts": attempts, f"{name}_accepted": st["accepted"], f"{name}_nfev": st["nfev"], f"{name}_readbacks": st["readbacks"],
+                    f"{name}_ms_per_call": 1e3 * t, f"{name}_ms_per_attempt": 1e3 * t / attempts})
+    res["bitwise_equal"] = bool(torch.equal(outs[True], outs[False]))
+    res["max_abs_diff"] = float((outs[True].double() - outs[False].double()).abs().max())
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--solver", choices=["heun", "euler"], default=None, help="(e): time Sampler.sample through this EDM / flow solver")
+    ap.add_argument("--solver", choices=["heun", "euler", "rk45"], default=None,
+                    help="(e): time Sampler.sample through this EDM / flow solver; rk45: (f), the adaptive flow-ODE solver")
+    ap.add_argument("--rtol", type=float, default=1e-3, help="(f)")
+    ap.add_argument("--atol", type=float, default=1e-6, help="(f)")
     ap.add_argument("--mode", choices=["diffusion", "flow"], default="diffusion")
     ap.add_argument("--fused", type=int, choices=[0, 1], default=None, help="(e): 0 = the tensor composition, 1 = the fused solver steps")
     ap.add_argument("--graph", action="store_true", help="(e): args.hip_graph=True")
@@ -166,6 +204,9 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_bench.py measures on the GPU only")
+    if a.solver == "rk45":
+        with torch.no_grad():
+            return rk45_bench(a)
     if a.solver or a.mode == "flow":
         return solver_bench(a)
     torch.manual_seed(0)

@@ -145,6 +145,9 @@ _PROTOS = {
     "vaw_edm_input": [_p, _p, _p, _i, _i, _p, _p, _p, _i, _l, _p],
     "vaw_edm_step": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _i, _i, _p, _p, _p, _i, _l, _p],
     "vaw_flow_step": [_i, _i, _i, _p, _p, _l, _f, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _l, _p],
+    "vaw_rk_stage": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _i, _i, _p, C.POINTER(_i), C.POINTER(_f), _i, _f, _p, _p, _p, _f, _f, _p, _l, _i, _l, _p],
+    "vaw_rk_scaled_sumsq": [_p, _p, _p, _p, _f, _f, _p, _l, _i, _l, _p],
+    "vaw_rk_sumsq_finish": [_p, _l, _p, _p],
     "vaw_prior_bpd": [_p, _f, _f, _p, _i, _l, _p],
     "vaw_resampler_update": [_p, _p, _i, _i, _i, _p, _p, _p, _p],
     "vaw_resampler_draw": [_p, _p, _i, _i, C.c_double, _p, _i, _p, _p, _p, _p],
@@ -242,6 +245,9 @@ def lib():
         if hasattr(L, "vaw_pairwise_workspace_bytes"):
             L.vaw_pairwise_workspace_bytes.argtypes = [_l, _l, _i]
             L.vaw_pairwise_workspace_bytes.restype = _l
+        if hasattr(L, "vaw_rk_partial_count"):
+            L.vaw_rk_partial_count.argtypes = [_i, _l]
+            L.vaw_rk_partial_count.restype = _l
         L.vaw_sumsq_workspace_floats.argtypes = []
         L.vaw_sumsq_workspace_floats.restype = _l
         L.vaw_debug_force_rowwise_attention.argtypes = [_i]
@@ -269,7 +275,7 @@ def exported_symbols():
                                    "vaw_sumsq_workspace_floats", "vaw_groupnorm_workspace_floats", "vaw_wgrad_grouped_desc_bytes",
                                    "vaw_conv3x3_wgrad_small_workspace_floats", "vaw_row_bwd_workspace_floats",
                                    "vaw_fp8_quantize_workspace_floats", "vaw_p8_set_reserved_cus", "vaw_reduce_rows_batched_desc_bytes", "vaw_fp8_quantize_batched_desc_bytes",
-                                   "vaw_gemm_default_knobs", "vaw_dropout_bits_words", "vaw_pairwise_workspace_bytes"])
+                                   "vaw_gemm_default_knobs", "vaw_dropout_bits_words", "vaw_pairwise_workspace_bytes", "vaw_rk_partial_count"])
 
 
 # VAW_STEP_FUSED (read once): 0 restores the step's unfused sequence of launches everywhere -- separate cast / column-sum

@@ -6,6 +6,7 @@
 // Each kernel has one loop body over per_sample / W items of W elements, W = 4 or 1 (common.h: loadw / storew, vec4_ok,
 // VAW_LAUNCH_W, row_grid); the per-element work is the same inlined function at either width, so the two give the same bits.
 #include "common.h"
+#include "flow_fields.h"
 
 // ---------------------------------------------------------------------------------------------
 // EDM.  Table row (VAW_EDM_COLS doubles) of step i:
@@ -162,39 +163,8 @@ extern "C" int vaw_edm_step(int kind, int pred_type, const float* cond, const fl
 // Flow matching.  Table row (VAW_FLOW_COLS floats) of one evaluation at time t:
 //   0 a  1 s  2 a'  3 s'  4 g2 = 2 s s'  5 g2/2  6 s^2  7 a^2 + s^2  8 s a' - a s'  9 sqrt(g2)
 //   and of the step that starts there:  10 dt  11 sqrt(|dt|)  12 dt/2  (13 t).
+// FlowRow / flow_row / flow_drift: flow_fields.h (shared with the adaptive stages of ode_adaptive.hip).
 // ---------------------------------------------------------------------------------------------
-struct FlowRow {
-    float a, s, da, ds, hg2, s2, den, vden;
-};
-__device__ __forceinline__ FlowRow flow_row(const float* r) {
-    FlowRow f;
-    f.a = r[0]; f.s = r[1]; f.da = r[2]; f.ds = r[3]; f.hg2 = r[5]; f.s2 = r[6]; f.den = r[7]; f.vden = r[8];
-    return f;
-}
-// _flow_fields + the drift: mean_type 0 START_X, 1 EPSILON, 2 VELOCITY, 3 VECTOR; sde: v - (g2/2) * score, else v.
-__device__ __forceinline__ float flow_drift(const FlowRow& f, int mt, bool sde, float o, float xt) {
-    float v, score = 0.f;
-    if (mt == 0) {
-        const float r = xt - f.a * o;
-        const float eps = r / f.s;
-        if (sde) score = (-r) / f.s2;
-        v = f.da * o + f.ds * eps;
-    } else if (mt == 1) {
-        const float x0 = (xt - f.s * o) / f.a;
-        if (sde) score = (-o) / f.s;
-        v = f.da * x0 + f.ds * o;
-    } else if (mt == 2) {
-        const float x0 = (f.a * xt - f.s * o) / f.den;
-        const float eps = (f.s * xt + f.a * o) / f.den;
-        if (sde) score = (-eps) / f.s;
-        v = f.da * x0 + f.ds * eps;
-    } else {
-        if (sde) score = (-((f.da * xt - f.a * o) / f.vden)) / f.s;
-        v = o;
-    }
-    return sde ? v - f.hg2 * score : v;
-}
-
 // kind 0 Euler:         x_out = (x + f0 dt) + kick           (kick = (sqrt(g2) noise) sqrt|dt|; none without noise, none for the ODE)
 // kind 1 Heun predict:  f0, kick stored;  x_out = the Euler step (the input of the second evaluation)
 // kind 2 Heun correct:  f1 = drift(x_pred, row1);  SDE x_out = (x + (0.5 (f0 + f1)) dt) + kick,  ODE x_out = x + (dt/2)(f0 + f1)

@@ -347,6 +347,72 @@ def flow_step(kind, sde, mean_type, cond, uncond, guidance_scale, x, noise, x_pr
     return x_out
 
 
+RK_STAGES = 7          # VAW_RK_STAGES
+
+
+def rk_partial_count(B, per_sample):
+    """Partial sums the rk kernels write for [B, per_sample] tensors (vaw_rk_partial_count): a function of the sizes alone."""
+    return int(L.lib().vaw_rk_partial_count(int(B), int(per_sample)))
+
+
+def _rk_partials(what, partials, B, n):
+    if not (partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= rk_partial_count(B, n)):
+        raise L.VawError(f"{what}: partials is not a contiguous float64 tensor of at least {rk_partial_count(B, n)} elements: "
+                         f"{partials.dtype} {tuple(partials.shape)}")
+
+
+def rk_stage(stage, mean_type, cond, uncond, guidance_scale, x, x_stage, coef, row, k, slots, coeffs, h, x_out=None, x_out_dup=None,
+             x_new=None, atol=0.0, rtol=0.0, partials=None):
+    """The pass after the network evaluation of stage `stage` of an adaptive Runge-Kutta step from x (vaw_rk_stage, float32;
+    include/vaw_hip.h): k[slots[stage]] from the network output (cond / uncond as in edm_step; cond=None: it is there
+    already), then with dy = sum coeffs[s] * k[slots[s]] either the next stage's state x + h * dy into x_out (and x_out_dup)
+    or, with `partials`, the partial sums of the squared error ratio (h * dy) / (atol + rtol * max(|x|, |x_new|)).  Bitwise
+    the tensor composition.  k: [RK_STAGES, *x.shape]; coeffs: a sequence of at most RK_STAGES Python floats (empty: k only)."""
+    need_cuda(cond, uncond, x, x_stage, coef, k, x_out, x_out_dup, x_new, partials)
+    _dense("rk_stage", torch.float32, x.shape, x, x_stage, x_out, x_out_dup, x_new)
+    _dense("rk_stage", torch.float32, (RK_STAGES, *x.shape), k)
+    if len(slots) != RK_STAGES or len(coeffs) > RK_STAGES:
+        raise L.VawError(f"rk_stage: {len(slots)} slots, {len(coeffs)} coefficients for {RK_STAGES} stages")
+    B = x.shape[0]
+    n = x.numel() // max(B, 1)
+    ld = n
+    if cond is not None:
+        _table("rk_stage", coef, torch.float32, FLOW_COLS, row)
+        _f32_parts("rk_stage", x, cond, uncond)
+        (cond, uncond), ld = _rows_in_place((cond, uncond), n)
+    if partials is not None:
+        _rk_partials("rk_stage", partials, B, n)
+    check(L.lib().vaw_rk_stage(int(stage), FLOW_MEAN[mean_type], ptr(cond), ptr(uncond), ld, float(guidance_scale), ptr(x), ptr(x_stage),
+                               ptr(coef) if cond is not None else 0, int(row), coef.shape[0] if cond is not None else 0, ptr(k),
+                               (C.c_int * RK_STAGES)(*[int(s) for s in slots]), (C.c_float * RK_STAGES)(*[float(c) for c in coeffs]),
+                               len(coeffs), float(h), ptr(x_out), ptr(x_out_dup), ptr(x_new), float(atol), float(rtol), ptr(partials),
+                               0 if partials is None else partials.numel(), B, n, stream_ptr()), "vaw_rk_stage")
+    return partials if partials is not None else x_out
+
+
+def rk_scaled_sumsq(u, v, a, b, atol, rtol, partials):
+    """Partial sums of ((u - v) / (atol + rtol * max(|a|, |b|)))^2 over float32 tensors of one shape (vaw_rk_scaled_sumsq):
+    the quotient in float32, squares and sums in float64.  v=None: u alone; b=None: |a| alone.  Fold with rk_sumsq_finish."""
+    need_cuda(u, v, a, b, partials)
+    _dense("rk_scaled_sumsq", torch.float32, u.shape, u, v, a, b)
+    B = u.shape[0]
+    n = u.numel() // max(B, 1)
+    _rk_partials("rk_scaled_sumsq", partials, B, n)
+    check(L.lib().vaw_rk_scaled_sumsq(ptr(u), ptr(v), ptr(a), ptr(b), float(atol), float(rtol), ptr(partials), partials.numel(), B, n,
+                                      stream_ptr()), "vaw_rk_scaled_sumsq")
+    return partials
+
+
+def rk_sumsq_finish(partials, count, out):
+    """out[0] = the first `count` partial sums, folded on the device in a fixed order (vaw_rk_sumsq_finish).  out: a float64
+    tensor (a one-element view of a larger one will do).  Returns out."""
+    need_cuda(partials, out)
+    if not (partials.dtype == out.dtype == torch.float64 and partials.is_contiguous() and 0 < count <= partials.numel() and out.numel() >= 1):
+        raise L.VawError(f"rk_sumsq_finish: {count} of {partials.dtype} {tuple(partials.shape)} into {out.dtype} {tuple(out.shape)}")
+    check(L.lib().vaw_rk_sumsq_finish(ptr(partials), int(count), ptr(out), stream_ptr()), "vaw_rk_sumsq_finish")
+    return out
+
+
 def finish_images(samples, out=None):
     """[B, C, H, W] f32 / f64 samples in [-1, 1] -> [B, H, W, C] uint8 (vaw_finish_images): bitwise
     ((x + 1) * 127.5).clamp(0, 255).to(uint8).permute(0, 2, 3, 1).contiguous() for finite x; NaN writes 0.

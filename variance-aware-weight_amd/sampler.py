@@ -94,7 +94,8 @@ class Sampler:
     Extensions: `decode_fn(latents) -> images in [-1, 1]` stands where the reference loads a diffusers VAE
     (args.in_chans == 4; the latents are handed over already divided by args.latent_scale); with args.cpu_rng the labels
     and every noise draw come from the CPU generator in the reference's order, which reproduces its CPU stream.
-    args.hip_graph=True (EDM and flow generators, whose loops do not synchronise with the host): the first batch runs eagerly,
+    args.hip_graph=True (EDM and flow generators, whose loops do not synchronise with the host; not the adaptive
+    solver="rk45", whose every step the host decides): the first batch runs eagerly,
     the second is captured into one graph on static label and output buffers, later batches replay it; the labels are drawn
     outside the graph in the same order, so images and labels are those of the eager run.  "auto" or absent: eager."""
 
@@ -173,7 +174,9 @@ class Sampler:
     def _use_graph(self):
         if getattr(self.args, "hip_graph", None) is not True:
             return False
-        why = ("not with args.cpu_rng (the noise would come from the host every step)" if self._cpu_rng() else
+        why = ("not with solver rk45 (the host decides every step from the error norm: nothing to capture)"
+               if self.args.model_mode == "flow" and self.args.solver == "rk45" else
+               "not with args.cpu_rng (the noise would come from the host every step)" if self._cpu_rng() else
                "not with args.parallel" if self.args.parallel else
                "the model's forward is not capturable" if getattr(self.model, "graph_capturable", True) is False else
                "needs a CUDA device" if torch.device(self.device).type != "cuda" else None)
@@ -258,7 +261,7 @@ class Sampler:
                 return flow_sde_sample(self.diffusion, cfg_model, noise, self.device, num_steps=a.sample_steps, solver=a.solver,
                                        randn_like=self._randn_like, y=class_labels)
             return flow_ode_sample(self.diffusion, cfg_model, noise, self.device, num_steps=a.sample_steps, solver=a.solver,
-                                   y=class_labels)
+                                   rtol=getattr(a, "rtol", None), atol=getattr(a, "atol", None), y=class_labels)
 
         return self._run(draw, num_samples, sample_size, num_classes, progress_bar, f"Generating Samples ({a.solver.capitalize()})",
                          graph=self._use_graph())

@@ -5,16 +5,22 @@
     tools/sampler.py:160-196 (`--solver euler|heun`, `--discretization`, `--schedule`, `--scaling`);
   * `flow_sde_sample`, `flow_ode_sample`: the FlowMatching samplers of tools/gaussian_diffusion.py:1343-1417.  The reference's
     ODE sampler integrates with torchdiffeq (adaptive dopri5 by default), which is not available here: the fixed-grid
-    solvers euler / midpoint / heun / rk4 are provided on the same time grid, and `dopri5` is refused -- parity unpinned
-    for that one entry point.  The SDE sampler is self-contained in the reference and pinned by tests/golden/samplers.pt.
+    solvers euler / midpoint / heun / rk4 are provided on the same time grid, and the adaptive integrator is provided under
+    a name of its own, `solver="rk45"`: the same Dormand-Prince 5(4) pair with first-same-as-last stage reuse, driven by the
+    step controller of scipy.integrate.solve_ivp(method="RK45") and pinned against it (tests/golden/rk45.npz).  It clips
+    its last step to land on t = 0 where torchdiffeq steps past the end and interpolates back, and torchdiffeq's controller
+    differs in details nothing here can check, so `dopri5` itself stays refused: step-for-step equality with torchdiffeq
+    is unpinned and not claimed.  The SDE sampler is self-contained in the reference and pinned by tests/golden/samplers.pt.
 
 The denoiser call is the hot part and runs on the HIP kernels.  On the GPU the update around it is fused too (`fused=None`):
 everything of a step that does not depend on x is computed once per grid into a device table, cached on the denoiser / flow
 object (`_edm_tables`, `_flow_tables`), and the Euler / Heun steps are single streaming kernels (vaw_edm_input, vaw_edm_step,
 vaw_flow_step; float64 for EDM, as in the reference) that read the table by row, fold the classifier-free guidance
 combination in and write the next network input: bitwise the tensor composition (`fused=False`), with no host
-synchronisation once the tables are cached, so a whole call can be captured into a graph."""
+synchronisation once the tables are cached, so a whole call can be captured into a graph.  The adaptive solver is the
+exception: the host decides every step from one 8-byte read-back of the error norm (vaw_rk_stage, vaw_rk_scaled_sumsq)."""
 
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -467,6 +473,246 @@ def _flow_unsupported(fm, noise, solver):
     return None
 
 
+# ---- adaptive Dormand-Prince 5(4) ---------------------------------------------------------------------------------------------
+# The tableau (C, A with B = A[6], error weights E) and the controller's constants, as scipy.integrate's RK45 has them.
+_DP_C = (0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0, 1.0)
+_DP_A = ((),
+         (1 / 5,),
+         (3 / 40, 9 / 40),
+         (44 / 45, -56 / 15, 32 / 9),
+         (19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729),
+         (9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656),
+         (35 / 384, 0.0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84))
+_DP_E = (-71 / 57600, 0.0, 71 / 16695, -71 / 1920, 17253 / 339200, -22 / 525, 1 / 40)
+_RK_SAFETY, _RK_MIN_FACTOR, _RK_MAX_FACTOR, _RK_EXPONENT = 0.9, 0.2, 10.0, -1 / 5
+
+
+def _ode_tolerances(fm, rtol, atol):
+    """rtol / atol of the adaptive solver: the keyword, then fm's attribute, then fm.args', then the reference's defaults."""
+    def pick(name, given, default):
+        for v in (given, getattr(fm, name, None), getattr(getattr(fm, "args", None), name, None)):
+            if v is not None:
+                return float(v)
+        return default
+    return pick("rtol", rtol, 1e-3), pick("atol", atol, 1e-6)
+
+
+def _rk_combine(coeffs, k):
+    """sum_j coeffs[j] * k[j] in float32: ascending, zero coefficients skipped, left to right (None if all are zero)."""
+    dy = None
+    for c, kj in zip(coeffs, k):
+        if c != 0:
+            dy = c * kj if dy is None else dy + c * kj
+    return dy
+
+
+def _rk_sumsq(u, scale):
+    """sum (u / scale)^2: the quotient in u's dtype (float32), squares and sum in float64, as a Python float."""
+    return float(((u / scale).to(torch.float64) ** 2).sum())
+
+
+class _RK45Composition:
+    """The arithmetic of an adaptive step as tensor operations (any device): what the fused kernels are checked against."""
+
+    def __init__(self, fm, model, noise, rtol, atol, model_kwargs):
+        self.fm, self.model, self.kwargs, self.rtol, self.atol = fm, model, model_kwargs, rtol, atol
+        self.x, self.k, self.nfev, self.readbacks = noise, [None] * 7, 0, 0
+
+    def drift(self, x, t):
+        self.nfev += 1
+        tb, out = _flow_eval(self.fm, self.model, x, torch.tensor(t, dtype=torch.float64, device=x.device), self.kwargs)
+        return _flow_fields(self.fm, out, x, tb)[0]
+
+    def start(self, t):
+        self.k[0] = self.drift(self.x, t)
+        scale = self.atol + self.rtol * self.x.abs()
+        self.readbacks += 1
+        return _rk_sumsq(self.x, scale), _rk_sumsq(self.k[0], scale)
+
+    def trial(self, t, h):
+        f1 = self.drift(self.x + h * _rk_combine((1.0,), self.k), t + h)
+        self.readbacks += 1
+        return _rk_sumsq(f1 - self.k[0], self.atol + self.rtol * self.x.abs())
+
+    def attempt(self, t, h, t_new, have_k1):
+        x, k = self.x, self.k
+        if not have_k1:
+            k[0] = self.drift(x, t)
+        for i in range(1, 7):
+            xi = x + h * _rk_combine(_DP_A[i], k)
+            k[i] = self.drift(xi, t + _DP_C[i] * h if i < 6 else t_new)
+        self.x_new = xi
+        err = h * _rk_combine(_DP_E, k)
+        self.readbacks += 1
+        return _rk_sumsq(err, self.atol + self.rtol * torch.maximum(x.abs(), xi.abs()))
+
+    def accept(self):
+        self.x, self.k[0] = self.x_new, self.k[6]
+
+    def result(self):
+        return self.x
+
+
+class _RK45Fused:
+    """The same on vaw_rk_stage / vaw_rk_scaled_sumsq.  x lives in the first half of a network-input buffer (`cur`), the
+    stage states go straight into another (`stg`), the seventh into a third (`new`), which is the next x: accepting a step
+    swaps `cur` and `new` and the slots of k1 and k7, and copies nothing.  Per attempt: one upload of the seven stage times,
+    the interpolant table computed from them on the device with the expressions of _flow_tables, the (network, vaw_rk_stage)
+    pairs, and one 8-byte read-back of the error's sum of squares."""
+
+    def __init__(self, fm, model, noise, rtol, atol, model_kwargs):
+        n, shape, dev = noise.shape[0], tuple(noise.shape), noise.device
+        self.fm, self.model, self.kwargs, self.rtol, self.atol, self.n = fm, model, model_kwargs, rtol, atol, n
+        y = model_kwargs.get("y")
+        cfg = model if hasattr(model, "guided_halves") else None
+        self.cfg, self.scale = cfg, (cfg.guidance_scale if cfg is not None else 1.0)
+        self.can = cfg is not None and cfg.class_cond and y is not None
+        self.stacked = None
+        if self.can and cfg.guidance_active(sum(cfg.interval) / 2):          # the scale alone can switch guidance off for good
+            if y.shape[0] != n:
+                raise AssertionError(f"CFG expects label batch size {n}, but got {y.shape[0]}.")
+            self.stacked = {**model_kwargs, "y": torch.cat((y, y.new_full(y.shape, cfg.null_label)))}
+        rows = 2 * n if self.stacked is not None else n
+        self.cur, self.stg, self.new = (torch.empty((rows, *shape[1:]), dtype=torch.float32, device=dev) for _ in range(3))
+        for part in self.half(self.cur):
+            if part is not None:
+                part.copy_(noise)
+        self.k = torch.empty((ops.RK_STAGES, *shape), dtype=torch.float32, device=dev)
+        self.slots = list(range(ops.RK_STAGES))
+        self.count = ops.rk_partial_count(n, noise[0].numel())
+        self.partials = torch.empty(self.count, dtype=torch.float64, device=dev)
+        self.sums = torch.zeros(2, dtype=torch.float64, device=dev)
+        self.mean_type = fm.model_mean_type.name
+        self.nfev, self.readbacks = 0, 0
+
+    def half(self, buf):
+        return buf[:self.n], (buf[self.n:] if self.stacked is not None else None)
+
+    def tables(self, times):
+        """For the stage times (host float64): the [len, FLOW_COLS] table on the device, the [len, 2n] float32 times the
+        network gets, and the guidance predicate of each on the host, from the float32 time."""
+        dev = self.cur.device
+        t = torch.tensor(times, dtype=torch.float64).to(dev).to(torch.float32).view(-1, 1)          # the one upload; expand_t_like_x
+        a, s, da, ds = self.fm.interpolant(t)
+        g2 = 2 * s * ds
+        zero = torch.zeros_like(t)
+        cols = [a, s, da, ds, g2, 0.5 * g2, s ** 2, a ** 2 + s ** 2, s * da - a * ds, torch.sqrt(g2), zero, zero, zero, t, zero, zero]
+        guided = [self.stacked is not None and self.cfg.guidance_active(float(np.float32(tm))) for tm in times]
+        return torch.cat(cols, 1).contiguous(), t.repeat(1, 2 * self.n), guided
+
+    def evaluate(self, tab, e, buf):
+        self.nfev += 1
+        coef, times, guided = tab
+        return _evaluate(self.model, self.cfg, guided, self.stacked, buf, self.n, times, e, None, self.kwargs)
+
+    def stage(self, i, out, tab, row, x_stage, coeffs, h, x_out=None, partials=False):
+        cond, uncond = out if out is not None else (None, None)
+        lo, hi = self.half(x_out) if x_out is not None else (None, None)
+        ops.rk_stage(i, self.mean_type, cond, uncond, self.scale, self.cur[:self.n], x_stage, tab[0] if tab is not None else None, row,
+                     self.k, self.slots, coeffs, h, lo, hi, self.new[:self.n] if partials else None, self.atol, self.rtol,
+                     self.partials if partials else None)
+
+    def sumsq(self, u, v, slot):
+        ops.rk_scaled_sumsq(u, v, self.cur[:self.n], None, self.atol, self.rtol, self.partials)
+        ops.rk_sumsq_finish(self.partials, self.count, self.sums[slot:])
+
+    def start(self, t):
+        tab = self.tables([t])
+        self.stage(0, self.evaluate(tab, 0, self.cur), tab, 0, None, (), 0.0)
+        self.sumsq(self.cur[:self.n], None, 0)
+        self.sumsq(self.k[self.slots[0]], None, 1)
+        self.readbacks += 1
+        return tuple(self.sums.tolist())
+
+    def trial(self, t, h):
+        tab = self.tables([t + h])
+        self.stage(0, None, None, 0, None, (1.0,), h, x_out=self.stg)
+        self.stage(1, self.evaluate(tab, 0, self.stg), tab, 0, self.stg[:self.n], (), 0.0)
+        self.sumsq(self.k[self.slots[1]], self.k[self.slots[0]], 0)
+        self.readbacks += 1
+        return self.sums[0].item()
+
+    def attempt(self, t, h, t_new, have_k1):
+        tab = self.tables([t + c * h for c in _DP_C[:6]] + [t_new])
+        self.stage(0, None if have_k1 else self.evaluate(tab, 0, self.cur), tab, 0, None, _DP_A[1], h, x_out=self.stg)
+        for i in range(1, 6):
+            self.stage(i, self.evaluate(tab, i, self.stg), tab, i, self.stg[:self.n], _DP_A[i + 1], h,
+                       x_out=self.stg if i < 5 else self.new)
+        self.stage(6, self.evaluate(tab, 6, self.new), tab, 6, self.new[:self.n], _DP_E, h, partials=True)
+        ops.rk_sumsq_finish(self.partials, self.count, self.sums)
+        self.readbacks += 1
+        return self.sums[0].item()
+
+    def accept(self):
+        self.cur, self.new = self.new, self.cur
+        self.slots[0], self.slots[6] = self.slots[6], self.slots[0]
+
+    def result(self):
+        return self.cur[:self.n].clone()
+
+
+def _rk45_integrate(fm, be, n_elems, max_attempts):
+    """From t = 1 to t = 0 with the step controller of scipy's RK45, in Python float64 on the host; `be` does the tensor work
+    and hands back sums of squares.  The batch is one system with one step size.  Every attempt is clipped to land on the
+    end exactly: the network is never evaluated beyond it and nothing is interpolated.  The first attempt evaluates its first
+    stage itself (the launch that writes the second stage's state needs h, which the first-step selection finds from that
+    same evaluation), every later one gets it from the step before: 2 + 6 * attempts + 1 network evaluations."""
+    t, t_end, direction = 1.0, 0.0, -1.0
+    interval = abs(t_end - t)
+    rms = lambda sumsq: math.sqrt(sumsq / n_elems)
+    # first step (Hairer, Norsett, Wanner I, II.4; scipy's select_initial_step with the order of the error estimator, 4)
+    d0, d1 = (rms(v) for v in be.start(t))
+    if not (math.isfinite(d0) and math.isfinite(d1)):
+        raise FloatingPointError(f"flow_ode_sample: non-finite state or drift at t={t} (before the first step, h undefined)")
+    h0 = min(1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1, interval)
+    d2 = rms(be.trial(t, direction * h0)) / h0
+    if not math.isfinite(d2):
+        raise FloatingPointError(f"flow_ode_sample: non-finite drift in the first-step trial at t={t}, h={direction * h0}")
+    h1 = max(1e-6, h0 * 1e-3) if d1 <= 1e-15 and d2 <= 1e-15 else (0.01 / max(d1, d2)) ** (1 / 5)
+    h_abs = min(100 * h0, h1, interval)
+    stats = dict(accepted=0, rejected=0, nfev=0, readbacks=0, h_min=math.inf, h_max=0.0, trace=[])
+    fm.last_ode_stats = stats
+    attempts, have_k1 = 0, False
+    try:
+        while direction * (t - t_end) < 0:
+            min_step = 10 * abs(float(np.nextafter(t, direction * np.inf)) - t)
+            h_abs = max(h_abs, min_step)
+            step_rejected = False
+            while True:
+                if h_abs < min_step:
+                    raise RuntimeError(f"flow_ode_sample: the step size fell below the spacing of t at t={t} (h={h_abs})")
+                if attempts >= max_attempts:
+                    raise RuntimeError(f"flow_ode_sample: more than max_attempts={max_attempts} attempts (t={t}, h={h_abs})")
+                t_new = t + h_abs * direction
+                if direction * (t_new - t_end) > 0:
+                    t_new = t_end
+                h = t_new - t
+                h_abs = abs(h)
+                attempts += 1
+                sumsq = be.attempt(t, h, t_new, have_k1)
+                have_k1 = True
+                norm = rms(sumsq) if math.isfinite(sumsq) else math.nan
+                stats["trace"].append((t, h, norm))
+                if not math.isfinite(norm):
+                    raise FloatingPointError(f"flow_ode_sample: non-finite error norm at t={t}, h={h}")
+                if norm < 1:
+                    factor = _RK_MAX_FACTOR if norm == 0 else min(_RK_MAX_FACTOR, _RK_SAFETY * norm ** _RK_EXPONENT)
+                    if step_rejected:
+                        factor = min(1.0, factor)
+                    stats["accepted"] += 1
+                    stats["h_min"], stats["h_max"] = min(stats["h_min"], h_abs), max(stats["h_max"], h_abs)
+                    h_abs *= factor
+                    be.accept()
+                    t = t_new
+                    break
+                h_abs *= max(_RK_MIN_FACTOR, _RK_SAFETY * norm ** _RK_EXPONENT)
+                step_rejected = True
+                stats["rejected"] += 1
+    finally:
+        stats["nfev"], stats["readbacks"] = be.nfev, be.readbacks
+    return be.result()
+
+
 @torch.no_grad()
 def flow_sde_sample(fm, model, noise, device=None, num_steps=50, solver="heun", randn_like=torch.randn_like, fused=None, **model_kwargs):
     """Reverse-time SDE of the flow (reference sde_sample :1374-1409): drift = v - (1/2) g^2 score with g^2 = 2 sigma_t sigma_t',
@@ -503,14 +749,28 @@ def flow_sde_sample(fm, model, noise, device=None, num_steps=50, solver="heun", 
 
 
 @torch.no_grad()
-def flow_ode_sample(fm, model, noise, device=None, num_steps=50, solver="heun", fused=None, **model_kwargs):
-    """Probability-flow ODE dx/dt = v(x, t) from t = 1 to 0 on the reference's grid linspace(1, 0, num_steps) (ode_sample
-    :1355-1366) with a FIXED-grid solver: euler | midpoint | heun | rk4.  The reference hands the same drift to
-    torchdiffeq.odeint (dopri5 by default); that adaptive integrator is not restated here.  fused: as in edm_sample, for
-    euler and heun (midpoint and rk4 stay the tensor composition; fused=True refuses them)."""
+def flow_ode_sample(fm, model, noise, device=None, num_steps=50, solver="heun", fused=None, rtol=None, atol=None, max_attempts=1000,
+                    **model_kwargs):
+    """Probability-flow ODE dx/dt = v(x, t) from t = 1 to 0: with a FIXED-grid solver, euler | midpoint | heun | rk4, on the
+    reference's grid linspace(1, 0, num_steps) (ode_sample :1355-1366), or adaptively with solver="rk45" (Dormand-Prince
+    5(4) under scipy's RK45 step controller, `_rk45_integrate`), which ignores num_steps and takes rtol / atol: the keyword,
+    else fm.rtol / fm.atol, else fm.args.rtol / fm.args.atol, else 1e-3 / 1e-6 (the reference's sample.py defaults) -- and
+    leaves fm.last_ode_stats = {accepted, rejected, nfev, readbacks, h_min, h_max (accepted steps), trace: (t, h, error
+    norm) of every attempt}.  It raises instead of looping: FloatingPointError on a non-finite error norm, RuntimeError when
+    the step falls below the spacing of t or after max_attempts attempts.  The reference hands the same drift to torchdiffeq.odeint (dopri5 by
+    default); `dopri5` stays refused because equality with torchdiffeq's steps cannot be pinned here.  Mean types whose
+    conversion is singular at an end of the interval (EPSILON on the linear path at t = 1, START_X at t = 0) are the
+    caller's business, as in the reference.  fused: as in edm_sample, for euler, heun and rk45 (midpoint and rk4 stay the
+    tensor composition; fused=True refuses them)."""
     if solver == "dopri5":
         raise NotImplementedError("flow_ode_sample: the adaptive dopri5 of torchdiffeq (not installed; parity unpinned) is not "
-                                  "restated; use euler | midpoint | heun | rk4 on the same grid")
+                                  "restated; use solver='rk45' (the same Dormand-Prince pair under scipy's step controller) or "
+                                  "euler | midpoint | heun | rk4 on the fixed grid")
+    if solver == "rk45":
+        rtol, atol = _ode_tolerances(fm, rtol, atol)
+        use = _want_fused(fused, noise, "flow_ode_sample", _flow_unsupported(fm, noise, "euler"))
+        backend = (_RK45Fused if use else _RK45Composition)(fm, model, noise, rtol, atol, model_kwargs)
+        return _rk45_integrate(fm, backend, noise.numel(), max_attempts)
     if solver not in ("euler", "midpoint", "heun", "rk4"):
         raise ValueError(f"Unknown solver: {solver}")
     if _want_fused(fused, noise, "flow_ode_sample", _flow_unsupported(fm, noise, solver)):

@@ -510,6 +510,33 @@ int vaw_gemm_plan(vaw_dtype dt, int a_kmajor, int b_kmajor, int64_t M, int64_t N
                   int64_t ldc, int64_t A, int64_t B, int64_t C, const vaw_epilogue* epi_host, int64_t workspace_floats,
                   const vaw_gemm_knobs* knobs, vaw_gemm_launch* out);
 
+/* Launch plan of vaw_gemm_fp8, likewise the one host function it takes every check and launch choice from (pure arithmetic: it
+ * can be asked without a GPU).  The arguments of vaw_gemm_fp8 with addresses as integers, used for null-ness and alignment only
+ * (colsum_rows_out is read: the stated capacity; scale_a / scale_b may be 0), plus cus: the CUs the persistent grid may use,
+ * 0 = what the process has now (vaw_p8_set_reserved_cus moves it); a stated value makes the plan a pure function.
+ * A refused call returns what vaw_gemm_fp8 returns, with the same error text, and leaves that code in status. */
+typedef struct {
+    int epi_kind;                   /* P8_* kind of csrc/gemm_epi.h: 0 STORE, 1 GELU, 2 DGELU, 3 GATE, 8 GELU_Q, 9 DGELU_Q (C as fp8
+                                     * bytes); -1 while no kind is chosen */
+    int a_e5m2;                     /* A holds e5m2 bytes (VAW_BF8), else e4m3 */
+    int c_fp8, c_e5m2;              /* C is written as fp8 bytes (c_fp8_state given), and their format */
+    int ntw;                        /* tile columns / 64 (3 | 4); tiles are 256 rows */
+    int tiles_m, tiles_n;           /* items = tiles_m * tiles_n * split, dealt to the workgroups round-robin */
+    int nk;                         /* K tiles of 128 */
+    int split;                      /* K splits: always 1 */
+    int grid, block;
+    int64_t lds_bytes;
+    int colsum_mode;                /* vaw_gemm_colsum_mode: NONE, FOLD (partial rows in the workspace, folded by vaw_reduce_rows) or
+                                     * DEFERRED (colsum_partial_out) */
+    int64_t colsum_rows;            /* partial rows the launch writes: ceil(M / 128), or 0 */
+    int64_t workspace_floats_used;  /* colsum_rows * N for FOLD, else 0 */
+    int launches;
+    int status;
+} vaw_gemm_fp8_launch;
+int vaw_gemm_fp8_plan(vaw_dtype a_format, int64_t M, int64_t N, int64_t K, int64_t A, int64_t lda, int64_t scale_a, int64_t B,
+                      int64_t ldb, int64_t scale_b, int64_t C, int64_t ldc, const vaw_epilogue* epi_host, int64_t c_fp8_state,
+                      vaw_dtype c_fp8_format, int64_t workspace, int64_t workspace_floats, int cus, vaw_gemm_fp8_launch* out);
+
 /* out[n] = beta*out[n] + sum_m X[m,n]  (bias gradients). X act dtype, out f32.  Two fixed-order stages through a
  * caller-provided f32 workspace of vaw_colsum_workspace_floats(M,N) elements: no atomics, bitwise reproducible. */
 int64_t vaw_colsum_workspace_floats(int64_t M, int64_t N);

@@ -23,6 +23,10 @@ Bound, element by element, the same expressions in absolute values (u = 2^-24, t
 One constant c per dtype, C_BOUND, the same for every variant and case: 1 for both.  Worst err / bound per variant on the MI355X
 (pytest -m gpu tests/test_gpu_gemm.py --junitxml): see MEASURED below and DESIGN.md.
 
+vaw_gemm_fp8 (FP8_CASES, the second half of this file; test_gemm_fp8_parity_cpu.py and test_gpu_gemm_fp8.py) goes through the same
+evaluate(): fp8 operand values, alpha times the two dequantisation scales on the accumulator, its own constant C_BOUND["fp8"], and
+for the kinds that write C as fp8 bytes the outputs Cq (decoded bytes) and amax (the running max) next to C.
+
 simulate() is the comparator's own test object: the reference rounded at the stated points ("kernel output" made on the CPU), with
 one injected fault at a time (FAULTS)."""
 import zlib
@@ -30,11 +34,14 @@ import zlib
 import torch
 
 U32 = 2.0 ** -24
-UNIT = {"bf16": 2.0 ** -8, "f32": U32}
-C_BOUND = {"bf16": 1.0, "f32": 1.0}
+UNIT = {"bf16": 2.0 ** -8, "f32": U32, "e4m3": 2.0 ** -4, "e5m2": 2.0 ** -3}      # half an ulp, relative
+C_BOUND = {"bf16": 1.0, "f32": 1.0, "fp8": 4.0}
+FMAX = {"e4m3": 448.0, "e5m2": 57344.0}                  # largest finite value
+FMAX_BYTE = {"e4m3": 0x7E, "e5m2": 0x7B}                 # ... and its byte pattern
+SUB_HALF = {"e4m3": 2.0 ** -10, "e5m2": 2.0 ** -17}      # half the smallest subnormal step
 EPI_F32_OPS = 8
 GELU_GRAD_SUP = 1.13              # sup |d/dx gelu_tanh(x)| = 1.1289 (x = 1.47)
-TORCH_DT = {"bf16": torch.bfloat16, "f32": torch.float32}
+TORCH_DT = {"bf16": torch.bfloat16, "f32": torch.float32, "e4m3": torch.float8_e4m3fn, "e5m2": torch.float8_e5m2}
 WS_FLOATS = 1 << 26               # the grow-only scratch ops.gemm hands to vaw_gemm when the call may need one
 
 # worst err / bound per variant on the MI355X, default process knobs, c = 1: (outputs stored as bf16, outputs stored as f32).  The
@@ -43,13 +50,39 @@ WS_FLOATS = 1 << 26               # the grow-only scratch ops.gemm hands to vaw_
 MEASURED = {"generic": (0.987, 0.686), "t128_bk32": (0.995, None), "t128_bk64": (0.988, 0.207), "ring256": (0.991, 0.209),
             "persistent": (0.991, 0.111), "small_m": (0.993, 0.212), "parked_drain": (0.986, 0.111), "warp_spec": (0.986, 0.111)}
 
+# vaw_gemm_fp8 per epilogue kind, same run, c = C_BOUND["fp8"] = 4: (outputs stored as bf16, outputs stored as f32, fp8 bytes, running max).
+# With c = 1 the f32-stored outputs gave 0.292 (K = 384), 0.339 (K = 256, cancelling products) and 2.067 (K = 128, 16 x 200), and
+# the whole-tile K = 128 GELU' case 1.045 on a bf16 output: one v_mfma_scale_f32_16x16x128_f8f6f4 does not add its 128 products as an
+# f32 chain.  It lines them up under the largest of them and cuts what lies about 13 bits below it (probe: 256 + 127 x 2^-6 comes
+# back as 257.875 for 257.984, 256 + 127 x 2^-10 as 256; max |err| over a 16 x 200 output = 2^-12.6 of that largest product at
+# K = 128), an error that does not grow with K while K u |A| |B| does -- so the shortest K is the worst case, and 4 is the next power
+# of two above it.  Every injected fault is still caught with c = 4 (test_gemm_fp8_parity_cpu.py; the closest is 85 times the bound).
+MEASURED_FP8 = {"P8_STORE": (0.981, 0.517, None, None), "P8_GELU": (0.982, None, None, None), "P8_GELU_Q": (0.982, None, 0.905, 0.037),
+                "P8_DGELU": (0.955, None, None, None), "P8_DGELU_Q": (0.921, None, 0.878, 0.491), "P8_GATE": (0.950, 0.030, None, None),
+                "wgrad_grouped": (None, 0.088, None, None)}
+
 P8 = ("P8_STORE", "P8_GELU", "P8_DGELU", "P8_GATE", "P8_SLAB", "P8_ANY", "P8_WGRAD", "P8_RESID")
 TARGET_FIELDS = ("variant", "ntw", "sm", "epi_kind", "split", "reduce", "rowsum_mode", "colsum_mode", "xcd")
 
 
-def rnd(x, dt):
-    """x (float64) rounded to the storage format, back in float64"""
+def rnd(x, dt, saturate=True):
+    """x (float64) rounded to the storage format, back in float64.  fp8: values beyond the largest finite one saturate (torch's own
+    cast does not: 500.0 -> NaN as e4m3fn), unless saturate = False"""
+    if dt in FMAX:
+        if saturate:
+            x = x.clamp(-FMAX[dt], FMAX[dt])
+        return x.float().to(TORCH_DT[dt]).double()
     return x.to(TORCH_DT[dt]).double()
+
+
+def fp8_bytes(x, dt):
+    """fp8 values (float64) -> their byte patterns (uint8)"""
+    return x.float().to(TORCH_DT[dt]).view(torch.uint8)
+
+
+def fp8_decode(b, dt):
+    """byte patterns (uint8) -> float64 values"""
+    return b.view(TORCH_DT[dt]).double()
 
 
 def gelu(x):
@@ -399,20 +432,35 @@ def products(c, t, fault=None):
 # reference, bound, simulated kernel
 # ------------------------------------------------------------------------------------------------------------------------------
 FAULTS = ("drop_k_tile", "bias_shift8", "gate_prev_sample", "rowadd_div", "resid_row_down", "drop_beta", "alpha_after_bias",
-          "colsum_last_row", "rowsum_one_split", "dgelu_unrounded")
+          "colsum_last_row", "rowsum_one_split", "dgelu_unrounded", "aux_in_row_down", "drop_scale_b", "a_decoded_as_e4m3",
+          "q_scale_not_inverted", "q_unsaturated", "q_amax_unrounded")
 FAULT_WITHIN_BOUND = ("dgelu_unrounded",)
+FP8_FAULTS = ("drop_scale_b", "a_decoded_as_e4m3", "q_scale_not_inverted", "q_unsaturated", "q_amax_unrounded")      # need an fp8 case
+
 
 
 def rounds_gradient(c):
     """parked-drain / warp-specialised GELU': the bf16 gradient is rounded before the multiply"""
-    return c["target"]["variant"] in ("parked_drain", "warp_spec") and c["act"] == 2
+    return c["target"].get("variant") in ("parked_drain", "warp_spec") and c["act"] == 2
 
 
 def fault_applies(c, fault):
     """a fault needs the epilogue field it corrupts"""
     return {"drop_k_tile": True, "bias_shift8": bool(c["bias"]), "gate_prev_sample": bool(c["gate"]), "rowadd_div": bool(c["rowadd"]),
-            "resid_row_down": bool(c["resid"]), "drop_beta": c["beta"] != 0.0, "alpha_after_bias": c["alpha"] != 1.0 and bool(c["bias"]),
-            "colsum_last_row": bool(c["colsum"]), "rowsum_one_split": bool(c["rowsum"]), "dgelu_unrounded": rounds_gradient(c)}[fault]
+            "resid_row_down": bool(c["resid"]), "drop_beta": c["beta"] != 0.0, "alpha_after_bias": alpha_eff(c) != 1.0 and bool(c["bias"]),
+            "colsum_last_row": bool(c["colsum"]), "rowsum_one_split": bool(c["rowsum"]), "dgelu_unrounded": rounds_gradient(c),
+            "aux_in_row_down": c["act"] == 2, "drop_scale_b": "scale_b" in c, "a_decoded_as_e4m3": c.get("a_fmt") == "e5m2",
+            "q_scale_not_inverted": bool(c.get("q_fmt")), "q_unsaturated": bool(c.get("q_fmt")), "q_amax_unrounded": bool(c.get("q_fmt"))}[fault]
+
+
+def alpha_eff(c, drop_scale_b=False):
+    """the factor on the accumulator, in float64: alpha, times the two f32 dequantisation scales of an fp8 case"""
+    a = float(c["alpha"])
+    if "scale_a" in c:
+        a *= float(rnd(torch.tensor(c["scale_a"], dtype=torch.float64), "f32"))
+        if not drop_scale_b:
+            a *= float(rnd(torch.tensor(c["scale_b"], dtype=torch.float64), "f32"))
+    return a
 
 
 def _rows(M, dev):
@@ -425,11 +473,13 @@ def evaluate(c, t, prod, stored=None, fault=None):
     the reference continues from its aux_out, and takes the column sums from its C."""
     acc, absacc, Aop, Bop = prod
     M, N, K, dt = c["M"], c["N"], c["K"], c["dt"]
-    dev, cb, u_act, u_out = acc.device, C_BOUND[c["dt"]], UNIT[c["dt"]], UNIT[out_dt(c)]
-    alpha, beta = c["alpha"], c["beta"]
+    dev, cb, u_act, u_out = acc.device, C_BOUND[c.get("cb", c["dt"])], UNIT[c["dt"]], UNIT[out_dt(c)]
+    alpha, beta = alpha_eff(c, drop_scale_b=fault == "drop_scale_b"), c["beta"]
     ref, bound, sim = {}, {}, {}
+    if fault == "a_decoded_as_e4m3":       # the e5m2 bytes of A read as e4m3
+        acc = fp8_decode(fp8_bytes(Aop.contiguous(), "e5m2"), "e4m3") @ Bop
     if fault == "drop_k_tile":
-        k0 = max(0, K - 64)
+        k0 = max(0, K - c.get("ktile", 64))
         acc = acc - Aop[:, k0:] @ Bop[k0:]
     bias = t["bias"] if c["bias"] else torch.zeros(N, dtype=torch.float64, device=dev)
     if fault == "bias_shift8":
@@ -447,7 +497,11 @@ def evaluate(c, t, prod, stored=None, fault=None):
         v = gelu(v)
         E = E * GELU_GRAD_SUP
     elif c["act"] == 2:
-        gp = gelu_grad(t["aux_in"])
+        ai = t["aux_in"]
+        if fault == "aux_in_row_down":         # the last 64-row tile reads the row below (the last row its own)
+            mi = _rows(M, dev)
+            ai = ai[torch.where(mi >= (M - 1) // 64 * 64, torch.clamp(mi + 1, max=M - 1), mi)]
+        gp = gelu_grad(ai)
         if rounds_gradient(c):
             R = UNIT["bf16"] * v.abs() * gp.abs()
             if fault != "dgelu_unrounded" and stored is None:
@@ -476,6 +530,19 @@ def evaluate(c, t, prod, stored=None, fault=None):
             v = v + beta * t["C_old"]
     ref["C"], bound["C"] = v, cb * (E + EPI_F32_OPS * U32 * mag) + R + u_out * v.abs()
     sim["C"] = rnd(v, out_dt(c))
+    if c.get("q_fmt"):
+        # C leaves as fp8 bytes: r = bf16(v), q = fmt(clamp(r / scale)); the running max takes max |r|.  "C" stays an output of the
+        # case: the bf16 tensor the bytes are made of (on the GPU the non-quantising twin launch writes it)
+        qf, sc = c["q_fmt"], t["q_scale"]
+        lim = FMAX[qf] * sc
+        vc = v.clamp(-lim, lim)
+        ref["Cq"], bound["Cq"] = vc, bound["C"] + UNIT[qf] * vc.abs() + SUB_HALF[qf] * sc
+        lo, hi = (v.abs() - bound["C"]).max(), (v.abs() + bound["C"]).max()       # max |r| for any r within the bound of v
+        ref["amax"], bound["amax"] = 0.5 * (lo + hi), 0.5 * (hi - lo)
+        if stored is None:
+            x = sim["C"] * sc if fault == "q_scale_not_inverted" else sim["C"] / sc
+            sim["Cq"] = rnd(x, qf, saturate=fault != "q_unsaturated") * sc
+            sim["amax"] = rnd(v.abs().max(), "f32") if fault == "q_amax_unrounded" else sim["C"].abs().max()
     if c["colsum"]:
         Cs = stored["C"] if stored is not None else sim["C"]
         old = c["colsum_beta"] * t["colsum_old"] if c["colsum"] == "out" else torch.zeros(N, dtype=torch.float64, device=dev)
@@ -516,6 +583,13 @@ def ratios(c, t, prod, got):
             continue
         q = torch.where(b > 0, err / torch.where(b > 0, b, torch.ones_like(b)), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
         out[k] = float(q.max())
+        if k == "Cq":          # an element certainly beyond the format's range must decode to exactly +-FMAX
+            lim = FMAX[c["q_fmt"]] * t["q_scale"]
+            sure = ref["C"].abs() - bound["C"] > lim
+            if not bool((got[k][sure] == torch.sign(ref["C"][sure]) * lim).all()):
+                out[k] = float("inf")
+        if k == "amax" and float(rnd(got[k], "bf16")) != float(got[k]):       # the max of bf16 values is one of them
+            out[k] = float("inf")
     return out
 
 
@@ -569,3 +643,160 @@ def plan_of(c, L, ops, knobs="default", addr=None, workspace=None):
     cap = -(-c["M"] // 64) if c["colsum"] == "partial" else None
     return ops.gemm_plan(*args, workspace_floats=workspace_floats(c) if workspace is None else workspace, knobs=knobs,
                          colsum_partial_rows=cap, **kw)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# vaw_gemm_fp8: A [M][K] values of a_fmt (e4m3 | e5m2), B [N][K] e4m3 values, both k-major; the same reference and bound with
+#     alpha_eff = alpha * scale_a * scale_b   (float64 product of the f32 scales; neither a power of two, and not equal)
+# on the accumulator (products of two fp8 values are exact in f32, so E = K u |alpha_eff| |A| |B| is the f32 accumulation alone),
+# C_BOUND["fp8"], and K tiles of 128.  The *_Q kinds write C as fp8 bytes of q_fmt:
+#     r = bf16(v), q = fmt(clamp(r / state[0], +-FMAX)), state[1] = max(state[1], max |r|)
+#     Cq:   |decode(q) state[0] - clamp(v, +-FMAX state[0])| <= bound(C as bf16) + UNIT[fmt] |clamp(v)| + SUB_HALF[fmt] state[0];
+#           an element with |v| - bound(C) > FMAX state[0] decodes to exactly +-FMAX; no NaN / Inf pattern
+#     amax: within [max(|v| - bound(C)), max(|v| + bound(C))], and a bf16 value
+# state[0] comes from the reference alone: the 0.99 quantile of |r| over FMAX (prepare_q), so about 1 % of the elements saturate.
+# ------------------------------------------------------------------------------------------------------------------------------
+FP8_SCALE_A = 0.3
+FP8_TARGET_FIELDS = ("epi_kind", "a_fmt", "ntw", "rounds")
+FP8_PAD = (16, 32, 8)
+FP8_KINDS = {("P8_STORE", "e4m3"), ("P8_GELU", "e4m3"), ("P8_GELU_Q", "e4m3"), ("P8_DGELU", "e4m3"), ("P8_DGELU_Q", "e4m3"),
+             ("P8_GATE", "e4m3"), ("P8_STORE", "e5m2"), ("P8_DGELU", "e5m2"), ("P8_DGELU_Q", "e5m2")}
+F32OUT = dict(out_f32=1)
+DGELU_PART = dict(act=2, colsum="partial")
+
+# shapes: M-and-N edges (264 x 200: 8 live rows in the second row tile, 200 of 256 columns; 200 x 264: 72 live columns in the second
+# 192-column tile), whole tiles with one K tile, the smallest admitted, and two launches of more than one item per workgroup on a
+# grid of 16 (cus = 16: run under vaw_p8_set_reserved_cus)
+E4, E3, W4, W3, S3, S4 = (264, 200, 256), (200, 264, 384), (256, 256, 128), (256, 192, 128), (16, 16, 128), (16, 200, 128)
+# (name, shape, a_fmt, epilogue, extras, target = (epi_kind, a_fmt, ntw, rounds > 1))
+_FP8_SPECS = [
+    ("f8_store_e4_ntw4_bias_edge", E4, "e4m3", BIAS, {}, ("P8_STORE", "e4m3", 4, False)),
+    ("f8_store_e4_ntw3_alpha_f32_edge", E3, "e4m3", dict(bias=1, alpha=0.25, out_f32=1), {}, ("P8_STORE", "e4m3", 3, False)),
+    ("f8_store_e4_ntw4_cancel_f32", E4, "e4m3", F32OUT, dict(regime="cancel"), ("P8_STORE", "e4m3", 4, False)),
+    ("f8_store_e4_ntw3_colsum_beta", W3, "e4m3", CS_OUT, {}, ("P8_STORE", "e4m3", 3, False)),
+    ("f8_store_e4_ntw4_colsum_partial_edge", E4, "e4m3", CS_PART, {}, ("P8_STORE", "e4m3", 4, False)),
+    ("f8_store_e4_ntw3_smallest", S3, "e4m3", BIAS, {}, ("P8_STORE", "e4m3", 3, False)),
+    ("f8_store_e4_ntw4_smallest_f32", S4, "e4m3", F32OUT, {}, ("P8_STORE", "e4m3", 4, False)),
+    ("f8_store_e4_ntw3_ld_padded", E3, "e4m3", BIAS, dict(pad=FP8_PAD), ("P8_STORE", "e4m3", 3, False)),
+    ("f8_store_e5_ntw4_bias_edge", E4, "e5m2", BIAS, {}, ("P8_STORE", "e5m2", 4, False)),
+    ("f8_store_e5_ntw3_colsum_partial_edge", E3, "e5m2", CS_PART, {}, ("P8_STORE", "e5m2", 3, False)),
+    ("f8_gelu_ntw4_wide_edge", E4, "e4m3", GELU, dict(regime="wide"), ("P8_GELU", "e4m3", 4, False)),
+    ("f8_gelu_ntw3_ld_padded_edge", E3, "e4m3", GELU, dict(pad=FP8_PAD), ("P8_GELU", "e4m3", 3, False)),
+    ("f8_gelu_ntw4_whole", W4, "e4m3", GELU, {}, ("P8_GELU", "e4m3", 4, False)),
+    ("f8_gelu_ntw3_rounds", (1288, 576, 256), "e4m3", GELU, dict(cus=16), ("P8_GELU", "e4m3", 3, True)),
+    ("f8_geluq_ntw4_ld_padded_edge", E4, "e4m3", GELU, dict(q_fmt="e4m3", pad=FP8_PAD), ("P8_GELU_Q", "e4m3", 4, False)),
+    ("f8_geluq_ntw3_edge", E3, "e4m3", GELU, dict(q_fmt="e4m3"), ("P8_GELU_Q", "e4m3", 3, False)),
+    ("f8_geluq_ntw3_whole_e5m2_out", W3, "e4m3", GELU, dict(q_fmt="e5m2"), ("P8_GELU_Q", "e4m3", 3, False)),
+    ("f8_dgelu_e4_ntw4_wide_edge", E4, "e4m3", DGELU, dict(regime="wide"), ("P8_DGELU", "e4m3", 4, False)),
+    ("f8_dgelu_e4_ntw3_colsum_partial_edge", E3, "e4m3", DGELU_PART, {}, ("P8_DGELU", "e4m3", 3, False)),
+    ("f8_dgelu_e4_ntw4_colsum_beta", W4, "e4m3", DGELU_CS, {}, ("P8_DGELU", "e4m3", 4, False)),
+    ("f8_dgelu_e4_ntw4_rounds_colsum_partial", (1032, 1000, 256), "e4m3", DGELU_PART, dict(cus=16), ("P8_DGELU", "e4m3", 4, True)),
+    ("f8_dgelu_e5_ntw4_colsum_partial_ld_padded_edge", E4, "e5m2", DGELU_PART, dict(pad=FP8_PAD), ("P8_DGELU", "e5m2", 4, False)),
+    ("f8_dgelu_e5_ntw3_wide_edge", E3, "e5m2", DGELU, dict(regime="wide"), ("P8_DGELU", "e5m2", 3, False)),
+    ("f8_dgeluq_e4_ntw4_edge", E4, "e4m3", DGELU, dict(q_fmt="e5m2"), ("P8_DGELU_Q", "e4m3", 4, False)),
+    ("f8_dgeluq_e4_ntw3_colsum_beta_edge", E3, "e4m3", DGELU_CS, dict(q_fmt="e4m3"), ("P8_DGELU_Q", "e4m3", 3, False)),
+    # the launch DiT's backward makes for fc2's input gradient: e5m2 dy, GELU', e5m2 bytes out, deferred column sums
+    ("f8_dgeluq_e5_ntw4_colsum_partial_ld_padded_edge", E4, "e5m2", DGELU_PART, dict(q_fmt="e5m2", pad=FP8_PAD), ("P8_DGELU_Q", "e5m2", 4, False)),
+    ("f8_dgeluq_e5_ntw3_edge", E3, "e5m2", DGELU, dict(q_fmt="e5m2"), ("P8_DGELU_Q", "e5m2", 3, False)),
+    ("f8_gate_ntw4_rpb27_edge", E4, "e4m3", GATE27, {}, ("P8_GATE", "e4m3", 4, False)),
+    ("f8_gate_ntw3_rpb24_ld_padded_edge", E3, "e4m3", GATE, dict(pad=FP8_PAD), ("P8_GATE", "e4m3", 3, False)),
+]
+
+
+def _build_fp8_cases():
+    out = {}
+    for name, (M, N, K), a_fmt, epi, kw, target in _FP8_SPECS:
+        assert name not in out, name
+        kw = dict(kw)
+        extra = dict(a_fmt=a_fmt, q_fmt=kw.pop("q_fmt", None), cus=kw.pop("cus", 256), scale_a=FP8_SCALE_A, scale_b=1.7 / K ** 0.5,
+                     cb="fp8", ktile=128)
+        c = _c(name, -1, (1, 1), M, N, K, (None,) * len(TARGET_FIELDS), **kw, **epi)
+        c.update(extra)
+        c["target"] = dict(zip(FP8_TARGET_FIELDS, target))
+        out[name] = c
+    return out
+
+
+FP8_CASES = _build_fp8_cases()
+
+
+def is_edge(c):
+    """live rows and live columns end inside a tile of the case's kernel"""
+    return c["M"] % 256 != 0 and c["N"] % (64 * c["target"]["ntw"]) != 0 and c["M"] > 256 - 64 and c["N"] > 64
+
+
+def make_fp8_inputs(c):
+    """as make_inputs: name -> float64 CPU tensor; A holds values of a_fmt, B e4m3 values (about N(0, 1) both: scale_b carries the
+    1 / sqrt(K)).  A *_Q case still needs prepare_q."""
+    g = torch.Generator().manual_seed(zlib.crc32(c["name"].encode()))
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    uni = lambda *s: (torch.rand(*s, generator=g, dtype=torch.float64) * 12.0 - 6.0)
+    M, N, K = c["M"], c["N"], c["K"]
+    A, B = rnd(r(M, K), c["a_fmt"]), rnd(r(N, K), "e4m3")
+    if c["regime"] == "cancel":
+        # the second half of K undoes the first but for one element in eight, which moves by a step or two of the format
+        h = K // 2
+        A[:, h:] = A[:, :h]
+        nudge = (torch.rand(N, h, generator=g, dtype=torch.float64) < 0.125).double()
+        B[:, h:] = rnd(-B[:, :h] * (1.0 + 0.125 * nudge), "e4m3")
+    wide = c["regime"] == "wide"
+    t = {"A": A, "B": B}
+    if c["bias"]:
+        t["bias"] = rnd(uni(N) if wide else r(N), "f32")
+    if c["act"] == 2:
+        t["aux_in"] = rnd(uni(M, N) if wide else r(M, N), "bf16")
+    if c["gate"]:
+        t["gate"] = rnd(r(-(-M // c["rpb"]), N), "f32")
+    if c["resid"]:
+        t["resid"] = rnd(r(M, N), "f32")
+    if c["colsum"] == "out":
+        t["colsum_old"] = rnd(r(N), "f32")
+    return t
+
+
+def prepare_q(c, t, prod):
+    """A *_Q case's scale, from the reference alone: t["q_scale"] = f32(0.99 quantile of |bf16(v)| / FMAX) as a float64 0-dim tensor on
+    the products' device.  -> the share of elements that saturate under it (the tests hold it between 0.1 % and 5 %)."""
+    if not c["q_fmt"]:
+        return None
+    r = rnd(evaluate(dict(c, q_fmt=None), t, prod)[0]["C"], "bf16").abs().flatten()
+    q99 = torch.sort(r).values[int(0.99 * (r.numel() - 1))]
+    t["q_scale"] = rnd(q99 / FMAX[c["q_fmt"]], "f32")
+    return float((r / t["q_scale"] > FMAX[c["q_fmt"]]).double().mean())
+
+
+def fp8_plan_call(c, addr=None):
+    """(positional arguments, keyword arguments) shared by ops.gemm_fp8_plan and ops.gemm_fp8 for the case.  addr: name -> device
+    address; None: aligned stand-ins."""
+    g = geometry(c)
+    if addr is None:
+        addr = {k: 1 << 20 for k in ("A", "B", "C", "scale_a", "scale_b", "bias", "aux_in", "aux_out", "gate", "resid", "colsum_out")}
+    args = (c["M"], c["N"], c["K"], addr["A"], g["lda"], addr["scale_a"], addr["B"], g["ldb"], addr["scale_b"], addr["C"], g["ldc"])
+    kw = dict(a_format=3 if c["a_fmt"] == "e5m2" else 2, act=c["act"], alpha=c["alpha"], out_f32=bool(c["out_f32"]), rows_per_batch=c["rpb"])
+    if c["bias"]:
+        kw["bias"] = addr["bias"]
+    if c["act"] == 2:
+        kw["aux_in"] = addr["aux_in"]
+    if c["aux_out"]:
+        kw["aux_out"] = addr["aux_out"]
+    if c["gate"]:
+        kw.update(gate=addr["gate"], gate_ld=g["gate_ld"], resid=addr["resid"])
+    if c["colsum"] == "out":
+        kw.update(colsum_out=addr["colsum_out"], colsum_beta=c["colsum_beta"])
+    return args, kw
+
+
+def fp8_plan_of(c, ops, cus=None, addr=None, workspace=None, q_state=1 << 20, part_rows=None, **kw_over):
+    """the launch vaw_gemm_fp8 makes for the case.  cus = None: the case's own (256, or 16 for the multi-round cases), 0: the process's;
+    part_rows: the capacity of the colsum_partial buffer when it is not the ceil(M / 128) rows the launch writes"""
+    args, kw = fp8_plan_call(c, addr)
+    kw.update(kw_over)
+    cap = (-(-c["M"] // 128) if part_rows is None else part_rows) if c["colsum"] == "partial" else None
+    ws = (WS_FLOATS if c["colsum"] == "out" else 0) if workspace is None else workspace
+    return ops.gemm_fp8_plan(*args, workspace_floats=ws, cus=c["cus"] if cus is None else cus, colsum_partial_rows=cap,
+                             out_fp8_state=q_state if c["q_fmt"] else 0, out_fp8_format=3 if c["q_fmt"] == "e5m2" else 2, **kw)
+
+
+def describe_fp8_plan(L, p):
+    """the fields of a planned fp8 launch a case declares, as a target tuple"""
+    return (L.P8_NAMES[p.epi_kind], "e5m2" if p.a_e5m2 else "e4m3", p.ntw, p.tiles_m * p.tiles_n * p.split > p.grid)

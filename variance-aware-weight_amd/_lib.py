@@ -59,6 +59,13 @@ class GemmLaunch(C.Structure):
                 ("status", _i)]
 
 
+class GemmFp8Launch(C.Structure):
+    """vaw_gemm_fp8_launch of include/vaw_hip.h: the launch vaw_gemm_fp8_plan picks for a vaw_gemm_fp8 call."""
+    _fields_ = [("epi_kind", _i), ("a_e5m2", _i), ("c_fp8", _i), ("c_e5m2", _i), ("ntw", _i), ("tiles_m", _i), ("tiles_n", _i), ("nk", _i),
+                ("split", _i), ("grid", _i), ("block", _i), ("lds_bytes", _l), ("colsum_mode", _i), ("colsum_rows", _l),
+                ("workspace_floats_used", _l), ("launches", _i), ("status", _i)]
+
+
 class DitWsPlan(C.Structure):
     """vaw_dit_ws_plan_t of include/vaw_hip.h: the byte sizes of the DiT engine's activation workspace."""
     _fields_ = [("records", _i), ("colsum_sets", _i), ("own_dy", _i), ("Bk", _i), ("block_bytes", _l), ("block_stat_bytes", _l),
@@ -82,7 +89,8 @@ GV_NAMES = ("generic", "t128_bk32", "t128_bk64", "ring256", "persistent", "small
 GR_NONE, GR_F32, GR_BF16, GR_F32_ROWSUM = range(4)
 GS_NONE, GS_FUSED, GS_SEPARATE = range(3)
 GC_NONE, GC_FOLD, GC_DEFERRED, GC_SEPARATE = range(4)
-P8_STORE, P8_GELU, P8_DGELU, P8_GATE, P8_SLAB, P8_ANY, P8_WGRAD, P8_RESID = range(8)
+P8_STORE, P8_GELU, P8_DGELU, P8_GATE, P8_SLAB, P8_ANY, P8_WGRAD, P8_RESID, P8_GELU_Q, P8_DGELU_Q = range(10)
+P8_NAMES = ("P8_STORE", "P8_GELU", "P8_DGELU", "P8_GATE", "P8_SLAB", "P8_ANY", "P8_WGRAD", "P8_RESID", "P8_GELU_Q", "P8_DGELU_Q")
 
 # vaw_row_kind / vaw_row_variant
 RESAMPLER_MAX_T = 4096      # VAW_RESAMPLER_MAX_T
@@ -177,6 +185,7 @@ _PROTOS = {
     "vaw_fp8_scale_update": [_p, _l, _p],
     "vaw_fp8_quantize_delayed_batched": [_i, _p, _p, _i, _p],
     "vaw_gemm_fp8": [_i, _l, _l, _l, _p, _l, _p, _p, _l, _p, _p, _l, C.POINTER(Epilogue), _p, _i, _p, _l, _p],
+    "vaw_gemm_fp8_plan": [_i, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, _l, C.POINTER(Epilogue), _l, _i, _l, _l, _i, C.POINTER(GemmFp8Launch)],
     "vaw_fp8_transpose": [_p, _l, _l, _l, _p, _l, _p],
     "vaw_ln_modulate_fwd_fp8": [_p, _p, _p, _l, _p, _p, _i, _p, _p, _i, _i, _i, _f, _p],
     "vaw_gate_bwd_fp8": [_p, _p, _p, _l, _p, _p, _i, _p, _l, _p, _i, _i, _i, _p, _l, _p],

@@ -487,32 +487,89 @@ extern "C" int vaw_fp8_scale_update(float* states, int64_t n, vaw_stream stream)
 }
 
 // ---- GEMM ---------------------------------------------------------------------------------------------------------------
-extern "C" int vaw_gemm_fp8(vaw_dtype a_format, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const float* scale_a, const void* B, int64_t ldb,
-                            const float* scale_b, void* C, int64_t ldc, const vaw_epilogue* ep, float* c_fp8_state, vaw_dtype c_fp8_format,
-                            float* workspace, int64_t workspace_floats, vaw_stream stream) {
+// vaw_gemm_fp8_plan: every check and every launch choice of vaw_gemm_fp8, as host arithmetic (no device call: tests sweep it on the
+// CPU).  Refusals in the order, and with the texts, the call has always made them.
+extern "C" int vaw_gemm_fp8_plan(vaw_dtype a_format, int64_t M, int64_t N, int64_t K, int64_t A, int64_t lda, int64_t scale_a, int64_t B,
+                                 int64_t ldb, int64_t scale_b, int64_t C, int64_t ldc, const vaw_epilogue* ep, int64_t c_fp8_state,
+                                 vaw_dtype c_fp8_format, int64_t workspace, int64_t workspace_floats, int cus, vaw_gemm_fp8_launch* out) {
+    VAW_CHECK_ARG(out, "gemm_fp8_plan: out is NULL");
+    (void)scale_a; (void)scale_b;          // NULL stands for 1: nothing to check
+    vaw_gemm_fp8_launch p = {};
+    p.status = VAW_ERR_INVALID;
+    p.epi_kind = -1;
+    p.split = 1;
+    *out = p;
     VAW_CHECK_ARG(a_format == VAW_FP8 || a_format == VAW_BF8, "gemm_fp8: a_format VAW_FP8 (e4m3) or VAW_BF8 (e5m2)");
     VAW_CHECK_ARG(M >= 16 && N >= 16 && K > 0 && K % 128 == 0 && A && B && C, "gemm_fp8: sizes (K %% 128 == 0)");
     VAW_CHECK_ARG(lda >= K && ldb >= K && ldc >= N && lda % 16 == 0 && ldb % 16 == 0 && N % 8 == 0 && ldc % 8 == 0, "gemm_fp8: leading dimensions");
-    VAW_CHECK_ARG((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, "gemm_fp8: 16-byte alignment");
-    EpiDev e{};
-    e.alpha = 1.f;
-    if (ep) {
-        e.bias = ep->bias; e.act = ep->act; e.aux_in = ep->aux_in; e.aux_out = ep->aux_out; e.gate = ep->gate;
-        e.gate_ld = ep->gate_ld; e.resid = ep->resid; e.rowadd = ep->rowadd; e.rpb = ep->rows_per_batch;
-        e.alpha = ep->alpha; e.beta = ep->beta; e.out_f32 = ep->out_f32; e.resid_act = ep->resid_is_act;
-    }
+    VAW_CHECK_ARG(((A | B | C) & 15) == 0, "gemm_fp8: 16-byte alignment");
+    GemmKnobs none{};
+    const EpiDev e = vaw_epi_dev(ep, none);                                  // (rpb <= 0 becomes 1; the check below reads the caller's)
     VAW_CHECK_ARG(!(ep && ep->rowsum_a_out), "gemm_fp8: rowsum_a_out is not offered (take bias gradients from the bf16 tensors)");
     VAW_CHECK_ARG(e.act >= 0 && e.act <= 2 && (e.act != 2 || e.aux_in), "gemm_fp8: act");
-    VAW_CHECK_ARG(!(e.gate || e.rowadd) || e.rpb > 0, "gemm_fp8: gate/rowadd need rows_per_batch");
+    VAW_CHECK_ARG(!(e.gate || e.rowadd) || ep->rows_per_batch > 0, "gemm_fp8: gate/rowadd need rows_per_batch");
     VAW_CHECK_ARG(!(e.act == 2 && e.gate) && !(e.resid && e.rowadd), "gemm_fp8: epilogue combination not offered");
-    if (e.rpb <= 0) e.rpb = 1;
-    float* const colsum_final = ep ? ep->colsum_out : nullptr;
-    float* const colsum_part = ep ? ep->colsum_partial_out : nullptr;       // deferred fold (vaw_reduce_rows_batched): see vaw_epilogue
-    VAW_CHECK_ARG(!colsum_part || (!colsum_final && ep->colsum_rows_out), "gemm_fp8: colsum_partial_out excludes colsum_out and needs colsum_rows_out");
-    const bool colsum_out = colsum_final || colsum_part;
-    VAW_CHECK_ARG(!colsum_part || *ep->colsum_rows_out >= (M + 127) / 128, "gemm_fp8: colsum_partial_out holds %ld rows, this launch writes %ld",
-                  (long)*ep->colsum_rows_out, (long)((M + 127) / 128));      // colsum_rows_out: capacity in, rows written out
-    VAW_CHECK_ARG(!colsum_final || (workspace && workspace_floats >= ((M + 127) / 128) * N), "gemm_fp8: colsum_out needs a workspace");
+    const bool cs_final = ep && ep->colsum_out, cs_part = ep && ep->colsum_partial_out;      // deferred fold (vaw_reduce_rows_batched): see vaw_epilogue
+    VAW_CHECK_ARG(!cs_part || (!cs_final && ep->colsum_rows_out), "gemm_fp8: colsum_partial_out excludes colsum_out and needs colsum_rows_out");
+    const bool colsum = cs_final || cs_part;
+    const int64_t rows128 = (M + 127) / 128;
+    VAW_CHECK_ARG(!cs_part || *ep->colsum_rows_out >= rows128, "gemm_fp8: colsum_partial_out holds %ld rows, this launch writes %ld",
+                  (long)*ep->colsum_rows_out, (long)rows128);                // colsum_rows_out: capacity in, rows written out
+    VAW_CHECK_ARG(!cs_final || (workspace && workspace_floats >= rows128 * N), "gemm_fp8: colsum_out needs a workspace");
+    // plan in units of the kernel's K tiles: 128 fp8 elements = one K tile = what 64 bf16 elements are to vaw_p8_plan
+    // (plain_f32 = false: no K split -- the long-K launches of the step are the weight gradients, served by vaw_wgrad_grouped)
+    const P8Plan pl = vaw_p8_plan(M, N, K / 2, false, colsum, workspace_floats, 1, cus > 0 ? cus : vaw_p8_cus_available());
+    const int bn = 64 * pl.ntw;
+    p.a_e5m2 = a_format == VAW_BF8;
+    p.c_fp8 = c_fp8_state != 0;
+    p.ntw = pl.ntw;
+    p.tiles_m = (int)((M + 255) / 256);
+    p.tiles_n = (int)((N + bn - 1) / bn);
+    p.nk = (int)(K / 128);
+    p.split = pl.split;
+    p.grid = pl.grid;
+    p.block = 512;
+    p.lds_bytes = vaw_lds_p8(pl.ntw);
+    p.colsum_mode = !colsum ? VAW_GC_NONE : cs_part ? VAW_GC_DEFERRED : VAW_GC_FOLD;
+    p.colsum_rows = colsum ? rows128 : 0;
+    p.workspace_floats_used = cs_final ? rows128 * N : 0;
+    p.launches = 1 + (cs_final ? 1 : 0);
+    *out = p;       // the launch as sized; status stays VAW_ERR_INVALID for the refusals below
+    const bool bf16_out = !e.out_f32;
+    VAW_CHECK_ARG(!c_fp8_state || ((c_fp8_format == VAW_FP8 || c_fp8_format == VAW_BF8) && bf16_out && (e.act == 1 || e.act == 2) && ldc % 8 == 0),
+                  "gemm_fp8: fp8 output is offered for the GELU / GELU' epilogues (C then holds bytes, row stride ldc bytes)");
+    p.c_e5m2 = p.c_fp8 && c_fp8_format == VAW_BF8;
+    if (e.act == 1 && e.aux_out && !e.gate && !e.resid && !e.rowadd && bf16_out && !colsum) p.epi_kind = p.c_fp8 ? P8_GELU_Q : P8_GELU;
+    else if (e.act == 2 && !e.bias && !e.aux_out && !e.gate && !e.resid && !e.rowadd && bf16_out) p.epi_kind = p.c_fp8 ? P8_DGELU_Q : P8_DGELU;
+    else if (e.act == 0 && e.gate && e.resid && !e.resid_act && e.aux_out && !e.rowadd && e.out_f32 && e.beta == 0.f && !colsum) p.epi_kind = P8_GATE;
+    else if (e.act == 0 && !e.aux_out && !e.gate && !e.resid && !e.rowadd && e.beta == 0.f) p.epi_kind = P8_STORE;
+    else {
+        out->status = VAW_ERR_UNSUPPORTED;
+        vaw_set_error("gemm_fp8: this epilogue combination has no fp8 kernel");
+        return VAW_ERR_UNSUPPORTED;
+    }
+    // instantiated: what the training step launches -- forward kinds with e4m3 activations, input-gradient kinds with e5m2 or
+    // e4m3 gradients
+    if (p.a_e5m2 && (p.epi_kind == P8_GELU || p.epi_kind == P8_GELU_Q || p.epi_kind == P8_GATE)) {
+        out->status = VAW_ERR_UNSUPPORTED;
+        vaw_set_error("gemm_fp8: the forward epilogues (GELU, gated residual) take e4m3 activations");
+        return VAW_ERR_UNSUPPORTED;
+    }
+    p.status = VAW_OK;
+    *out = p;
+    return VAW_OK;
+}
+
+extern "C" int vaw_gemm_fp8(vaw_dtype a_format, int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const float* scale_a, const void* B, int64_t ldb,
+                            const float* scale_b, void* C, int64_t ldc, const vaw_epilogue* ep, float* c_fp8_state, vaw_dtype c_fp8_format,
+                            float* workspace, int64_t workspace_floats, vaw_stream stream) {
+    vaw_gemm_fp8_launch p;
+    const int rc = vaw_gemm_fp8_plan(a_format, M, N, K, (int64_t)(uintptr_t)A, lda, (int64_t)(uintptr_t)scale_a, (int64_t)(uintptr_t)B, ldb,
+                                     (int64_t)(uintptr_t)scale_b, (int64_t)(uintptr_t)C, ldc, ep, (int64_t)(uintptr_t)c_fp8_state, c_fp8_format,
+                                     (int64_t)(uintptr_t)workspace, workspace_floats, 0, &p);
+    if (rc != VAW_OK) return rc;
+    EpiDev e = vaw_epi_dev(ep, GemmKnobs{});
+    e.direct_epi = 0;
     e.M = M; e.N = N; e.ldc = ldc; e.C = C; e.slab = workspace; e.nt_off = 1;
     e.scale_a = scale_a; e.scale_b = scale_b;
     {
@@ -520,45 +577,25 @@ extern "C" int vaw_gemm_fp8(vaw_dtype a_format, int64_t M, int64_t N, int64_t K,
         if (dbg < 0) { const char* v = getenv("VAW_GEMM_DEBUG"); dbg = v ? atoi(v) : 0; }
         e.debug = dbg;
     }
-    e.colpart = colsum_part ? colsum_part : colsum_final ? workspace : nullptr;
-    // plan in units of the kernel's K tiles: 128 fp8 elements = one K tile = what 64 bf16 elements are to vaw_p8_plan
-    // (plain_f32 = false: no K split -- the long-K launches of the step are the weight gradients, served by vaw_wgrad_grouped)
-    const P8Plan pl = vaw_p8_plan(M, N, K / 2, false, colsum_out, workspace_floats, 1, vaw_p8_cus_available());
-    hipStream_t s = (hipStream_t)stream;
-    const int bn = 64 * pl.ntw, tiles_m = (int)((M + 255) / 256), tiles_n = (int)((N + bn - 1) / bn), nk = (int)(K / 128);
-    int epi;
-    const bool bf16_out = !e.out_f32;
+    e.colpart = p.colsum_mode == VAW_GC_DEFERRED ? ep->colsum_partial_out : p.colsum_mode == VAW_GC_FOLD ? workspace : nullptr;
     e.q_state = c_fp8_state;
-    e.q_e5m2 = c_fp8_format == VAW_BF8;
-    VAW_CHECK_ARG(!c_fp8_state || ((c_fp8_format == VAW_FP8 || c_fp8_format == VAW_BF8) && bf16_out && (e.act == 1 || e.act == 2) && ldc % 8 == 0),
-                  "gemm_fp8: fp8 output is offered for the GELU / GELU' epilogues (C then holds bytes, row stride ldc bytes)");
-    if (e.act == 1 && e.aux_out && !e.gate && !e.resid && !e.rowadd && bf16_out && !e.colpart) epi = c_fp8_state ? P8_GELU_Q : P8_GELU;
-    else if (e.act == 2 && !e.bias && !e.aux_out && !e.gate && !e.resid && !e.rowadd && bf16_out) epi = c_fp8_state ? P8_DGELU_Q : P8_DGELU;
-    else if (e.act == 0 && e.gate && e.resid && !e.resid_act && e.aux_out && !e.rowadd && e.out_f32 && e.beta == 0.f && !e.colpart) epi = P8_GATE;
-    else if (e.act == 0 && !e.aux_out && !e.gate && !e.resid && !e.rowadd && e.beta == 0.f) epi = P8_STORE;
-    else {
-        vaw_set_error("gemm_fp8: this epilogue combination has no fp8 kernel");
-        return VAW_ERR_UNSUPPORTED;
-    }
-    // instantiated: what the training step launches -- forward kinds with e4m3 activations, input-gradient kinds with e5m2 or
-    // e4m3 gradients
+    e.q_e5m2 = p.c_e5m2;
+    hipStream_t s = (hipStream_t)stream;
 #define F8_GO(EPIv, FMT)                                                                                                         \
     do {                                                                                                                         \
-        if (pl.ntw == 4) p8_launch_fp8_one<4, EPIv, FMT>(A, lda, B, ldb, nk, tiles_m, tiles_n, pl.split, pl.grid, e, s);          \
-        else p8_launch_fp8_one<3, EPIv, FMT>(A, lda, B, ldb, nk, tiles_m, tiles_n, pl.split, pl.grid, e, s);                      \
+        if (p.ntw == 4) p8_launch_fp8_one<4, EPIv, FMT>(A, lda, B, ldb, p.nk, p.tiles_m, p.tiles_n, p.split, p.grid, e, s);       \
+        else p8_launch_fp8_one<3, EPIv, FMT>(A, lda, B, ldb, p.nk, p.tiles_m, p.tiles_n, p.split, p.grid, e, s);                  \
     } while (0)
-    const bool e5 = a_format == VAW_BF8;
-    if (epi == P8_STORE) { if (e5) F8_GO(P8_STORE, 2); else F8_GO(P8_STORE, 1); }
-    else if (epi == P8_DGELU) { if (e5) F8_GO(P8_DGELU, 2); else F8_GO(P8_DGELU, 1); }
-    else if (epi == P8_DGELU_Q) { if (e5) F8_GO(P8_DGELU_Q, 2); else F8_GO(P8_DGELU_Q, 1); }
-    else if (e5) {
-        vaw_set_error("gemm_fp8: the forward epilogues (GELU, gated residual) take e4m3 activations");
-        return VAW_ERR_UNSUPPORTED;
-    } else if (epi == P8_GELU) F8_GO(P8_GELU, 1);
-    else if (epi == P8_GELU_Q) F8_GO(P8_GELU_Q, 1);
-    else F8_GO(P8_GATE, 1);
+    switch (p.epi_kind) {
+        case P8_STORE: if (p.a_e5m2) F8_GO(P8_STORE, 2); else F8_GO(P8_STORE, 1); break;
+        case P8_DGELU: if (p.a_e5m2) F8_GO(P8_DGELU, 2); else F8_GO(P8_DGELU, 1); break;
+        case P8_DGELU_Q: if (p.a_e5m2) F8_GO(P8_DGELU_Q, 2); else F8_GO(P8_DGELU_Q, 1); break;
+        case P8_GELU: F8_GO(P8_GELU, 1); break;
+        case P8_GELU_Q: F8_GO(P8_GELU_Q, 1); break;
+        default: F8_GO(P8_GATE, 1); break;
+    }
     VAW_CHECK_LAUNCH("gemm_fp8");
-    if (colsum_part) *ep->colsum_rows_out = (M + 127) / 128;
-    else if (colsum_final) return vaw_reduce_rows(workspace, (M + 127) / 128, N, colsum_final, ep->colsum_beta, stream);
+    if (p.colsum_mode == VAW_GC_DEFERRED) *ep->colsum_rows_out = p.colsum_rows;
+    else if (p.colsum_mode == VAW_GC_FOLD) return vaw_reduce_rows(workspace, p.colsum_rows, N, ep->colsum_out, ep->colsum_beta, stream);
     return VAW_OK;
 }

@@ -682,6 +682,29 @@ def gemm_fp8(M, N, K, A, lda, scale_a, B, ldb, scale_b, Cp, ldc, *, a_format=L.F
         tr.add(2, True, a_format == L.FP8, M, N, K, e0, e1, float(nb))
 
 
+def gemm_fp8_plan(M, N, K, A, lda, scale_a, B, ldb, scale_b, Cp, ldc, *, a_format=L.FP8, workspace=16, workspace_floats=0, cus=0,
+                  colsum_partial_rows=None, out_fp8_state=0, out_fp8_format=L.FP8, check_status=True, **epi):
+    """The launch vaw_gemm_fp8 makes for this call (vaw_gemm_fp8_plan: host arithmetic, no GPU).  Arguments as for gemm_fp8(), the
+    addresses used for null-ness and alignment only; out_fp8_state = address of the delayed-scaling state of an fp8 output (0: none)
+    and out_fp8_format its format; colsum_partial_rows = capacity of a colsum_partial buffer (any non-zero address stands for it);
+    workspace_floats = 0 stands for no workspace; cus = 0: the CUs the process may use now, else a stated count.
+    check_status = False returns the plan of a refused call (status != 0) instead of raising."""
+    e = Epilogue(epi.get("bias") or None, epi.get("act", 0), epi.get("aux_in") or None, epi.get("aux_out") or None, epi.get("gate") or None,
+                 epi.get("gate_ld", 0), epi.get("resid") or None, epi.get("rowadd") or None, epi.get("rows_per_batch", 0),
+                 epi.get("alpha", 1.0), epi.get("beta", 0.0), 1 if epi.get("out_f32") else 0, epi.get("colsum_out") or None,
+                 epi.get("colsum_beta", 0.0), 1 if epi.get("resid_is_act") else 0, epi.get("rowsum_a_out") or None,
+                 epi.get("rowsum_a_beta", 0.0))
+    rows = C.c_int64(colsum_partial_rows or 0)
+    if colsum_partial_rows is not None:
+        e.colsum_partial_out, e.colsum_rows_out = epi.get("colsum_partial_out", 16), C.pointer(rows)
+    p = L.GemmFp8Launch()
+    rc = L.lib().vaw_gemm_fp8_plan(a_format, M, N, K, A, lda, scale_a, B, ldb, scale_b, Cp, ldc, C.byref(e), out_fp8_state, out_fp8_format,
+                                   workspace if workspace_floats > 0 else 0, workspace_floats, cus, C.byref(p))
+    if check_status:
+        check(rc, "vaw_gemm_fp8_plan")
+    return p
+
+
 class WgradProblem(C.Structure):
     """vaw_wgrad_problem of include/vaw_hip.h."""
     _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("dw", C.c_void_p), ("M", C.c_int64), ("N", C.c_int64),

@@ -277,7 +277,8 @@ int vaw_resampler_draw(const double* ring, const int64_t* seen, int T, int H, do
                        int64_t* out_t, float* out_w, double* p, vaw_stream stream);
 
 /* ---------------------------------------------------------------------------
- * Evaluation metrics from activations  (evaluations/evaluator.py: ManifoldEstimator, DistanceBlock, Evaluator.compute_statistics)
+ * Evaluation metrics from activations  (evaluations/evaluator.py: ManifoldEstimator, DistanceBlock, Evaluator.compute_statistics,
+ * Evaluator.compute_inception_score)
  * ------------------------------------------------------------------------- */
 
 /* out[i] = sum_k X[i][k]^2 in f32, X: f32 [n][D] row-major, any D >= 1 (rows need no alignment).  Fixed order: 64 partial sums,
@@ -318,6 +319,34 @@ int vaw_pairwise_within(const float* U, int64_t nu, const float* V, int64_t nv, 
  * fully and is symmetric bit for bit.  n = 1 gives 0 / 0 = NaN as numpy does. */
 int vaw_col_mean_f64(const float* X, int64_t n, int D, double* mu, vaw_stream stream);
 int vaw_cov_f64(const float* X, int64_t n, int D, const double* mu, double* sigma, vaw_stream stream);
+
+/* Inception score from pool activations (Evaluator.compute_inception_score :180-193 behind _create_softmax_graph: a matrix product
+ * without bias, a row softmax, exp(mean_i sum_c p (ln p - ln mean_i p)) per split of rows).
+ *
+ * vaw_head_logits: logits[i][c] = sum_k X[i][k] * Wt[c][k].  X: f32 [n][D], Wt: f32 [C][D] (the class-major copy of the [D][C]
+ * weight), logits: f32, rows ld >= C floats apart.  Any D, C >= 1, rows need no alignment.  One block per 128 x 128 output tile on
+ * the pairwise tile: every element is one k-ordered f32 MFMA chain in one accumulator, K is never split, so a logit has the same
+ * bits whatever tile or launch made it.  Rows >= n and columns >= C are not stored.
+ *
+ * vaw_is_rows: per row of `in` (f32 [n][C], rows ld apart), one wave, float64, every sum 64 lane-strided partials in ascending c
+ * folded by the xor butterfly.  probs = 0, a row of logits l:  lse = m + log sum_c exp(l_c - m) with m = max_c l_c, and
+ * h = sum_c p_c (l_c - lse) with p_c = exp(l_c - lse).  probs = 1, a row of probabilities p:  h = sum_c p_c log p_c, lse = 0.
+ *
+ * vaw_is_colsums: colsum[s][c] = sum over the rows i of split s of p_ic (p as above; lse from vaw_is_rows, unused when probs) in
+ * float64, one chain in ascending i per (s, c), no atomics.  The n rows of the call are the global rows row0 .. row0 + n; split s
+ * holds the global rows s * split_size .. (s + 1) * split_size.  colsum: f64 [number of splits][C], the whole array.  A split whose
+ * first row lies in this call starts from 0, any other continues from the value in memory: calls must come in ascending row0 and
+ * cover every row once, and the result does not depend on where they cut.
+ *
+ * vaw_is_finish: scores[s] = exp(H - sum_c m_c log m_c), H = (sum_i h_i) / n_s over the n_s rows of split s (the last one ragged),
+ * m_c = colsum[s][c] / n_s; h: f64 [N].  This is mean_i sum_c p (ln p - ln m) with the inner sum split.
+ *
+ * Wherever p = 0 or m_c = 0 the term is its limit 0 (numpy gives 0 * -inf = NaN there). */
+int vaw_head_logits(const float* X, int64_t n, int D, const float* Wt, int C, float* logits, int64_t ld, vaw_stream stream);
+int vaw_is_rows(const float* in, int64_t n, int C, int64_t ld, int probs, double* lse, double* h, vaw_stream stream);
+int vaw_is_colsums(const float* in, const double* lse, int64_t n, int C, int64_t ld, int probs, int64_t row0, int64_t split_size, double* colsum,
+                   vaw_stream stream);
+int vaw_is_finish(const double* h, const double* colsum, int64_t N, int C, int64_t split_size, double* scores, vaw_stream stream);
 
 /* ---------------------------------------------------------------------------
  * Dense layers  (nn.Linear / Conv2d(k=p,s=p) / Conv1d(k=1) in models/dit.py, models/unet.py;

@@ -2,6 +2,7 @@
 """Times the evaluation metrics of vaw_amd.evaluator on synthetic activations.
 
     python tools/metrics_bench.py [--sizes 10000 50000] [--out FILE.json]
+    python tools/metrics_bench.py --inception-score [--sizes 10000 50000] [--out FILE.json]
 
 Activations are non-negative and of low rank plus noise, like pooled ReLU features: max(z P + off + 0.01 noise, 0) with rank 64,
 generated on the device from a seed; the sample set is drawn with z scaled by 0.8 and shifted by 0.5.  Per N it reports the median
@@ -14,6 +15,10 @@ over the repeats (after one warm-up of the same shapes) of
     triangle;
   * at N = 10000 only, the host baseline: the same arithmetic in numpy (float32 distances through the norm expansion in row blocks,
     np.partition / comparisons; float64 np.mean / np.cov).  The reference's TensorFlow path cannot run without TensorFlow.
+With --inception-score it times the Inception score instead (D = 2048, C = 1008, the weight 3 / sqrt(D) randn as in the tests): the
+head product vaw_head_logits alone (device events, rate 2 N D C / t), the float64 row pass, class sums and finish alone, and
+compute_inception_score end to end (device activations in, one float out); at N = 10000 the host baseline is float32 numpy, the
+arithmetic the reference's TensorFlow graph and its numpy tail perform.
 One JSON object is printed (and written to --out).  It needs the GPU: there is no host path to time."""
 import argparse
 import json
@@ -97,17 +102,66 @@ def host_prec_recall(f1, f2, k=3, block=2000):
     return float(in2.mean()), float(in1.mean())
 
 
+def host_inception_score(acts, w, split_size=5000):
+    """float32 numpy: softmax(acts @ w), then the reference's expression per split."""
+    logits = acts @ w
+    e = np.exp(logits - logits.max(1, keepdims=True))
+    preds = e / e.sum(1, keepdims=True)
+    scores = []
+    for i in range(0, len(preds), split_size):
+        part = preds[i:i + split_size]
+        kl = part * (np.log(part) - np.log(np.expand_dims(np.mean(part, 0), 0)))
+        scores.append(np.exp(np.mean(np.sum(kl, 1))))
+    return float(np.mean(scores))
+
+
+def inception_rows(args):
+    d, c, split = 2048, 1008, 5000
+    g = torch.Generator(device="cuda").manual_seed(100)
+    w = torch.randn(d, c, device="cuda", generator=g) * 3 / d ** 0.5
+    head = ev._SoftmaxHead(w)
+    wt = head.class_major()
+    sizes = {}
+    for n in args.sizes:
+        reps = args.repeats if n <= 20000 else max(3, args.repeats // 2 + 1)
+        x = features(n, d, 0, True)
+        row = dict(inception_score=ev.compute_inception_score(x, head, split))
+        row["compute_inception_score"] = summary(host_clock(lambda: ev.compute_inception_score(x, head, split), 1, reps))
+        logits = torch.empty(n, c, device="cuda", dtype=torch.float32)
+        s = summary(device_clock(lambda: ops.head_logits(x, wt, logits), 1, reps))
+        s["tflops_f32"] = 2.0 * n * d * c / s["median_s"] * 1e-12
+        s["share_of_f32_peak"] = s["tflops_f32"] / PEAK_F32_TFLOPS
+        row["head_logits"] = s
+        lse, h = ops.is_rows(logits)
+        colsum = torch.zeros(-(-n // split), c, device="cuda", dtype=torch.float64)
+        row["is_rows"] = summary(device_clock(lambda: ops.is_rows(logits, False, lse, h), 1, reps))
+        row["is_colsums"] = summary(device_clock(lambda: ops.is_colsums(logits, lse, 0, split, colsum), 1, reps))
+        row["is_finish"] = summary(device_clock(lambda: ops.is_finish(h, colsum, split), 1, reps))
+        if n == args.host_baseline_at:
+            xh, wh = x.cpu().numpy(), w.cpu().numpy()
+            host_inception_score(xh[:1000], wh)
+            t0 = time.perf_counter()
+            row["host_numpy_inception_score"] = host_inception_score(xh, wh, split)
+            row["host_numpy_inception_score_s"] = time.perf_counter() - t0
+            row["host_threads"] = torch.get_num_threads()
+        sizes[str(n)] = row
+        del x, logits
+        torch.cuda.empty_cache()
+    return sizes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[10000, 50000])
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--host-baseline-at", type=int, default=10000)
+    ap.add_argument("--inception-score", action="store_true", help="time the Inception score instead of FID / precision / recall")
     ap.add_argument("--out")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "metrics_bench needs the GPU: the metric kernels have no host path"
     vaw_amd.lib()
     result = dict(gpu=torch.cuda.get_device_name(0), date=time.strftime("%Y-%m-%d"), peak_f32_tflops=PEAK_F32_TFLOPS, sizes={})
-    for n in args.sizes:
+    for n in ([] if args.inception_score else args.sizes):
         reps = args.repeats if n <= 20000 else max(3, args.repeats // 2 + 1)
         row = {}
         ref, sample = features(n, 2048, 0, False), features(n, 2048, 0, True)
@@ -150,6 +204,8 @@ def main():
         result["sizes"][str(n)] = row
         del ref, sample
         torch.cuda.empty_cache()
+    if args.inception_score:
+        result["sizes"] = inception_rows(args)
     line = json.dumps(result)
     print(line)
     if args.out:

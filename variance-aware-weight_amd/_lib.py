@@ -207,6 +207,10 @@ _PROTOS = {
     "vaw_pairwise_within": [_p, _l, _p, _l, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p],
     "vaw_col_mean_f64": [_p, _l, _i, _p, _p],
     "vaw_cov_f64": [_p, _l, _i, _p, _p, _p],
+    "vaw_head_logits": [_p, _l, _i, _p, _i, _p, _l, _p],
+    "vaw_is_rows": [_p, _l, _i, _l, _i, _p, _p, _p],
+    "vaw_is_colsums": [_p, _p, _l, _i, _l, _i, _l, _l, _p, _p],
+    "vaw_is_finish": [_p, _p, _l, _i, _l, _p, _p],
 }
 
 _lib = None

@@ -9,6 +9,9 @@
 // distance therefore has the same bits whatever tile, block or launch computed it, which is what makes the results independent
 // of every chunking above.  The 128 x 128 distances never leave the CU: they are staged through LDS in two 128 x 64 halves and
 // consumed there (a sorted k-list per thread, or the radius comparisons).
+//
+// Inception score.  The head product logits = X Wt^T is the same tile (pw_product, one block per 128 x 128 output tile, the
+// accumulators stored straight to memory); the softmax, the entropies and the class marginals are float64 sums in a fixed order.
 #include <math.h>
 
 #include "common.h"
@@ -345,6 +348,103 @@ __global__ __launch_bounds__(256) void cov_f64_kernel(const float* __restrict__ 
         }
 }
 
+// logits[i][c] = sum_k X[i][k] Wt[c][k]: block b owns row tile b / tiles_c and column tile b % tiles_c (the 8 column tiles of the
+// real head land on the 8 XCDs, each of which keeps its 1 MB slice of Wt in L2).  Rows >= n and columns >= C are products of the
+// zero padding and are not stored.
+__global__ __launch_bounds__(256) void head_logits_kernel(const float* __restrict__ X, int64_t n, int D, const float* __restrict__ Wt, int C,
+                                                          float* __restrict__ logits, int64_t ld, int tiles_c) {
+    __shared__ PwShared sh;
+    const int64_t row0 = (int64_t)(blockIdx.x / tiles_c) * PW_T, col0 = (int64_t)(blockIdx.x % tiles_c) * PW_T;
+    f32x16 acc[2][2];
+    pw_product(X, n, row0, Wt, C, col0, D, sh, acc);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wm = w >> 1, wn = w & 1, l31 = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t row = row0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, col = col0 + wn * 64 + j * 32 + l31;
+                if (row < n && col < C) logits[row * ld + col] = acc[i][j][r];
+            }
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+    return v;
+}
+
+// One wave per row, every sum 64 lane-strided partials in ascending c folded by the xor butterfly.  From logits: m = max_c l_c,
+// lse = m + log sum_c exp(l_c - m), h = sum_c p_c (l_c - lse) with p_c = exp(l_c - lse).  PROBS: the row holds p_c itself,
+// h = sum_c p_c log p_c and lse is written as 0.  A term with p = 0 is its limit 0.
+template <bool PROBS>
+__global__ __launch_bounds__(256) void is_rows_kernel(const float* __restrict__ in, int64_t n, int C, int64_t ld, double* __restrict__ lse,
+                                                      double* __restrict__ h) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const float* x = in + row * ld;
+    const int lane = threadIdx.x & 63;
+    double L = 0.0, hs = 0.0;
+    if constexpr (!PROBS) {
+        float mf = -INFINITY;
+        for (int c = lane; c < C; c += 64) mf = fmaxf(mf, x[c]);
+        const double m = (double)wave_max(mf);
+        double s = 0.0;
+        for (int c = lane; c < C; c += 64) s = s + exp((double)x[c] - m);
+        L = m + log(wave_sum_f64(s));
+    }
+    for (int c = lane; c < C; c += 64) {
+        const double g = PROBS ? 0.0 : (double)x[c] - L;
+        const double p = PROBS ? (double)x[c] : exp(g);
+        if (p > 0.0) hs = hs + p * (PROBS ? log(p) : g);
+    }
+    hs = wave_sum_f64(hs);
+    if (lane == 0) {
+        lse[row] = L;
+        h[row] = hs;
+    }
+}
+
+// colsum[s][c] = sum of p_ic over the rows i of split s, one chain in ascending i per (s, c): thread (k, c) walks the rows of
+// the launch (global rows row0 .. row0 + n) that lie in split s = row0 / split + k.  A split that began in an earlier launch is
+// continued from the value in memory, which a float64 store and load return unchanged: the chain does not see the cut.
+template <bool PROBS>
+__global__ __launch_bounds__(64) void is_colsums_kernel(const float* __restrict__ in, const double* __restrict__ lse, int64_t n, int C, int64_t ld,
+                                                        int64_t row0, int64_t split, double* __restrict__ colsum) {
+    const int c = (int)blockIdx.y * 64 + threadIdx.x;
+    if (c >= C) return;
+    const int64_t s = row0 / split + blockIdx.x;
+    const int64_t a = s * split > row0 ? s * split : row0, b = (s + 1) * split < row0 + n ? (s + 1) * split : row0 + n;
+    double* out = colsum + s * C + c;
+    double acc = a == s * split ? 0.0 : *out;
+#pragma unroll 4
+    for (int64_t g = a; g < b; ++g) {
+        const int64_t i = g - row0;
+        const double v = (double)in[i * ld + c];
+        acc = acc + (PROBS ? v : exp(v - lse[i]));
+    }
+    *out = acc;
+}
+
+// scores[s] = exp(H - sum_c m_c log m_c), H = (sum_i h_i) / n_s over the rows of split s, m_c = colsum[s][c] / n_s: one wave per
+// split, both sums lane-strided partials in ascending index and the xor butterfly; m_c = 0 adds its limit 0.
+__global__ __launch_bounds__(64) void is_finish_kernel(const double* __restrict__ h, const double* __restrict__ colsum, int64_t N, int C, int64_t split,
+                                                       double* __restrict__ scores) {
+    const int64_t s = blockIdx.x, a = s * split, b = a + split < N ? a + split : N;
+    const int lane = threadIdx.x;
+    const double ns = (double)(b - a);
+    double hs = 0.0, e = 0.0;
+    for (int64_t i = a + lane; i < b; i += 64) hs = hs + h[i];
+    for (int c = lane; c < C; c += 64) {
+        const double m = colsum[s * C + c] / ns;
+        if (m > 0.0) e = e + m * log(m);
+    }
+    hs = wave_sum_f64(hs);
+    e = wave_sum_f64(e);
+    if (lane == 0) scores[s] = exp(hs / ns - e);
+}
+
 int pw_splits(int64_t nv) {
     const int64_t tiles = (nv + PW_T - 1) / PW_T;
     return (int)(tiles < PW_SPLITS ? tiles : PW_SPLITS);
@@ -436,6 +536,52 @@ int vaw_cov_f64(const float* X, int64_t n, int D, const double* mu, double* sigm
     const int64_t blocks = (int64_t)tiles * (tiles + 1) / 2;
     cov_f64_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(X, n, D, mu, sigma, tiles);
     VAW_CHECK_LAUNCH("vaw_cov_f64");
+    return VAW_OK;
+}
+
+int vaw_head_logits(const float* X, int64_t n, int D, const float* Wt, int C, float* logits, int64_t ld, vaw_stream stream) {
+    const int64_t tiles_m = (n + PW_T - 1) / PW_T, tiles_c = ((int64_t)C + PW_T - 1) / PW_T;
+    VAW_CHECK_ARG(n >= 1 && D >= 1 && C >= 1 && ld >= C && n <= ((int64_t)1 << 31) - PW_T && C <= (1 << 30) && tiles_m * tiles_c <= 0x7fffffff,
+                  "vaw_head_logits: sizes n %lld D %d C %d ld %lld out of range", (long long)n, D, C, (long long)ld);
+    VAW_CHECK_ARG(X && Wt && logits, "vaw_head_logits: null pointer");
+    head_logits_kernel<<<dim3((unsigned)(tiles_m * tiles_c)), 256, 0, (hipStream_t)stream>>>(X, n, D, Wt, C, logits, ld, (int)tiles_c);
+    VAW_CHECK_LAUNCH("vaw_head_logits");
+    return VAW_OK;
+}
+
+int vaw_is_rows(const float* in, int64_t n, int C, int64_t ld, int probs, double* lse, double* h, vaw_stream stream) {
+    VAW_CHECK_ARG(n >= 1 && C >= 1 && ld >= C && (n + 3) / 4 <= 0x7fffffff, "vaw_is_rows: sizes n %lld C %d ld %lld out of range", (long long)n, C,
+                  (long long)ld);
+    VAW_CHECK_ARG(in && lse && h, "vaw_is_rows: null pointer");
+    const dim3 grid((unsigned)((n + 3) / 4));
+    if (probs) is_rows_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(in, n, C, ld, lse, h);
+    else is_rows_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(in, n, C, ld, lse, h);
+    VAW_CHECK_LAUNCH("vaw_is_rows");
+    return VAW_OK;
+}
+
+int vaw_is_colsums(const float* in, const double* lse, int64_t n, int C, int64_t ld, int probs, int64_t row0, int64_t split_size, double* colsum,
+                   vaw_stream stream) {
+    VAW_CHECK_ARG(n >= 1 && C >= 1 && ld >= C && row0 >= 0 && row0 <= ((int64_t)1 << 40) && n <= ((int64_t)1 << 40) && split_size >= 1 &&
+                      split_size <= ((int64_t)1 << 40) && C <= 65535 * 64,
+                  "vaw_is_colsums: sizes n %lld C %d ld %lld row0 %lld split_size %lld out of range", (long long)n, C, (long long)ld, (long long)row0,
+                  (long long)split_size);
+    const int64_t splits = (row0 + n - 1) / split_size - row0 / split_size + 1;
+    VAW_CHECK_ARG(splits <= 0x7fffffff, "vaw_is_colsums: %lld splits in one launch", (long long)splits);
+    VAW_CHECK_ARG(in && colsum && (probs || lse), "vaw_is_colsums: null pointer");
+    const dim3 grid((unsigned)splits, (unsigned)((C + 63) / 64));
+    if (probs) is_colsums_kernel<true><<<grid, 64, 0, (hipStream_t)stream>>>(in, lse, n, C, ld, row0, split_size, colsum);
+    else is_colsums_kernel<false><<<grid, 64, 0, (hipStream_t)stream>>>(in, lse, n, C, ld, row0, split_size, colsum);
+    VAW_CHECK_LAUNCH("vaw_is_colsums");
+    return VAW_OK;
+}
+
+int vaw_is_finish(const double* h, const double* colsum, int64_t N, int C, int64_t split_size, double* scores, vaw_stream stream) {
+    VAW_CHECK_ARG(N >= 1 && N <= ((int64_t)1 << 40) && C >= 1 && split_size >= 1 && split_size <= ((int64_t)1 << 40) && (N + split_size - 1) / split_size <= 0x7fffffff,
+                  "vaw_is_finish: sizes N %lld C %d split_size %lld out of range", (long long)N, C, (long long)split_size);
+    VAW_CHECK_ARG(h && colsum && scores, "vaw_is_finish: null pointer");
+    is_finish_kernel<<<dim3((unsigned)((N + split_size - 1) / split_size)), 64, 0, (hipStream_t)stream>>>(h, colsum, N, C, split_size, scores);
+    VAW_CHECK_LAUNCH("vaw_is_finish");
     return VAW_OK;
 }
 

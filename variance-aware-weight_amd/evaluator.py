@@ -1,18 +1,26 @@
-"""FID statistics, Frechet distance and precision / recall from Inception activations: the part of the reference's
-evaluations/evaluator.py that follows `compute_activations`, with the reference's names and return types and no TensorFlow.
+"""FID statistics, Frechet distance, precision / recall and the Inception score from Inception activations: the part of the
+reference's evaluations/evaluator.py that follows `compute_activations`, with the reference's names and return types and no
+TensorFlow.
 
-The all-pairs distance work of `ManifoldEstimator` and the float64 mean / covariance of `compute_statistics` run as HIP kernels
-(csrc/metrics.hip); percentile clamping, the means of the flags and the matrix square root of the Frechet distance stay on the host
-in numpy / scipy as the reference has them.  Inputs are numpy arrays or torch tensors, on the CPU or on the device; they are
-uploaded once as float32 and a contiguous float32 device tensor is used in place.
+The all-pairs distance work of `ManifoldEstimator`, the float64 mean / covariance of `compute_statistics` and the whole of
+`compute_inception_score` -- the head product pool activations x softmax weight, the row softmax, the per-split entropies and class
+marginals -- run as HIP kernels (csrc/metrics.hip); percentile clamping, the means of the flags, the mean over the splits and the
+matrix square root of the Frechet distance stay on the host in numpy / scipy as the reference has them.  Inputs are numpy arrays or
+torch tensors, on the CPU or on the device; they are uploaded once as float32 and a contiguous float32 device tensor is used in place.
 
-Deliberate difference: the reference computes distances in fp16 and falls back to f32 only when that overflows, so its radii and
-comparisons are quantised to fp16 (about 0.25 at typical pool-feature distances).  Here every distance is f32:
+The Inception score needs one array from the user: the `[2048, 1008]` operand of the graph's `softmax/logits/MatMul` (there is no
+bias), as an array or a `.npy` / `.npz` path (INTEGRATION.md says how to get it out of the graph file offline).
+
+Deliberate differences.  (1) The reference computes distances in fp16 and falls back to f32 only when that overflows, so its radii
+and comparisons are quantised to fp16 (about 0.25 at typical pool-feature distances).  Here every distance is f32:
 max((|u|^2 - 2 u.v) + |v|^2, 0) with the dot product an ordered f32 fma chain.  Precision and recall can differ from a TensorFlow
-run in the third decimal.
+run in the third decimal.  (2) The reference reduces the Inception score in float32 numpy and computes 0 * log 0 = NaN once a
+float32 softmax underflows (a logit about 104 below its row's maximum): the whole score is then NaN.  Here the softmax and both
+sums are float64 and a term with p = 0 or a class marginal of 0 is its limit 0, so the score stays finite.
 
-Not built: the Inception feature extractor and `compute_inception_score` (their weights are a download), and
+Not built: the Inception feature extractor (`compute_activations` / `read_activations`: its weights are a download) and
 `ManifoldEstimator.evaluate` (realism scores)."""
+import os
 import warnings
 
 import numpy as np
@@ -197,9 +205,154 @@ def compute_prec_recall(activations_ref, activations_sample, manifold_estimator=
     return (float(pr[0][0]), float(pr[1][0]))
 
 
-def metrics_from_activations(ref_acts, sample_acts, ref_stats=None, ref_stats_spatial=None):
+MAX_SOFTMAX_ROWS = 65536      # rows per launch when softmax_batch_size is None: 264 MB of logits at C = 1008
+
+
+class _SoftmaxHead:
+    """The [D, C] softmax weight, checked where it lies; its class-major [C, D] device copy is made on first use and kept."""
+
+    def __init__(self, softmax_weight, what="compute_inception_score"):
+        w = softmax_weight
+        if isinstance(w, (str, os.PathLike)):
+            w = np.load(w)
+            if isinstance(w, np.lib.npyio.NpzFile):
+                if "softmax_weight" not in w.files:
+                    raise ValueError(f"{what}: {softmax_weight} has no array named softmax_weight (it holds {w.files})")
+                w = w["softmax_weight"]
+        if isinstance(w, np.ndarray):
+            w = torch.from_numpy(np.ascontiguousarray(w)) if w.flags.writeable else torch.tensor(w)
+        if not isinstance(w, torch.Tensor):
+            raise ValueError(f"{what}: softmax_weight must be a numpy array, a torch tensor or a .npy / .npz path, got {type(w).__name__}")
+        if w.dim() != 2 or w.shape[0] < 1 or w.shape[1] < 1:
+            raise ValueError(f"{what}: softmax_weight must be 2-D [D, C], got shape {tuple(w.shape)}")
+        if not w.is_floating_point() or not bool(torch.isfinite(w).all()):
+            raise ValueError(f"{what}: softmax_weight must be floating point without NaN or inf")
+        self.weight = w
+        self.width, self.classes = w.shape
+        self._wt = None
+
+    def class_major(self):
+        if self._wt is None:
+            w = self.weight if self.weight.is_cuda else self.weight.to(torch.float32).cuda()
+            self._wt = w.to(torch.float32).t().contiguous()
+        return self._wt
+
+
+def _split_size(what, split_size):
+    if int(split_size) != split_size or split_size < 1:
+        raise ValueError(f"{what}: split_size must be a positive integer, got {split_size}")
+    return int(split_size)
+
+
+def _batch_rows(what, softmax_batch_size):
+    if softmax_batch_size is None:
+        return MAX_SOFTMAX_ROWS
+    if int(softmax_batch_size) != softmax_batch_size or softmax_batch_size < 1:
+        raise ValueError(f"{what}: softmax_batch_size must be a positive integer or None, got {softmax_batch_size}")
+    return int(softmax_batch_size)
+
+
+def _finite_scores(what, scores):
+    scores = scores.cpu().numpy()
+    if not np.isfinite(scores).all():
+        raise ValueError(f"{what}: a split's score is not finite (logits or probabilities beyond float32 / float64 range)")
+    return scores
+
+
+def inception_split_scores(activations, softmax_weight, split_size=5000, softmax_batch_size=None, what="inception_split_scores"):
+    """float64 [splits]: exp(mean_i sum_c p_ic (ln p_ic - ln mean_i p_ic)) of every split of split_size rows (the last one ragged),
+    p = softmax(activations @ softmax_weight).  compute_inception_score is the mean of these."""
+    head = softmax_weight if isinstance(softmax_weight, _SoftmaxHead) else _SoftmaxHead(softmax_weight, what)
+    acts = _as_tensor(activations, what)
+    if acts.shape[1] != head.width:
+        raise ValueError(f"{what}: activations are {acts.shape[1]} wide, softmax_weight is [{head.width}, {head.classes}]")
+    split, batch = _split_size(what, split_size), _batch_rows(what, softmax_batch_size)
+    x = _device_features(acts, what)
+    _norms(x, what)
+    wt = head.class_major()
+    n, C = x.shape[0], head.classes
+    split, batch = min(split, n), min(batch, n)
+    lse = torch.empty(n, device=x.device, dtype=torch.float64)
+    h = torch.empty(n, device=x.device, dtype=torch.float64)
+    colsum = torch.zeros(-(-n // split), C, device=x.device, dtype=torch.float64)
+    logits = torch.empty(batch, C, device=x.device, dtype=torch.float32)
+    for r0 in range(0, n, batch):
+        r1 = min(r0 + batch, n)
+        rows = ops.head_logits(x[r0:r1], wt, logits[:r1 - r0])
+        ops.is_rows(rows, False, lse[r0:r1], h[r0:r1])
+        ops.is_colsums(rows, lse[r0:r1], r0, split, colsum)
+    return _finite_scores(what, ops.is_finish(h, colsum, split))
+
+
+def compute_inception_score(activations, softmax_weight, split_size=5000, softmax_batch_size=None):
+    """The reference's Evaluator.compute_inception_score: the mean over the splits of inception_split_scores.  activations: [N, D]
+    pool activations; softmax_weight: the [D, C] weight of the reference's softmax graph (an array or a .npy / .npz path);
+    softmax_batch_size caps the rows per launch and so the logits buffer, and no output bit depends on it."""
+    return float(np.mean(inception_split_scores(activations, softmax_weight, split_size, softmax_batch_size, "compute_inception_score")))
+
+
+def inception_split_scores_from_probs(preds, split_size=5000, what="inception_split_scores_from_probs"):
+    """inception_split_scores on given [N, C] probabilities (rows need not sum to 1)."""
+    p = _as_tensor(preds, what)
+    split = _split_size(what, split_size)
+    if not bool(torch.isfinite(p).all()) or bool((p < 0).any()):
+        raise ValueError(f"{what}: probabilities must be finite and non-negative")
+    p = _device_features(p, what)
+    n, C = p.shape
+    split = min(split, n)
+    colsum = torch.zeros(-(-n // split), C, device=p.device, dtype=torch.float64)
+    h = torch.empty(n, device=p.device, dtype=torch.float64)
+    for r0 in range(0, n, MAX_SOFTMAX_ROWS):
+        rows = p[r0:r0 + MAX_SOFTMAX_ROWS]
+        ops.is_rows(rows, True, None, h[r0:r0 + MAX_SOFTMAX_ROWS])
+        ops.is_colsums(rows, None, r0, split, colsum, probs=True)
+    return _finite_scores(what, ops.is_finish(h, colsum, split))
+
+
+def inception_score_from_probs(preds, split_size=5000):
+    """The second half of the reference's compute_inception_score on given [N, C] probabilities (rows need not sum to 1)."""
+    return float(np.mean(inception_split_scores_from_probs(preds, split_size, "inception_score_from_probs")))
+
+
+class Evaluator:
+    """The reference's Evaluator without its TensorFlow session: what follows compute_activations.  softmax_weight is the [D, C]
+    matrix of the Inception graph's softmax head (array or .npy / .npz path), needed by compute_inception_score only."""
+
+    def __init__(self, softmax_weight=None, manifold_estimator=None, softmax_batch_size=None):
+        self.softmax_batch_size = None if softmax_batch_size is None else _batch_rows("Evaluator", softmax_batch_size)
+        self.manifold_estimator = manifold_estimator or ManifoldEstimator()
+        self.softmax_head = None if softmax_weight is None else _SoftmaxHead(softmax_weight, "Evaluator")
+
+    def compute_activations(self, batches):
+        raise NotImplementedError("Evaluator.compute_activations: the Inception feature extractor is not built on the HIP path "
+                                  "(its weights are a download); start from pool / spatial activations")
+
+    def read_activations(self, npz_path):
+        raise NotImplementedError("Evaluator.read_activations: the Inception feature extractor is not built on the HIP path "
+                                  "(its weights are a download); start from pool / spatial activations")
+
+    def read_statistics(self, npz_path, activations):
+        obj = np.load(npz_path)
+        if "mu" in list(obj.keys()):
+            return FIDStatistics(obj["mu"], obj["sigma"]), FIDStatistics(obj["mu_s"], obj["sigma_s"])
+        return tuple(self.compute_statistics(x) for x in activations)
+
+    def compute_statistics(self, activations):
+        return compute_statistics(activations)
+
+    def compute_inception_score(self, activations, split_size=5000):
+        if self.softmax_head is None:
+            raise ValueError("Evaluator.compute_inception_score: no softmax_weight was given to the constructor")
+        return compute_inception_score(activations, self.softmax_head, split_size, self.softmax_batch_size)
+
+    def compute_prec_recall(self, activations_ref, activations_sample):
+        return compute_prec_recall(activations_ref, activations_sample, self.manifold_estimator)
+
+
+def metrics_from_activations(ref_acts, sample_acts, ref_stats=None, ref_stats_spatial=None, softmax_weight=None, split_size=5000):
     """What calculate_metrics does after compute_activations: ref_acts / sample_acts are (pool [N, 2048], spatial [N, 2023])
-    tuples; reference statistics that are given are used instead of being recomputed.  Returns dict(fid, sfid, precision, recall)."""
+    tuples; reference statistics that are given are used instead of being recomputed.  Returns dict(fid, sfid, precision, recall),
+    and with a softmax_weight also inception_score, of the sample pool activations."""
     for name, acts in (("ref_acts", ref_acts), ("sample_acts", sample_acts)):
         if not isinstance(acts, (tuple, list)) or len(acts) != 2:
             raise ValueError(f"metrics_from_activations: {name} must be a (pool, spatial) pair")
@@ -207,11 +360,20 @@ def metrics_from_activations(ref_acts, sample_acts, ref_stats=None, ref_stats_sp
     shapes = [[_as_tensor(a, what) for a in acts] for acts in (ref_acts, sample_acts)]
     _same_width(what, shapes[0][0], shapes[1][0])
     _same_width(what, shapes[0][1], shapes[1][1])
+    head = None
+    if softmax_weight is not None:
+        head = softmax_weight if isinstance(softmax_weight, _SoftmaxHead) else _SoftmaxHead(softmax_weight, what)
+        if head.width != shapes[1][0].shape[1]:
+            raise ValueError(f"{what}: pool activations are {shapes[1][0].shape[1]} wide, softmax_weight is [{head.width}, {head.classes}]")
+        _split_size(what, split_size)
     ref_pool = _device_features(ref_acts[0], "metrics_from_activations")
     sample_pool = _device_features(sample_acts[0], "metrics_from_activations")
     ref_stats = ref_stats if ref_stats is not None else compute_statistics(ref_pool)
     ref_stats_spatial = ref_stats_spatial if ref_stats_spatial is not None else compute_statistics(ref_acts[1])
     sample_stats, sample_stats_spatial = compute_statistics(sample_pool), compute_statistics(sample_acts[1])
     prec, recall = compute_prec_recall(ref_pool, sample_pool)
-    return dict(fid=float(sample_stats.frechet_distance(ref_stats)), sfid=float(sample_stats_spatial.frechet_distance(ref_stats_spatial)),
-                precision=prec, recall=recall)
+    out = dict(fid=float(sample_stats.frechet_distance(ref_stats)), sfid=float(sample_stats_spatial.frechet_distance(ref_stats_spatial)),
+               precision=prec, recall=recall)
+    if head is not None:
+        out["inception_score"] = compute_inception_score(sample_pool, head, split_size)
+    return out

@@ -1215,3 +1215,73 @@ def cov_f64(x, mu):
     sigma = torch.empty(x.shape[1], x.shape[1], device=x.device, dtype=torch.float64)
     check(L.lib().vaw_cov_f64(ptr(x), x.shape[0], x.shape[1], ptr(mu), ptr(sigma), stream_ptr()), "vaw_cov_f64")
     return sigma
+
+
+def _rows_f32(what, name, t):
+    """f32 [n, C] on the GPU with unit column stride, rows at least C apart (a row-strided view of a wider buffer is fine)."""
+    need_cuda(t)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{what}: {name} must be a non-empty float32 [n, C] tensor with unit column stride, got {t.dtype} {tuple(t.shape)} "
+                         f"strides {tuple(t.stride())}")
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def head_logits(x, wt, out=None):
+    """f32 [n, C]: out[i][c] = sum_k x[i][k] wt[c][k] for x [n, D] and the class-major weight wt [C, D], every element one ordered
+    f32 MFMA chain.  `out` may be a row-strided view; nothing outside its n x C elements is written."""
+    _features("head_logits", x, wt)
+    n, C = x.shape[0], wt.shape[0]
+    if out is None:
+        out = torch.empty(n, C, device=x.device, dtype=torch.float32)
+    ld = _rows_f32("head_logits", "out", out)
+    if tuple(out.shape) != (n, C):
+        raise ValueError(f"head_logits: out must be of shape {(n, C)}, got {tuple(out.shape)}")
+    check(L.lib().vaw_head_logits(ptr(x), n, x.shape[1], ptr(wt), C, ptr(out), ld, stream_ptr()), "vaw_head_logits")
+    return out
+
+
+def is_rows(rows, probs=False, lse=None, h=None):
+    """(lse, h), float64 [n]: of every row of logits its log-sum-exp and sum_c p_c (l_c - lse) with p = softmax; with probs=True the
+    rows are probabilities, h = sum_c p_c log p_c (0 log 0 = 0) and lse is 0."""
+    ld = _rows_f32("is_rows", "rows", rows)
+    n, C = rows.shape
+    lse = torch.empty(n, device=rows.device, dtype=torch.float64) if lse is None else lse
+    h = torch.empty(n, device=rows.device, dtype=torch.float64) if h is None else h
+    _per_row("is_rows", "lse", lse, n, dtype=torch.float64)
+    _per_row("is_rows", "h", h, n, dtype=torch.float64)
+    check(L.lib().vaw_is_rows(ptr(rows), n, C, ld, int(bool(probs)), ptr(lse), ptr(h), stream_ptr()), "vaw_is_rows")
+    return lse, h
+
+
+def is_colsums(rows, lse, row0, split_size, colsum, probs=False):
+    """colsum[s][c] += the probabilities of the rows (global rows row0 .. row0 + n) that lie in split s, each (s, c) one float64
+    chain in ascending row order which a later call continues; calls come in ascending row0.  colsum: float64 [splits, C]."""
+    ld = _rows_f32("is_colsums", "rows", rows)
+    n, C = rows.shape
+    row0, split_size = int(row0), int(split_size)
+    if row0 < 0 or split_size < 1:
+        raise ValueError(f"is_colsums: row0 = {row0}, split_size = {split_size} out of range")
+    if not probs:
+        _per_row("is_colsums", "lse", lse, n, dtype=torch.float64)
+    need_cuda(colsum)
+    if colsum.dtype != torch.float64 or colsum.dim() != 2 or not colsum.is_contiguous() or colsum.shape[1] != C \
+            or colsum.shape[0] * split_size < row0 + n:
+        raise ValueError(f"is_colsums: colsum must be a contiguous float64 [splits >= {-(-(row0 + n) // split_size)}, {C}] tensor, got "
+                         f"{colsum.dtype} {tuple(colsum.shape)}")
+    check(L.lib().vaw_is_colsums(ptr(rows), None if probs else ptr(lse), n, C, ld, int(bool(probs)), row0, split_size, ptr(colsum), stream_ptr()),
+          "vaw_is_colsums")
+
+
+def is_finish(h, colsum, split_size):
+    """float64 [splits]: exp(mean_i h_i - sum_c m_c log m_c) per split of split_size rows (the last one ragged), m = colsum / rows."""
+    need_cuda(h, colsum)
+    split_size = int(split_size)
+    if h.dtype != torch.float64 or h.dim() != 1 or not h.is_contiguous() or h.shape[0] < 1 or split_size < 1:
+        raise ValueError(f"is_finish: h must be a non-empty contiguous float64 [N] tensor and split_size >= 1, got {h.dtype} {tuple(h.shape)}, {split_size}")
+    N = h.shape[0]
+    S = -(-N // split_size)
+    if colsum.dtype != torch.float64 or colsum.dim() != 2 or not colsum.is_contiguous() or colsum.shape[0] != S or colsum.shape[1] < 1:
+        raise ValueError(f"is_finish: colsum must be a contiguous float64 [{S}, C] tensor, got {colsum.dtype} {tuple(colsum.shape)}")
+    scores = torch.empty(S, device=h.device, dtype=torch.float64)
+    check(L.lib().vaw_is_finish(ptr(h), ptr(colsum), N, colsum.shape[1], split_size, ptr(scores), stream_ptr()), "vaw_is_finish")
+    return scores

@@ -830,6 +830,46 @@ int vaw_col2im3x3(vaw_dtype dt, const void* dcol, void* dx, int B, int H, int W,
  * of 64 (mode 0 / 1), ... */
 int vaw_conv3x3(vaw_dtype dt, int mode, const void* act, const void* act2, const void* w, void* out, int B, int H, int W,
                 int Ci, int Co, const vaw_epilogue* epi_host, float* workspace, int64_t workspace_floats, vaw_stream stream);
+/* Launch plan of vaw_conv3x3: the one host function it (and the persistent kernel's conv entry) takes every check and launch choice
+ * from (pure arithmetic: it can be asked without a GPU).  The arguments of vaw_conv3x3 with addresses as integers, used for
+ * null-ness and alignment only (a NULL workspace counts as workspace_floats = 0); knobs: NULL = the process's own (vaw_gemm_plan
+ * describes them; the conv reads tile, force_generic and xcdsplit), cus: the CUs a persistent grid may use, 0 = what the process has
+ * (then the knobs' own count, if they state one).
+ * Order: invalid arguments (VAW_ERR_INVALID) -> shapes the explicit vaw_im2col3x3 + vaw_gemm path must take (VAW_ERR_UNSUPPORTED)
+ * -> workspace checks -> kernel.  The persistent 256-row kernel where the switch and the shape allow (tile 2 / 3 / 4, or by shape
+ * from half the CUs' worth of items; modes 0 / 1: bias and act-dtype residual epilogues only, Co resp. Ci >= 64, whole 64-pixel
+ * tiles; mode 2: the transposed problem dW^T [9 Ci][Co] with at least two K splits), the 128 x 128 kernel everywhere else.
+ * Both "rowsum_a_out (bias gradient) belongs to mode 2" and "mode 2 takes rowsum_a_out, not colsum_out" are refused on EVERY shape;
+ * they used to be reached only once the persistent kernel had declined, so that a mode 0 / 1 call with rowsum_a_out was refused at
+ * one shape and ran, its argument misread, at another. */
+typedef enum { VAW_CVR_NONE = 0, VAW_CVR_F32 = 1, VAW_CVR_F32_ROWSUM = 2, VAW_CVR_SLAB_T = 3 } vaw_conv_reduce;
+typedef enum { VAW_CVB_NONE = 0, VAW_CVB_FUSED = 1, VAW_CVB_FOLD = 2, VAW_CVB_SEPARATE = 3 } vaw_conv_bias_grad;
+typedef struct {
+    int variant;                    /* vaw_gemm_variant: VAW_GV_T128_BK64 (gemm_bf16_kernel<.., 64, CONV>) | VAW_GV_PERSISTENT */
+    int ntw;                        /* persistent: tile columns / 64 (3 | 4); else 0 */
+    int epi_kind;                   /* persistent: P8_STORE | P8_RESID | P8_SLAB (gemm_epi.h); else -1 */
+    int transposed;                 /* 1: the kernel computes dW^T [9 Ci][Co] (persistent, mode 2); the reduce transposes it back */
+    int64_t M, N, K;                /* the GEMM problem the kernel runs: mode 0 [pixels][Co] over 9 Ci, mode 1 [pixels][Ci] over 9 Co,
+                                     * mode 2 [Co][9 Ci] (transposed: [9 Ci][Co]) over the pixels */
+    int split;                      /* K splits (1 = none) */
+    int xcd_parts;                  /* 8 / split for the 128 x 128 kernel's K-range-per-XCD mapping, else 0 */
+    int grid_x, grid_y, block;
+    int64_t lds_bytes;
+    int reduce;                     /* vaw_conv_reduce: none | splitk_reduce f32 | the same, folding the bias gradient's partial rows |
+                                     * p8_conv_wgrad_reduce_kernel (transposes the slabs; folds the partial rows when there are any) */
+    int bias_grad;                  /* vaw_conv_bias_grad: rowsum_a_out of mode 2.  FUSED: partial rows from the kernel, folded by the reduce
+                                     * pass; FOLD: the un-split 128 x 128 launch's one row, by vaw_reduce_rows; SEPARATE: a vaw_colsum
+                                     * pass over dy (256-column persistent kernel, or no room behind the slabs) */
+    int colsum_mode;                /* vaw_gemm_colsum_mode: VAW_GC_NONE | VAW_GC_FOLD (colsum_out, modes 0 / 1: 128 x 128 kernel only) */
+    int64_t colsum_rows;            /* partial rows of column sums the launch writes (0 without column sums) */
+    int64_t workspace_floats_used;  /* slabs [split][M][N], then bias-gradient partials [split][Co]; column-sum rows from 0 (never with
+                                     * slabs); a separate vaw_colsum pass reuses the workspace */
+    int launches;                   /* kernels enqueued, passes included */
+    int status;                     /* vaw_status: VAW_OK, or what vaw_conv3x3 returns before launching anything */
+} vaw_conv3x3_launch;
+int vaw_conv3x3_plan(vaw_dtype dt, int mode, int64_t act, int64_t act2, int64_t w, int64_t out, int B, int H, int W, int Ci, int Co,
+                     const vaw_epilogue* epi_host, int64_t workspace, int64_t workspace_floats, const vaw_gemm_knobs* knobs, int cus,
+                     vaw_conv3x3_launch* plan);
 /* conv3x3 weight gradient for the 3-channel stem / output convs (Ci <= 4 or Co <= 4), where a GEMM would be 3 wide:
  * dw[co][tap][ci] (f32, channels-last weight layout) = beta*dw + sum_m dy[m,co] * x[pixel(m)+tap, ci]; chunk
  * partials in the workspace are folded in a fixed order. */

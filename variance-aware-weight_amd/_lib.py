@@ -59,6 +59,13 @@ class GemmLaunch(C.Structure):
                 ("status", _i)]
 
 
+class Conv3x3Launch(C.Structure):
+    """vaw_conv3x3_launch of include/vaw_hip.h: the launch vaw_conv3x3_plan picks for a vaw_conv3x3 call."""
+    _fields_ = [("variant", _i), ("ntw", _i), ("epi_kind", _i), ("transposed", _i), ("M", _l), ("N", _l), ("K", _l), ("split", _i),
+                ("xcd_parts", _i), ("grid_x", _i), ("grid_y", _i), ("block", _i), ("lds_bytes", _l), ("reduce", _i), ("bias_grad", _i),
+                ("colsum_mode", _i), ("colsum_rows", _l), ("workspace_floats_used", _l), ("launches", _i), ("status", _i)]
+
+
 class GemmFp8Launch(C.Structure):
     """vaw_gemm_fp8_launch of include/vaw_hip.h: the launch vaw_gemm_fp8_plan picks for a vaw_gemm_fp8 call."""
     _fields_ = [("epi_kind", _i), ("a_e5m2", _i), ("c_fp8", _i), ("c_e5m2", _i), ("ntw", _i), ("tiles_m", _i), ("tiles_n", _i), ("nk", _i),
@@ -89,6 +96,11 @@ GV_NAMES = ("generic", "t128_bk32", "t128_bk64", "ring256", "persistent", "small
 GR_NONE, GR_F32, GR_BF16, GR_F32_ROWSUM = range(4)
 GS_NONE, GS_FUSED, GS_SEPARATE = range(3)
 GC_NONE, GC_FOLD, GC_DEFERRED, GC_SEPARATE = range(4)
+# vaw_conv_reduce / vaw_conv_bias_grad
+CVR_NONE, CVR_F32, CVR_F32_ROWSUM, CVR_SLAB_T = range(4)
+CVR_NAMES = ("CVR_NONE", "CVR_F32", "CVR_F32_ROWSUM", "CVR_SLAB_T")
+CVB_NONE, CVB_FUSED, CVB_FOLD, CVB_SEPARATE = range(4)
+CVB_NAMES = ("CVB_NONE", "CVB_FUSED", "CVB_FOLD", "CVB_SEPARATE")
 P8_STORE, P8_GELU, P8_DGELU, P8_GATE, P8_SLAB, P8_ANY, P8_WGRAD, P8_RESID, P8_GELU_Q, P8_DGELU_Q = range(10)
 P8_NAMES = ("P8_STORE", "P8_GELU", "P8_DGELU", "P8_GATE", "P8_SLAB", "P8_ANY", "P8_WGRAD", "P8_RESID", "P8_GELU_Q", "P8_DGELU_Q")
 
@@ -193,6 +205,7 @@ _PROTOS = {
     "vaw_attn_plan": [_i, _i, C.POINTER(AttnDesc), _l, _l, _l, _l, _l, _l, _l, C.POINTER(AttnLaunch)],
     "vaw_gn_plan": [_i, _i, _i, _i, _i, _i, C.POINTER(GnLaunch)],
     "vaw_gemm_plan": [_i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _l, _l, C.POINTER(Epilogue), _l, C.POINTER(GemmKnobs), C.POINTER(GemmLaunch)],
+    "vaw_conv3x3_plan": [_i, _i, _l, _l, _l, _l, _i, _i, _i, _i, _i, C.POINTER(Epilogue), _l, _l, C.POINTER(GemmKnobs), _i, C.POINTER(Conv3x3Launch)],
     "vaw_dit_ws_plan": [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(DitWsPlan)],
     "vaw_latent_qsample": [_p, _p, _p, _p, _p, _p, _i, _f, _f, _p, _p, _p, _i, _l, _p],
     "vaw_wmse_fwd_t": [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _f, _i, _l, _p],

@@ -741,9 +741,8 @@ static_assert(FastCfg<32>::lds_bytes == vaw_lds_t128(32) && FastCfg<64>::lds_byt
 // launchers of the other translation units: the tile parameters, epilogue kind and grid are the plan's
 void vaw_sm_launch(int mb, int nb, int stages, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda,
                    const bf16_t* b, int64_t ldb, const EpiDev& e, hipStream_t s);      // gemm_sm.hip
-bool vaw_p8_conv(int mode, const bf16_t* act, const bf16_t* act2, const bf16_t* w, void* out, int B, int H, int W, int Ci, int Co,
-                 EpiDev e, float* workspace, int64_t workspace_floats, int force, hipStream_t s, float* bias_grad, float bias_beta,
-                 int* bias_done);
+void vaw_p8_conv(const vaw_conv3x3_launch& p, int mode, const bf16_t* act, const bf16_t* act2, const bf16_t* w, void* out, int H, int W,
+                 int Ci, int Co, EpiDev e, float* workspace, hipStream_t s, float* bias_grad, float bias_beta);
 void vaw_p8_launch(const P8Plan& pl, int epi, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda,
                    const bf16_t* b, int64_t ldb, const EpiDev& e, hipStream_t s);
 void vaw_pd_launch(int ntw, int epi, int b_kmajor, int64_t M, int64_t N, int64_t K, const bf16_t* a, int64_t lda, const bf16_t* b,
@@ -879,65 +878,35 @@ extern "C" int vaw_gemm(vaw_dtype dt, int a_kmajor, int b_kmajor, int64_t M, int
 extern "C" int vaw_conv3x3(vaw_dtype dt, int mode, const void* act, const void* act2, const void* w, void* out, int B, int H,
                            int W, int Ci, int Co, const vaw_epilogue* ep, float* workspace, int64_t workspace_floats,
                            vaw_stream stream) {
-    VAW_CHECK_ARG(mode >= 0 && mode <= 2 && act && (w || mode == 2) && out && B > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0,
-                  "conv3x3: bad arguments");
-    if (dt != VAW_BF16 || vaw_gemm_knobs_state().force_generic) return VAW_ERR_UNSUPPORTED;
-    const int64_t Mpix = (int64_t)B * H * W;
-    int64_t M, N, K;
-    if (mode == 0) { M = Mpix; N = Co; K = 9LL * Ci; if (Ci % 64) return VAW_ERR_UNSUPPORTED; }
-    else if (mode == 1) { M = Mpix; N = Ci; K = 9LL * Co; if (Co % 64) return VAW_ERR_UNSUPPORTED; }
-    else { M = Co; N = 9LL * Ci; K = Mpix; if (Ci % 8 || Mpix % 64 || Co % 8 || !act2) return VAW_ERR_UNSUPPORTED; }
-    if (N % 8 || M < 16 || N < 16 || Mpix >= (1LL << 31)) return VAW_ERR_UNSUPPORTED;
-    if ((((uintptr_t)act | (uintptr_t)act2 | (uintptr_t)w | (uintptr_t)out) & 15) != 0) return VAW_ERR_UNSUPPORTED;
-    const GemmKnobs& k = vaw_gemm_knobs_state();
-    EpiDev e = vaw_epi_dev(ep, k);
+    // validate -> plan -> launch: every check and choice is vaw_conv3x3_plan's (gemm_plan.hip); the code below only carries it out
+    vaw_conv3x3_launch p;
+    int rc = vaw_conv3x3_plan(dt, mode, (int64_t)(uintptr_t)act, (int64_t)(uintptr_t)act2, (int64_t)(uintptr_t)w, (int64_t)(uintptr_t)out, B, H,
+                              W, Ci, Co, ep, (int64_t)(uintptr_t)workspace, workspace_floats, nullptr, 0, &p);
+    if (rc) return rc;         // (every refusal: nothing has been launched)
+    EpiDev e = vaw_epi_dev(ep, vaw_gemm_knobs_state());
     e.debug = 0;            // (the ablation switch of VAW_GEMM_DEBUG belongs to vaw_gemm's launches)
     if (mode == 2) e.out_f32 = 1;
-    VAW_CHECK_ARG(e.beta == 0.f || e.out_f32, "conv3x3: beta needs f32 output");
-    float* colsum_out = ep ? ep->colsum_out : nullptr;
-    const float colsum_beta = ep ? ep->colsum_beta : 0.f;
-    const int64_t ldc = N;
-    e.M = M; e.N = N; e.ldc = ldc; e.C = out; e.slab = workspace;
-    const bool epi_aligned = e.gate_ld % 4 == 0 && ((((uintptr_t)e.bias | (uintptr_t)e.aux_in | (uintptr_t)e.aux_out |
-                                                     (uintptr_t)e.gate | (uintptr_t)e.resid | (uintptr_t)e.rowadd) & 15) == 0);
-    if (!epi_aligned) return VAW_ERR_UNSUPPORTED;
-    VAW_CHECK_ARG(!colsum_out || (workspace && workspace_floats >= ((M + 127) / 128) * N), "conv3x3: colsum_out needs a workspace");
+    const int64_t Mpix = (int64_t)B * H * W, M = p.M, N = p.N;
+    e.M = M; e.N = N; e.ldc = N; e.C = out; e.slab = workspace;
+    float* const rowsum_out = ep ? ep->rowsum_a_out : nullptr;
+    const float rowsum_beta = ep ? ep->rowsum_a_beta : 0.f;
     hipStream_t s = (hipStream_t)stream;
-    {   // the persistent 256-row-tile kernel first (gemm_p8_conv.hip); shapes it declines stay on the 128 x 128 kernel below
-        const int force = k.tile == -1 ? -1 : k.tile == 4 ? 1 : (k.tile == 2 || k.tile == 3) ? k.tile : 0;
-        float* rowsum_out8 = ep ? ep->rowsum_a_out : nullptr;
-        int bias_done = 0;
-        if (!colsum_out && (mode != 2 || act2) && force != 0 &&
-            vaw_p8_conv(mode, (const bf16_t*)act, (const bf16_t*)act2, (const bf16_t*)w, out, B, H, W, Ci, Co, e, workspace, workspace_floats,
-                        force, s, mode == 2 ? rowsum_out8 : nullptr, ep ? ep->rowsum_a_beta : 0.f, &bias_done)) {
-            VAW_CHECK_LAUNCH("conv3x3_p8");
-            if (rowsum_out8 && !bias_done)     // bias gradient = column sums of dy [Mpix][Co], as a pass of its own
-                return vaw_colsum(dt, act, Mpix, Co, Co, rowsum_out8, ep->rowsum_a_beta, workspace, workspace_floats, stream);
-            return VAW_OK;
-        }
+    if (p.variant == VAW_GV_PERSISTENT) {      // gemm_p8_conv.hip
+        vaw_p8_conv(p, mode, (const bf16_t*)act, (const bf16_t*)act2, (const bf16_t*)w, out, H, W, Ci, Co, e, workspace, s, rowsum_out, rowsum_beta);
+        VAW_CHECK_LAUNCH("conv3x3_p8");
+        if (p.bias_grad == VAW_CVB_SEPARATE)     // bias gradient = column sums of dy [Mpix][Co], as a pass of its own
+            return vaw_colsum(dt, act, Mpix, Co, Co, rowsum_out, rowsum_beta, workspace, workspace_floats, stream);
+        return VAW_OK;
     }
     const int tiles_n = (int)((N + BN - 1) / BN);
-    const int64_t n_wg = ((M + BM - 1) / BM) * tiles_n;
-    const int nk_total = (int)(K / 64);
-    const bool plain_f32 = mode == 2 && !e.bias && !e.act;
-    float* rowsum_out = ep ? ep->rowsum_a_out : nullptr;
-    const float rowsum_beta = ep ? ep->rowsum_a_beta : 0.f;
-    VAW_CHECK_ARG(!rowsum_out || mode == 2, "conv3x3: rowsum_a_out (bias gradient) belongs to mode 2");
-    VAW_CHECK_ARG(!(colsum_out && mode == 2), "conv3x3: mode 2 takes rowsum_a_out, not colsum_out");
-    const bool bias_grad = rowsum_out != nullptr;        // sum over pixels of dy (row sums of A = dy^T)
-    int split = (colsum_out && !bias_grad) ? 1 : pick_split(n_wg, K, M * N, workspace_floats - (bias_grad ? 64 * M : 0), plain_f32);
-    if (colsum_out && !bias_grad) e.colpart = workspace;
-    split = no_empty_split(nk_total, split);
+    const int n_wg = (int)((M + BM - 1) / BM) * tiles_n;
+    const int nk_total = (int)(p.K / 64);
+    if (p.colsum_mode == VAW_GC_FOLD) e.colpart = workspace;
     float* rowpart = nullptr;
-    if (bias_grad) {
-        VAW_CHECK_ARG(workspace && workspace_floats >= (split > 1 ? split * M * N : 0) + split * M, "conv3x3: bias gradient needs a workspace");
-        rowpart = e.rowpart = workspace + (split > 1 ? split * M * N : 0);
-    }
-    const int xparts = xcd_parts_for(k, split);
-    dim3 grid((unsigned)n_wg, (unsigned)split);
-    if (xparts) grid = dim3((unsigned)(8 * ((n_wg + xparts - 1) / xparts)), 1);
+    if (p.bias_grad != VAW_CVB_NONE) rowpart = e.rowpart = workspace + (p.split > 1 ? (int64_t)p.split * M * N : 0);     // behind the slabs
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
     const ConvGeom cg{H, W, Ci, Co};
-    const int lds = FastCfg<64>::lds_bytes;
+    const int lds = (int)p.lds_bytes;
 #define LAUNCH_CONV(AKv, BKv, CV, Aptr, LDA, Bptr, LDB)                                                                  \
     do {                                                                                                                 \
         static bool attr_done = false;                                                                                   \
@@ -946,15 +915,15 @@ extern "C" int vaw_conv3x3(vaw_dtype dt, int mode, const void* act, const void* 
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);                                  \
             attr_done = true;                                                                                            \
         }                                                                                                                \
-        gemm_bf16_kernel<AKv, BKv, 64, CV><<<grid, 256, lds, s>>>((const bf16_t*)(Aptr), LDA, (const bf16_t*)(Bptr), LDB, \
-                                                                  nk_total, tiles_n, (int)n_wg, split, e, cg, xparts);   \
+        gemm_bf16_kernel<AKv, BKv, 64, CV><<<grid, p.block, lds, s>>>((const bf16_t*)(Aptr), LDA, (const bf16_t*)(Bptr), LDB, \
+                                                                      nk_total, tiles_n, n_wg, p.split, e, cg, p.xcd_parts); \
     } while (0)
     if (mode == 0) LAUNCH_CONV(true, true, 1, act, (int64_t)Ci, w, 9LL * Ci);
     else if (mode == 1) LAUNCH_CONV(true, false, 2, act, (int64_t)Co, w, 9LL * Ci);
     else LAUNCH_CONV(false, false, 3, act, (int64_t)Co, act2, (int64_t)Ci);
-    if (split > 1) splitk_reduce(VAW_GR_F32, workspace, split, M, N, ldc, out, e.alpha, e.beta, s, rowpart, rowsum_out, rowsum_beta);
+    if (p.reduce != VAW_CVR_NONE) splitk_reduce(VAW_GR_F32, workspace, p.split, M, N, N, out, e.alpha, e.beta, s, rowpart, rowsum_out, rowsum_beta);
     VAW_CHECK_LAUNCH("conv3x3");
-    if (bias_grad && split == 1) return vaw_reduce_rows(rowpart, split, M, rowsum_out, rowsum_beta, stream);
-    if (colsum_out) return vaw_reduce_rows(workspace, (M + BM - 1) / BM, N, colsum_out, colsum_beta, stream);
+    if (p.bias_grad == VAW_CVB_FOLD) return vaw_reduce_rows(rowpart, 1, M, rowsum_out, rowsum_beta, stream);
+    if (p.colsum_mode == VAW_GC_FOLD) return vaw_reduce_rows(workspace, p.colsum_rows, N, ep->colsum_out, ep->colsum_beta, stream);
     return VAW_OK;
 }

@@ -50,38 +50,21 @@ p8_conv_wgrad_reduce_kernel(const float* __restrict__ slab, int S, int Mt, int N
     }
 }
 
-// mode 0 forward, 1 input gradient, 2 weight gradient.  Returns false when the shape should stay on gemm.hip's kernel.
-bool vaw_p8_conv(int mode, const bf16_t* act, const bf16_t* act2, const bf16_t* w, void* out, int B, int H, int W, int Ci, int Co,
-                 EpiDev e, float* workspace, int64_t workspace_floats, int force, hipStream_t s, float* bias_grad, float bias_beta,
-                 int* bias_done) {
-    const int64_t Mpix = (int64_t)B * H * W;
-    if (Mpix * (Ci > Co ? Ci : Co) >= (1LL << 31) || Mpix % 64) return false;
-    int64_t M, N, K;
-    if (mode == 0) { M = Mpix; N = Co; K = 9LL * Ci; if (Ci % 64) return false; }
-    else if (mode == 1) { M = Mpix; N = Ci; K = 9LL * Co; if (Co % 64) return false; }
-    else { M = 9LL * Ci; N = Co; K = Mpix; if (Ci % 8 || Co % 8 || !workspace) return false; }     // transposed problem
-    if (N % 8 || N < 64) return false;
-    if (mode != 2 && (e.act || e.aux_out || e.gate || e.rowadd || e.out_f32 || e.beta != 0.f || e.colpart)) return false;
-    if (mode != 2 && e.resid && !e.resid_act) return false;
-    const P8Plan pl = vaw_p8_plan(M, N, K, mode == 2, false, workspace_floats, force, vaw_p8_cus_available());
-    if (!pl.use) return false;
-    if (mode == 2 && pl.split < 2) return false;                    // (always K-split in practice: K = pixels, few tiles)
-    const int bn = 64 * pl.ntw, tiles_m = (int)((M + 255) / 256), tiles_n = (int)((N + bn - 1) / bn), nk = (int)(K / 64);
+// mode 0 forward, 1 input gradient, 2 weight gradient: the launch vaw_conv3x3_plan chose (variant VAW_GV_PERSISTENT), carried out.
+void vaw_p8_conv(const vaw_conv3x3_launch& p, int mode, const bf16_t* act, const bf16_t* act2, const bf16_t* w, void* out, int H, int W,
+                 int Ci, int Co, EpiDev e, float* workspace, hipStream_t s, float* bias_grad, float bias_beta) {
+    const int64_t M = p.M, N = p.N;        // mode 2: the transposed problem, M = 9 Ci, N = Co
+    const int bn = 64 * p.ntw, tiles_m = (int)((M + 255) / 256), tiles_n = (int)((N + bn - 1) / bn), nk = (int)(p.K / 64);
     const P8Conv cg{H, W, Ci, Co};
     e.M = M; e.N = N; e.ldc = N; e.C = out; e.slab = workspace; e.colpart = nullptr; e.rowpart = nullptr; e.nt_off = 1;
-    *bias_done = 0;
-    if (mode == 2 && bias_grad && pl.ntw == 3 && workspace_floats >= (int64_t)pl.split * M * N + (int64_t)pl.split * N) {
-        // bias gradient on the same launch (192-column kernel only: the 256-column one has no registers left for it)
-        e.rowpart = workspace + (int64_t)pl.split * M * N;
-        *bias_done = 1;
-    }
+    if (p.bias_grad == VAW_CVB_FUSED) e.rowpart = workspace + (int64_t)p.split * M * N;      // behind the slabs
 #define P8C(AKv, BKv, EPIv, CV, a, lda, b, ldb)                                                                                   \
     do {                                                                                                                          \
-        if (pl.ntw == 4) p8_launch_conv<AKv, BKv, 4, EPIv, CV>(a, lda, b, ldb, nk, tiles_m, tiles_n, pl.split, pl.grid, e, cg, s); \
-        else p8_launch_conv<AKv, BKv, 3, EPIv, CV>(a, lda, b, ldb, nk, tiles_m, tiles_n, pl.split, pl.grid, e, cg, s);             \
+        if (p.ntw == 4) p8_launch_conv<AKv, BKv, 4, EPIv, CV>(a, lda, b, ldb, nk, tiles_m, tiles_n, p.split, p.grid_x, e, cg, s); \
+        else p8_launch_conv<AKv, BKv, 3, EPIv, CV>(a, lda, b, ldb, nk, tiles_m, tiles_n, p.split, p.grid_x, e, cg, s);             \
     } while (0)
     if (mode == 0) {
-        if (e.resid) P8C(true, true, P8_RESID, 1, act, (int64_t)Ci, w, 9LL * Ci);
+        if (p.epi_kind == P8_RESID) P8C(true, true, P8_RESID, 1, act, (int64_t)Ci, w, 9LL * Ci);
         else P8C(true, true, P8_STORE, 1, act, (int64_t)Ci, w, 9LL * Ci);
     } else if (mode == 1) {
         P8C(true, false, P8_STORE, 2, act, (int64_t)Co, w, 9LL * Ci);
@@ -89,7 +72,6 @@ bool vaw_p8_conv(int mode, const bf16_t* act, const bf16_t* act2, const bf16_t* 
         const float beta = e.beta;
         P8C(false, false, P8_SLAB, 3, act2, (int64_t)Ci, act, (int64_t)Co);      // A = x (gathered), B = dy
         dim3 grid((unsigned)((M + 31) / 32), (unsigned)((N + 63) / 64));
-        p8_conv_wgrad_reduce_kernel<<<grid, 256, 0, s>>>(workspace, pl.split, (int)M, (int)N, (float*)out, beta, e.rowpart, bias_grad, bias_beta);
+        p8_conv_wgrad_reduce_kernel<<<grid, 256, 0, s>>>(workspace, p.split, (int)M, (int)N, (float*)out, beta, e.rowpart, bias_grad, bias_beta);
     }
-    return true;
 }

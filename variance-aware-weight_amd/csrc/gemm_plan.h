@@ -1,6 +1,6 @@
 // Host side shared by the GEMM translation units: the knobs, the persistent kernel's shape plan, the LDS size of every kernel
 // (asserted against the kernels' own configuration where they are defined) and the vaw_epilogue -> EpiDev copy.
-// vaw_gemm_plan (gemm_plan.hip) is the one place a launch choice of vaw_gemm is made.
+// vaw_gemm_plan (gemm_plan.hip) is the one place a launch choice of vaw_gemm is made, vaw_conv3x3_plan (same file) of vaw_conv3x3.
 #pragma once
 #include "gemm_epi.h"
 
@@ -15,7 +15,7 @@ struct P8Plan {
 };
 P8Plan vaw_p8_plan(int64_t M, int64_t N, int64_t K, bool plain_f32, bool want_colsum, int64_t ws_floats, int force, int cus);
 
-// ---- split-K arithmetic shared by vaw_gemm_plan and vaw_conv3x3
+// ---- split-K arithmetic shared by vaw_gemm_plan and vaw_conv3x3_plan
 // Split-K factor: only for plain f32-output epilogues (the weight gradients: long K = B*T, few output tiles),
 // sized so the launch has ~2 workgroups per CU, each split keeping >= 256 of K, within the workspace.
 inline int pick_split(int64_t tiles, int64_t K, int64_t MN, int64_t ws_floats, bool plain_f32) {

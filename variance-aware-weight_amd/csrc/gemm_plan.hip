@@ -290,3 +290,103 @@ extern "C" int vaw_gemm_plan(vaw_dtype dt, int a_kmajor, int b_kmajor, int64_t M
     out->status = p.status = VAW_OK;
     return VAW_OK;
 }
+
+// vaw_conv3x3_plan: every check and launch choice of vaw_conv3x3 (gemm.hip) and of the persistent kernel's conv entry
+// (gemm_p8_conv.hip).  Invalid arguments first, then the shapes the explicit path must take, then the kernel.
+extern "C" int vaw_conv3x3_plan(vaw_dtype dt, int mode, int64_t act, int64_t act2, int64_t w, int64_t out, int B, int H, int W, int Ci,
+                                int Co, const vaw_epilogue* ep, int64_t workspace, int64_t ws, const vaw_gemm_knobs* knobs, int cus,
+                                vaw_conv3x3_launch* plan) {
+    VAW_CHECK_ARG(plan, "conv3x3_plan: plan is NULL");
+    vaw_conv3x3_launch p = {};
+    p.status = VAW_ERR_INVALID;
+    p.epi_kind = -1;
+    p.split = p.grid_y = 1;
+    *plan = p;
+    const GemmKnobs& k = knobs ? *knobs : vaw_gemm_knobs_state();
+    if (cus <= 0) cus = k.cus > 0 ? k.cus : vaw_p8_cus_available();
+    if (!workspace || ws < 0) ws = 0;
+    VAW_CHECK_ARG(mode >= 0 && mode <= 2 && act && (w || mode == 2) && out && B > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0,
+                  "conv3x3: bad arguments");
+    EpiDev e = vaw_epi_dev(ep, k);
+    if (mode == 2) e.out_f32 = 1;
+    const bool colsum = ep && ep->colsum_out, bias_grad = ep && ep->rowsum_a_out;
+    VAW_CHECK_ARG(!bias_grad || mode == 2, "conv3x3: rowsum_a_out (bias gradient) belongs to mode 2");
+    VAW_CHECK_ARG(!(colsum && mode == 2), "conv3x3: mode 2 takes rowsum_a_out, not colsum_out");
+    // ---- shapes of the explicit path: nothing is launched
+    const auto unsupported = [&] { plan->status = VAW_ERR_UNSUPPORTED; return VAW_ERR_UNSUPPORTED; };
+    if (dt != VAW_BF16 || k.force_generic) return unsupported();
+    const int64_t Mpix = (int64_t)B * H * W;
+    int64_t M, N, K;           // the 128 x 128 kernel's problem
+    if (mode == 0) { M = Mpix; N = Co; K = 9LL * Ci; if (Ci % 64) return unsupported(); }
+    else if (mode == 1) { M = Mpix; N = Ci; K = 9LL * Co; if (Co % 64) return unsupported(); }
+    else { M = Co; N = 9LL * Ci; K = Mpix; if (Ci % 8 || Mpix % 64 || Co % 8 || !act2) return unsupported(); }
+    if (N % 8 || M < 16 || N < 16 || Mpix >= (1LL << 31)) return unsupported();
+    if (((act | act2 | w | out) & 15) != 0) return unsupported();
+    VAW_CHECK_ARG(e.beta == 0.f || e.out_f32, "conv3x3: beta needs f32 output");
+    const bool epi_aligned = e.gate_ld % 4 == 0 && ((((uintptr_t)e.bias | (uintptr_t)e.aux_in | (uintptr_t)e.aux_out | (uintptr_t)e.gate |
+                                                     (uintptr_t)e.resid | (uintptr_t)e.rowadd) & 15) == 0);
+    if (!epi_aligned) return unsupported();
+    VAW_CHECK_ARG(!colsum || ws >= ((M + 127) / 128) * N, "conv3x3: colsum_out needs a workspace");
+    p.launches = 1;
+    // ---- the persistent 256-row kernel first; mode 2 runs the transposed problem dW^T [9 Ci][Co] there, always K-split
+    const int force = k.tile == -1 ? -1 : k.tile == 4 ? 1 : (k.tile == 2 || k.tile == 3) ? k.tile : 0;
+    const int64_t M8 = mode == 2 ? N : M, N8 = mode == 2 ? M : N;
+    bool p8 = !colsum && force != 0 && Mpix * (Ci > Co ? Ci : Co) < (1LL << 31) && Mpix % 64 == 0 && N8 >= 64 && (mode != 2 || ws > 0);
+    if (mode != 2 && (e.act || e.aux_out || e.gate || e.rowadd || e.out_f32 || e.beta != 0.f || (e.resid && !e.resid_act))) p8 = false;
+    if (p8) {
+        const P8Plan pl = vaw_p8_plan(M8, N8, K, mode == 2, false, ws, force, cus);
+        if (pl.use && (mode != 2 || pl.split >= 2)) {
+            p.variant = VAW_GV_PERSISTENT;
+            p.ntw = pl.ntw;
+            p.epi_kind = mode == 2 ? P8_SLAB : (mode == 0 && e.resid) ? P8_RESID : P8_STORE;
+            p.transposed = mode == 2;
+            p.M = M8, p.N = N8, p.K = K;
+            p.split = pl.split;
+            p.grid_x = pl.grid;
+            p.block = 512;
+            p.lds_bytes = vaw_lds_p8(pl.ntw);
+            if (mode == 2) {
+                p.reduce = VAW_CVR_SLAB_T;
+                p.launches += 1;
+                p.workspace_floats_used = (int64_t)pl.split * M8 * N8;
+                // bias gradient on the same launch: 192-column kernel only (the 256-column one has no registers left for it)
+                if (bias_grad && pl.ntw == 3 && ws >= p.workspace_floats_used + (int64_t)pl.split * N8) {
+                    p.bias_grad = VAW_CVB_FUSED;
+                    p.workspace_floats_used += (int64_t)pl.split * N8;
+                } else if (bias_grad) {      // column sums of dy [pixels][Co], as a pass of its own
+                    p.bias_grad = VAW_CVB_SEPARATE;
+                    vaw_row_launch rp;
+                    const int rc = vaw_row_plan(VAW_ROW_COLSUM, dt, Mpix, 1, Co, Co, act, ws, &rp);
+                    if (rc) return rc;
+                    if (rp.workspace_floats > p.workspace_floats_used) p.workspace_floats_used = rp.workspace_floats;
+                    p.launches += 2;
+                }
+            }
+            *plan = p;
+            plan->status = p.status = VAW_OK;
+            return VAW_OK;
+        }
+    }
+    // ---- 128 x 128
+    const int64_t n_wg = ((M + 127) / 128) * ((N + 127) / 128);
+    const bool plain_f32 = mode == 2 && !e.bias && !e.act;
+    p.variant = VAW_GV_T128_BK64;
+    p.M = M, p.N = N, p.K = K;
+    p.split = no_empty_split((int)(K / 64), colsum ? 1 : pick_split(n_wg, K, M * N, ws - (bias_grad ? 64 * M : 0), plain_f32));
+    const int64_t slabs = p.split > 1 ? (int64_t)p.split * M * N : 0;
+    VAW_CHECK_ARG(!bias_grad || (ws > 0 && ws >= slabs + p.split * M), "conv3x3: bias gradient needs a workspace");
+    p.xcd_parts = xcd_parts_for(k, p.split);
+    p.grid_x = p.xcd_parts ? (int)(8 * ((n_wg + p.xcd_parts - 1) / p.xcd_parts)) : (int)n_wg;
+    p.grid_y = p.xcd_parts ? 1 : p.split;
+    p.block = 256;
+    p.lds_bytes = vaw_lds_t128(64);
+    p.reduce = p.split == 1 ? VAW_CVR_NONE : bias_grad ? VAW_CVR_F32_ROWSUM : VAW_CVR_F32;
+    p.bias_grad = !bias_grad ? VAW_CVB_NONE : p.split > 1 ? VAW_CVB_FUSED : VAW_CVB_FOLD;
+    p.colsum_mode = colsum ? VAW_GC_FOLD : VAW_GC_NONE;
+    p.colsum_rows = colsum ? (M + 127) / 128 : 0;
+    p.workspace_floats_used = slabs + (bias_grad ? (int64_t)p.split * M : 0) + p.colsum_rows * N;
+    p.launches += (p.reduce != VAW_CVR_NONE) + (p.bias_grad == VAW_CVB_FOLD) + colsum;
+    *plan = p;
+    plan->status = p.status = VAW_OK;
+    return VAW_OK;
+}

@@ -776,6 +776,25 @@ def conv3x3(dt, mode, act, act2, w, out, B, H, W, Ci, Co, *, bias=None, resid=No
     return True
 
 
+def conv3x3_plan(dt, mode, act, act2, w, out, B, H, W, Ci, Co, *, workspace=16, workspace_floats=0, knobs=None, cus=0, check_status=True,
+                 **epi):
+    """The launch vaw_conv3x3 makes for this call (vaw_conv3x3_plan: host arithmetic, no GPU).  Arguments and epilogue keywords as
+    for conv3x3(), the addresses used for null-ness and alignment only; workspace_floats = 0 stands for no workspace; knobs = None:
+    the process's own, else a GemmKnobs (default_gemm_knobs); cus = 0: the CUs the process may use now (or the knobs' count).
+    check_status = False returns the plan of a refused call (status -1 invalid, -3 the explicit path) instead of raising."""
+    e = Epilogue(epi.get("bias") or None, epi.get("act", 0), None, epi.get("aux_out") or None, epi.get("gate") or None, epi.get("gate_ld", 0),
+                 epi.get("resid") or None, epi.get("rowadd") or None, 0, 1.0, epi.get("beta", 0.0),
+                 1 if (mode == 2 or epi.get("out_f32")) else 0, epi.get("colsum_out") or None, epi.get("colsum_beta", 0.0),
+                 1 if epi.get("resid_is_act", True) else 0, epi.get("rowsum_a_out") or None, epi.get("rowsum_a_beta", 0.0))
+    p = L.Conv3x3Launch()
+    rc = L.lib().vaw_conv3x3_plan(dt, mode, act or 0, act2 or 0, w or 0, out or 0, B, H, W, Ci, Co, C.byref(e),
+                                  workspace if workspace_floats > 0 else 0, workspace_floats, C.byref(knobs) if knobs is not None else None,
+                                  cus, C.byref(p))
+    if check_status:
+        check(rc, "vaw_conv3x3_plan")
+    return p
+
+
 fallbacks = {}       # (op, variant, shape...) -> times a bf16 launch left the fast kernels for the explicit path
 
 

@@ -772,7 +772,10 @@ int vaw_conv3x3_narrow(vaw_dtype dt, int mode, const void* in, const void* w, co
 /* GroupNorm32 (tools/nn.py:17-19,93-100; G groups, eps) fused with what follows it in ResBlock._forward
  * (unet.py:236-256):  y = act( GN(x)*gamma + beta [ *(1 + scale[b,c]) + shift[b,c] ] ), act = SiLU if silu else id.
  * scale/shift: f32 rows with stride film_ld (the emb_layers output), or both NULL.  mean/rstd: f32 [B*G] saved.
- * workspace: vaw_groupnorm_workspace_floats(B, HW, C) f32. */
+ * workspace: vaw_groupnorm_workspace_floats(B, HW, C) f32.
+ * All three entry points return VAW_ERR_INVALID before any launch for a NULL required pointer, scale without shift (or the
+ * reverse) and a pointer off the alignment of the launch vaw_gn_plan picks: 16 bytes for x, y, dout, dx, dx_add on the flat
+ * kernels and in f32, 8 bytes for bf16 on the quad kernels; 16 bytes for gamma, beta, scale and shift. */
 int64_t vaw_groupnorm_workspace_floats(int B, int HW, int C);
 int vaw_groupnorm_fwd(vaw_dtype dt, const void* x, const float* gamma, const float* beta, const float* scale,
                       const float* shift, int64_t film_ld, int silu, void* y, float* mean, float* rstd, int B, int HW,

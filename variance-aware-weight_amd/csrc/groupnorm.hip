@@ -612,12 +612,26 @@ static void gn_by_flags(F&& f, bool flag, Rest... rest) {
 static inline GnsGeom gns_geom(int C, const vaw_gn_launch& p) { return GnsGeom{C / 8, p.nt, p.rpi, p.rows}; }
 static inline dim3 gn_grid(const vaw_gn_launch& p) { return dim3(p.grid_x, p.grid_y, p.grid_z); }
 
+// Alignment the launch the plan chose assumes: the flat kernels move bf16 octets (16 bytes), the quad kernels channel quads (16 bytes
+// of f32, 8 of bf16); gamma, beta and the FiLM rows are read as f32 quads by the quad kernels and are held to that on both mappings.
+static inline bool gn_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+static inline size_t gn_act_align(vaw_dtype dt, const vaw_gn_launch& p) { return p.variant == VAW_GNV_FLAT || dt == VAW_F32 ? 16 : 8; }
+static int gn_check_params(const char* who, const float* gamma, const float* beta, const float* scale, const float* shift, int64_t film_ld) {
+    VAW_CHECK_ARG((scale == nullptr) == (shift == nullptr), "%s: scale and shift go together", who);
+    VAW_CHECK_ARG(!scale || film_ld % 4 == 0, "%s: film_ld must be a multiple of 4", who);
+    VAW_CHECK_ARG(gn_aligned(gamma, 16) && gn_aligned(beta, 16), "%s: gamma and beta must be 16-byte aligned", who);
+    VAW_CHECK_ARG(gn_aligned(scale, 16) && gn_aligned(shift, 16), "%s: scale and shift must be 16-byte aligned", who);
+    return VAW_OK;
+}
+
 // The apply pass on given statistics: vaw_groupnorm_fwd's last launch and all of vaw_groupnorm_apply, so one plan by construction.
-static int gn_apply_launch(vaw_dtype dt, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
+static int gn_apply_launch(const char* who, vaw_dtype dt, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                            const float* scale, const float* shift, int64_t film_ld, int silu, void* y, int B, int HW, int C, int G,
                            hipStream_t s) {
     vaw_gn_launch p;
     if (int rc = vaw_gn_plan(VAW_GN_APPLY, dt, B, HW, C, G, &p)) return rc;
+    VAW_CHECK_ARG(gn_aligned(x, gn_act_align(dt, p)) && gn_aligned(y, gn_act_align(dt, p)), "%s: x and y must be %d-byte aligned", who,
+                  (int)gn_act_align(dt, p));
     if (p.variant == VAW_GNV_FLAT) {
         gn_by_flags([&](auto S, auto F) {
             gns_apply_kernel<4, S.value, F.value><<<gn_grid(p), p.block, 0, s>>>((const bf16_t*)x, mean, rstd, gamma, beta, scale, shift, film_ld,
@@ -635,8 +649,10 @@ extern "C" int vaw_groupnorm_fwd(vaw_dtype dt, const void* x, const float* gamma
     vaw_gn_launch p;
     if (int rc = vaw_gn_plan(VAW_GN_FWD_SUMS, dt, B, HW, C, G, &p)) return rc;
     VAW_CHECK_ARG(workspace, "groupnorm_fwd: null workspace");
-    VAW_CHECK_ARG((scale == nullptr) == (shift == nullptr), "groupnorm_fwd: scale and shift go together");
-    VAW_CHECK_ARG(!scale || film_ld % 4 == 0, "groupnorm_fwd: film_ld must be a multiple of 4");
+    VAW_CHECK_ARG(x && y && gamma && beta && mean && rstd, "groupnorm_fwd: null pointer");
+    if (int rc = gn_check_params("groupnorm_fwd", gamma, beta, scale, shift, film_ld)) return rc;
+    VAW_CHECK_ARG(gn_aligned(x, gn_act_align(dt, p)) && gn_aligned(y, gn_act_align(dt, p)), "groupnorm_fwd: x and y must be %d-byte aligned",
+                  (int)gn_act_align(dt, p));
     hipStream_t s = (hipStream_t)stream;
     float* part = workspace + p.off_part;
     if (p.variant == VAW_GNV_FLAT) {
@@ -645,7 +661,7 @@ extern "C" int vaw_groupnorm_fwd(vaw_dtype dt, const void* x, const float* gamma
         BY_DTYPE(dt, (gn_fwd_sums_kernel<T><<<gn_grid(p), p.block, 0, s>>>((const T*)x, HW, C, B, p.nch, part)));
     }
     gn_group_stats_kernel<<<ceil_div(B * G, 128), 128, 0, s>>>(part, p.nch, B, C, G, HW, eps, mean, rstd);
-    if (int rc = gn_apply_launch(dt, x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, y, B, HW, C, G, s)) return rc;
+    if (int rc = gn_apply_launch("groupnorm_fwd", dt, x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, y, B, HW, C, G, s)) return rc;
     VAW_CHECK_LAUNCH("groupnorm_fwd");
     return VAW_OK;
 }
@@ -654,9 +670,8 @@ extern "C" int vaw_groupnorm_apply(vaw_dtype dt, const void* x, const float* mea
                                    const float* beta, const float* scale, const float* shift, int64_t film_ld, int silu, void* y,
                                    int B, int HW, int C, int G, vaw_stream stream) {
     VAW_CHECK_ARG(x && y && mean && rstd && gamma && beta, "groupnorm_apply: null pointer");
-    VAW_CHECK_ARG((scale == nullptr) == (shift == nullptr), "groupnorm_apply: scale and shift go together");
-    VAW_CHECK_ARG(!scale || film_ld % 4 == 0, "groupnorm_apply: film_ld must be a multiple of 4");
-    if (int rc = gn_apply_launch(dt, x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, y, B, HW, C, G, (hipStream_t)stream)) return rc;
+    if (int rc = gn_check_params("groupnorm_apply", gamma, beta, scale, shift, film_ld)) return rc;
+    if (int rc = gn_apply_launch("groupnorm_apply", dt, x, mean, rstd, gamma, beta, scale, shift, film_ld, silu, y, B, HW, C, G, (hipStream_t)stream)) return rc;
     VAW_CHECK_LAUNCH("groupnorm_apply");
     return VAW_OK;
 }
@@ -670,7 +685,12 @@ extern "C" int vaw_groupnorm_bwd(vaw_dtype dt, const void* dout, const void* x, 
     if (int rc = vaw_gn_plan(VAW_GN_BWD_SUMS, dt, B, HW, C, G, &ps)) return rc;
     if (int rc = vaw_gn_plan(VAW_GN_BWD_APPLY, dt, B, HW, C, G, &pa)) return rc;
     VAW_CHECK_ARG(workspace, "groupnorm_bwd: null workspace");
-    VAW_CHECK_ARG(!scale || (shift && dscale && dshift && film_ld % 4 == 0), "groupnorm_bwd: FiLM needs shift, dscale, dshift");
+    VAW_CHECK_ARG(dout && x && mean && rstd && gamma && beta && dx && dgamma && dbeta, "groupnorm_bwd: null pointer");
+    if (int rc = gn_check_params("groupnorm_bwd", gamma, beta, scale, shift, film_ld)) return rc;
+    VAW_CHECK_ARG(!scale || (dscale && dshift), "groupnorm_bwd: FiLM needs shift, dscale, dshift");
+    const size_t al = gn_act_align(dt, ps);
+    VAW_CHECK_ARG(gn_aligned(dout, al) && gn_aligned(x, al) && gn_aligned(dx, al) && gn_aligned(dx_add, al),
+                  "groupnorm_bwd: dout, x, dx and dx_add must be %d-byte aligned", (int)al);
     hipStream_t s = (hipStream_t)stream;
     const int64_t BC = (int64_t)B * C;
     float *part = workspace + ps.off_part, *sums = workspace + ps.off_sums, *S1 = workspace + ps.off_s1, *S2 = workspace + ps.off_s2;

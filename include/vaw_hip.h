@@ -249,6 +249,42 @@ int vaw_rk_scaled_sumsq(const float* u, const float* v, const float* a, const fl
 int vaw_rk_sumsq_finish(const double* partials, int64_t count, double* out, vaw_stream stream);
 
 /* ---------------------------------------------------------------------------
+ * Log-likelihood of a flow model  (samplers.py: flow_log_likelihood).  With t = 0 data, t = 1 noise and dx/dt = v(x, t):
+ *   log p0(x0) = log N(x(1); 0, I) + int_0^1 div v(x(t), t) dt,   div v estimated with fixed Hutchinson probes eps:
+ *   g = (d out / d x)^T eps is one vector-Jacobian product of the network, tr ~ sum eps * g.
+ * Conventions of the adaptive stages above: float32 state with every operation rounded on its own, the model output read in
+ * place by row stride (the first C of a learn_sigma model's 2C channels need no copy), 16-byte accesses when
+ * per_sample % 4 == 0, model_ld % 4 == 0 and every pointer is 16-byte aligned, scalar ones with a bound check otherwise.
+ * The divergence is float64: products and sums in an order fixed by per_sample alone (no atomics), so a row's bits depend
+ * neither on the batch, nor on the alignment, nor on the run.  A row longer than one workgroup's stream (1024 elements)
+ * leaves one partial per workgroup, vaw_rk_partial_count(B, per_sample) in all, that a second launch folds left to right.
+ * ------------------------------------------------------------------------- */
+
+/* Floats per row of the log-likelihood table, one row per network evaluation at time t:  0 A  1 B  2 t  3 unused,
+ * with v = A*x + B*out: convert_model_output_to_vector collapsed per mean type (host float64, stored as float32)
+ *   START_X   A = s'/s             B = a' - a s'/s          EPSILON  A = a'/a   B = s' - s a'/a
+ *   VELOCITY  A = (a a' + s s')/(a^2 + s^2)   B = (a s' - s a')/(a^2 + s^2)      VECTOR   A = 0   B = 1 */
+#define VAW_FLOW_LOGP_COLS 4
+
+/* The pass after the network evaluation and the vector-Jacobian product of stage `stage` (0..VAW_RK_STAGES-1) of an explicit
+ * Runge-Kutta step from x with signed step h:
+ *   k[stage]    = A*x_stage + B*out            (coef[row]; x_stage == NULL: the stage state is x), float32
+ *   d[stage][b] = A*n + B * sum_i eps[b,i]*g[b,i]     float64, n = per_sample
+ *   ncoef > 0:  x_out = x + float(h) * sum_{s < ncoef} float(a[s]) * k[s]   ascending, zero coefficients skipped, left to
+ *               right: the next stage's state, written straight into the next network input -- or, on the last stage, x_new
+ *   delta != NULL (last stage, a = the step's weights):  delta[b] += h * sum_{s < ncoef} a[s] * d[s][b]   float64, same order
+ * k: [VAW_RK_STAGES][B*per_sample] float32; d: [VAW_RK_STAGES][B] float64; a: host pointer; x_out must not overlap an input.
+ * partials: vaw_rk_partial_count(B, per_sample) doubles, needed (and touched) only when per_sample > 1024. */
+int vaw_flow_logp_stage(int stage, const float* out, int64_t model_ld, const float* g, const float* eps, const float* x,
+                        const float* x_stage, const float* coef, int row, int rows, float* k, double* d, const double* a, int ncoef,
+                        double h, float* x_out, double* delta, double* partials, int64_t partials_cap, int B, int64_t per_sample,
+                        vaw_stream stream);
+
+/* logp[b] = -1/2 sum_i z[b,i]^2 - (per_sample/2) ln 2 pi, float64, summed as above. */
+int vaw_flow_logp_prior(const float* z, double* logp, double* partials, int64_t partials_cap, int B, int64_t per_sample,
+                        vaw_stream stream);
+
+/* ---------------------------------------------------------------------------
  * Loss-aware timestep sampling on the device  (tools/resample.py: LossSecondMomentResampler)
  * ------------------------------------------------------------------------- */
 

@@ -24,7 +24,14 @@ With `--solver rk45` the run is
  (f) flow_ode_sample(solver="rk45") over a stand-in network (0.6 tanh(2x) + 0.5 sin(12 t) + 0.02 y: three tensor operations, so
      the time is the solver's own) on `--batch` x 4 x S x S noise (S = `--image-size` or 32), linear path, VELOCITY,
      `--rtol` / `--atol`: attempts, network evaluations and read-backs of a call, and the median ms per attempt of `--repeats`
-     calls, fused (vaw_rk_stage) and as the tensor composition (`fused=False`) alternating, each after a warm-up call."""
+     calls, fused (vaw_rk_stage) and as the tensor composition (`fused=False`) alternating, each after a warm-up call.
+
+With `--logp` the run is
+ (g) one flow_log_likelihood sweep (`--steps` grid points, `--solver euler|heun`, cosine path, VELOCITY) of `--batch` samples
+     through `--model`: the median ms of `--repeats` sweeps with the full backward per evaluation (the model wrapped so that it
+     shows no input_grad_only) and with input_grad_only(), alternating after a warm-up sweep of each, and whether both give the
+     same logp bit for bit; then the pass after a network call alone (Heun's second stage on max(`--batch`, 1024) rows):
+     vaw_flow_logp_stage against the tensor composition in us, device events over `--iters` calls on rotating buffers."""
 import argparse
 import json
 import os
@@ -179,8 +186,79 @@ def rk45_bench(a):
     print(json.dumps(res))
 
 
+class FullBackward(torch.nn.Module):
+    """The model without its input_grad_only(): flow_log_likelihood then runs the full backward per evaluation."""
+
+    def __init__(self, model):
+        super().__init__()
+        self.model = model
+
+    def forward(self, x, t, **kw):
+        return self.model(x, t, **kw)
+
+
+def logp_bench(a):
+    """(g): one flow_log_likelihood sweep, with the full backward per evaluation and with input_grad_only()."""
+    torch.manual_seed(0)
+    model, C, H = build_model(a, learn_sigma=False)
+    args = SimpleNamespace(weight_type="lambda", gamma=0.0, learn_sigma=False, p2_gamma=1, p2_k=1, path_type="cosine")
+    fm = vaw_amd.FlowMatching(args=args, model_mean_type=vaw_amd.ModelMeanType.VELOCITY)
+    x = torch.randn(a.batch, C, H, H, device="cuda")
+    y = torch.arange(a.batch, device="cuda") % a.num_classes
+    solver = a.solver or "heun"
+    full = FullBackward(model).eval()
+    outs = {}
+
+    def run(m, name):
+        outs[name] = fm.calc_bpd(m, x, num_steps=a.steps, solver=solver, generator=torch.Generator(device="cuda").manual_seed(1), y=y)
+
+    t_full, t_only = wall_pair(lambda: run(full, "full"), lambda: run(model, "only_dx"), max(a.repeats, 3))
+    nfev = outs["only_dx"]["nfev"]
+    # the pass after a network call alone: Heun's second stage (reads out, x_1, g, eps, x, k_0; writes k_1, x_new: 32 B/element),
+    # the kernel against the tensor composition, over rotating sets larger than the 256 MiB Infinity Cache
+    R, n = max(a.batch, 1024), C * H * H
+    A, B, h, b = 0.25, -1.5, 0.125, (0.5, 0.5)
+    coef = torch.tensor([[A, B, 0.0, 0.0]], device="cuda")
+    sets = []
+    with torch.no_grad():
+        for _ in range(max(2, int(400e6 // (R * n * 4 * 8)) + 1)):
+            t = lambda: torch.randn(R, C, H, H, device="cuda")
+            k = torch.randn(ops.RK_STAGES, R, C, H, H, device="cuda")          # (only slots 0 and 1 are touched)
+            sets.append(dict(out=t(), g=t(), eps=torch.randint(0, 2, (R, C, H, H), device="cuda").float() * 2 - 1, x=t(), xs=t(), k=k,
+                             d=torch.randn(ops.RK_STAGES, R, device="cuda", dtype=torch.float64), xn=t(),
+                             delta=torch.zeros(R, device="cuda", dtype=torch.float64)))
+        partials = torch.empty(ops.rk_partial_count(R, n), device="cuda", dtype=torch.float64)
+
+        def fused(s):
+            return lambda: ops.flow_logp_stage(1, s["out"], s["g"], s["eps"], s["x"], s["xs"], coef, 0, s["k"], s["d"], b, h, x_out=s["xn"],
+                                               delta=s["delta"], partials=partials)
+
+        def comp(s):
+            def run_comp():
+                kv = A * s["xs"] + B * s["out"]
+                dv = A * n + B * (s["eps"].to(torch.float64) * s["g"].to(torch.float64)).flatten(1).sum(1)
+                xn = s["x"] + h * (b[0] * s["k"][0] + b[1] * kv)
+                return kv, xn, s["delta"] + h * (b[0] * s["d"][0] + b[1] * dv)
+            return run_comp
+
+        fused(sets[0])()
+        kv, xn, _ = comp(sets[0])()
+        assert torch.equal(sets[0]["k"][1], kv) and torch.equal(sets[0]["xn"], xn), "the stage kernel differs from the composition"
+        stage_us = events_us([fused(s) for s in sets], a.iters)
+        comp_us = events_us([comp(s) for s in sets], a.iters)
+    print(json.dumps({"part": "g", "model": a.model, "stage_rows": R, "stage_elements_per_row": n, "stage_kernel_us": stage_us,
+                      "stage_composition_us": comp_us, "stage_kernel_algorithmic_TBps": 32.0 * R * n / stage_us / 1e6, "dtype": "fp32" if a.fp32 else "bf16", "batch": a.batch, "grid_points": a.steps, "solver": solver,
+                      "evaluations": nfev, "full_backward_ms_per_sweep": 1e3 * t_full, "input_grad_only_ms_per_sweep": 1e3 * t_only,
+                      "full_backward_ms_per_evaluation": 1e3 * t_full / nfev, "input_grad_only_ms_per_evaluation": 1e3 * t_only / nfev,
+                      "logp_bitwise_equal": bool(torch.equal(outs["full"]["logp"], outs["only_dx"]["logp"])),
+                      "bpd_mean": float(outs["only_dx"]["bpd"].mean())}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--logp", action="store_true",
+                    help="(g): time one flow_log_likelihood sweep of --steps grid points (--solver euler|heun, default heun) with the full "
+                         "backward per evaluation and with input_grad_only()")
     ap.add_argument("--solver", choices=["heun", "euler", "rk45"], default=None,
                     help="(e): time Sampler.sample through this EDM / flow solver; rk45: (f), the adaptive flow-ODE solver")
     ap.add_argument("--rtol", type=float, default=1e-3, help="(f)")
@@ -204,6 +282,8 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sample_bench.py measures on the GPU only")
+    if a.logp:
+        return logp_bench(a)
     if a.solver == "rk45":
         with torch.no_grad():
             return rk45_bench(a)

@@ -168,6 +168,8 @@ _PROTOS = {
     "vaw_rk_stage": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _i, _i, _p, C.POINTER(_i), C.POINTER(_f), _i, _f, _p, _p, _p, _f, _f, _p, _l, _i, _l, _p],
     "vaw_rk_scaled_sumsq": [_p, _p, _p, _p, _f, _f, _p, _l, _i, _l, _p],
     "vaw_rk_sumsq_finish": [_p, _l, _p, _p],
+    "vaw_flow_logp_stage": [_i, _p, _l, _p, _p, _p, _p, _p, _i, _i, _p, _p, C.POINTER(C.c_double), _i, C.c_double, _p, _p, _p, _l, _i, _l, _p],
+    "vaw_flow_logp_prior": [_p, _p, _p, _l, _i, _l, _p],
     "vaw_prior_bpd": [_p, _f, _f, _p, _i, _l, _p],
     "vaw_resampler_update": [_p, _p, _i, _i, _i, _p, _p, _p, _p],
     "vaw_resampler_draw": [_p, _p, _i, _i, C.c_double, _p, _i, _p, _p, _p, _p],

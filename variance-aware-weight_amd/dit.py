@@ -220,6 +220,7 @@ class _DiTFn(torch.autograd.Function):
     def forward(ctx, anchor, model, x, t, y):
         out = model._forward_impl(x, t, y)
         ctx.model, ctx.gen, ctx.need_dx = model, model._ws_cur.gen, x.requires_grad
+        ctx.only_dx = bool(model._input_grad_only)
         ctx.x_shape = x.shape
         return out
 
@@ -231,7 +232,9 @@ class _DiTFn(torch.autograd.Function):
         if m._ws_cur.ckpt != bool(m.activation_checkpointing):
             raise L.VawError("DiT backward: activation_checkpointing was switched between this forward and its backward "
                              "(the workspace of the forward was laid out for the other mode)")
-        dx = m._backward_impl(dout.contiguous(), ctx.need_dx)
+        if bool(m._input_grad_only) != ctx.only_dx:
+            raise L.VawError("DiT backward: input_grad_only() was entered or left between this forward and its backward")
+        dx = m._backward_impl(dout.contiguous(), ctx.need_dx, ctx.only_dx)
         # the anchor only ties this node into the graph: nobody reads its gradient, and a defined one costs a fill and, from the
         # second step on, an accumulate launch per backward
         return (None if L.STEP_FUSED else torch.zeros_like(m._anchor)), None, dx, None, None
@@ -330,6 +333,9 @@ class DiT(FlatModule):
         self._fp8_w, self._fp8_epoch, self._fp8_wstates, self._fp8_wgroup = {}, None, None, None
         self._ws = {}
 
+    _ONLY_DX_FP8 = ("input_grad_only() does not combine with compute_dtype='fp8': the delayed-scaling state of the fp8 tensors would "
+                    "move during an evaluation")
+
     _CKPT_FP8 = ("activation_checkpointing does not combine with compute_dtype='fp8': re-running a block's forward would update its "
                  "delayed-scaling state twice per step, and the per-block transposed fp8 copies would have to be shared too")
 
@@ -394,6 +400,8 @@ class DiT(FlatModule):
     def forward(self, x, t, y, **kwargs):
         """x [N,C,H,W] f32, t [N] (float timesteps, already rescaled), y [N] int64 -> (eps [N,C_out,H,W] f32, None)."""
         L.need_cuda(x, t, y)
+        if self._input_grad_only and self._fp8:
+            raise ValueError(self._ONLY_DX_FP8)
         out = _DiTFn.apply(self._anchor, self, x, t, y)
         return out, None
 
@@ -615,15 +623,25 @@ class DiT(FlatModule):
             ops.colsum(dt, dmod_a + es * r0, B, nrows, ld, gb, beta)
         return dmod_a
 
-    def _backward_impl(self, dout, need_dx):
+    def _backward_impl(self, dout, need_dx, only_dx=False):
+        """only_dx (FlatModule.input_grad_only): the chain that leads to dx and nothing else -- no weight-gradient, bias-gradient or
+        fold launch, no grouped launch, no adaLN weight gradient, no conditioning path, no hook, and the flat gradient buffer is
+        neither allocated nor addressed.  The launches that remain are the full backward's with the same arguments (their
+        by-products -- dgate / dshift / dscale in ws.dmod, partial column sums in ws.cp -- land in the workspace as always), so dx
+        has the full backward's bits."""
         ws = self._ws_cur
         B = ws.B
         dt, D, T, Dm, Lyr, ld = self._dt, self.D, self.T, self.Dm, self.depth, self.mod_cols
         M, lib, st = B * T, L.lib(), L.stream_ptr()
         H = W = self.image_size
-        beta = 1.0 if self.grads_live() else 0.0
-        self._gbase = self.flat_grads().data_ptr()
-        hook = self.grad_ready_hook
+        if only_dx:
+            if ws.fp8:
+                raise ValueError(self._ONLY_DX_FP8)
+            beta, self._gbase, hook = 0.0, None, None      # (_g() of no address: a launch that slipped through would raise)
+        else:
+            beta = 1.0 if self.grads_live() else 0.0
+            self._gbase = self.flat_grads().data_ptr()
+            hook = self.grad_ready_hook
         ada_half = self._ada_split_block() if hook else None      # early adaLN bucket only when somebody listens (DDP)
         # (ws.dDm / ws.dqkv / ws.dyb are None, and ptr() of them 0, when the shared record carries its own dy operands: activation
         # recomputation in the deferred mode.  They are read only on the `not own_dy` side below, which that mode never takes.)
@@ -666,7 +684,8 @@ class DiT(FlatModule):
 
         # head: unpatchify^T, final linear, final LN+modulate (+ the gate backward of the last block's MLP branch)
         L.check(lib.vaw_unpatchify_bwd(dt, ptr(dout), ptr(ws.dotok), B, self.out_channels, H, W, self.patch_size, st), "unpatchify_bwd")
-        self._wgrad(dt, "final_layer.linear.", ptr(ws.dotok), ptr(ws.xf), self.No, D, M, beta)
+        if not only_dx:
+            self._wgrad(dt, "final_layer.linear.", ptr(ws.dotok), ptr(ws.xf), self.No, D, M, beta)
         ops.gemm(dt, 1, 0, M, D, self.No, ptr(ws.dotok), self.No, self._w("final_layer.linear.weight"), D, dD, D)
         mo, dmo = mod + 4 * (6 * Lyr * D), dmod + 4 * (6 * Lyr * D)
         ln_bwd_and_gate(dD, ptr(ws.xres[2 * Lyr]), ptr(ws.meanf), ptr(ws.rstdf), mo + 4 * D, 0, dmo, dmo + 4 * D,
@@ -736,17 +755,17 @@ class DiT(FlatModule):
                 ops.gate_bwd(dt, dres, ptr(b["y2"]), mo + 4 * 5 * D, ld, dy2, dmo + 4 * 5 * D, ld, B, T, D, cp["fc2"].buf.data_ptr())
             # MLP branch.  dy2, dgate and the partial column sums of dy2 (fc2's bias gradient) came out of the row kernel that
             # produced this block's incoming residual gradient; bias gradients are folded per group (fold_bias)
-            if not defer:
+            if not defer and not only_dx:
                 self._wgrad(dt, pre + "mlp.fc2.", dy2, ptr(b["a"]), D, Dm, M, beta, bias=False)
             fuse_dh = fp8 and ws.d_bwd and self.fp8_fuse_epilogue and M % 64 == 0       # fc2's input-gradient epilogue writes dhid as fp8
             self._linear_dgrad(ws, b, "f_dy2", None if fuse_rows else dy2, pre + "mlp.fc2.", M, D, Dm, b["f_dhid"].epilogue_target() if fuse_dh else dhid, act=2,
                                aux_in=ptr(b["hpre"]), colsum_partial=cp["fc1"], **({"out_fp8": b["f_dhid"]} if fuse_dh else {}))
-            if not defer:
+            if not defer and not only_dx:
                 self._wgrad(dt, pre + "mlp.fc1.", dhid, ptr(b["xm2"]), Dm, D, M, beta, bias=False)
             self._linear_dgrad(ws, b, "f_dhid", None if (fp8 and fuse_dh) else dhid, pre + "mlp.fc1.", M, Dm, D, dD)
             ln_bwd_and_gate(dD, xmid, ptr(b["mean2"]), ptr(b["rstd2"]), mo + 4 * 4 * D, dres, dmo + 4 * 3 * D, dmo + 4 * 4 * D, (l, "attn"))
             # attention branch (dy1 etc. from the fused row kernel just above)
-            if not defer:
+            if not defer and not only_dx:
                 self._wgrad(dt, pre + "attn.proj.", dy1, ptr(b["ao"]), D, D, M, beta, bias=False)
             self._linear_dgrad(ws, b, "f_dy1", None if fuse_rows else dy1, pre + "attn.proj.", M, D, D, ptr(ws.dao))
             q = ptr(b["qkv"])
@@ -757,7 +776,9 @@ class DiT(FlatModule):
             if not qkv_bias_folded:
                 ops.attn_bwd(dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(ws.dao), ptr(b["lse"]),
                              ptr(ws.delta), dq, dq + es * D, dq + 2 * es * D)
-                if defer:
+                if only_dx:
+                    pass
+                elif defer:
                     ops.colsum(dt, dq, M, 3 * D, 3 * D, cp["qkv"].buf.data_ptr(), 0.0, device=dout.device)     # one complete row
                     cp["qkv"].rows.value = 1
                 else:      # (the per-layer launch takes the bias gradient from its staged dy tiles)
@@ -769,7 +790,9 @@ class DiT(FlatModule):
             last_cast = fuse_tail and l == 0
             ln_bwd_and_gate(dD, xin, ptr(b["mean1"]), ptr(b["rstd1"]), mo + 4 * D, dres, dmo, dmo + 4 * D,
                             (l - 1, "mlp") if (l and not ckpt) else None, dx_act=ptr(ws.dao) if last_cast else 0)
-            if defer:
+            if only_dx:
+                pass
+            elif defer:
                 pending.append(l)
                 if ckpt or l == group_cut:      # (recomputation: the operands are gone once the next block is re-run)
                     pending.reverse()
@@ -795,12 +818,15 @@ class DiT(FlatModule):
             dx0 = dD
         else:
             dx0 = dres
-        self._wgrad(dt, "x_embedder.proj.", dx0, ptr(ws.xp), D, self.Kp, M, beta)
+        if not only_dx:
+            self._wgrad(dt, "x_embedder.proj.", dx0, ptr(ws.xp), D, self.Kp, M, beta)
         dx = None
         if need_dx:
             ops.gemm(dt, 1, 0, M, self.Kp, D, dx0, D, self._w("x_embedder.proj.weight"), self.Kp, ptr(ws.dxp), self.Kp, out_f32=True)
             dx = torch.empty(B, self.in_channels, H, W, device=dout.device, dtype=torch.float32)
             L.check(lib.vaw_patchify_bwd(ptr(ws.dxp), ptr(dx), B, self.in_channels, H, W, self.patch_size, st), "patchify_bwd")
+        if only_dx:
+            return dx
         # conditioning path: adaLN (all blocks at once, or the rows the early bucket has not covered), label table, timestep MLP
         rows = ld if ada_half is None else 6 * ada_half * D
         dmod_a = self._adaln_wgrad(dt, ws, 0, rows, B, beta)

@@ -6,6 +6,8 @@ bf16 buffer of the same layout holds the shadow weights the MFMA kernels read.  
 the gradient-norm kernel, the EMA kernel and the RCCL all-reduce buckets are then single passes over
 contiguous ranges instead of ~150 per-tensor launches.  state_dict keys stay the reference's.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -154,6 +156,28 @@ class FlatModule(nn.Module):
         """Drop gradients (set_to_none semantics): the next backward overwrites instead of accumulating."""
         for p in self._flat_params:
             p.grad = None
+
+    # ---- evaluation backward: dx and nothing else --------------------------------------------------------------------------
+    _input_grad_only = False
+
+    @contextlib.contextmanager
+    def input_grad_only(self):
+        """Inside the context a forward plus backward of the model yields the input gradient and nothing else: no weight- or
+        bias-gradient launch, no gradient hook, no attach_grads, and the flat gradient buffer is neither allocated nor written
+        (what a kernel produces on the side and cannot be told to omit goes to scratch).  dx is bitwise the full backward's.
+        For a vector-Jacobian product at evaluation time -- the Hutchinson probes of samplers.flow_log_likelihood, between two
+        micro-steps of a gradient accumulation, on an EMA copy that never had a gradient buffer.  The flag is recorded at
+        forward and checked at backward: entering or leaving in between raises VawError.  Refuses compute_dtype='fp8' with a
+        ValueError (the delayed-scaling state would move during an evaluation)."""
+        if getattr(self, "compute_dtype", None) == "fp8":
+            raise ValueError("input_grad_only() does not combine with compute_dtype='fp8': the delayed-scaling state of the fp8 "
+                             "tensors would move during an evaluation")
+        before = self._input_grad_only
+        self._input_grad_only = True
+        try:
+            yield self
+        finally:
+            self._input_grad_only = before
 
     # ---- sharded optimizer (ZeRO-1, bf16 mode): after a step only the bf16 shadow is gathered -- the f32 masters of OTHER ranks'
     # chunks are stale until optimizer.consolidate() / trainer.consolidate() (a collective: every rank calls it).  The flag lives

@@ -622,6 +622,12 @@ class FlowMatching:
             return alpha_t, sigma_t, d_alpha_t, -d_alpha_t
         raise NotImplementedError()
 
+    def calc_bpd(self, model, x_start, **kw):
+        """Per-sample log-likelihood and bits/dim of x_start under the flow (samplers.flow_log_likelihood, whose keywords and
+        result dict these are): the flow-side sibling of GaussianDiffusion.calc_bpd_loop."""
+        from .samplers import flow_log_likelihood
+        return flow_log_likelihood(self, model, x_start, **kw)
+
     def sample_t(self, x_start):
         td = self.args.time_dist
         if td[0] == "uniform":

@@ -413,6 +413,56 @@ def rk_sumsq_finish(partials, count, out):
     return out
 
 
+FLOW_LOGP_COLS = 4          # VAW_FLOW_LOGP_COLS
+
+
+def flow_logp_stage(stage, out, g, eps, x, x_stage, coef, row, k, d, coeffs, h, x_out=None, delta=None, partials=None):
+    """The pass after the network evaluation and the vector-Jacobian product of stage `stage` of a Runge-Kutta step of the
+    log-likelihood integration (vaw_flow_logp_stage; include/vaw_hip.h): k[stage] = A * x_stage + B * out from coef[row]
+    (float32, bitwise the tensor composition), d[stage] = A * n + B * sum(eps * g) per row in float64, and with `coeffs`
+    x + h * sum coeffs[s] * k[s] into x_out; with `delta` (the last stage) delta += h * sum coeffs[s] * d[s] in float64.
+    out: the x-shaped float32 view of the network output, read in place; k: [RK_STAGES, *x.shape] float32; d: [RK_STAGES, B]
+    float64; coeffs: at most RK_STAGES Python floats; partials: rk_partial_count(B, per_sample) float64 (rows over 1024)."""
+    need_cuda(out, g, eps, x, x_stage, coef, k, d, x_out, delta, partials)
+    _dense("flow_logp_stage", torch.float32, x.shape, x, x_stage, g, eps, x_out)
+    _dense("flow_logp_stage", torch.float32, (RK_STAGES, *x.shape), k)
+    B = x.shape[0]
+    n = x.numel() // max(B, 1)
+    _dense("flow_logp_stage", torch.float64, (RK_STAGES, B), d)
+    _dense("flow_logp_stage", torch.float64, (B,), delta)
+    _table("flow_logp_stage", coef, torch.float32, FLOW_LOGP_COLS, row)
+    _f32_parts("flow_logp_stage", x, out)
+    if len(coeffs) > RK_STAGES or (len(coeffs) > 0) != (x_out is not None):
+        raise L.VawError(f"flow_logp_stage: {len(coeffs)} coefficients for {RK_STAGES} stages, x_out {'given' if x_out is not None else 'missing'}")
+    if x_out is not None and any(x_out.data_ptr() == t.data_ptr() for t in (x, x_stage, g, eps) if t is not None):
+        raise L.VawError("flow_logp_stage: x_out overlaps an input")
+    if partials is not None:
+        _rk_partials("flow_logp_stage", partials, B, n)
+    (out,), ld = _rows_in_place((out,), n)
+    check(L.lib().vaw_flow_logp_stage(int(stage), ptr(out), ld, ptr(g), ptr(eps), ptr(x), ptr(x_stage), ptr(coef), int(row), coef.shape[0],
+                                      ptr(k), ptr(d), (C.c_double * RK_STAGES)(*[float(c) for c in coeffs]), len(coeffs), float(h),
+                                      ptr(x_out), ptr(delta), ptr(partials), 0 if partials is None else partials.numel(), B, n,
+                                      stream_ptr()), "vaw_flow_logp_stage")
+    return x_out
+
+
+def flow_logp_prior(z, partials=None):
+    """log N(z; 0, I) per row, float64 [B] (vaw_flow_logp_prior): -1/2 sum z^2 - (n / 2) ln 2 pi with squares and sums in
+    float64 in a fixed order.  partials as in flow_logp_stage (allocated when a row needs them and none is given)."""
+    need_cuda(z, partials)
+    _f32c(z)
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    if partials is None and n > 1024:
+        partials = torch.empty(rk_partial_count(B, n), dtype=torch.float64, device=z.device)
+    if partials is not None:
+        _rk_partials("flow_logp_prior", partials, B, n)
+    logp = torch.empty(B, dtype=torch.float64, device=z.device)
+    check(L.lib().vaw_flow_logp_prior(ptr(z), ptr(logp), ptr(partials), 0 if partials is None else partials.numel(), B, n, stream_ptr()),
+          "vaw_flow_logp_prior")
+    return logp
+
+
 def finish_images(samples, out=None):
     """[B, C, H, W] f32 / f64 samples in [-1, 1] -> [B, H, W, C] uint8 (vaw_finish_images): bitwise
     ((x + 1) * 127.5).clamp(0, 255).to(uint8).permute(0, 2, 3, 1).contiguous() for finite x; NaN writes 0.

@@ -11,6 +11,9 @@
     its last step to land on t = 0 where torchdiffeq steps past the end and interpolates back, and torchdiffeq's controller
     differs in details nothing here can check, so `dopri5` itself stays refused: step-for-step equality with torchdiffeq
     is unpinned and not claimed.  The SDE sampler is self-contained in the reference and pinned by tests/golden/samplers.pt.
+  * `flow_log_likelihood`: the same ODE run from data to noise together with the integral of its divergence, i.e. the
+    per-sample log-likelihood of a flow model (no counterpart in the reference): Hutchinson probes, one vector-Jacobian
+    product per evaluation under `model.input_grad_only()`, and one kernel per stage (vaw_flow_logp_stage).
 
 The denoiser call is the hot part and runs on the HIP kernels.  On the GPU the update around it is fused too (`fused=None`):
 everything of a step that does not depend on x is computed once per grid into a device table, cached on the denoiser / flow
@@ -20,6 +23,7 @@ combination in and write the next network input: bitwise the tensor composition 
 synchronisation once the tables are cached, so a whole call can be captured into a graph.  The adaptive solver is the
 exception: the host decides every step from one 8-byte read-back of the error norm (vaw_rk_stage, vaw_rk_scaled_sumsq)."""
 
+import contextlib
 import math
 from types import SimpleNamespace
 
@@ -29,7 +33,7 @@ import torch
 from . import ops
 from .gaussian_diffusion import ModelMeanType
 
-__all__ = ["EDMDenoiser", "edm_sample", "flow_sde_sample", "flow_ode_sample"]
+__all__ = ["EDMDenoiser", "edm_sample", "flow_sde_sample", "flow_ode_sample", "flow_log_likelihood"]
 
 
 def _unwrap(out):
@@ -798,3 +802,202 @@ def flow_ode_sample(fm, model, noise, device=None, num_steps=50, solver="heun", 
             k3 = v(x + 0.5 * dt * k2, t0 + 0.5 * dt)
             x = x + dt / 6 * (k1 + 2 * k2 + 2 * k3 + v(x + dt * k3, t1))
     return x
+
+
+# ---- log-likelihood along the probability-flow ODE ----------------------------------------------------------------------------
+# Explicit tableaus (c, a, b) of the fixed-grid solvers of the augmented system (state, accumulated divergence).
+_LOGP_TABLEAUS = {"euler": ((0.0,), ((),), (1.0,)),
+                  "heun": ((0.0, 1.0), ((), (1.0,)), (0.5, 0.5)),
+                  "rk4": ((0.0, 0.5, 0.5, 1.0), ((), (0.5,), (0.0, 0.5), (0.0, 0.0, 1.0)), (1 / 6, 1 / 3, 1 / 3, 1 / 6))}
+_LN_2PI = 1.8378770664093453
+
+
+def _flow_logp_ab(fm, t):
+    """(A, B) of v = A * x + B * out at time t as Python floats: the reference's convert_model_output_to_vector (`_flow_fields`)
+    collapsed per mean type, from the interpolant in float64 on the host.  Not finite where the conversion is singular."""
+    a, s, da, ds = (v.reshape(()) for v in fm.interpolant(torch.tensor([float(t)], dtype=torch.float64)))
+    mt = fm.model_mean_type.name
+    if mt == "START_X":
+        A, B = ds / s, da - a * (ds / s)
+    elif mt == "EPSILON":
+        A, B = da / a, ds - s * (da / a)
+    elif mt == "VELOCITY":
+        den = a ** 2 + s ** 2
+        A, B = (a * da + s * ds) / den, (a * ds - s * da) / den
+    elif mt == "VECTOR":
+        A, B = torch.zeros_like(a), torch.ones_like(a)
+    else:
+        raise ValueError(f"flow_log_likelihood: model_mean_type {mt} has no vector field in the reference")
+    return float(A), float(B)
+
+
+def _flow_logp_tables(fm, solver, num_steps, t_span):
+    """The grid of flow_log_likelihood on the host, cached on `fm`: per network evaluation the time (float64) and (A, B)
+    (float64; the float32 table the kernel reads is made from them), per step h.  Raises where A or B is not finite."""
+    t_lo, t_hi = float(t_span[0]), float(t_span[1])
+    key = ("logp", solver, int(num_steps), fm.path_type, fm.model_mean_type.name, t_lo, t_hi)
+    cache = fm.__dict__.setdefault("_solver_tables", {})
+    if key in cache:
+        return cache[key]
+    c, a, b = _LOGP_TABLEAUS[solver]
+    grid = np.linspace(t_lo, t_hi, num_steps, dtype=np.float64)
+    times, ab, hs = [], [], []
+    for k in range(num_steps - 1):
+        h = float(grid[k + 1] - grid[k])
+        hs.append(h)
+        for ci in c:
+            t = float(grid[k + 1]) if ci == 1.0 else float(grid[k]) + ci * h
+            A, B = _flow_logp_ab(fm, t)
+            if not (math.isfinite(A) and math.isfinite(B)):
+                raise ValueError(f"flow_log_likelihood: the vector field of a {fm.model_mean_type.name} model on the {fm.path_type!r} path "
+                                 f"is singular at the grid time t={t} (A={A}, B={B}); move t_span off that end")
+            times.append(t)
+            ab.append((A, B))
+    tab = SimpleNamespace(c=c, a=a, b=b, times=times, ab=ab, h=hs, solver=solver, num_steps=num_steps, device={})
+    cache[key] = tab
+    return tab
+
+
+def _flow_logp_device(tab, rows, dtype, device):
+    """(coef [evaluations, ops.FLOW_LOGP_COLS] float32, times [evaluations, rows] in `dtype`) on `device`: one upload each."""
+    key = (int(rows), dtype, str(device))
+    if key not in tab.device:
+        coef = torch.tensor([[A, B, t, 0.0] for (A, B), t in zip(tab.ab, tab.times)], dtype=torch.float64).to(torch.float32)
+        times = torch.tensor(tab.times, dtype=torch.float64).to(dtype).view(-1, 1).expand(len(tab.times), rows)
+        tab.device[key] = (coef.to(device).contiguous(), times.to(device).contiguous())
+    return tab.device[key]
+
+
+def _logp_probes(kind, shape, dtype, device, generator):
+    """The Hutchinson probes of one call: drawn once, on the generator's device (the tensor's without one)."""
+    gdev = generator.device if generator is not None else device
+    if kind == "rademacher":
+        eps = torch.randint(0, 2, shape, generator=generator, device=gdev).to(dtype) * 2 - 1
+    else:
+        eps = torch.randn(shape, generator=generator, device=gdev, dtype=torch.float32).to(dtype)
+    return eps.to(device).contiguous()
+
+
+def _logp_network(model, xin, t_rows, eps, model_kwargs):
+    """One network evaluation and one vector-Jacobian product: (the x-shaped view of the output, g = (d out / d x)^T eps).
+    `xin` is the network-input buffer itself, made a leaf; a learn_sigma model's probe is zero on its variance channels."""
+    C = xin.shape[1]
+    with torch.enable_grad():
+        leaf = xin.detach().requires_grad_(True)
+        only_dx = model.input_grad_only() if hasattr(model, "input_grad_only") else contextlib.nullcontext()
+        with only_dx:
+            out = _unwrap(model(leaf, t_rows, **model_kwargs))
+            probe = eps.to(out.dtype)
+            if out.shape[1] != C:
+                probe = torch.cat((probe, probe.new_zeros((out.shape[0], out.shape[1] - C, *out.shape[2:]))), 1)
+            (g,) = torch.autograd.grad(out, leaf, probe)
+    return out.detach()[:, :C], g.detach()
+
+
+def _logp_refusals(fm, model, solver, n_probes, probe, num_steps, model_kwargs):
+    """Everything flow_log_likelihood refuses, with the reason, before anything is launched: the model to evaluate."""
+    what = "flow_log_likelihood"
+    if solver in ("rk45", "dopri5"):
+        raise ValueError(f"{what}: solver {solver!r} is not offered: adaptive control of the augmented state (x, accumulated "
+                         "divergence) is out of scope; use euler | heun | rk4 on the fixed grid")
+    if solver not in _LOGP_TABLEAUS:
+        raise ValueError(f"{what}: unknown solver {solver!r} (euler | heun | rk4)")
+    if fm.model_mean_type.name == "SCORE":
+        raise ValueError(f"{what}: model_mean_type SCORE has no vector field in the reference (convert_model_output_to_vector refuses it)")
+    if int(n_probes) < 1:
+        raise ValueError(f"{what}: n_probes={n_probes} (at least one Hutchinson probe)")
+    if probe not in ("rademacher", "gaussian"):
+        raise ValueError(f"{what}: probe {probe!r} (rademacher | gaussian)")
+    if int(num_steps) < 2:
+        raise ValueError(f"{what}: num_steps={num_steps} (the grid needs both ends)")
+    if getattr(model, "training", False):
+        raise ValueError(f"{what}: the model is in training mode (label / dropout masks would be redrawn at every evaluation and the "
+                         "integrand would not be a function of (x, t)); call model.eval() first")
+    if hasattr(model, "guided_halves"):
+        if model.class_cond and model_kwargs.get("y") is not None and abs(model.guidance_scale - 1.0) >= 1e-8:
+            raise ValueError(f"{what}: IntervalCFG with guidance_scale={model.guidance_scale}: a guided field is not the flow of a "
+                             "normalised density, so its divergence integral is no log-likelihood; evaluate the wrapped model")
+        model = model.model
+        if getattr(model, "training", False):
+            raise ValueError(f"{what}: the wrapped model is in training mode; call model.eval() first")
+    if getattr(model, "compute_dtype", None) == "fp8":
+        raise ValueError(f"{what}: compute_dtype='fp8' models are refused: the delayed-scaling state would move during an evaluation")
+    return model
+
+
+def flow_log_likelihood(fm, model, x, *, num_steps=50, solver="heun", t_span=(0.0, 1.0), n_probes=1, probe="rademacher",
+                        generator=None, offset_bits=0.0, fused=None, **model_kwargs):
+    """Per-sample log-likelihood of x under the flow model, by the instantaneous change of variables along the
+    probability-flow ODE (the reference's convention: t = 0 data, t = 1 noise, dx/dt = v(x, t)):
+
+        log p0(x0) = log N(x(t_hi); 0, I) + int_{t_lo}^{t_hi} div v(x(t), t) dt
+
+    integrated together with x by `solver` = euler | heun | rk4 on linspace(t_lo, t_hi, num_steps) (float64 on the host, the
+    state in x's dtype).  The divergence is estimated with Hutchinson probes: eps is drawn once per call from `generator`
+    (`probe` = "rademacher": +-1, exact in bf16, or "gaussian") and held fixed over the whole integration, so the integrand is
+    smooth in t; per evaluation g = (d out / d x)^T eps is one vector-Jacobian product (torch.autograd.grad; under
+    model.input_grad_only() where the model has it, so no weight gradient is computed or touched) and div v = A n + B sum
+    eps * g with v = A x + B out.  n_probes = K stacks K copies of the batch on the batch axis (one model call of K N rows) and
+    averages their divergence rows in float64.  The reference has no counterpart; any torch module works as the model.
+
+    Returns a dict: logp, prior_logp, delta_logp (float64 [N], nats), bpd = -logp / (n ln 2) + offset_bits (offset_bits = 7.0
+    for 8-bit pixels scaled to [-1, 1]: the density of the unscaled integers), z (the state at t_hi), nfev, nvjp.
+
+    fused: as in edm_sample.  None = vaw_flow_logp_stage / vaw_flow_logp_prior on the GPU (float32 x), False = the tensor
+    composition on any device (float64 x allowed), True = fused or an error.  Refused with the reason before any launch: a
+    model in training mode, an IntervalCFG whose guidance can be active, SCORE, the adaptive solvers, a grid time at which the
+    field's conversion is singular (EPSILON on the linear path at t = 1, START_X at t = 0), fp8 models, n_probes < 1."""
+    model = _logp_refusals(fm, model, solver, n_probes, probe, num_steps, model_kwargs)
+    tab = _flow_logp_tables(fm, solver, int(num_steps), t_span)
+    use = _want_fused(fused, x, "flow_log_likelihood", None if x.dtype == torch.float32 else f"{x.dtype} x")
+    K, N, shape = int(n_probes), x.shape[0], tuple(x.shape)
+    rows, n = K * N, x[0].numel()
+    stacked = lambda v: v.repeat(K, *([1] * (v.dim() - 1))) if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == N and K > 1 else v
+    kwargs = {name: stacked(v) for name, v in model_kwargs.items()}
+    eps = _logp_probes(probe, (rows, *shape[1:]), x.dtype, x.device, generator)
+    coef, times = _flow_logp_device(tab, rows, x.dtype, x.device)
+    S, e = len(tab.c), 0
+    stage_coeffs = lambda i: tab.b if i == S - 1 else tab.a[i + 1]
+    x0 = stacked(x.detach()).contiguous()
+    if use:
+        bufs = [torch.empty_like(x0) for _ in range(S)]
+        nxt = torch.empty_like(x0)
+        bufs[0].copy_(x0)
+        k = torch.empty((ops.RK_STAGES, *x0.shape), dtype=torch.float32, device=x.device)
+        d = torch.zeros((ops.RK_STAGES, rows), dtype=torch.float64, device=x.device)
+        delta = torch.zeros(rows, dtype=torch.float64, device=x.device)
+        partials = torch.empty(ops.rk_partial_count(rows, n), dtype=torch.float64, device=x.device) if n > 1024 else None
+        for h in tab.h:
+            for i in range(S):
+                out, g = _logp_network(model, bufs[i], times[e], eps, kwargs)
+                last = i == S - 1
+                if out.dtype != torch.float32:
+                    out = out.to(torch.float32)
+                ops.flow_logp_stage(i, out, g, eps, bufs[0], bufs[i] if i else None, coef, e, k, d, stage_coeffs(i), h,
+                                    x_out=nxt if last else bufs[i + 1], delta=delta if last else None, partials=partials)
+                e += 1
+            bufs[0], nxt = nxt, bufs[0]
+        z = bufs[0]
+        prior = ops.flow_logp_prior(z, partials)
+    else:
+        # the same arithmetic as tensor operations: the table's float32 (A, B) for a float32 state, the float64 ones otherwise
+        widen = (lambda v: float(np.float32(v))) if x.dtype == torch.float32 else float
+        cur, delta = x0, torch.zeros(rows, dtype=torch.float64, device=x.device)
+        for h in tab.h:
+            ks, ds, xs = [], [], cur
+            for i in range(S):
+                out, g = _logp_network(model, xs.contiguous(), times[e], eps, kwargs)
+                A, B = (widen(v) for v in tab.ab[e])
+                ks.append(A * xs + B * out)
+                ds.append(A * n + B * (eps.to(torch.float64) * g.to(torch.float64)).flatten(1).sum(1))
+                xs = cur + h * _rk_combine(stage_coeffs(i), ks)
+                e += 1
+            delta = delta + h * _rk_combine(tab.b, ds)
+            cur = xs
+        z = cur
+        prior = -0.5 * (z.to(torch.float64) ** 2).flatten(1).sum(1) - 0.5 * n * _LN_2PI
+    delta_logp = delta.view(K, N).mean(0) if K > 1 else delta
+    prior_logp, z = prior[:N], z[:N]
+    logp = prior_logp + delta_logp
+    return {"logp": logp, "prior_logp": prior_logp, "delta_logp": delta_logp, "bpd": -logp / (n * math.log(2.0)) + offset_bits,
+            "z": z.clone() if use else z, "nfev": e, "nvjp": e}

@@ -350,9 +350,14 @@ class UNetModel(FlatModule):
         def bw():
             dx = self._new(a.M, C)
             dsc = self._demb + (film - self._emb_base) if film else 0
+            if self._only_dx:      # d gamma / d beta leave the same pass as dx: to scratch, never into the flat gradients
+                side = self._new(2 * C, dtype=torch.float32)
+                dgam, dbet = ptr(side), ptr(side) + 4 * C
+            else:
+                dgam, dbet = self._g(name + ".weight"), self._g(name + ".bias")
             L.check(lib.vaw_groupnorm_bwd(dt, ptr(y.grad), ptr(a.t), ptr(mean), ptr(rstd), gam, bet, sc or None, sh or None,
                                           self.emb_cols, 1 if silu else 0, ptr(a.grad) if a.grad is not None else None,
-                                          ptr(dx), self._g(name + ".weight"), self._g(name + ".bias"), self._beta,
+                                          ptr(dx), dgam, dbet, self._beta,
                                           dsc or None, (dsc + 4 * C) if dsc else None, self.emb_cols, B, HW, C, 32,
                                           ptr(ops.scratch_f32(self._flat.device, lib.vaw_groupnorm_workspace_floats(B, HW, C))),
                                           L.stream_ptr()), "groupnorm_bwd")
@@ -386,11 +391,12 @@ class UNetModel(FlatModule):
         def bw():
             dy = y.grad
             need_dx = a.grad is not None or self._needs_grad(a)
-            gw, gb = self._g(name + ".weight"), self._g(name + ".bias")
             colb = None
+            if not self._only_dx:
+                gw, gb = self._g(name + ".weight"), self._g(name + ".bias")
             # the bias gradient rides on the implicit weight-gradient GEMM (row sums of the dy tiles it stages anyway)
-            fused = min(Ci, Co) > 4 and ops.conv3x3(dt, 2, ptr(dy), ptr(a.t), None, gw, *geo, beta=self._beta, rowsum_a_out=gb,
-                                                    rowsum_a_beta=self._beta)
+            fused = self._only_dx or (min(Ci, Co) > 4 and ops.conv3x3(dt, 2, ptr(dy), ptr(a.t), None, gw, *geo, beta=self._beta,
+                                                                      rowsum_a_out=gb, rowsum_a_beta=self._beta))
             if not fused:
                 ops.colsum(dt, ptr(dy), M, Co, Co, gb, self._beta, device=self._flat.device)
                 if min(Ci, Co) <= 4:       # 3-channel stem / output conv: dedicated skinny weight-gradient kernel
@@ -431,8 +437,10 @@ class UNetModel(FlatModule):
 
         def bw():
             dy = y.grad
-            deferred = self._defer_wgrad(M, Co, Ci, dy, a.t)
-            if deferred:
+            deferred = not self._only_dx and self._defer_wgrad(M, Co, Ci, dy, a.t)
+            if self._only_dx:
+                pass
+            elif deferred:
                 # deferred: one grouped launch per stage and pixel count (_flush_wgrads); the bias gradient now
                 self._pend_wgrad.setdefault(M, []).append((dy, a.t, self._g(wname), Co, Ci))
                 ops.colsum(dt, ptr(dy), M, Co, Co, self._g(bname), self._beta, device=self._flat.device)
@@ -556,8 +564,9 @@ class UNetModel(FlatModule):
         y = _Act(a.t, a.B, a.H, a.W, a.C)
 
         def bw():
-            L.check(L.lib().vaw_rowvec_sum(self._dt, ptr(y.grad), self._demb + 4 * off, self.emb_cols, a.B, a.H * a.W, a.C, 0.0,
-                                           L.stream_ptr()), "rowvec_sum")
+            if not self._only_dx:      # (the gradient of the conditioning path's table: nobody reads it then)
+                L.check(L.lib().vaw_rowvec_sum(self._dt, ptr(y.grad), self._demb + 4 * off, self.emb_cols, a.B, a.H * a.W, a.C, 0.0,
+                                               L.stream_ptr()), "rowvec_sum")
             self._acc(a, y.grad)
             y.grad = None
         self._push(bw)
@@ -655,7 +664,7 @@ class UNetModel(FlatModule):
 
     def _stage_done(self, stage):
         self._flush_wgrads()
-        if self.grad_ready_hook:
+        if self.grad_ready_hook and not self._only_dx:
             self.grad_ready_hook(stage)
 
     # ---- deferred weight gradients of the 1x1 layers (attention qkv / proj_out, skip connections) ---------------------------
@@ -710,6 +719,7 @@ class UNetModel(FlatModule):
             self._tape.append(bw)
 
     _FWD_STATE = ("_s", "_x_act", "_out_act", "_emb_base", "_need_dx")
+    _only_dx = False          # True while the backward of a forward made under input_grad_only() runs (_UNetFn.backward)
 
     def _forward_impl(self, x, t, y, need_dx, record=True):
         """record=False (forward under torch.no_grad(): sampling, evaluation) builds no tape and leaves the tape and the
@@ -794,8 +804,15 @@ class UNetModel(FlatModule):
     def _backward_impl(self, dout):
         dt, lib, st, s = self._dt, L.lib(), L.stream_ptr(), self._s
         B, ted, mc, f32 = dout.shape[0], self.time_embed_dim, self.model_channels, torch.float32
-        self._beta = 1.0 if self.grads_live() else 0.0
-        self._gbase = self.flat_grads().data_ptr()
+        only_dx = self._only_dx
+        if only_dx:
+            # FlatModule.input_grad_only: the closures skip every weight- / bias-gradient launch and queue nothing (_pend_wgrad stays
+            # empty), GroupNorm's d gamma / d beta go to scratch, the FiLM gradients (fused into GroupNorm backward) into demb_t below,
+            # which nobody reads; the flat gradient buffer is neither allocated nor addressed
+            self._beta, self._gbase = 0.0, None
+        else:
+            self._beta = 1.0 if self.grads_live() else 0.0
+            self._gbase = self.flat_grads().data_ptr()
         demb_t = torch.zeros(B, self.emb_cols, device=dout.device, dtype=f32)
         self._demb = ptr(demb_t)
         h = self._out_act
@@ -810,6 +827,9 @@ class UNetModel(FlatModule):
             xa = self._x_act
             dx = torch.empty(B, xa.C, xa.H, xa.W, device=dout.device, dtype=f32)
             L.check(lib.vaw_nhwc_to_nchw(dt, ptr(xa.grad), ptr(dx), B, xa.C, xa.H * xa.W, st), "nhwc_to_nchw")
+        if only_dx:
+            self._s, self._x_act, self._out_act = {}, None, None
+            return dx
         # FiLM table -> emb -> time MLP / label table
         beta = self._beta
         first = self._resblocks[0]._vaw_name + ".emb_layers.1."
@@ -854,6 +874,7 @@ class _UNetFn(torch.autograd.Function):
         ctx.model = model
         out = model._forward_impl(x, t, y, x.requires_grad, record=model._record_next)
         ctx.gen = model._tape_gen
+        ctx.only_dx = bool(model._input_grad_only)
         return out
 
     @staticmethod
@@ -865,7 +886,13 @@ class _UNetFn(torch.autograd.Function):
         if m._ckpt_fwd != bool(m.activation_checkpointing):
             raise L.VawError("UNet backward: activation_checkpointing was switched between this forward and its backward "
                              "(the tape of the forward was built for the other mode)")
-        dx = m._backward_impl(dout.contiguous())
+        if bool(m._input_grad_only) != ctx.only_dx:
+            raise L.VawError("UNet backward: input_grad_only() was entered or left between this forward and its backward")
+        m._only_dx = ctx.only_dx
+        try:
+            dx = m._backward_impl(dout.contiguous())
+        finally:
+            m._only_dx = False
         return torch.zeros_like(m._anchor), None, dx, None, None
 
 

@@ -212,6 +212,33 @@ int vaw_flow_step(int kind, int sde, int mean_type, const float* cond, const flo
                   const float* coef, int row0, int row1, int rows, float* x_out, float* x_out_dup, int B, int64_t per_sample,
                   vaw_stream stream);
 
+/* Linear multistep samplers in the data-prediction form (dpm_sample: DPM-Solver++ 2M, its SDE variant, exponential
+ * Adams-Bashforth up to order 3; sigma(t) = t, s = 1).  One network evaluation per step; the update is
+ *   x' = a*x + b0*D0 + b1*D1 + b2*D2 + c*noise
+ * with D0 the denoised image of this evaluation and D1, D2 those of the two steps before (kept as float32: they are float32
+ * values).  Doubles per row of the table, one row per step:
+ *   0 a   1 b0   2 b1   3 b2   4 c   (float64 coefficients of the update)
+ *   5 sigma as float32   6 c_in   7 c_in^2   8 sigma*c_in   (the float32 scalars of the denoiser's preconditioning at this
+ *   evaluation, stored widened)   9 c_in of the next evaluation   10, 11 unused */
+#define VAW_DPM_COLS 12
+
+/* The network input of the first evaluation:  model_in (and model_in_dup, the second half of the stacked guided input)
+ * = c_in * float(x), c_in = coef[row][6] as float32.  coef: [rows][VAW_DPM_COLS] float64, row < rows. */
+int vaw_dpm_input(const double* x, const double* coef, int row, int rows, float* model_in, float* model_in_dup, int B,
+                  int64_t per_sample, vaw_stream stream);
+
+/* After the network evaluation of step `row`.  o = the (guided) network output, x32 = float(x);  denoised (float32, as the
+ * denoiser forms it): pred_type 0 EPSILON x32 - sigma*o,  1 START_X o,  2 VELOCITY c_in^2*x32 - (sigma*c_in)*o;  clamped to
+ * [-1, 1] when clip != 0 (NaN stays NaN);  written to d0_out.  Then in float64, every operation rounded on its own,
+ *   acc = a*x + b0*double(D0);  d1 != NULL: acc = acc + b1*double(d1);  d2 != NULL (needs d1): acc = acc + b2*double(d2);
+ *   noise != NULL: acc = acc + c*noise;   x_out = acc   (x_out may be x: a lane reads its elements before it writes them)
+ * and, when model_in != NULL, the next network input coef[row][9] (as float32) * float(x_out) into model_in and, when
+ * model_in_dup != NULL, there as well.  The last step (a = 0, b0 = 1) passes no model_in. */
+int vaw_dpm_step(int pred_type, int clip, const float* cond, const float* uncond, int64_t model_ld, float guidance_scale,
+                 const double* x, const float* d1, const float* d2, const double* noise, const double* coef, int row, int rows,
+                 double* x_out, float* d0_out, float* model_in, float* model_in_dup, int B, int64_t per_sample,
+                 vaw_stream stream);
+
 /* ---------------------------------------------------------------------------
  * Adaptive explicit Runge-Kutta steps of the flow ODE  (flow_ode_sample(solver="rk45"): Dormand-Prince 5(4), the step
  * controller on the host).  Same conventions as the solver steps above: float32, every operation rounded on its own, the

@@ -12,7 +12,7 @@ For a learn_sigma model under IntervalCFG (scale 2.5, active on part of the chai
  (d) a full Sampler.sample of one batch (DDIM, `--steps` steps), fused and through the composition of (b).
 (a) / (b) and the two forms of (c) / (d) alternate inside one timed run.  One JSON line at the end.
 
-With `--solver heun|euler` (EDM sampler) or `--mode flow` (flow SDE sampler, Heun unless `--solver euler`) the run is instead
+With `--solver heun|euler` (EDM sampler), `--solver dpmpp2m|dpmpp2m_sde|expab` (multistep samplers, one evaluation per step) or `--mode flow` (flow SDE sampler, Heun unless `--solver euler`) the run is instead
  (e) one Sampler.sample of `--batches` batches of `--batch` images, `--steps` solver steps, guidance `--guidance`: the time of
      each batch on a host clock (every batch ends in the device-to-host copy of its images), the first `--skip` batches left
      out (tables, workspaces and, with `--graph`, the capture), median / min / max of the rest in ms.  `--fused 0` runs the
@@ -25,6 +25,12 @@ With `--solver rk45` the run is
      the time is the solver's own) on `--batch` x 4 x S x S noise (S = `--image-size` or 32), linear path, VELOCITY,
      `--rtol` / `--atol`: attempts, network evaluations and read-backs of a call, and the median ms per attempt of `--repeats`
      calls, fused (vaw_rk_stage) and as the tensor composition (`fused=False`) alternating, each after a warm-up call.
+
+With `--dpm-kernel` the run is
+ (h) vaw_dpm_step alone on `--batch` x 4 x S x S (S = `--image-size` or 64) float64 states over rotating sets larger than the
+     256 MiB Infinity Cache, device events over `--iters` calls: unguided with two nodes (dpmpp2m: 8 + 4 + 4 read, 8 + 4 + 4
+     written = 32 B/element) and guided with three nodes and noise (52 B/element), in us and algorithmic TB/s, checked once
+     against the tensor composition.
 
 With `--logp` the run is
  (g) one flow_log_likelihood sweep (`--steps` grid points, `--solver euler|heun`, cosine path, VELOCITY) of `--batch` samples
@@ -136,7 +142,9 @@ def solver_bench(a):
         args.hip_graph = True
     if a.fused is not None:
         import vaw_amd.sampler as sm
-        for name in ("edm_sample", "flow_sde_sample", "flow_ode_sample"):
+        for name in ("edm_sample", "dpm_sample", "flow_sde_sample", "flow_ode_sample"):
+            if not hasattr(sm, name):          # an older --tree
+                continue
             setattr(sm, name, functools.partial(getattr(sm, name), fused=bool(a.fused)))
     diff = vaw_amd.FlowMatching(args=args, model_mean_type=vaw_amd.ModelMeanType.VELOCITY) if flow else None
     s = vaw_amd.Sampler(args, torch.device("cuda"), model, diff, **(dict(decode_fn=(lambda z: z[:, :3])) if C == 4 else {}))
@@ -150,11 +158,56 @@ def solver_bench(a):
     stamps.append(time.perf_counter())
     s.sample(a.batch * a.batches, a.batch, H, a.num_classes)
     ms = sorted(1e3 * (t1 - t0) for t0, t1 in zip(stamps[a.skip:-1], stamps[a.skip + 1:]))
-    evals = (2 * a.steps - 1 if solver == "heun" else a.steps)
+    evals = (2 * a.steps - 1 if solver == "heun" else a.steps)          # euler and the multistep solvers: one per step
     print(json.dumps({"part": "e", "model": a.model, "dtype": "fp32" if a.fp32 else "bf16", "mode": a.mode, "solver": solver, "steps": a.steps,
                       "batch": a.batch, "guidance": a.guidance, "fused": a.fused, "graph": bool(a.graph), "tree": a.tree or ".",
                       "evaluations_per_batch": evals, "batches_timed": len(ms), "ms_per_batch_median": ms[len(ms) // 2],
                       "ms_per_batch_min": ms[0], "ms_per_batch_max": ms[-1]}))
+
+
+def dpm_kernel_bench(a):
+    """(h): vaw_dpm_step against its bytes."""
+    from vaw_amd import samplers
+    S, N = a.image_size or 64, a.batch
+    shape = (N, 4, S, S)
+    net = vaw_amd.EDMDenoiser(torch.nn.Identity(), S, 4).to("cuda")
+    lo, hi = samplers._edm_sigma_range(net, "edm", None, None, 1e-3)
+    coef = samplers._dpm_tables(net, torch.device("cuda"), N, 18, lo, hi, 7, "dpmpp2m_sde", None, "edm", 1e-3, 1.0, 1.0).coef.clone()
+    coef[:, 3] = 0.125
+    elems = N * 4 * S * S
+    sets = []
+    for _ in range(max(2, int(600e6 // (elems * 52)) + 1)):
+        sets.append(dict(x=torch.randn(shape, device="cuda", dtype=torch.float64), nz=torch.randn(shape, device="cuda", dtype=torch.float64),
+                         out=torch.randn((2 * N, *shape[1:]), device="cuda"), d=[torch.randn(shape, device="cuda") for _ in range(3)],
+                         buf=torch.empty((2 * N, *shape[1:]), device="cuda")))
+    row = 9
+
+    def plain(s):
+        return lambda: ops.dpm_step("EPSILON", False, s["out"][:N], None, 1.0, s["x"], s["d"][1], None, None, coef, row, x_out=s["x"],
+                                    d0_out=s["d"][0], model_in=s["buf"][:N])
+
+    def full(s):
+        return lambda: ops.dpm_step("EPSILON", False, s["out"][:N], s["out"][N:], SCALE, s["x"], s["d"][1], s["d"][2], s["nz"], coef, row,
+                                    x_out=s["x"], d0_out=s["d"][0], model_in=s["buf"][:N], model_in_dup=s["buf"][N:])
+
+    s0 = sets[0]
+    o = s0["out"][N:] + SCALE * (s0["out"][:N] - s0["out"][N:])
+    sigma = coef[row, 5].float()
+    den = s0["x"].float() - sigma * o
+    ref = coef[row, 0] * s0["x"] + coef[row, 1] * den.double()
+    ref = ref + coef[row, 2] * s0["d"][1].double()
+    ref = ref + coef[row, 3] * s0["d"][2].double()
+    ref = ref + coef[row, 4] * s0["nz"]
+    full(s0)()
+    assert torch.equal(s0["x"], ref) and torch.equal(s0["d"][0], den), "vaw_dpm_step differs from the composition"
+    del o, den, ref
+    res = {"part": "h", "batch": N, "elements": elems, "rotating_sets": len(sets)}
+    for name, mk, nbytes in (("two_nodes_unguided", plain, 32), ("three_nodes_guided_noise", full, 52)):
+        fns = [mk(s) for s in sets]
+        events_us(fns, 2 * len(fns))
+        us = events_us(fns, a.iters)
+        res[f"{name}_us"], res[f"{name}_bytes_per_element"], res[f"{name}_algorithmic_TBps"] = us, nbytes, nbytes * elems / us / 1e6
+    print(json.dumps(res))
 
 
 def rk45_bench(a):
@@ -259,8 +312,9 @@ def main():
     ap.add_argument("--logp", action="store_true",
                     help="(g): time one flow_log_likelihood sweep of --steps grid points (--solver euler|heun, default heun) with the full "
                          "backward per evaluation and with input_grad_only()")
-    ap.add_argument("--solver", choices=["heun", "euler", "rk45"], default=None,
-                    help="(e): time Sampler.sample through this EDM / flow solver; rk45: (f), the adaptive flow-ODE solver")
+    ap.add_argument("--solver", choices=["heun", "euler", "dpmpp2m", "dpmpp2m_sde", "expab", "rk45"], default=None,
+                    help="(e): time Sampler.sample through this EDM / multistep / flow solver; rk45: (f), the adaptive flow-ODE solver")
+    ap.add_argument("--dpm-kernel", action="store_true", help="(h): vaw_dpm_step alone against its bytes")
     ap.add_argument("--rtol", type=float, default=1e-3, help="(f)")
     ap.add_argument("--atol", type=float, default=1e-6, help="(f)")
     ap.add_argument("--mode", choices=["diffusion", "flow"], default="diffusion")
@@ -284,6 +338,9 @@ def main():
         raise SystemExit("sample_bench.py measures on the GPU only")
     if a.logp:
         return logp_bench(a)
+    if a.dpm_kernel:
+        with torch.no_grad():
+            return dpm_kernel_bench(a)
     if a.solver == "rk45":
         with torch.no_grad():
             return rk45_bench(a)

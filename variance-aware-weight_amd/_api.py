@@ -10,7 +10,7 @@ from .gaussian_diffusion import (FlowMatching, GaussianDiffusion, LossType, Mode
 from .optim import FusedAdamW  # noqa: F401
 from .parallel import DistributedDataParallel  # noqa: F401
 from .data import DevicePrefetcher, LatentBatchLoader, LatentH5Dataset, ShardedSampler  # noqa: F401
-from .samplers import EDMDenoiser, edm_sample, flow_log_likelihood, flow_ode_sample, flow_sde_sample  # noqa: F401
+from .samplers import EDMDenoiser, dpm_sample, edm_sample, flow_log_likelihood, flow_ode_sample, flow_sde_sample  # noqa: F401
 from .respace import SpacedDiffusion, space_timesteps  # noqa: F401
 from .sampler import IntervalCFG, Sampler, sync_ema_model  # noqa: F401
 from .resample import (DeviceLossSecondMomentResampler, LossSecondMomentResampler, UniformSampler, create_named_schedule_sampler)  # noqa: F401

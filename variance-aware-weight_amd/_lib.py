@@ -164,6 +164,8 @@ _PROTOS = {
     "vaw_finish_images": [_p, _i, _p, _i, _i, _i, _i, _p],
     "vaw_edm_input": [_p, _p, _p, _i, _i, _p, _p, _p, _i, _l, _p],
     "vaw_edm_step": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _i, _i, _p, _p, _p, _i, _l, _p],
+    "vaw_dpm_input": [_p, _p, _i, _i, _p, _p, _i, _l, _p],
+    "vaw_dpm_step": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _l, _p],
     "vaw_flow_step": [_i, _i, _i, _p, _p, _l, _f, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _l, _p],
     "vaw_rk_stage": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _i, _i, _p, C.POINTER(_i), C.POINTER(_f), _i, _f, _p, _p, _p, _f, _f, _p, _l, _i, _l, _p],
     "vaw_rk_scaled_sumsq": [_p, _p, _p, _p, _f, _f, _p, _l, _i, _l, _p],

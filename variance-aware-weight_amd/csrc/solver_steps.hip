@@ -1,5 +1,5 @@
-// Solver steps of the EDM (Euler / Heun, float64) and flow-matching (SDE / ODE, float32) samplers: one streaming pass each
-// around the denoiser call.  The coefficients of a step do not depend on x; they come from a device table built once per
+// Solver steps of the EDM (Euler / Heun, float64), linear multistep (DPM-Solver++ 2M / 2M-SDE / exponential Adams-Bashforth,
+// float64) and flow-matching (SDE / ODE, float32) samplers: one streaming pass each around the denoiser call.  The coefficients of a step do not depend on x; they come from a device table built once per
 // grid (samplers.py) and are read by row index.  Every operation is rounded on its own, in the order of the tensor
 // composition these kernels replace (this file is built with -ffp-contract=off; divisions and square roots are IEEE).
 // The model output of a guided call is the stacked [2N, ...] tensor read in place: rows model_ld floats apart.
@@ -25,13 +25,15 @@ __device__ __forceinline__ EdmEval edm_eval(const double* r) {
 }
 // f32 model input of EDMDenoiser.forward for the f64 state x at an evaluation: c_in * f32(x / s)
 __device__ __forceinline__ float edm_model_in(const EdmEval& e, double x) { return e.cin * (float)(x / e.s); }
-// dx/dt of _Path.slope with the denoised image of EDMDenoiser.forward (pred: 0 EPSILON, 1 START_X, 2 VELOCITY) for model output o
+// the denoised image of EDMDenoiser.forward (pred: 0 EPSILON, 1 START_X, 2 VELOCITY) for model output o at the f32 state x32
+__device__ __forceinline__ float edm_denoised(int pred, float sigma, float cin2, float sc, float x32, float o) {
+    if (pred == 0) return x32 - sigma * o;
+    if (pred == 1) return o;
+    return cin2 * x32 - sc * o;
+}
+// dx/dt of _Path.slope with that denoised image
 __device__ __forceinline__ double edm_slope(const EdmEval& e, int pred, double x, float o) {
-    const float x32 = (float)(x / e.s);
-    float den;
-    if (pred == 0) den = x32 - e.sigma * o;
-    else if (pred == 1) den = o;
-    else den = e.cin2 * x32 - e.sc * o;
+    const float den = edm_denoised(pred, e.sigma, e.cin2, e.sc, (float)(x / e.s), o);
     return e.k1 * x - e.k2 * (double)den;
 }
 
@@ -156,6 +158,114 @@ extern "C" int vaw_edm_step(int kind, int pred_type, const float* cond, const fl
                            model_in, model_in_dup, per_sample, kind, pred_type};
     VAW_LAUNCH_W(edm_step_kernel, vec, row_grid(vec ? per_sample / 4 : per_sample, B), 256, stream, a);
     VAW_CHECK_LAUNCH("edm_step");
+    return VAW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Linear multistep samplers (dpm_sample).  Table row (VAW_DPM_COLS doubles) of step i:
+//   0 a  1 b0  2 b1  3 b2  4 c  of  x' = a x + b0 D0 + b1 D1 + b2 D2 + c noise;  5 sigma (f32)  6 c_in  7 c_in^2  8 sigma*c_in of
+//   this evaluation (the f32 scalars of EDMDenoiser.forward, stored widened);  9 c_in of the next evaluation.
+// The denoised images D0, D1, D2 are f32 values and stay f32 in memory; the state is f64.
+// ---------------------------------------------------------------------------------------------
+template <int W>
+__global__ void dpm_input_kernel(const double* __restrict__ x, const double* __restrict__ coef, float* __restrict__ min,
+                                 float* __restrict__ min2, int64_t n) {
+    const float cin = (float)coef[6];
+    const int64_t base = (int64_t)blockIdx.y * n;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / W; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = base + W * i;
+        double xv[W];
+        float mi[W];
+        loadw<W>(x + o, xv);
+#pragma unroll
+        for (int j = 0; j < W; ++j) mi[j] = cin * (float)xv[j];
+        storew<W>(min + o, mi);
+        if (min2) storew<W>(min2 + o, mi);
+    }
+}
+
+extern "C" int vaw_dpm_input(const double* x, const double* coef, int row, int rows, float* model_in, float* model_in_dup, int B,
+                             int64_t per_sample, vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "dpm_input: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(x && coef && model_in, "dpm_input: null pointer");
+    VAW_CHECK_ARG(row >= 0 && row < rows, "dpm_input: row %d outside the table of %d rows", row, rows);
+    VAW_CHECK_ARG(((uintptr_t)x & 7) == 0 && ((uintptr_t)coef & 7) == 0, "dpm_input: float64 pointer not aligned to 8 bytes");
+    const bool vec = vec4_ok(per_sample, 0, {x, model_in, model_in_dup});
+    VAW_LAUNCH_W(dpm_input_kernel, vec, row_grid(vec ? per_sample / 4 : per_sample, B), 256, stream, x,
+                 coef + (int64_t)row * VAW_DPM_COLS, model_in, model_in_dup, per_sample);
+    VAW_CHECK_LAUNCH("dpm_input");
+    return VAW_OK;
+}
+
+// x_out may be x (no __restrict__ on either): a lane loads its W elements of every input before it stores any
+struct DpmStepArgs {
+    const float *cond, *uncond;
+    int64_t ld;
+    float gs;
+    const double *x, *noise, *coef;
+    const float *d1, *d2;
+    double* x_out;
+    float *d0_out, *min, *min2;
+    int64_t n;
+    int pred, clip;
+};
+
+template <int W>
+__global__ void dpm_step_kernel(const DpmStepArgs a) {
+    const double* r = a.coef;
+    const double ca = r[0], b0 = r[1], b1 = r[2], b2 = r[3], cn = r[4];
+    const float sigma = (float)r[5], cin2 = (float)r[7], sc = (float)r[8], cin_next = (float)r[9];
+    const int pred = a.pred;
+    const bool clip = a.clip != 0;
+    const int64_t n = a.n, base = (int64_t)blockIdx.y * n, mbase = (int64_t)blockIdx.y * a.ld;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n / W; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = base + W * i;
+        double xv[W], nz[W];
+        float c[W], u[W], p1[W], p2[W], d0[W], mi[W];
+        loadw<W>(a.x + o, xv);
+        loadw<W>(a.cond + mbase + W * i, c);
+        if (a.uncond) loadw<W>(a.uncond + mbase + W * i, u);
+        if (a.d1) loadw<W>(a.d1 + o, p1);
+        if (a.d2) loadw<W>(a.d2 + o, p2);
+        if (a.noise) loadw<W>(a.noise + o, nz);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const float m = a.uncond ? cfg_mix(c[j], u[j], a.gs) : c[j];
+            float den = edm_denoised(pred, sigma, cin2, sc, (float)xv[j], m);
+            if (clip) den = den < -1.f ? -1.f : (den > 1.f ? 1.f : den);          // torch.clamp: NaN stays NaN
+            d0[j] = den;
+            double acc = ca * xv[j] + b0 * (double)den;
+            if (a.d1) acc = acc + b1 * (double)p1[j];
+            if (a.d2) acc = acc + b2 * (double)p2[j];
+            if (a.noise) acc = acc + cn * nz[j];
+            xv[j] = acc;
+            mi[j] = cin_next * (float)acc;
+        }
+        storew<W>(a.d0_out + o, d0);
+        storew<W>(a.x_out + o, xv);
+        if (a.min) storew<W>(a.min + o, mi);
+        if (a.min2) storew<W>(a.min2 + o, mi);
+    }
+}
+
+extern "C" int vaw_dpm_step(int pred_type, int clip, const float* cond, const float* uncond, int64_t model_ld, float guidance_scale,
+                            const double* x, const float* d1, const float* d2, const double* noise, const double* coef, int row,
+                            int rows, double* x_out, float* d0_out, float* model_in, float* model_in_dup, int B, int64_t per_sample,
+                            vaw_stream stream) {
+    VAW_CHECK_ARG(B > 0 && per_sample > 0, "dpm_step: bad sizes B=%d per_sample=%ld", B, (long)per_sample);
+    VAW_CHECK_ARG(pred_type >= 0 && pred_type <= 2, "dpm_step: bad pred_type %d", pred_type);
+    VAW_CHECK_ARG(cond && x && coef && x_out && d0_out, "dpm_step: null pointer");
+    VAW_CHECK_ARG(d1 || !d2, "dpm_step: d2 (the third node) needs d1");
+    VAW_CHECK_ARG(model_in || !model_in_dup, "dpm_step: model_in_dup needs model_in");
+    VAW_CHECK_ARG(model_ld >= per_sample, "dpm_step: model_ld %ld < per_sample %ld", (long)model_ld, (long)per_sample);
+    VAW_CHECK_ARG(row >= 0 && row < rows, "dpm_step: row %d outside the table of %d rows", row, rows);
+    VAW_CHECK_ARG(((uintptr_t)x & 7) == 0 && ((uintptr_t)noise & 7) == 0 && ((uintptr_t)x_out & 7) == 0 && ((uintptr_t)coef & 7) == 0,
+                  "dpm_step: float64 pointer not aligned to 8 bytes");
+    const bool vec = vec4_ok(per_sample, model_ld, {cond, uncond, x, d1, d2, noise, x_out, d0_out, model_in, model_in_dup});
+    const DpmStepArgs a = {cond, uncond, model_ld, guidance_scale, x, noise, coef + (int64_t)row * VAW_DPM_COLS, d1, d2, x_out,
+                           d0_out, model_in, model_in_dup, per_sample, pred_type, clip};
+    VAW_LAUNCH_W(dpm_step_kernel, vec, row_grid(vec ? per_sample / 4 : per_sample, B), 256, stream, a);
+    VAW_CHECK_LAUNCH("dpm_step");
     return VAW_OK;
 }
 

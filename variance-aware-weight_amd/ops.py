@@ -332,6 +332,40 @@ def edm_step(kind, pred_type, cond, uncond, guidance_scale, x_hat, d_cur, coef, 
     return d_cur if kind == STEP_PREDICT else x_out
 
 
+DPM_COLS = 12          # VAW_DPM_COLS
+
+
+def dpm_input(x, coef, row, model_in, model_in_dup=None):
+    """The network input of the first evaluation of a multistep sampler (vaw_dpm_input): c_in * float32(x), c_in = coef[row, 6],
+    into model_in (and model_in_dup, the second half of a stacked guided input).  Bitwise EDMDenoiser.forward's product."""
+    need_cuda(x, coef, model_in, model_in_dup)
+    _dense("dpm_input", torch.float64, x.shape, x)
+    _dense("dpm_input", torch.float32, x.shape, model_in, model_in_dup)
+    _table("dpm_input", coef, torch.float64, DPM_COLS, row)
+    B = x.shape[0]
+    check(L.lib().vaw_dpm_input(ptr(x), ptr(coef), int(row), coef.shape[0], ptr(model_in), ptr(model_in_dup), B, x.numel() // max(B, 1),
+                                stream_ptr()), "vaw_dpm_input")
+    return model_in
+
+
+def dpm_step(pred_type, clip, cond, uncond, guidance_scale, x, d1, d2, noise, coef, row, x_out, d0_out, model_in=None, model_in_dup=None):
+    """After the network evaluation of step `row` of a multistep sampler (vaw_dpm_step): the denoised image D0 (float32, clamped
+    to [-1, 1] with clip) into d0_out, x_out = a*x + b0*D0 (+ b1*d1) (+ b2*d2) (+ c*noise) in float64 with the row's
+    coefficients (x_out may be x), and the next network input into model_in (and model_in_dup).  d1 / d2: the float32 denoised
+    images of the two steps before, None where the step has fewer nodes; cond / uncond, pred_type as in edm_step.  Returns x_out."""
+    need_cuda(cond, uncond, x, d1, d2, noise, coef, x_out, d0_out, model_in, model_in_dup)
+    _dense("dpm_step", torch.float64, x.shape, x, noise, x_out)
+    _dense("dpm_step", torch.float32, x.shape, d1, d2, d0_out, model_in, model_in_dup)
+    _table("dpm_step", coef, torch.float64, DPM_COLS, row)
+    _f32_parts("dpm_step", x, cond, uncond)
+    B = x.shape[0]
+    (cond, uncond), ld = _rows_in_place((cond, uncond), x.numel() // max(B, 1))
+    check(L.lib().vaw_dpm_step(EDM_PRED[pred_type], 1 if clip else 0, ptr(cond), ptr(uncond), ld, float(guidance_scale), ptr(x), ptr(d1),
+                               ptr(d2), ptr(noise), ptr(coef), int(row), coef.shape[0], ptr(x_out), ptr(d0_out), ptr(model_in),
+                               ptr(model_in_dup), B, x.numel() // max(B, 1), stream_ptr()), "vaw_dpm_step")
+    return x_out
+
+
 def flow_step(kind, sde, mean_type, cond, uncond, guidance_scale, x, noise, x_pred, f0, kick, coef, row0, row1, x_out, x_out_dup=None):
     """One step of the flow samplers after a network evaluation (vaw_flow_step), float32: see include/vaw_hip.h.  Returns x_out.
     mean_type: a key of FLOW_MEAN; cond / uncond as in edm_step."""

@@ -7,7 +7,7 @@ import torch
 import torch.distributed as dist
 
 from . import dist_util, ops
-from .samplers import EDMDenoiser, edm_sample, flow_ode_sample, flow_sde_sample
+from .samplers import DPM_SOLVERS, EDMDenoiser, dpm_sample, edm_sample, flow_ode_sample, flow_sde_sample
 
 
 class IntervalCFG(torch.nn.Module):
@@ -94,7 +94,7 @@ class Sampler:
     Extensions: `decode_fn(latents) -> images in [-1, 1]` stands where the reference loads a diffusers VAE
     (args.in_chans == 4; the latents are handed over already divided by args.latent_scale); with args.cpu_rng the labels
     and every noise draw come from the CPU generator in the reference's order, which reproduces its CPU stream.
-    args.hip_graph=True (EDM and flow generators, whose loops do not synchronise with the host; not the adaptive
+    args.hip_graph=True (EDM, multistep and flow generators, whose loops do not synchronise with the host; not the adaptive
     solver="rk45", whose every step the host decides): the first batch runs eagerly,
     the second is captured into one graph on static label and output buffers, later batches replay it; the labels are drawn
     outside the graph in the same order, so images and labels are those of the eager run.  "auto" or absent: eager."""
@@ -118,6 +118,11 @@ class Sampler:
 
     def _build_cfg_model(self, num_classes):
         return IntervalCFG(self.model, num_classes, self.args.guidance_scale, self.args.interval, self.args.class_cond).eval()
+
+    def _build_denoiser(self, image_size, num_classes):
+        a = self.args
+        return EDMDenoiser(self._build_cfg_model(num_classes), img_resolution=image_size, img_channels=a.in_chans,
+                           label_dim=num_classes, noise_schedule=a.path_type, amp=a.amp, pred_type=a.mean_type).to(self.device)
 
     def _randint(self, high, sample_size):
         if self._cpu_rng():
@@ -237,8 +242,7 @@ class Sampler:
 
     def edm_sampler(self, num_samples, sample_size, image_size, num_classes, progress_bar=False):
         a = self.args
-        net = EDMDenoiser(self._build_cfg_model(num_classes), img_resolution=image_size, img_channels=a.in_chans,
-                          label_dim=num_classes, noise_schedule=a.path_type, amp=a.amp, pred_type=a.mean_type).to(self.device)
+        net = self._build_denoiser(image_size, num_classes)
 
         def draw(class_labels):
             latents = self._randn([sample_size, net.img_channels, net.img_resolution, net.img_resolution])
@@ -246,6 +250,22 @@ class Sampler:
                               solver=a.solver, discretization=a.discretization, schedule=a.schedule, scaling=a.scaling)
 
         return self._run(draw, num_samples, sample_size, num_classes, progress_bar, f"Generating Samples ({a.solver.capitalize()})",
+                         graph=self._use_graph())
+
+    def dpm_sampler(self, num_samples, sample_size, image_size, num_classes, progress_bar=False):
+        """The multistep solvers of samplers.dpm_sample (args.solver dpmpp2m | dpmpp2m_sde | expab): one evaluation per step.
+        Optional args: eta, s_noise (dpmpp2m_sde; 1.0), order (expab; 3), clip_denoised (False)."""
+        a = self.args
+        net = self._build_denoiser(image_size, num_classes)
+
+        def draw(class_labels):
+            latents = self._randn([sample_size, net.img_channels, net.img_resolution, net.img_resolution])
+            return dpm_sample(net, latents, class_labels=class_labels, randn_like=self._randn_like, num_steps=a.sample_steps,
+                              solver=a.solver, order=getattr(a, "order", None), discretization=a.discretization,
+                              eta=getattr(a, "eta", 1.0), s_noise=getattr(a, "s_noise", 1.0),
+                              clip_denoised=getattr(a, "clip_denoised", False))
+
+        return self._run(draw, num_samples, sample_size, num_classes, progress_bar, f"Generating Samples ({a.solver})",
                          graph=self._use_graph())
 
     def flow_matching_sampler(self, num_samples, sample_size, image_size, num_classes, progress_bar=False):
@@ -272,5 +292,7 @@ class Sampler:
         if self.args.model_mode == "diffusion":
             if self.args.solver == "ddim":
                 return self.ddim_sampler(num_samples, sample_size, image_size, num_classes, progress_bar)
+            if self.args.solver in DPM_SOLVERS:
+                return self.dpm_sampler(num_samples, sample_size, image_size, num_classes, progress_bar)
             return self.edm_sampler(num_samples, sample_size, image_size, num_classes, progress_bar)
         raise ValueError(f"Unsupported model_mode: {self.args.model_mode}")

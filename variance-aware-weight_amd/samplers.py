@@ -3,6 +3,10 @@
   * `EDMDenoiser` + `edm_sample`: the Karras et al. (EDM) deterministic / stochastic Euler-Heun sampler over a DDPM-trained
     denoiser -- behaviour of the reference's tools/cfg_edm.py (`Net` :15-108, `ablation_sampler` :111-210) as driven by
     tools/sampler.py:160-196 (`--solver euler|heun`, `--discretization`, `--schedule`, `--scaling`);
+  * `dpm_sample`: linear multistep solvers in the data-prediction form over the same denoiser and noise levels (DPM-Solver++ 2M,
+    its SDE variant, exponential Adams-Bashforth up to order 3; no counterpart in the reference): one network evaluation per
+    step, the update x' = a x + b0 D0 + b1 D1 + b2 D2 + c noise from a per-grid table (`_dpm_tables`), one kernel per step
+    (vaw_dpm_step).
   * `flow_sde_sample`, `flow_ode_sample`: the FlowMatching samplers of tools/gaussian_diffusion.py:1343-1417.  The reference's
     ODE sampler integrates with torchdiffeq (adaptive dopri5 by default), which is not available here: the fixed-grid
     solvers euler / midpoint / heun / rk4 are provided on the same time grid, and the adaptive integrator is provided under
@@ -33,7 +37,7 @@ import torch
 from . import ops
 from .gaussian_diffusion import ModelMeanType
 
-__all__ = ["EDMDenoiser", "edm_sample", "flow_sde_sample", "flow_ode_sample", "flow_log_likelihood"]
+__all__ = ["EDMDenoiser", "edm_sample", "dpm_sample", "flow_sde_sample", "flow_ode_sample", "flow_log_likelihood"]
 
 
 def _unwrap(out):
@@ -345,6 +349,195 @@ def edm_sample(net, latents, class_labels=None, randn_like=torch.randn_like, num
         x_mid = x_hat + alpha * h * d_cur
         d_mid = path.slope(x_mid, t_mid, net(x_mid / path.s(t_mid), path.sigma(t_mid), class_labels, **model_kwargs).to(torch.float64))
         x = x_hat + h * ((1 - 1 / (2 * alpha)) * d_cur + 1 / (2 * alpha) * d_mid)
+    return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# linear multistep solvers in the data-prediction form: one network evaluation per step
+# ---------------------------------------------------------------------------------------------------------------------
+DPM_SOLVERS = ("dpmpp2m", "dpmpp2m_sde", "expab")
+
+
+def _expab_weights(lam, lam_next):
+    """The weights b_j of the exponential Adams-Bashforth step from lam[0] to lam_next (lam: the nodes, newest first, 0-dim
+    tensors or numbers):  sum_j b_j p(lam[j]) = int_{lam[0]}^{lam_next} e^{-(lam_next - tau)} p(tau) dtau  for every polynomial p
+    of degree < len(lam) <= 3.  With u = tau - lam[0] the moments of the kernel are I_0 = -expm1(-h), I_k = h^k - k I_{k-1};
+    the weights integrate the Lagrange basis over the nodes u_0 = 0, u_j = lam[j] - lam[0]."""
+    lam = [torch.as_tensor(v, dtype=torch.float64) for v in lam]
+    h = torch.as_tensor(lam_next, dtype=torch.float64) - lam[0]
+    I0 = -torch.expm1(-h)
+    if len(lam) == 1:
+        return [I0]
+    I1 = h - I0
+    u1 = lam[1] - lam[0]
+    if len(lam) == 2:
+        b1 = I1 / u1
+        return [I0 - b1, b1]
+    I2 = h ** 2 - 2 * I1
+    u2 = lam[2] - lam[0]
+    return [(I2 - (u1 + u2) * I1 + u1 * u2 * I0) / (u1 * u2), (I2 - u2 * I1) / (u1 * (u1 - u2)), (I2 - u1 * I1) / (u2 * (u2 - u1))]
+
+
+def _dpm_2m_weights(sig_cur, sig_next, h, h_last, eta, s_noise):
+    """(a, b0, b1, c) of the DPM-Solver++(2M) step in its midpoint form, h_last=None: the first-order step.  One routine for
+    the deterministic solver (eta = 0: a = sig_next / sig_cur, J = -expm1(-h), c = 0) and its SDE variant."""
+    eta_h = eta * h
+    a = sig_next / sig_cur * torch.exp(-eta_h)
+    J = -torch.expm1(-h - eta_h)
+    c = sig_next * torch.sqrt(-torch.expm1(-2 * eta_h)) * s_noise
+    if h_last is None:
+        return a, J, 0.0, c
+    w = 1 / (2 * (h_last / h))
+    return a, J * (1 + w), -(J * w), c
+
+
+def _dpm_tables(net, device, batch, num_steps, lo, hi, rho, solver, order, discretization, epsilon_s, eta, s_noise):
+    """Everything of dpm_sample's loop that does not depend on x, computed once per grid in float64 on `device` and cached on
+    the denoiser:
+      sigma   [num_steps + 1] float64: the snapped noise levels, then 0
+      coef    [num_steps, ops.DPM_COLS] float64 on the device (include/vaw_hip.h): a, b0, b1, b2, c of
+              x' = a x + b0 D0 + b1 D1 + b2 D2 + c noise, then the float32 scalars of EDMDenoiser.forward at this evaluation
+              (sigma, c_in, c_in^2, sigma c_in) widened, then c_in of the next evaluation
+      steps   [num_steps, 2 * batch] int32 on the device: the chain index handed to the network (a guided call takes a whole
+              row, any other its first half)
+      nodes, noise_on, t_mean   host lists: how many denoised images step i combines (1..3), whether it adds noise, and the
+              mean timestep as the network sees it (the argument of the guidance predicate), from one read-back.
+    For a denoiser that only follows the protocol (no chain: an analytic D(x; sigma)) the evaluation columns stay zero and
+    steps / t_mean are None: the composition needs neither.  Raises ValueError where two adjacent snapped levels do not decrease."""
+    key = ("dpm", solver, order, num_steps, discretization, float(lo), float(hi), rho, epsilon_s, float(eta), float(s_noise), int(batch),
+           str(device))
+    cache = net.__dict__.setdefault("_solver_tables", {})
+    if key in cache:
+        return cache[key]
+    sig = net.round_sigma(_noise_levels(net, discretization, num_steps, lo, hi, rho, epsilon_s, device))
+    sig = torch.cat([sig, torch.zeros_like(sig[:1])])
+    lam = -sig[:num_steps].log()
+    chain = hasattr(net, "nearest_index") and hasattr(net, "M")
+
+    def evaluation(sigma64):
+        sigma = sigma64.to(torch.float32).reshape(-1, 1, 1, 1)               # EDMDenoiser.forward
+        c_in = 1 / (sigma ** 2 + 1).sqrt()
+        step = (net.M - 1 - net.nearest_index(sigma).to(torch.float32)).flatten()
+        return [sigma, c_in, c_in ** 2, sigma * c_in], step
+
+    rows, steps, t_mean, nodes = [], [], [], []
+    for i in range(num_steps):
+        last = i == num_steps - 1
+        q = 1 if last or i == 0 else 2 if solver != "expab" else min(order, i + 1)
+        if last:                                                              # sigma_next = 0: x' = D0
+            w = [0.0, 1.0, 0.0, 0.0, 0.0]
+        elif solver == "expab":
+            b = _expab_weights([lam[i - j] for j in range(q)], lam[i + 1])
+            w = [sig[i + 1] / sig[i], *b, *([0.0] * (3 - q)), 0.0]
+        else:
+            h = lam[i + 1] - lam[i]
+            a, b0, b1, c = _dpm_2m_weights(sig[i], sig[i + 1], h, lam[i] - lam[i - 1] if q == 2 else None, eta, s_noise)
+            w = [a, b0, b1, 0.0, c]
+        ev = [0.0] * 5
+        if chain:
+            scalars, step = evaluation(sig[i])
+            ev = scalars + [0.0 if last else evaluation(sig[i + 1])[0][1]]
+            steps.append(step.repeat(2 * batch).int())
+            t_mean.append(steps[-1][:batch].float().mean())                  # IntervalCFG.forward's read-back
+        rows.append(_row(w + ev, torch.float64, device, ops.DPM_COLS))
+        nodes.append(q)
+    coef = torch.stack(rows).contiguous()
+    host = torch.cat([sig, torch.stack(t_mean).to(torch.float64)] if chain else [sig]).tolist()
+    for i in range(num_steps):
+        if not host[i] > host[i + 1]:
+            raise ValueError(f"dpm_sample: the snapped noise levels do not decrease at step {i} (sigma {host[i]!r} -> {host[i + 1]!r}): "
+                             "h <= 0 there; use fewer steps or another discretization")
+    tab = SimpleNamespace(coef=coef, sigma=sig, steps=torch.stack(steps).contiguous() if chain else None, nodes=nodes,
+                          noise_on=[solver == "dpmpp2m_sde" and eta > 0 and i < num_steps - 1 for i in range(num_steps)],
+                          t_mean=host[num_steps + 1:] if chain else [None] * num_steps, solver=solver, num_steps=num_steps)
+    cache[key] = tab
+    return tab
+
+
+def _dpm_sample_fused(net, latents, class_labels, randn_like, tab, clip_denoised, model_kwargs):
+    """dpm_sample's loop on the fused kernels: vaw_dpm_input once, then per step the network, the noise draw where the step
+    adds noise, and vaw_dpm_step, which also writes the next network input.  The float32 denoised images of the last three
+    steps live in three buffers rotated by reference.  No host synchronisation."""
+    n, shape = latents.shape[0], tuple(latents.shape)
+    kwargs = {**model_kwargs, "y": class_labels}
+    cfg, guided, scale, stacked = _guidance(net.model, class_labels, tab.t_mean, kwargs)
+    if stacked is not None and class_labels.shape[0] != n:
+        raise AssertionError(f"CFG expects label batch size {n}, but got {class_labels.shape[0]}.")
+    buf = torch.empty(((2 * n if stacked is not None else n), *shape[1:]), dtype=torch.float32, device=latents.device)
+    lo, hi = buf[:n], (buf[n:] if stacked is not None else None)
+    x = latents.to(torch.float64) * tab.sigma[0]
+    hist = [torch.empty(shape, dtype=torch.float32, device=latents.device) for _ in range(3)]          # D0 (written), D1, D2
+    ops.dpm_input(x, tab.coef, 0, lo, hi)
+    for i in range(tab.num_steps):
+        cond, uncond = _evaluate(net.model, cfg, guided, stacked, buf, n, tab.steps, i, net.img_channels, kwargs)
+        noise = randn_like(x) if tab.noise_on[i] else None
+        more = i < tab.num_steps - 1
+        ops.dpm_step(net.pred_type, clip_denoised, cond, uncond, scale, x, hist[1] if tab.nodes[i] >= 2 else None,
+                     hist[2] if tab.nodes[i] >= 3 else None, noise, tab.coef, i, x_out=x, d0_out=hist[0],
+                     model_in=lo if more else None, model_in_dup=hi if more else None)
+        hist = [hist[2], hist[0], hist[1]]
+    return x
+
+
+@torch.no_grad()
+def dpm_sample(net, latents, class_labels=None, randn_like=torch.randn_like, num_steps=18, sigma_min=None, sigma_max=None, rho=7,
+               solver="dpmpp2m", order=None, discretization="edm", eta=1.0, s_noise=1.0, clip_denoised=False, epsilon_s=1e-3,
+               fused=None, **model_kwargs):
+    """x_0 (float64) from `latents` ~ N(0, I) with a linear multistep solver in the data-prediction form: ONE evaluation of
+    `net` (an EDMDenoiser, or anything with net(x, sigma, labels, **kw), round_sigma, sigma_min, sigma_max) per step, on the
+    noise levels of edm_sample (schedule "linear", scaling "none": sigma(t) = t, s = 1), the last step landing on sigma = 0.
+    With lambda = -log sigma, h = lambda_{i+1} - lambda_i, r = h_last / h:
+      solver="dpmpp2m"      DPM-Solver++(2M), midpoint form: x' = (sigma_{i+1} / sigma_i) x - expm1(-h) ((1 + 1/(2r)) D0 - 1/(2r) D1),
+                            first step first order
+      solver="dpmpp2m_sde"  its stochastic variant, eta_h = eta h, J = -expm1(-h - eta_h):
+                            x' = (sigma_{i+1} / sigma_i) e^{-eta_h} x + J (1 + 1/(2r)) D0 - J/(2r) D1
+                                 + sigma_{i+1} sqrt(-expm1(-2 eta_h)) s_noise noise;   eta = 0 is dpmpp2m, coefficient for coefficient
+      solver="expab"        exponential Adams-Bashforth of `order` 1..3 (default 3): x' = (sigma_{i+1} / sigma_i) x + the exact
+                            integral of e^{-(lambda_{i+1} - tau)} P(tau), P the Lagrange polynomial through the last
+                            min(order, i + 1) denoised images (`_expab_weights`)
+    and x' = D0 on the last step.  The coefficients a, b0, b1, b2, c of a step are computed once per grid (`_dpm_tables`);
+    the update is acc = a x + b0 D0, then + b1 D1, + b2 D2, + c noise where the step has them, every operation rounded on
+    its own in float64, D the float32 denoised image (clamped to [-1, 1] with clip_denoised) widened.  randn_like(x) is drawn
+    once per step that adds noise (dpmpp2m_sde with eta > 0, all steps but the last).  fused: as in edm_sample (None =
+    vaw_dpm_input / vaw_dpm_step on the GPU, bitwise the composition below)."""
+    if solver not in DPM_SOLVERS:
+        raise ValueError(f"solver {solver!r} (one of {DPM_SOLVERS})")
+    if solver == "expab":
+        order = 3 if order is None else order
+        if order not in (1, 2, 3):
+            raise ValueError(f"dpm_sample: order {order!r} of expab is not 1, 2 or 3")
+    elif order is not None:
+        raise ValueError(f"dpm_sample: order is a parameter of solver 'expab', not of {solver!r} (second order)")
+    if eta < 0 or s_noise < 0:
+        raise ValueError(f"dpm_sample: eta {eta!r} and s_noise {s_noise!r} must not be negative")
+    if num_steps < 2:
+        raise ValueError(f"dpm_sample: num_steps {num_steps!r} < 2")
+    if solver != "dpmpp2m_sde":
+        eta, s_noise = 0.0, 1.0
+    lo, hi = _edm_sigma_range(net, discretization, sigma_min, sigma_max, epsilon_s)
+    pred_type = getattr(net, "pred_type", None)
+    unsupported = (None if pred_type in ops.EDM_PRED and hasattr(net, "nearest_index") else
+                   f"pred_type {pred_type!r}" if pred_type is not None else "a denoiser without EDMDenoiser's chain")
+    use = _want_fused(fused, latents, "dpm_sample", unsupported)
+    tab = _dpm_tables(net, latents.device, latents.shape[0], num_steps, lo, hi, rho, solver, order, discretization, epsilon_s, eta, s_noise)
+    if use:
+        return _dpm_sample_fused(net, latents, class_labels, randn_like, tab, clip_denoised, model_kwargs)
+    x = latents.to(torch.float64) * tab.sigma[0]
+    hist = []
+    for i in range(num_steps):
+        d0 = net(x, tab.sigma[i], class_labels, **model_kwargs)
+        if clip_denoised:
+            d0 = d0.clamp(-1, 1)
+        a, b0, b1, b2, c = tab.coef[i, :5].unbind()
+        acc = a * x + b0 * d0.to(torch.float64)
+        if tab.nodes[i] >= 2:
+            acc = acc + b1 * hist[0].to(torch.float64)
+        if tab.nodes[i] >= 3:
+            acc = acc + b2 * hist[1].to(torch.float64)
+        if tab.noise_on[i]:
+            acc = acc + c * randn_like(x)
+        x = acc
+        hist = [d0] + hist[:1]
     return x
 
 

@@ -659,6 +659,22 @@ int vaw_reduce_rows_batched(int n_jobs, const vaw_reduce_job* jobs, float beta, 
  * mean/rstd: f32 [B*T] saved for backward. */
 int vaw_ln_modulate_fwd(vaw_dtype dt, const float* x, const float* shift, const float* scale, int64_t mod_ld,
                         void* out, float* mean, float* rstd, int B, int T, int D, float eps, vaw_stream stream);
+/* The GEMM kernels round the gated residual add differently: the persistent kernel's gated epilogue is one fma, the others round the
+ * product first.  1 / 0: whether vaw_gemm gives the gated launch [B*T, D] = [B*T, D] x [D, D]^T (bias, aux_out, gate, f32 residual,
+ * aligned operands: a DiT block's proj) to the former, with the process's GEMM knobs -- the rounding vaw_gate_resid_ln_modulate_fwd
+ * then uses, so that it is bitwise that launch followed by vaw_ln_modulate_fwd.  Host arithmetic, no GPU needed. */
+int vaw_gate_resid_fwd_contracts(int B, int T, int D);
+/* The gated residual add of a branch and the LayerNorm + modulate that reads its result, in one pass over the rows (bf16 mode;
+ * models/dit.py:135-136 -> :125,135 of the next consumer):
+ *   x_out[b,t,:] = y[b,t,:] * gate[b,:] + x_in[b,t,:]    (rounded as vaw_gemm's gated-residual epilogue rounds it for these rows today:
+ *                                                         vaw_gate_resid_fwd_contracts)
+ *   out = modulate(LayerNorm(x_out), shift, scale), mean, rstd    (the bits vaw_ln_modulate_fwd gives on x_out)
+ * y, out: bf16 [B*T, D]; x_in, x_out: f32 [B*T, D], not the same buffer; gate (row stride gate_ld), shift / scale (mod_ld): f32 rows
+ * per sample.  out == NULL: the residual only -- shift, scale, mean and rstd are not touched.  dt must be VAW_BF16, D % 4 == 0,
+ * D <= 2048, the strides multiples of 4 and every base 16-byte aligned: anything else is refused (VAW_ERR_INVALID) before any launch. */
+int vaw_gate_resid_ln_modulate_fwd(vaw_dtype dt, const void* y, const float* gate, int64_t gate_ld, const float* x_in, float* x_out,
+                                   const float* shift, const float* scale, int64_t mod_ld, void* out, float* mean, float* rstd,
+                                   int B, int T, int D, float eps, vaw_stream stream);
 /* Backward of the above, fused with the residual-stream gradient:
  *   dx[b,t,:]   = (dres_in ? dres_in : 0) + LN'(dout * (1+scale))
  *   dshift[b,:] = sum_t dout ;  dscale[b,:] = sum_t dout * xhat     (rows with stride dmod_ld)
@@ -690,16 +706,19 @@ int64_t vaw_row_bwd_workspace_floats(int B, int T, int D);
  * rows: B, T, D as the entry point's, workspace_floats = what the caller would pass (0 = none), ldx / base_addr unused;
  * colsum: M = B * T rows (pass T = 1), N = D columns, row stride ldx, base_addr = the address of X (its alignment picks the path).
  *   nc: workgroups per sample (grid.y; > 1: row_bwd_finish_kernel folds them), rows_per_chunk: T rows per chunk;
- *   colsum: nc = partial rows of the workspace (grid.y), rows_per_chunk = rows per partial row. */
+ *   colsum: nc = partial rows of the workspace (grid.y), rows_per_chunk = rows per partial row.
+ * VAW_ROW_GATE_LN_FWD (vaw_gate_resid_ln_modulate_fwd): ldx = the OR of gate_ld and mod_ld, base_addr = the OR of the addresses of
+ *   its vector operands; anything but bf16 rows, D % 4 == 0, strides that are multiples of 4 and 16-byte aligned bases is refused. */
 typedef enum { VAW_ROW_LN_FWD = 0, VAW_ROW_LN_FWD_FP8 = 1, VAW_ROW_LN_BWD = 2, VAW_ROW_GATE_BWD = 3, VAW_ROW_GATE_BWD_FP8 = 4,
-               VAW_ROW_LN_BWD_GATE = 5, VAW_ROW_LN_BWD_GATE_FP8 = 6, VAW_ROW_COLSUM = 7 } vaw_row_kind;
+               VAW_ROW_LN_BWD_GATE = 5, VAW_ROW_LN_BWD_GATE_FP8 = 6, VAW_ROW_COLSUM = 7, VAW_ROW_GATE_LN_FWD = 8 } vaw_row_kind;
 typedef enum {
     VAW_RV_LN_FWD = 0,          /* ln_modulate_fwd_kernel<T, NV> */
     VAW_RV_ROW_BWD = 1,         /* row_bwd_kernel<T, NV, false>: LayerNorm backward */
     VAW_RV_ROW_GATE = 2,        /* row_bwd_kernel<T, NV, true>: gate backward */
     VAW_RV_ROW_FUSE = 3,        /* row_bwd_kernel<T, NV, false, QOUT, true>: fused, per-sample sums in registers */
     VAW_RV_ROW_FUSE8 = 4,       /* row_bwd_fuse8_kernel<NV, QOUT>: fused, per-wave sums in LDS slabs (bf16) */
-    VAW_RV_COLSUM_BF16X8 = 5, VAW_RV_COLSUM_VEC4 = 6, VAW_RV_COLSUM_SCALAR = 7
+    VAW_RV_COLSUM_BF16X8 = 5, VAW_RV_COLSUM_VEC4 = 6, VAW_RV_COLSUM_SCALAR = 7,
+    VAW_RV_GATE_LN_FWD = 8      /* gate_resid_ln_fwd_kernel<NV, LN>: gated residual + LayerNorm forward, one wave per row (bf16) */
 } vaw_row_variant;
 typedef struct {
     int variant;                /* vaw_row_variant */

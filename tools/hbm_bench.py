@@ -72,9 +72,23 @@ def main():
         report("ln_modulate_fwd (6 B/elem)", timeit(fns, a.iters), 6.0 * M * D)
         del sets, fns
 
+    if want("gatelnfwd"):
+        sets = []
+        for _ in range(NSET):
+            s = dict(y=torch.randn(M, D, device=dev).bfloat16(), xin=torch.randn(M, D, device=dev), xout=torch.empty(M, D, device=dev),
+                     out=torch.empty(M, D, device=dev, dtype=torch.bfloat16), mean=torch.empty(M, device=dev), rstd=torch.empty(M, device=dev))
+            sets.append(s)
+        fns = [(lambda s=s: ops.gate_resid_ln_modulate_fwd(BF16, ptr(s["y"]), ptr(mod) + 8 * D, 6 * D, ptr(s["xin"]), ptr(s["xout"]), ptr(mod),
+                                                           ptr(mod) + 4 * D, 6 * D, ptr(s["out"]), ptr(s["mean"]), ptr(s["rstd"]), B, T, D)) for s in sets]
+        report("gate_resid + ln_modulate_fwd (12 B/elem)", timeit(fns, a.iters), 12.0 * M * D)
+        fns = [(lambda s=s: ops.gate_resid_ln_modulate_fwd(BF16, ptr(s["y"]), ptr(mod) + 8 * D, 6 * D, ptr(s["xin"]), ptr(s["xout"]), 0, 0, 6 * D,
+                                                           0, 0, 0, B, T, D)) for s in sets]
+        report("gate_resid alone (8 B/elem)", timeit(fns, a.iters), 8.0 * M * D)
+        del sets, fns
+
     if want("rowbwd"):
         sets = []
-        dmod = torch.zeros(B, 6 * D, device=dev)
+        dmod =torch.zeros(B, 6 * D, device=dev)
         colp = torch.zeros(B, D, device=dev)
         for _ in range(NSET):
             s = dict(dout=torch.randn(M, D, device=dev).bfloat16(), x=torch.randn(M, D, device=dev), mean=torch.randn(M, device=dev),

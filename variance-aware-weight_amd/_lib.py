@@ -107,8 +107,10 @@ P8_NAMES = ("P8_STORE", "P8_GELU", "P8_DGELU", "P8_GATE", "P8_SLAB", "P8_ANY", "
 # vaw_row_kind / vaw_row_variant
 RESAMPLER_MAX_T = 4096      # VAW_RESAMPLER_MAX_T
 
-ROW_LN_FWD, ROW_LN_FWD_FP8, ROW_LN_BWD, ROW_GATE_BWD, ROW_GATE_BWD_FP8, ROW_LN_BWD_GATE, ROW_LN_BWD_GATE_FP8, ROW_COLSUM = range(8)
-RV_LN_FWD, RV_ROW_BWD, RV_ROW_GATE, RV_ROW_FUSE, RV_ROW_FUSE8, RV_COLSUM_BF16X8, RV_COLSUM_VEC4, RV_COLSUM_SCALAR = range(8)
+(ROW_LN_FWD, ROW_LN_FWD_FP8, ROW_LN_BWD, ROW_GATE_BWD, ROW_GATE_BWD_FP8, ROW_LN_BWD_GATE, ROW_LN_BWD_GATE_FP8, ROW_COLSUM,
+ ROW_GATE_LN_FWD) = range(9)
+(RV_LN_FWD, RV_ROW_BWD, RV_ROW_GATE, RV_ROW_FUSE, RV_ROW_FUSE8, RV_COLSUM_BF16X8, RV_COLSUM_VEC4, RV_COLSUM_SCALAR,
+ RV_GATE_LN_FWD) = range(9)
 
 # vaw_gn_pass / vaw_gn_variant
 GN_FWD_SUMS, GN_APPLY, GN_BWD_SUMS, GN_BWD_APPLY = range(4)
@@ -124,6 +126,8 @@ _PROTOS = {
     "vaw_gemm_uses_bf16_mfma": [_i, _l, _l, _l, _p, _l, _p, _l],
     "vaw_colsum": [_i, _p, _l, _l, _l, _p, _f, _p, _l, _p],
     "vaw_ln_modulate_fwd": [_i, _p, _p, _p, _l, _p, _p, _p, _i, _i, _i, _f, _p],
+    "vaw_gate_resid_fwd_contracts": [_i, _i, _i],      # returns 1 / 0, not a status
+    "vaw_gate_resid_ln_modulate_fwd": [_i, _p, _p, _l, _p, _p, _p, _p, _l, _p, _p, _p, _i, _i, _i, _f, _p],
     "vaw_ln_modulate_bwd": [_i, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _l, _i, _i, _i, _p, _l, _p],
     "vaw_gate_bwd": [_i, _p, _p, _p, _l, _p, _p, _l, _p, _i, _i, _i, _p, _l, _p],
     "vaw_reduce_rows": [_p, _l, _l, _p, _f, _p],
@@ -311,6 +315,9 @@ def exported_symbols():
 # VAW_STEP_FUSED (read once): 0 restores the step's unfused sequence of launches everywhere -- separate cast / column-sum
 # passes in the DiT backward, tensor operations for the latent sample, the coefficient gathers and the batch means of the loss
 STEP_FUSED = os.environ.get("VAW_STEP_FUSED", "1") != "0"
+# VAW_ROWS_FWD_FUSED (read once): 0 restores the gated-residual epilogue of proj / fc2 followed by a LayerNorm launch of
+# its own in the bf16 DiT block forward, in place of the plain store and vaw_gate_resid_ln_modulate_fwd
+ROWS_FWD_FUSED = os.environ.get("VAW_ROWS_FWD_FUSED", "1") != "0"
 
 
 def check(rc, what):

@@ -8,6 +8,37 @@
 
 #include "common.h"
 
+// The LayerNorm + modulate of ONE token row held in a wave's registers (v[i]: the four columns of slab i of this lane, zero beyond D;
+// s: the lane's sum of them, slab by slab).  ln_modulate_fwd_kernel and gate_resid_ln_fwd_kernel both go through these two, so they
+// give the same bits on the same row: slab sums per lane, wave_sum, rsqrtf, then (x - mean) * rstd * (1 + scale) + shift.
+template <int NV>
+__device__ __forceinline__ void ln_row_stats(const f32x4 (&v)[NV], float s, int lane, int D, float eps, float& mean, float& rstd) {
+    mean = wave_sum(s) / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < D) {
+            f32x4 d = v[i] - mean;
+            q += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
+        }
+    }
+    rstd = rsqrtf(wave_sum(q) / (float)D + eps);
+}
+__device__ __forceinline__ f32x4 ln_modulate4(f32x4 v, float mean, float rstd, f32x4 sc, f32x4 sh) {
+    f32x4 xh = (v - mean) * rstd;
+    return xh * (1.f + sc) + sh;
+}
+template <typename T, int NV>
+__device__ __forceinline__ void ln_row_store(const f32x4 (&v)[NV], float mean, float rstd, const float* __restrict__ sc,
+                                             const float* __restrict__ sh, T* __restrict__ orow, int lane, int D) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c < D) store4(orow + c, ln_modulate4(v[i], mean, rstd, load4(sc + c), load4(sh + c)));
+    }
+}
+
 // NV = number of 256-column slabs a lane walks (D <= 256*NV), D % 4 == 0.
 template <typename T, int NV>
 __global__ void __launch_bounds__(256)
@@ -52,17 +83,8 @@ ln_modulate_fwd_kernel(const float* __restrict__ x, const float* __restrict__ sh
 #pragma unroll
             for (int i = 0; i < NV; ++i) nx[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x + (row + rstep) * D + colc[i]));
         }
-        const float mean = wave_sum(s) / (float)D;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            if (c < D) {
-                f32x4 d = v[i] - mean;
-                q += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
-            }
-        }
-        const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
+        float mean, rstd;
+        ln_row_stats<NV>(v, s, lane, D, eps, mean, rstd);
         if (lane == 0) {
             mean_out[row] = mean;
             rstd_out[row] = rstd;
@@ -80,15 +102,7 @@ ln_modulate_fwd_kernel(const float* __restrict__ x, const float* __restrict__ sh
             }
             continue;
         }
-        T* orow = out + row * D;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            if (c < D) {
-                f32x4 xh = (v[i] - mean) * rstd;
-                store4(orow + c, xh * (1.f + load4(sc + c)) + load4(sh + c));
-            }
-        }
+        ln_row_store<T, NV>(v, mean, rstd, sc, sh, out + row * D, lane, D);
     }
     if (q_out) {          // one look at the running max per WORKGROUP (the four waves' maxima meet in LDS)
         __shared__ float wmax[4];
@@ -96,6 +110,98 @@ ln_modulate_fwd_kernel(const float* __restrict__ x, const float* __restrict__ sh
         if (lane == 0) wmax[threadIdx.x >> 6] = am;
         __syncthreads();
         if (threadIdx.x < 64) fp8_amax_commit(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])), q_state + 1, lane);
+    }
+}
+
+// The gated residual add of a DiT branch and the LayerNorm + modulate that reads its result, as one pass over the rows (bf16 mode):
+//   x_out = float(y) * gate + x_in          -- what the GEMM's gated-residual epilogue writes from the same y, gate and residual:
+//                                             contract != 0: one rounding (gemm_p8_kernel<.., P8_GATE, ..>: v_pk_fma_f32; this file is
+//                                             built with contraction off, so the fma is spelled out), else the product rounded first
+//                                             (epi_row8 of the other kernels); vaw_gate_resid_fwd_contracts says which
+//   out   = (x_out - mean) * rstd * (1 + scale) + shift, mean, rstd     -- ln_row_stats / ln_row_store: the bits of ln_modulate_fwd_kernel
+// LN = false: the residual only.  12 bytes per element (8 without the LayerNorm) against 6 + 6 + the 10 of the GEMM epilogue it relieves.
+// Streaming as ln_modulate_fwd_kernel: one wave per row, a grid of one resident round, wave-uniform row bases with one clamped column
+// offset per lane and slab (no branch around a load), and the NEXT row's y, residual and gate requested before the current row is
+// worked on (y and the residual non-temporally: read once).  The sample's (1 + scale) and shift rows (L2) are requested at the top of
+// the row, ahead of the next row's loads (loads retire in order) and two wave reductions before their use.
+template <int NV, bool LN>
+__global__ void __launch_bounds__(256)
+gate_resid_ln_fwd_kernel(const bf16_t* __restrict__ y, const float* __restrict__ gate, int64_t gate_ld, const float* __restrict__ x_in,
+                         float* __restrict__ x_out, const float* __restrict__ shift, const float* __restrict__ scale, int64_t mod_ld,
+                         bf16_t* __restrict__ out, float* __restrict__ mean_out, float* __restrict__ rstd_out, int64_t M, int Tt, int D,
+                         float eps, int contract) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t row0 = (int64_t)blockIdx.x * 4 + wave, rstep = (int64_t)gridDim.x * 4;
+    bool act[NV];
+    unsigned col[NV], colc[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        col[i] = (unsigned)(i * 64 + lane) * 4u;
+        act[i] = col[i] < (unsigned)D;
+        colc[i] = act[i] ? col[i] : 0u;
+    }
+    bf16x4 ny[NV];
+    f32x4 nx[NV], ng[NV];
+    auto issue = [&](int64_t row) __attribute__((always_inline)) {
+        const bf16_t* const y_r = y + row * D;
+        const float* const x_r = x_in + row * D;
+        const float* const g_r = gate + (row / Tt) * gate_ld;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            ny[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(y_r + colc[i]));
+            nx[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x_r + colc[i]));
+            ng[i] = load4(g_r + colc[i]);
+        }
+    };
+    if (row0 < M) issue(row0);
+    for (int64_t row = row0; row < M; row += rstep) {
+        f32x4 scv[LN ? NV : 1], shv[LN ? NV : 1];
+        if (LN) {
+            const float* const sc = scale + (row / Tt) * mod_ld;
+            const float* const sh = shift + (row / Tt) * mod_ld;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                scv[i] = load4(sc + colc[i]);
+                shv[i] = load4(sh + colc[i]);
+            }
+        }
+        f32x4 v[NV];
+        float s = 0.f;
+        if (contract) {       // (uniform) one rounding, the persistent GEMM's epilogue
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const f32x4 r = {__builtin_fmaf((float)ny[i][0], ng[i][0], nx[i][0]), __builtin_fmaf((float)ny[i][1], ng[i][1], nx[i][1]),
+                                 __builtin_fmaf((float)ny[i][2], ng[i][2], nx[i][2]), __builtin_fmaf((float)ny[i][3], ng[i][3], nx[i][3])};
+                v[i] = act[i] ? r : f32x4{0, 0, 0, 0};
+            }
+        } else {              // the product rounded first, the row epilogue of the other GEMM kernels (contraction is off in this file)
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const f32x4 yf = {(float)ny[i][0], (float)ny[i][1], (float)ny[i][2], (float)ny[i][3]};
+                v[i] = act[i] ? yf * ng[i] + nx[i] : f32x4{0, 0, 0, 0};
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NV; ++i) s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
+        if (row + rstep < M) issue(row + rstep);
+        float* const xo = x_out + row * D;
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+            if (act[i]) __builtin_nontemporal_store(v[i], reinterpret_cast<f32x4*>(xo + col[i]));
+        if (LN) {
+            float mean, rstd;
+            ln_row_stats<NV>(v, s, lane, D, eps, mean, rstd);
+            if (lane == 0) {
+                mean_out[row] = mean;
+                rstd_out[row] = rstd;
+            }
+            bf16_t* const orow = out + row * D;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                if (act[i]) store4(orow + col[i], ln_modulate4(v[i], mean, rstd, scv[i], shv[i]));
+            }
+        }
     }
 }
 
@@ -452,8 +558,27 @@ static constexpr size_t kRowLdsMax = 160 * 1024;     // gfx950: LDS per CU, the 
 
 extern "C" int vaw_row_plan(vaw_row_kind kind, vaw_dtype dt, int64_t B, int64_t T, int64_t D, int64_t ldx, int64_t base_addr,
                             int64_t workspace_floats, vaw_row_launch* out) {
-    VAW_CHECK_ARG(out && kind >= VAW_ROW_LN_FWD && kind <= VAW_ROW_COLSUM, "row_plan: bad kind %d", (int)kind);
+    VAW_CHECK_ARG(out && kind >= VAW_ROW_LN_FWD && kind <= VAW_ROW_GATE_LN_FWD, "row_plan: bad kind %d", (int)kind);
     vaw_row_launch p = {};
+    if (kind == VAW_ROW_GATE_LN_FWD) {
+        // the fused gated residual + LayerNorm forward: bf16 rows only, every vector operand on a 16-byte boundary (ldx = the OR of
+        // the gate / modulation row strides, base_addr = the OR of the operand addresses); one wave per row as VAW_ROW_LN_FWD
+        VAW_CHECK_ARG(dt == VAW_BF16, "gate_resid_ln_modulate_fwd: bf16 rows only (dt=%d)", (int)dt);
+        VAW_CHECK_ARG(B > 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 2048 && B < (1 << 30) && T < (1 << 30),
+                      "gate_resid_ln_modulate_fwd: need D%%4==0, D<=2048 (D=%ld)", (long)D);
+        VAW_CHECK_ARG(ldx >= 0 && ldx % 4 == 0, "gate_resid_ln_modulate_fwd: gate_ld and mod_ld must be multiples of 4");
+        VAW_CHECK_ARG((base_addr & 15) == 0, "gate_resid_ln_modulate_fwd: every operand must be 16-byte aligned");
+        const int nv = pick_nv((int)D);
+        const int64_t wgs = (B * T + 3) / 4;
+        p.variant = VAW_RV_GATE_LN_FWD;
+        p.nv = nv <= 6 ? nv : 8;
+        p.nc = 1;
+        p.rows_per_chunk = (int)T;
+        p.grid_x = (int)(wgs < (1LL << 30) ? wgs : (1LL << 30));
+        p.block = 256;
+        *out = p;
+        return VAW_OK;
+    }
     if (kind == VAW_ROW_COLSUM) {
         const int64_t M = B * T, N = D;
         VAW_CHECK_ARG(B > 0 && T > 0 && N > 0 && ldx >= N, "colsum: bad sizes");
@@ -577,6 +702,60 @@ extern "C" int vaw_ln_modulate_fwd_fp8(const float* x, const float* shift, const
     DISPATCH_NV(plan.nv, (ln_modulate_fwd_kernel<bf16_t, NV><<<plan.grid_x, plan.block, 0, s>>>(x, shift, scale, mod_ld, nullptr, mean, rstd, M, T, D, eps,
                                                                                              (unsigned char*)q_out, q_state, q_format == VAW_BF8)));
     VAW_CHECK_LAUNCH("ln_modulate_fwd_fp8");
+    return VAW_OK;
+}
+
+// The GEMM kernels do not round the gated residual add alike: the persistent kernel's P8_GATE epilogue contracts y * gate + resid to
+// one fma, the 64-, 128- and 256-row kernels and the generic one round the product first (their epilogue multiplies and adds behind
+// separate run-time switches).  The row pass rounds as the kernel does that vaw_gemm gives the gated launch of the same rows today:
+// [B*T, D] = [B*T, D] x [D, D]^T with bias, aux_out, gate and an f32 residual, every operand aligned (proj's launch; fc2's differs in
+// K only).  1: one rounding (fma), 0: two.  Host arithmetic (vaw_gemm_plan), follows the process's GEMM knobs like vaw_gemm itself.
+extern "C" int vaw_gate_resid_fwd_contracts(int B, int T, int D) {
+    if (B <= 0 || T <= 0 || D <= 0) return 0;
+    vaw_epilogue e = {};          // (addresses stand for null-ness and alignment only)
+    e.bias = (const float*)0x1000;
+    e.aux_out = (void*)0x1000;
+    e.gate = (const float*)0x1000;
+    e.gate_ld = 6 * (int64_t)D;
+    e.resid = (const void*)0x1000;
+    e.rows_per_batch = T;
+    e.alpha = 1.f;
+    e.out_f32 = 1;
+    vaw_gemm_launch g;
+    const int64_t M = (int64_t)B * T;
+    if (vaw_gemm_plan(VAW_BF16, 1, 1, M, D, D, D, D, D, 0x1000, 0x1000, 0x1000, &e, 0, nullptr, &g) != VAW_OK) return 0;
+    return g.variant == VAW_GV_PERSISTENT && g.epi_kind == 3 /* P8_GATE (gemm_epi.h) */ && g.split == 1;
+}
+
+// x_out = y * gate + x_in and, unless out is NULL, the LayerNorm + modulate of x_out: see gate_resid_ln_fwd_kernel
+extern "C" int vaw_gate_resid_ln_modulate_fwd(vaw_dtype dt, const void* y, const float* gate, int64_t gate_ld, const float* x_in,
+                                              float* x_out, const float* shift, const float* scale, int64_t mod_ld, void* out,
+                                              float* mean, float* rstd, int B, int T, int D, float eps, vaw_stream stream) {
+    VAW_CHECK_ARG(y && gate && x_in && x_out && x_in != x_out, "gate_resid_ln_modulate_fwd: y, gate, x_in and a separate x_out are required");
+    VAW_CHECK_ARG(!out || (shift && scale && mean && rstd), "gate_resid_ln_modulate_fwd: out needs shift, scale, mean and rstd");
+    const uintptr_t addrs = (uintptr_t)y | (uintptr_t)gate | (uintptr_t)x_in | (uintptr_t)x_out |
+                            (out ? (uintptr_t)out | (uintptr_t)shift | (uintptr_t)scale : 0);
+    ROW_PLAN(VAW_ROW_GATE_LN_FWD, dt, B, T, D, (gate_ld < 0 || mod_ld < 0) ? -1 : (gate_ld | (out ? mod_ld : 0)), (int64_t)(addrs & 15), 0);
+    const int64_t M = (int64_t)B * T;
+    const int contract = vaw_gate_resid_fwd_contracts(B, T, D);
+    // one resident round of workgroups, every wave several rows (as vaw_ln_modulate_fwd)
+    static int per_cu[2][9] = {};
+    const int nvk = plan.nv, li = out ? 1 : 0;
+    if (!per_cu[li][nvk]) {
+        int nb = 0;
+        if (out) { DISPATCH_NV(nvk, (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gate_resid_ln_fwd_kernel<NV, true>, 256, 0)); }
+        else { DISPATCH_NV(nvk, (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gate_resid_ln_fwd_kernel<NV, false>, 256, 0)); }
+        per_cu[li][nvk] = nb > 0 && nb <= 8 ? nb : 8;
+    }
+    const int64_t cap = 256LL * per_cu[li][nvk];
+    const int grid = (int)(plan.grid_x < cap ? plan.grid_x : cap);
+    hipStream_t s = (hipStream_t)stream;
+    if (out) {
+        DISPATCH_NV(nvk, (gate_resid_ln_fwd_kernel<NV, true><<<grid, plan.block, 0, s>>>((const bf16_t*)y, gate, gate_ld, x_in, x_out, shift, scale, mod_ld, (bf16_t*)out, mean, rstd, M, T, D, eps, contract)));
+    } else {
+        DISPATCH_NV(nvk, (gate_resid_ln_fwd_kernel<NV, false><<<grid, plan.block, 0, s>>>((const bf16_t*)y, gate, gate_ld, x_in, x_out, nullptr, nullptr, 0, nullptr, nullptr, nullptr, M, T, D, eps, contract)));
+    }
+    VAW_CHECK_LAUNCH("gate_resid_ln_modulate_fwd");
     return VAW_OK;
 }
 

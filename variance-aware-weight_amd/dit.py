@@ -521,12 +521,21 @@ class DiT(FlatModule):
         ops.gemm(dt, 1, 1, M, D, self.Kp, ptr(ws.xp), self.Kp, self._w("x_embedder.proj.weight"), self.Kp, ptr(ws.xres[0]), D,
                  bias=self._p32("x_embedder.proj.bias"), rowadd=self._p32("pos_embed"), rows_per_batch=T, out_f32=True)
         mod = ptr(ws.mod)
+        mo = mod + 4 * (6 * Lyr * D)
+        # (bf16 mode, VAW_ROWS_FWD_FUSED: the row pass behind a block's fc2 also writes the LayerNorm of the NEXT consumer of the
+        # residual stream -- the next block's LN1 into that block's record, the final layer's after the last block)
+        ln_done = False
         for l in range(Lyr):
             self._need(l + 1)
-            self._block_fwd(ws, l)
-        mo = mod + 4 * (6 * Lyr * D)
+            if l + 1 < Lyr:
+                nb, mn = ws.blk[l + 1], mod + 4 * (6 * (l + 1) * D)
+                nxt = (mn, mn + 4 * D, ptr(nb["xm"]), ptr(nb["mean1"]), ptr(nb["rstd1"]))
+            else:
+                nxt = (mo, mo + 4 * D, ptr(ws.xf), ptr(ws.meanf), ptr(ws.rstdf))
+            ln_done = self._block_fwd(ws, l, ln1=not ln_done, nxt=nxt)
         self._need(Lyr + 1)
-        ops.ln_modulate_fwd(dt, ptr(ws.xres[2 * Lyr]), mo, mo + 4 * D, ld, ptr(ws.xf), ptr(ws.meanf), ptr(ws.rstdf), B, T, D)
+        if not ln_done:
+            ops.ln_modulate_fwd(dt, ptr(ws.xres[2 * Lyr]), mo, mo + 4 * D, ld, ptr(ws.xf), ptr(ws.meanf), ptr(ws.rstdf), B, T, D)
         ops.gemm(dt, 1, 1, M, self.No, D, ptr(ws.xf), D, self._w("final_layer.linear.weight"), D, ptr(ws.otok), self.No,
                  bias=self._p32("final_layer.linear.bias"), out_f32=True)
         out = torch.empty(B, self.out_channels, H, W, device=x.device, dtype=torch.float32)
@@ -535,38 +544,81 @@ class DiT(FlatModule):
             ws.calib_fwd = True
         return out
 
-    def _block_fwd(self, ws, l, xout=None):
+    def _rows_fwd_sites(self, ws, l):
+        """(proj, fc2): whether block l's gated residual add runs in the row pass with the LayerNorm behind it
+        (ops.gate_resid_ln_modulate_fwd) instead of in the GEMM's epilogue.  bf16 mode only, and only where vaw_gemm hands the
+        gated launch to the persistent kernel -- the launches whose epilogue was measured to cost more than the row pass (DESIGN
+        6.0 round 6) -- and the row pass rounds y * gate + x as that kernel does (one fma; vaw_gate_resid_fwd_contracts), so the
+        results are what they were.  Elsewhere (small batches: the 64- and 128-row kernels) the GEMM keeps its epilogue."""
+        if not (L.ROWS_FWD_FUSED and self._dt == BF16 and not ws.fp8):
+            return False, False
+        if not L.lib().vaw_gate_resid_fwd_contracts(ws.B, self.T, self.D):
+            return False, False
+        D, Dm, M, T, ld = self.D, self.Dm, ws.B * self.T, self.T, self.mod_cols
+        b, mo = ws.blk[l], ptr(ws.mod) + 4 * (6 * l * D)
+        xin, xmid, xo = ptr(ws.xres[2 * l]), ptr(ws.xres[2 * l + 1]), ptr(ws.xres[2 * l + 2])
+
+        def persistent(name, K, x, out, y, gate, resid):
+            # (asked at every call, like vaw_gemm itself: the plan follows the process's GEMM knobs and the CUs it may use)
+            p = ops.gemm_plan(BF16, 1, 1, M, D, K, ptr(x), K, self._w(name + "weight"), K, out, D, bias=self._p32(name + "bias"),
+                              aux_out=ptr(y), gate=gate, gate_ld=ld, resid=resid, rows_per_batch=T, out_f32=True, check_status=False)
+            return p.status == 0 and p.variant == L.GV_PERSISTENT and p.epi_kind == L.P8_GATE
+
+        return (persistent(f"blocks.{l}.attn.proj.", D, b["ao"], xmid, b["y1"], mo + 4 * 2 * D, xin),
+                persistent(f"blocks.{l}.mlp.fc2.", Dm, b["a"], xo, b["y2"], mo + 4 * 5 * D, xmid))
+
+    def _block_fwd(self, ws, l, xout=None, ln1=True, nxt=None):
         """Forward of block l from its input row ws.xres[2l] and the resident modulation into its record: seven launches (LN +
         modulate, qkv, attention, proj + gated residual, LN + modulate, fc1 + GELU, fc2 + gated residual).  _forward_impl runs it
         for every block; with activation recomputation _backward_impl runs it again right before the block's backward, with fc2's
-        residual output sent to the scratch row `xout` -- the kernels are deterministic, so the record is refilled bit for bit."""
+        residual output sent to the scratch row `xout` -- the kernels are deterministic, so the record is refilled bit for bit.
+        Where _rows_fwd_sites says so, still seven: proj and fc2 store their branch value only, and one row pass behind each
+        does the gated residual add and the LayerNorm that reads it -- LN2 behind proj; behind fc2 the LayerNorm of the next
+        consumer, nxt = (shift, scale, out, mean, rstd), so that the next block starts at its qkv (ln1 = False: this block's LN1
+        is already in its record).  Returns whether nxt was written.  A recomputed block (`xout`) refills its own LN1 with the
+        plain launch (the same bits), and its fc2 stops at y2: nothing reads the scratch row, and the record behind it is not its own."""
         B, dt, D, T, Dm, ld = ws.B, self._dt, self.D, self.T, self.Dm, self.mod_cols
         M = B * T
         b, pre = ws.blk[l], f"blocks.{l}."
         mo = ptr(ws.mod) + 4 * (6 * l * D)
         xin, xmid = ptr(ws.xres[2 * l]), ptr(ws.xres[2 * l + 1])
+        recompute = xout is not None
         if xout is None:
             xout = ptr(ws.xres[2 * l + 2])
+        rows_proj, rows_fc2 = self._rows_fwd_sites(ws, l)
         fuse_rows = ws.fp8 and ws.d_fwd and self.fp8_fuse_epilogue and self.fp8_fuse_rows and M % 64 == 0 and D % 128 == 0    # LN writes fp8 itself
         if fuse_rows:
             ops.ln_modulate_fwd_fp8(xin, mo, mo + 4 * D, ld, b["f_xm"], ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
-        else:
+        elif ln1 or recompute:
             ops.ln_modulate_fwd(dt, xin, mo, mo + 4 * D, ld, ptr(b["xm"]), ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
         self._linear_fwd(ws, b, "f_xm", None if fuse_rows else b["xm"], pre + "attn.qkv.", M, 3 * D, D, ptr(b["qkv"]), 3 * D)
         q = ptr(b["qkv"])
         es = self._wsize
         ops.attn_fwd(dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(b["lse"]))
-        self._linear_fwd(ws, b, "f_ao", b["ao"], pre + "attn.proj.", M, D, D, xmid, D, aux_out=ptr(b["y1"]), gate=mo + 4 * 2 * D,
-                         gate_ld=ld, resid=xin, rows_per_batch=T, out_f32=True)
-        if fuse_rows:
-            ops.ln_modulate_fwd_fp8(xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, b["f_xm2"], ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
+        if rows_proj:
+            self._linear_fwd(ws, b, "f_ao", b["ao"], pre + "attn.proj.", M, D, D, ptr(b["y1"]), D)
+            ops.gate_resid_ln_modulate_fwd(dt, ptr(b["y1"]), mo + 4 * 2 * D, ld, xin, xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld,
+                                           ptr(b["xm2"]), ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
         else:
-            ops.ln_modulate_fwd(dt, xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, ptr(b["xm2"]), ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
+            self._linear_fwd(ws, b, "f_ao", b["ao"], pre + "attn.proj.", M, D, D, xmid, D, aux_out=ptr(b["y1"]), gate=mo + 4 * 2 * D,
+                             gate_ld=ld, resid=xin, rows_per_batch=T, out_f32=True)
+            if fuse_rows:
+                ops.ln_modulate_fwd_fp8(xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, b["f_xm2"], ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
+            else:
+                ops.ln_modulate_fwd(dt, xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, ptr(b["xm2"]), ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
         fuse_a = ws.fp8 and ws.d_fwd and self.fp8_fuse_epilogue and M % 64 == 0      # fc1's epilogue writes `a` as e4m3 itself
         self._linear_fwd(ws, b, "f_xm2", None if fuse_rows else b["xm2"], pre + "mlp.fc1.", M, Dm, D, b["f_a"].epilogue_target() if fuse_a else ptr(b["a"]), Dm,
                          act=1, aux_out=ptr(b["hpre"]), **({"out_fp8": b["f_a"]} if fuse_a else {}))
+        if rows_fc2:
+            self._linear_fwd(ws, b, "f_a", b["a"], pre + "mlp.fc2.", M, D, Dm, ptr(b["y2"]), D)
+            if recompute:
+                return False
+            sh, sc, out, mean, rstd = nxt if nxt is not None else (0, 0, 0, 0, 0)
+            ops.gate_resid_ln_modulate_fwd(dt, ptr(b["y2"]), mo + 4 * 5 * D, ld, xmid, xout, sh, sc, ld, out, mean, rstd, B, T, D)
+            return nxt is not None
         self._linear_fwd(ws, b, "f_a", None if fuse_a else b["a"], pre + "mlp.fc2.", M, D, Dm, xout, D, aux_out=ptr(b["y2"]),
                          gate=mo + 4 * 5 * D, gate_ld=ld, resid=xmid, rows_per_batch=T, out_f32=True)
+        return False
 
     def _linear_fwd(self, ws, b, fkey, x, name, M, N, K, out, ldc, **epi):
         """y = x W^T + bias with the block's epilogue: bf16 / f32 MFMA GEMM, or (fp8 mode) quantise x (keeping x^T for the weight

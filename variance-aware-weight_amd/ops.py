@@ -974,6 +974,13 @@ def ln_modulate_fwd(dt, x, shift, scale, mod_ld, out, mean, rstd, B, T, D, eps=1
           "vaw_ln_modulate_fwd")
 
 
+def gate_resid_ln_modulate_fwd(dt, y, gate, gate_ld, x_in, x_out, shift, scale, mod_ld, out, mean, rstd, B, T, D, eps=1e-6):
+    """x_out = y * gate + x_in and, unless out is 0, out / mean / rstd = ln_modulate_fwd of x_out, in one launch (bf16 rows)."""
+    check(L.lib().vaw_gate_resid_ln_modulate_fwd(dt, y, gate, gate_ld, x_in, x_out, shift or None, scale or None, mod_ld, out or None,
+                                                 mean or None, rstd or None, B, T, D, eps, stream_ptr()),
+          "vaw_gate_resid_ln_modulate_fwd")
+
+
 def ln_modulate_fwd_fp8(x, shift, scale, mod_ld, f8, mean, rstd, B, T, D, eps=1e-6, pool=2):
     """ln_modulate_fwd whose output goes straight into the Fp8 `f8` (row-major bytes + running max; delayed scaling state current)."""
     q = f8.epilogue_target(pool)

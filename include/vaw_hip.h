@@ -375,6 +375,33 @@ int vaw_ksmallest_merge(const float* parts, int64_t n, int P, int k1, int64_t pa
 int vaw_pairwise_within(const float* U, int64_t nu, const float* V, int64_t nv, int D, const float* norm_u, const float* norm_v,
                         const float* radii_u, int Ku, const float* radii_v, int Kv, uint8_t* u_in, uint8_t* v_in, vaw_stream stream);
 
+/* Polynomial-kernel row sums on the same tile (kernel inception distance: the unbiased MMD^2 of Binkowski et al. 2018), float64:
+ *   rowsum[b][i] = sum_j (gamma * dot(U[u_idx[b][i]], V[v_idx[b][j]]) + coef0)^degree      b < batches, i < nu, j < nv
+ * u_idx: int32 [batches][nu], v_idx: int32 [batches][nv], rows of U and V; null = the rows 0 .. nu-1 / 0 .. nv-1 themselves in every
+ * batch.  No gathered copy is made.  The caller guarantees that every index is a row of its matrix (vaw_amd.ops checks on the host).
+ * skip_diagonal != 0 leaves out the pairs with u_idx[b][i] == v_idx[b][j] (i == j without tables): the i != j sums of the unbiased
+ * estimator without a subtraction.  dot is the f32 MFMA chain of the distances, widened to double; t = gamma * dot + coef0, the power
+ * t * t * .. * t multiplied left to right, degree in 1 .. 8, gamma and coef0 finite.
+ * Summation order, fixed by (nu, nv) alone, no atomics: the columns are cut into S <= 16 ranges of 128-column tiles; within a range
+ * a row's columns with (j mod 64) < 32 go to one float64 partial and the others to a second, each in ascending j; the 2 S partials
+ * of a row are added in ascending order.  A second launch gives the same bits, and so does a batch launched alone.
+ * ws: at least vaw_pairwise_polysum_workspace_bytes(nu, nv, batches) = batches * nu * 2 S * 8 bytes (0 for sizes that are refused). */
+int64_t vaw_pairwise_polysum_workspace_bytes(int64_t nu, int64_t nv, int batches);
+int vaw_pairwise_polysum(const float* U, int64_t nu, const float* V, int64_t nv, int D, const int32_t* u_idx, const int32_t* v_idx, int batches,
+                         double gamma, double coef0, int degree, int skip_diagonal, double* rowsum, void* ws, int64_t ws_bytes,
+                         vaw_stream stream);
+
+/* Density and coverage (Naeem et al. 2020) in one pass over d(i, j) of vaw_pairwise_within, compared strictly (d < r, the published
+ * definition; vaw_pairwise_within keeps the reference's d <= r):
+ *   u_count[i][q] += #{ j : d(i, j) < radii_v[j][q] }        u_count: int32 [nu][Kv]
+ *   v_in[j][q]     = 1 if any i has d(i, j) < radii_v[j][q]   v_in: uint8 [nv][Kv]
+ * radii_v: f32 [nv][Kv], 1 <= Kv <= 4.  The caller zeroes both outputs before the first call and may cut U and V into calls in any
+ * way: counts are integers and a flag byte only goes from 0 to 1.  ws: at least vaw_pairwise_count_workspace_bytes(nu, nv, Kv)
+ * = nu * 2 S * Kv * 4 bytes of per-range counts, which a second kernel adds into u_count. */
+int64_t vaw_pairwise_count_workspace_bytes(int64_t nu, int64_t nv, int Kv);
+int vaw_pairwise_count_within(const float* U, int64_t nu, const float* V, int64_t nv, int D, const float* norm_u, const float* norm_v,
+                              const float* radii_v, int Kv, int32_t* u_count, uint8_t* v_in, void* ws, int64_t ws_bytes, vaw_stream stream);
+
 /* np.mean(X, axis=0) and np.cov(X, rowvar=False) of Evaluator.compute_statistics :175-178 in f64 from f32 X [n][D] (widened
  * exactly).  mu[c] = (sum_i X[i][c]) / n: 16 partial sums per column, partial p = rows p, p+16, ... ascending, added p ascending.
  * sigma[a][b] = (sum_i (X[i][a] - mu[a]) * (X[i][b] - mu[b])) / (n - 1): two-pass and centred, one f64 fma chain over

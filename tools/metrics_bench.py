@@ -3,6 +3,8 @@
 
     python tools/metrics_bench.py [--sizes 10000 50000] [--out FILE.json]
     python tools/metrics_bench.py --inception-score [--sizes 10000 50000] [--out FILE.json]
+    python tools/metrics_bench.py --kid [--sizes 50000] [--out FILE.json]
+    python tools/metrics_bench.py --density-coverage [--sizes 50000] [--out FILE.json]
 
 Activations are non-negative and of low rank plus noise, like pooled ReLU features: max(z P + off + 0.01 noise, 0) with rank 64,
 generated on the device from a seed; the sample set is drawn with z scaled by 0.8 and shifted by 0.5.  Per N it reports the median
@@ -19,6 +21,13 @@ With --inception-score it times the Inception score instead (D = 2048, C = 1008,
 head product vaw_head_logits alone (device events, rate 2 N D C / t), the float64 row pass, class sums and finish alone, and
 compute_inception_score end to end (device activations in, one float out); at N = 10000 the host baseline is float32 numpy, the
 arithmetic the reference's TensorFlow graph and its numpy tail perform.
+With --kid it times the polynomial-kernel row sums (D = 2048, degree 3, gamma 1 / D, coef0 1): one launch of the full sets N x N, and
+the KID protocol shape, 100 subsets of 1000 rows of the N-row sets through two index tables in one launch, each beside
+vaw_pairwise_within at the same nu, nv, D (for the protocol shape one 1000 x 1000 launch, times the 100 subsets); then
+polynomial_mmd2 and compute_kid end to end, and at the protocol shape the host baseline, float64 numpy on gathered copies (three
+subsets, scaled to 100).  With --density-coverage it times vaw_pairwise_count_within N x N beside vaw_pairwise_within, and
+compute_density_coverage end to end (nearest_k = 5).  vaw_pairwise_within is the same kernel, instruction for instruction, as the
+one before the two entry points were added, so it stands for the parent commit.
 One JSON object is printed (and written to --out).  It needs the GPU: there is no host path to time."""
 import argparse
 import json
@@ -150,18 +159,101 @@ def inception_rows(args):
     return sizes
 
 
+def rated(times, flop):
+    s = summary(times)
+    s["tflops_f32"] = flop / s["median_s"] * 1e-12
+    s["share_of_f32_peak"] = s["tflops_f32"] / PEAK_F32_TFLOPS
+    return s
+
+
+def within_launch(u, v):
+    """One vaw_pairwise_within launch on u x v with one radius per point (the radii of the sets themselves)."""
+    est = ev.ManifoldEstimator()
+    nu, nv = ops.row_sqnorms(u), ops.row_sqnorms(v)
+    ru, rv = torch.from_numpy(est.manifold_radii(u)).cuda(), torch.from_numpy(est.manifold_radii(v)).cuda()
+    u_in = torch.zeros(len(u), 1, device="cuda", dtype=torch.uint8)
+    v_in = torch.zeros(len(v), 1, device="cuda", dtype=torch.uint8)
+    return lambda: ops.pairwise_within(u, v, nu, nv, ru, rv, u_in, v_in)
+
+
+def host_kid_subset(x, y, gamma):
+    """float64 numpy: the unbiased cubic-kernel MMD^2 of two gathered subsets."""
+    m = len(x)
+    kxx, kyy, kxy = ((gamma * (a @ b.T) + 1.0) ** 3 for a, b in ((x, x), (y, y), (x, y)))
+    return (kxx.sum() - np.trace(kxx)) / (m * (m - 1)) + (kyy.sum() - np.trace(kyy)) / (m * (m - 1)) - 2 * kxy.mean()
+
+
+def kid_rows(args):
+    d, subsets, size = 2048, 100, 1000
+    gamma = 1.0 / d
+    sizes = {}
+    for n in args.sizes:
+        reps = args.repeats if n <= 20000 else max(3, args.repeats // 2 + 1)
+        ref, sample = features(n, d, 0, False), features(n, d, 0, True)
+        row = dict(kid=ev.compute_kid(ref, sample), mmd2_full_sets=ev.polynomial_mmd2(ref, sample))
+        row["polysum_full"] = rated(device_clock(lambda: ops.pairwise_polysum(ref, sample, gamma, 1.0, 3), 1, reps), 2.0 * n * n * d)
+        row["within_full"] = rated(device_clock(within_launch(ref, sample), 1, reps), 2.0 * n * n * d)
+        row["polysum_full_over_within"] = row["polysum_full"]["median_s"] / row["within_full"]["median_s"]
+        ri, si = ev.kid_subset_indices(n, n, subsets, size, 0)
+        ri, si = torch.from_numpy(ri).cuda(), torch.from_numpy(si).cuda()
+        row["polysum_protocol"] = rated(device_clock(lambda: ops.pairwise_polysum(ref, sample, gamma, 1.0, 3, ri, si), 1, reps),
+                                        2.0 * subsets * size * size * d)
+        one = rated(device_clock(within_launch(ref[:size].contiguous(), sample[:size].contiguous()), 1, reps), 2.0 * size * size * d)
+        row["within_one_subset"] = one
+        row["polysum_protocol_over_100_within"] = row["polysum_protocol"]["median_s"] / (subsets * one["median_s"])
+        row["compute_kid"] = summary(host_clock(lambda: ev.compute_kid(ref, sample), 1, reps))
+        row["polynomial_mmd2"] = summary(host_clock(lambda: ev.polynomial_mmd2(ref, sample), 1, reps))
+        if n == args.sizes[0]:
+            xh, yh = ref.cpu().numpy(), sample.cpu().numpy()
+            rj, sj = ri.cpu().numpy(), si.cpu().numpy()
+            t0 = time.perf_counter()
+            for b in range(3):
+                host_kid_subset(xh[rj[b]].astype(np.float64), yh[sj[b]].astype(np.float64), gamma)
+            row["host_numpy_kid_s_scaled_to_100_subsets"] = (time.perf_counter() - t0) * subsets / 3
+            row["host_threads"] = torch.get_num_threads()
+        sizes[str(n)] = row
+        del ref, sample
+        torch.cuda.empty_cache()
+    return sizes
+
+
+def density_coverage_rows(args):
+    d = 2048
+    sizes = {}
+    for n in args.sizes:
+        reps = args.repeats if n <= 20000 else max(3, args.repeats // 2 + 1)
+        ref, sample = features(n, d, 0, False), features(n, d, 0, True)
+        row = dict(density_coverage=ev.compute_density_coverage(ref, sample))
+        row["compute_density_coverage"] = summary(host_clock(lambda: ev.compute_density_coverage(ref, sample), 1, reps))
+        est = ev.ManifoldEstimator(nhood_sizes=(5,))
+        radii = torch.from_numpy(est.manifold_radii(ref)).cuda()
+        n_ref, n_sample = ops.row_sqnorms(ref), ops.row_sqnorms(sample)
+        counts = torch.zeros(n, 1, device="cuda", dtype=torch.int32)
+        covered = torch.zeros(n, 1, device="cuda", dtype=torch.uint8)
+        row["count_within"] = rated(device_clock(lambda: ops.pairwise_count_within(sample, ref, n_sample, n_ref, radii, counts, covered), 1, reps),
+                                    2.0 * n * n * d)
+        row["within"] = rated(device_clock(within_launch(sample, ref), 1, reps), 2.0 * n * n * d)
+        row["count_within_over_within"] = row["count_within"]["median_s"] / row["within"]["median_s"]
+        sizes[str(n)] = row
+        del ref, sample
+        torch.cuda.empty_cache()
+    return sizes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[10000, 50000])
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--host-baseline-at", type=int, default=10000)
     ap.add_argument("--inception-score", action="store_true", help="time the Inception score instead of FID / precision / recall")
+    ap.add_argument("--kid", action="store_true", help="time the polynomial-kernel row sums and KID instead")
+    ap.add_argument("--density-coverage", action="store_true", help="time the counts under radii and density / coverage instead")
     ap.add_argument("--out")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "metrics_bench needs the GPU: the metric kernels have no host path"
     vaw_amd.lib()
     result = dict(gpu=torch.cuda.get_device_name(0), date=time.strftime("%Y-%m-%d"), peak_f32_tflops=PEAK_F32_TFLOPS, sizes={})
-    for n in ([] if args.inception_score else args.sizes):
+    for n in ([] if args.inception_score or args.kid or args.density_coverage else args.sizes):
         reps = args.repeats if n <= 20000 else max(3, args.repeats // 2 + 1)
         row = {}
         ref, sample = features(n, 2048, 0, False), features(n, 2048, 0, True)
@@ -206,6 +298,10 @@ def main():
         torch.cuda.empty_cache()
     if args.inception_score:
         result["sizes"] = inception_rows(args)
+    if args.kid:
+        result["kid"] = kid_rows(args)
+    if args.density_coverage:
+        result["density_coverage"] = density_coverage_rows(args)
     line = json.dumps(result)
     print(line)
     if args.out:

@@ -16,6 +16,7 @@ from .sampler import IntervalCFG, Sampler, sync_ema_model  # noqa: F401
 from .resample import (DeviceLossSecondMomentResampler, LossSecondMomentResampler, UniformSampler, create_named_schedule_sampler)  # noqa: F401
 from .trainer import Trainer, ema, sample_from_latent  # noqa: F401
 from .utils import get_lr_lambda, load_checkpoint, save_checkpoint, set_random_seed, warmup_cosine_lr  # noqa: F401
-from .evaluator import (Evaluator, FIDStatistics, ManifoldEstimator, compute_inception_score, compute_prec_recall,  # noqa: F401
-                        compute_statistics, inception_score_from_probs, inception_split_scores, inception_split_scores_from_probs,
-                        metrics_from_activations)
+from .evaluator import (Evaluator, FIDStatistics, ManifoldEstimator, compute_density_coverage, compute_inception_score,  # noqa: F401
+                        compute_kid, compute_prec_recall, compute_statistics, inception_score_from_probs, inception_split_scores,
+                        inception_split_scores_from_probs, kid_subset_indices, kid_subset_scores, metrics_from_activations,
+                        polynomial_mmd2)

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get("VAW_HIP_LIB") or os.path.join(_HERE, "libvaw_hip.so")
 F32, BF16, FP8, BF8 = 0, 1, 2, 3
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16}
 
-_p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 
 class Epilogue(C.Structure):
@@ -226,6 +226,8 @@ _PROTOS = {
     "vaw_pairwise_ksmallest": [_p, _l, _p, _l, _i, _p, _p, _i, _p, _p, _l, _p],
     "vaw_ksmallest_merge": [_p, _l, _i, _i, _l, _l, _p, _p],
     "vaw_pairwise_within": [_p, _l, _p, _l, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p],
+    "vaw_pairwise_polysum": [_p, _l, _p, _l, _i, _p, _p, _i, _d, _d, _i, _i, _p, _p, _l, _p],
+    "vaw_pairwise_count_within": [_p, _l, _p, _l, _i, _p, _p, _p, _i, _p, _p, _p, _l, _p],
     "vaw_col_mean_f64": [_p, _l, _i, _p, _p],
     "vaw_cov_f64": [_p, _l, _i, _p, _p, _p],
     "vaw_head_logits": [_p, _l, _i, _p, _i, _p, _l, _p],
@@ -279,6 +281,11 @@ def lib():
         if hasattr(L, "vaw_pairwise_workspace_bytes"):
             L.vaw_pairwise_workspace_bytes.argtypes = [_l, _l, _i]
             L.vaw_pairwise_workspace_bytes.restype = _l
+        if hasattr(L, "vaw_pairwise_polysum_workspace_bytes"):
+            L.vaw_pairwise_polysum_workspace_bytes.argtypes = [_l, _l, _i]
+            L.vaw_pairwise_polysum_workspace_bytes.restype = _l
+            L.vaw_pairwise_count_workspace_bytes.argtypes = [_l, _l, _i]
+            L.vaw_pairwise_count_workspace_bytes.restype = _l
         if hasattr(L, "vaw_rk_partial_count"):
             L.vaw_rk_partial_count.argtypes = [_i, _l]
             L.vaw_rk_partial_count.restype = _l
@@ -309,7 +316,8 @@ def exported_symbols():
                                    "vaw_sumsq_workspace_floats", "vaw_groupnorm_workspace_floats", "vaw_wgrad_grouped_desc_bytes",
                                    "vaw_conv3x3_wgrad_small_workspace_floats", "vaw_row_bwd_workspace_floats",
                                    "vaw_fp8_quantize_workspace_floats", "vaw_p8_set_reserved_cus", "vaw_reduce_rows_batched_desc_bytes", "vaw_fp8_quantize_batched_desc_bytes",
-                                   "vaw_gemm_default_knobs", "vaw_dropout_bits_words", "vaw_pairwise_workspace_bytes", "vaw_rk_partial_count"])
+                                   "vaw_gemm_default_knobs", "vaw_dropout_bits_words", "vaw_pairwise_workspace_bytes", "vaw_rk_partial_count",
+                                   "vaw_pairwise_polysum_workspace_bytes", "vaw_pairwise_count_workspace_bytes"])
 
 
 # VAW_STEP_FUSED (read once): 0 restores the step's unfused sequence of launches everywhere -- separate cast / column-sum

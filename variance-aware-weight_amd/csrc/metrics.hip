@@ -8,7 +8,9 @@
 // k = 0 .. D-1 in order in ONE accumulator, K is never split, the zero padding past D only appends fma(0, 0, acc) = acc.  A
 // distance therefore has the same bits whatever tile, block or launch computed it, which is what makes the results independent
 // of every chunking above.  The 128 x 128 distances never leave the CU: they are staged through LDS in two 128 x 64 halves and
-// consumed there (a sorted k-list per thread, or the radius comparisons).
+// consumed there (a sorted k-list per thread, the radius comparisons or their counts).  The polynomial-kernel row sums of the kernel
+// inception distance stage the dot products themselves and add (gamma dot + coef0)^degree per row in float64 in a fixed order;
+// their operands may be read through index tables (pw_product_of with PwGatheredRows).
 //
 // Inception score.  The head product logits = X Wt^T is the same tile (pw_product, one block per 128 x 128 output tile, the
 // accumulators stored straight to memory); the softmax, the entropies and the class marginals are float64 sums in a fixed order.
@@ -51,9 +53,37 @@ __device__ __forceinline__ void pw_stage(float* s, const float (&r)[8]) {
     for (int p = 0; p < 8; ++p) s[kk * PW_LD + rr + 16 * p] = r[p];
 }
 
-// acc[i][j] = U[row0 + 64 wm + 32 i ..][:] . V[col0 + 64 wn + 32 j ..][:]^T for the wave (wm, wn) of the 2 x 2 waves
-__device__ __forceinline__ void pw_product(const float* __restrict__ U, int64_t nu, int64_t row0, const float* __restrict__ V, int64_t nv,
-                                           int64_t col0, int D, PwShared& sh, f32x16 (&acc)[2][2]) {
+// The fetch through an index table: src[p] is the row of X that the thread's tile row rr + 16 p reads (idx[row], the row itself
+// without a table), -1 past the last row.  It is read once per tile; the fetch itself is pw_fetch with the row replaced.
+__device__ __forceinline__ void pw_source_rows(const int* __restrict__ idx, int64_t n, int64_t row0, int (&src)[8]) {
+    const int rr = threadIdx.x >> 4;
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        const int64_t row = row0 + rr + 16 * p;
+        src[p] = row < n ? (idx ? idx[row] : (int)row) : -1;
+    }
+}
+__device__ __forceinline__ void pw_fetch_rows(const float* __restrict__ X, const int (&src)[8], int D, int k0, float (&r)[8]) {
+    const int k = k0 + (threadIdx.x & 15);
+#pragma unroll
+    for (int p = 0; p < 8; ++p) r[p] = (src[p] >= 0 && k < D) ? X[src[p] * (int64_t)D + k] : 0.f;
+}
+
+// the two ways a tile operand is read: the rows row0 .. of X [n][D], or rows picked by an index table
+struct PwRows {
+    const float* __restrict__ X;
+    int64_t n, row0;
+    __device__ __forceinline__ void fetch(int D, int k0, float (&r)[8]) const { pw_fetch(X, n, D, row0, k0, r); }
+};
+struct PwGatheredRows {
+    const float* __restrict__ X;
+    int src[8];
+    __device__ __forceinline__ void fetch(int D, int k0, float (&r)[8]) const { pw_fetch_rows(X, src, D, k0, r); }
+};
+
+// acc[i][j] = A[64 wm + 32 i ..][:] . B[64 wn + 32 j ..][:]^T for the wave (wm, wn) of the 2 x 2 waves
+template <class RowsA, class RowsB>
+__device__ __forceinline__ void pw_product_of(const RowsA& A, const RowsB& B, int D, PwShared& sh, f32x16 (&acc)[2][2]) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -61,8 +91,8 @@ __device__ __forceinline__ void pw_product(const float* __restrict__ U, int64_t 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     float ra[8], rb[8];
-    pw_fetch(U, nu, D, row0, 0, ra);
-    pw_fetch(V, nv, D, col0, 0, rb);
+    A.fetch(D, 0, ra);
+    B.fetch(D, 0, rb);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wm = w >> 1, wn = w & 1, l31 = lane & 31, h = lane >> 5;
     for (int k0 = 0; k0 < D; k0 += PW_BK) {
         __syncthreads();
@@ -70,8 +100,8 @@ __device__ __forceinline__ void pw_product(const float* __restrict__ U, int64_t 
         pw_stage(sh.b, rb);
         __syncthreads();
         if (k0 + PW_BK < D) {
-            pw_fetch(U, nu, D, row0, k0 + PW_BK, ra);
-            pw_fetch(V, nv, D, col0, k0 + PW_BK, rb);
+            A.fetch(D, k0 + PW_BK, ra);
+            B.fetch(D, k0 + PW_BK, rb);
         }
 #pragma unroll
         for (int kk = 0; kk < PW_BK; kk += 2) {
@@ -84,6 +114,12 @@ __device__ __forceinline__ void pw_product(const float* __restrict__ U, int64_t 
             acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
         }
     }
+}
+
+// acc[i][j] = U[row0 + 64 wm + 32 i ..][:] . V[col0 + 64 wn + 32 j ..][:]^T
+__device__ __forceinline__ void pw_product(const float* __restrict__ U, int64_t nu, int64_t row0, const float* __restrict__ V, int64_t nv,
+                                           int64_t col0, int D, PwShared& sh, f32x16 (&acc)[2][2]) {
+    pw_product_of(PwRows{U, nu, row0}, PwRows{V, nv, col0}, D, sh, acc);
 }
 
 // The waves of column half c write d(i, j) = max((norm_u[i] - 2 dot) + norm_v[j], 0) of their 64 x 64 quarter into sh.d
@@ -104,6 +140,19 @@ __device__ __forceinline__ void pw_write_half(PwShared& sh, const f32x16 (&acc)[
                 if (row0 + row >= nu || col0 + c * 64 + col >= nv) d = INFINITY;
                 sh.d[row * PW_DLD + col] = d;
             }
+}
+
+// the same staging of the dot products themselves (the padding is a product of zeros; the reader masks it by row and column)
+__device__ __forceinline__ void pw_write_half_dots(PwShared& sh, const f32x16 (&acc)[2][2], int c) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wm = w >> 1, wn = w & 1, l31 = lane & 31, h = lane >> 5;
+    if (wn != c) return;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                sh.d[(wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * PW_DLD + j * 32 + l31] = acc[i][j][r];
 }
 
 template <int K> __device__ __forceinline__ void list_insert(float (&list)[K], float v) {
@@ -242,6 +291,140 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (row < nu)
         for (int q = 0; q < Kv; ++q)
             if (uf >> q & 1) u_in[row * Kv + q] = 1;
+}
+
+// parts[b][row][2 s + half] = sum over the columns j of split s that thread `half` of the row's pair scanned, in ascending j, of
+// (gamma (u_i . v_j) + coef0)^degree in float64: the f32 dot product widened, t = gamma dot + coef0, then t t .. t multiplied left
+// to right.  Rows and columns of batch b are read through u_idx[b] / v_idx[b] (null: the rows themselves).  A column past nv adds
+// nothing, and with skip neither does one whose source row is the row's own.  The column ids of a tile lie in sh.rv as integers.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void pw_polysum_kernel(const float* __restrict__ U, int64_t nu, const float* __restrict__ V, int64_t nv, int D,
+                                                         const int* __restrict__ u_idx, const int* __restrict__ v_idx, double gamma, double coef0,
+                                                         int degree, int skip, double* __restrict__ parts, int S, int64_t tiles_n, int64_t tiles_m) {
+    __shared__ PwShared sh;
+    int* cid = reinterpret_cast<int*>(sh.rv);
+    const int t = threadIdx.x, s = (int)(blockIdx.x % S);
+    const int64_t rt = blockIdx.x / S, b = rt / tiles_m, row0 = rt % tiles_m * PW_T;
+    const int* ui = u_idx ? u_idx + b * nu : nullptr;
+    const int* vi = v_idx ? v_idx + b * nv : nullptr;
+    PwGatheredRows ra{U, {}}, rb{V, {}};
+    pw_source_rows(ui, nu, row0, ra.src);
+    const int64_t row = row0 + (t >> 1);
+    const int rid = (skip && row < nu) ? (ui ? ui[row] : (int)row) : -2;      // -2: no column has it, the diagonal stays
+    int64_t t0, t1;
+    pw_tile_range(tiles_n, S, s, t0, t1);
+    f32x16 acc[2][2];
+    double sum = 0.0;
+    for (int64_t ct = t0; ct < t1; ++ct) {
+        const int64_t col0 = ct * PW_T;
+        __syncthreads();
+        if (t < PW_T) cid[t] = col0 + t < nv ? (vi ? vi[col0 + t] : (int)(col0 + t)) : -1;
+        pw_source_rows(vi, nv, col0, rb.src);
+        pw_product_of(ra, rb, D, sh, acc);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            if (c) __syncthreads();
+            pw_write_half_dots(sh, acc, c);
+            __syncthreads();
+            const float* drow = sh.d + (t >> 1) * PW_DLD + (t & 1) * 32;
+            const int* ids = cid + c * 64 + (t & 1) * 32;
+            for (int j = 0; j < 32; ++j) {
+                const double x = gamma * (double)drow[j] + coef0;
+                double p = x;
+                for (int q = 1; q < degree; ++q) p = p * x;
+                if (ids[j] >= 0 && ids[j] != rid) sum = sum + p;
+            }
+        }
+    }
+    if (row < nu) parts[(b * nu + row) * (2 * S) + 2 * s + (t & 1)] = sum;
+}
+
+// out[r] = parts[r][0] + parts[r][1] + ... + parts[r][P - 1], left to right
+__global__ __launch_bounds__(256) void polysum_fold_kernel(const double* __restrict__ parts, int64_t n, int P, double* __restrict__ out) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    double a = 0.0;
+    for (int p = 0; p < P; ++p) a = a + parts[r * P + p];
+    out[r] = a;
+}
+
+// One pass over d(i, j) against the radii of the columns, strictly below (pw_within_kernel takes <=):
+//   parts[row][2 s + half][q] = #{ j scanned by thread `half` of the row's pair in split s : d(row, j) < radii_v[j][q] }
+//   v_in[j][q] = 1 if any row i has d(i, j) < radii_v[j][q], the byte store of pw_within_kernel
+// Counts are integers: no order or chunking shows in them.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void pw_count_within_kernel(const float* __restrict__ U, int64_t nu, const float* __restrict__ V, int64_t nv, int D,
+                                                              const float* __restrict__ norm_u, const float* __restrict__ norm_v,
+                                                              const float* __restrict__ radii_v, int Kv, int* __restrict__ parts,
+                                                              uint8_t* __restrict__ v_in, int S, int64_t tiles_n) {
+    __shared__ PwShared sh;
+    const int t = threadIdx.x, s = (int)(blockIdx.x % S);
+    const int64_t row0 = (int64_t)(blockIdx.x / S) * PW_T;
+    if (t < PW_T) sh.nu[t] = row0 + t < nu ? norm_u[row0 + t] : 0.f;
+    int64_t t0, t1;
+    pw_tile_range(tiles_n, S, s, t0, t1);
+    f32x16 acc[2][2];
+    int cnt[PW_RMAX] = {0, 0, 0, 0};
+    for (int64_t ct = t0; ct < t1; ++ct) {
+        const int64_t col0 = ct * PW_T;
+        __syncthreads();
+        if (t < PW_T) {
+            const bool in = col0 + t < nv;
+            sh.nv[t] = in ? norm_v[col0 + t] : 0.f;
+#pragma unroll
+            for (int c = 0; c < PW_RMAX; ++c) sh.rv[t * PW_RMAX + c] = (in && c < Kv) ? radii_v[(col0 + t) * Kv + c] : -1.f;
+        }
+        pw_product(U, nu, row0, V, nv, col0, D, sh, acc);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            if (c) __syncthreads();
+            pw_write_half(sh, acc, c, row0, nu, col0, nv);
+            __syncthreads();
+            {   // this thread's row against the radii of 32 columns
+                const float* drow = sh.d + (t >> 1) * PW_DLD + (t & 1) * 32;
+                const float* rv = sh.rv + (c * 64 + (t & 1) * 32) * PW_RMAX;
+#pragma unroll 4
+                for (int j = 0; j < 32; ++j) {
+                    const float d = drow[j];
+#pragma unroll
+                    for (int q = 0; q < PW_RMAX; ++q) cnt[q] += (int)(d < rv[j * PW_RMAX + q]);
+                }
+            }
+            {   // this thread's column, with its own radii, against 32 rows
+                const int col = t & 63, r0 = (t >> 6) * 32;
+                float rq[PW_RMAX];
+#pragma unroll
+                for (int q = 0; q < PW_RMAX; ++q) rq[q] = sh.rv[(c * 64 + col) * PW_RMAX + q];
+                unsigned vf = 0;
+#pragma unroll 4
+                for (int r = r0; r < r0 + 32; ++r) {
+                    const float d = sh.d[r * PW_DLD + col];
+#pragma unroll
+                    for (int q = 0; q < PW_RMAX; ++q) vf |= (unsigned)(d < rq[q]) << q;
+                }
+                const int64_t gc = col0 + c * 64 + col;
+                if (gc < nv)
+                    for (int q = 0; q < Kv; ++q)
+                        if (vf >> q & 1) v_in[gc * Kv + q] = 1;
+            }
+        }
+    }
+    const int64_t row = row0 + (t >> 1);
+    if (row < nu) {
+        int* o = parts + (row * (2 * S) + 2 * s + (t & 1)) * (int64_t)Kv;
+#pragma unroll
+        for (int q = 0; q < PW_RMAX; ++q)
+            if (q < Kv) o[q] = cnt[q];
+    }
+}
+
+// u_count[row][q] += parts[row][0][q] + ... + parts[row][P - 1][q]: thread e owns element e = row * Kv + q
+__global__ __launch_bounds__(256) void count_fold_kernel(const int* __restrict__ parts, int64_t n, int P, int Kv, int* __restrict__ u_count) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * Kv) return;
+    const int64_t row = e / Kv;
+    const int q = (int)(e % Kv);
+    int a = 0;
+    for (int p = 0; p < P; ++p) a += parts[(row * P + p) * Kv + q];
+    u_count[e] += a;
 }
 
 // out[i] = sum_k X[i][k]^2: one wave per row, lane l adds k = l, l + 64, ... ascending into one accumulator, then the 64
@@ -518,6 +701,58 @@ int vaw_pairwise_within(const float* U, int64_t nu, const float* V, int64_t nv, 
     pw_within_kernel<<<dim3((unsigned)(tiles_m * S)), 256, 0, (hipStream_t)stream>>>(U, nu, V, nv, D, norm_u, norm_v, radii_u, Ku, radii_v, Kv,
                                                                                     u_in, v_in, S, tiles_n);
     VAW_CHECK_LAUNCH("vaw_pairwise_within");
+    return VAW_OK;
+}
+
+int64_t vaw_pairwise_polysum_workspace_bytes(int64_t nu, int64_t nv, int batches) {
+    if (nu < 1 || nv < 1 || batches < 1) return 0;
+    return (int64_t)batches * nu * 2 * pw_splits(nv) * (int64_t)sizeof(double);
+}
+
+int vaw_pairwise_polysum(const float* U, int64_t nu, const float* V, int64_t nv, int D, const int32_t* u_idx, const int32_t* v_idx, int batches,
+                         double gamma, double coef0, int degree, int skip_diagonal, double* rowsum, void* ws, int64_t ws_bytes,
+                         vaw_stream stream) {
+    if (!pw_sizes_ok("vaw_pairwise_polysum", nu, nv, D)) return VAW_ERR_INVALID;
+    const int S = pw_splits(nv);
+    const int64_t tiles_m = (nu + PW_T - 1) / PW_T, tiles_n = (nv + PW_T - 1) / PW_T;
+    VAW_CHECK_ARG(batches >= 1 && (int64_t)batches * tiles_m * S <= 0x7fffffff && ((int64_t)batches * nu + 255) / 256 <= 0x7fffffff,
+                  "vaw_pairwise_polysum: batches %d out of range for nu %lld nv %lld", batches, (long long)nu, (long long)nv);
+    VAW_CHECK_ARG(degree >= 1 && degree <= 8, "vaw_pairwise_polysum: degree %d outside 1 .. 8", degree);
+    VAW_CHECK_ARG(isfinite(gamma) && isfinite(coef0), "vaw_pairwise_polysum: gamma %g or coef0 %g is not finite", gamma, coef0);
+    VAW_CHECK_ARG(U && V && rowsum && ws, "vaw_pairwise_polysum: null pointer");
+    const int64_t need = vaw_pairwise_polysum_workspace_bytes(nu, nv, batches);
+    VAW_CHECK_ARG(ws_bytes >= need, "vaw_pairwise_polysum: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
+    double* parts = (double*)ws;
+    hipStream_t st = (hipStream_t)stream;
+    pw_polysum_kernel<<<dim3((unsigned)(batches * tiles_m * S)), 256, 0, st>>>(U, nu, V, nv, D, u_idx, v_idx, gamma, coef0, degree,
+                                                                             skip_diagonal != 0, parts, S, tiles_n, tiles_m);
+    VAW_CHECK_LAUNCH("vaw_pairwise_polysum");
+    const int64_t rows = (int64_t)batches * nu;
+    polysum_fold_kernel<<<dim3((unsigned)((rows + 255) / 256)), 256, 0, st>>>(parts, rows, 2 * S, rowsum);
+    VAW_CHECK_LAUNCH("vaw_pairwise_polysum");
+    return VAW_OK;
+}
+
+int64_t vaw_pairwise_count_workspace_bytes(int64_t nu, int64_t nv, int Kv) {
+    if (nu < 1 || nv < 1 || Kv < 1 || Kv > PW_RMAX) return 0;
+    return nu * 2 * pw_splits(nv) * Kv * (int64_t)sizeof(int32_t);
+}
+
+int vaw_pairwise_count_within(const float* U, int64_t nu, const float* V, int64_t nv, int D, const float* norm_u, const float* norm_v,
+                              const float* radii_v, int Kv, int32_t* u_count, uint8_t* v_in, void* ws, int64_t ws_bytes, vaw_stream stream) {
+    if (!pw_sizes_ok("vaw_pairwise_count_within", nu, nv, D)) return VAW_ERR_INVALID;
+    VAW_CHECK_ARG(Kv >= 1 && Kv <= PW_RMAX, "vaw_pairwise_count_within: Kv %d outside 1 .. %d", Kv, PW_RMAX);
+    VAW_CHECK_ARG(U && V && norm_u && norm_v && radii_v && u_count && v_in && ws, "vaw_pairwise_count_within: null pointer");
+    const int64_t need = vaw_pairwise_count_workspace_bytes(nu, nv, Kv);
+    VAW_CHECK_ARG(ws_bytes >= need, "vaw_pairwise_count_within: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need);
+    const int S = pw_splits(nv);
+    const int64_t tiles_m = (nu + PW_T - 1) / PW_T, tiles_n = (nv + PW_T - 1) / PW_T;
+    int* parts = (int*)ws;
+    hipStream_t st = (hipStream_t)stream;
+    pw_count_within_kernel<<<dim3((unsigned)(tiles_m * S)), 256, 0, st>>>(U, nu, V, nv, D, norm_u, norm_v, radii_v, Kv, parts, v_in, S, tiles_n);
+    VAW_CHECK_LAUNCH("vaw_pairwise_count_within");
+    count_fold_kernel<<<dim3((unsigned)((nu * Kv + 255) / 256)), 256, 0, st>>>(parts, nu, 2 * S, Kv, u_count);
+    VAW_CHECK_LAUNCH("vaw_pairwise_count_within");
     return VAW_OK;
 }
 

@@ -1,4 +1,4 @@
-"""FID statistics, Frechet distance, precision / recall and the Inception score from Inception activations: the part of the
+"""FID statistics, Frechet distance, precision / recall, the Inception score, KID and density / coverage from Inception activations: the part of the
 reference's evaluations/evaluator.py that follows `compute_activations`, with the reference's names and return types and no
 TensorFlow.
 
@@ -17,6 +17,11 @@ max((|u|^2 - 2 u.v) + |v|^2, 0) with the dot product an ordered f32 fma chain.  
 run in the third decimal.  (2) The reference reduces the Inception score in float32 numpy and computes 0 * log 0 = NaN once a
 float32 softmax underflows (a logit about 104 below its row's maximum): the whole score is then NaN.  Here the softmax and both
 sums are float64 and a term with p = 0 or a class marginal of 0 is its limit 0, so the score stays finite.
+
+Beside the reference's metrics: the kernel inception distance (`polynomial_mmd2`, `kid_subset_scores`, `compute_kid`: the unbiased
+polynomial-kernel MMD^2 of Binkowski et al. 2018, float64 row sums in a fixed order from one launch per kernel matrix, the subsets
+read through index tables) and density / coverage (`ManifoldEstimator.evaluate_dc`, `compute_density_coverage`: Naeem et al. 2020,
+counts and flags under the same radii, compared with `<` where precision / recall keep the reference's `<=`).
 
 Not built: the Inception feature extractor (`compute_activations` / `read_activations`: its weights are a download) and
 `ManifoldEstimator.evaluate` (realism scores)."""
@@ -188,6 +193,153 @@ class ManifoldEstimator:
         self.last_status = (status_1.cpu().numpy().astype(bool), status_2.cpu().numpy().astype(bool))
         return (np.mean(self.last_status[1].astype(np.float64), axis=0), np.mean(self.last_status[0].astype(np.float64), axis=0))
 
+    def evaluate_dc(self, features_real, radii_real, features_fake):
+        """(density [K], coverage [K]) as float64 (Naeem et al. 2020): density[c] is the number of pairs (fake i, real j) with
+        d(i, j) < radii_real[j, c], over nhood_sizes[c] times the number of fake points; coverage[c] the share of real points with a
+        fake point strictly inside radii_real[:, c].  Strictly below, where evaluate_pr takes <=.  The counts [M, K] and the flags
+        [N, K] stay in last_counts / last_covered."""
+        features_real, features_fake = _as_tensor(features_real, "evaluate_dc"), _as_tensor(features_fake, "evaluate_dc")
+        _same_width("evaluate_dc", features_real, features_fake)
+        r = torch.tensor(np.asarray(radii_real, dtype=np.float32))         # a copy: torch warns on read-only arrays
+        if r.dim() != 2 or tuple(r.shape) != (features_real.shape[0], self.num_nhoods):
+            raise ValueError(f"evaluate_dc: radii_real must be [{features_real.shape[0]}, {self.num_nhoods}], got {tuple(r.shape)}")
+        if min(self.nhood_sizes) < 1:
+            raise ValueError(f"evaluate_dc: density divides by the neighbourhood size, nhood_sizes {self.nhood_sizes} holds 0")
+        real, fake = _device_features(features_real, "evaluate_dc"), _device_features(features_fake, "evaluate_dc")
+        r = r.to(real.device).contiguous()
+        n_real, n_fake = _norms(real, "evaluate_dc"), _norms(fake, "evaluate_dc")
+        counts = torch.zeros(fake.shape[0], r.shape[1], device=real.device, dtype=torch.int32)
+        covered = torch.zeros(real.shape[0], r.shape[1], device=real.device, dtype=torch.uint8)
+        for b1 in range(0, fake.shape[0], self.row_batch_size):
+            e1 = min(b1 + self.row_batch_size, fake.shape[0])
+            for b2 in range(0, real.shape[0], self.col_batch_size):
+                e2 = min(b2 + self.col_batch_size, real.shape[0])
+                ops.pairwise_count_within(fake[b1:e1], real[b2:e2], n_fake[b1:e1], n_real[b2:e2], r[b2:e2], counts[b1:e1], covered[b2:e2])
+        self.last_counts, self.last_covered = counts.cpu().numpy(), covered.cpu().numpy().astype(bool)
+        density = self.last_counts.sum(0, dtype=np.int64) / (np.asarray(self.nhood_sizes, np.float64) * fake.shape[0])
+        return (density, np.mean(self.last_covered.astype(np.float64), axis=0))
+
+
+def _dc_args(what, activations_ref, activations_sample, nearest_k):
+    """The argument checks of compute_density_coverage, made before anything is uploaded."""
+    ref, sample = _as_tensor(activations_ref, what), _as_tensor(activations_sample, what)
+    _same_width(what, ref, sample)
+    if isinstance(nearest_k, bool) or int(nearest_k) != nearest_k or not 1 <= nearest_k < ops.KSMALLEST_MAX:
+        raise ValueError(f"{what}: nearest_k must be an integer in 1 .. {ops.KSMALLEST_MAX - 1}, got {nearest_k}")
+    if ref.shape[0] <= nearest_k:
+        raise ValueError(f"{what}: N = {ref.shape[0]} reference points, more than nearest_k = {nearest_k} are needed")
+    return ref, sample, int(nearest_k)
+
+
+def compute_density_coverage(activations_ref, activations_sample, nearest_k=5, manifold_estimator=None):
+    """(density, coverage) of the sample set against the reference set (Naeem et al. 2020) with the radii of the reference set's
+    nearest_k-th neighbours, itself counted as the 0-th.  A given estimator lends its batch sizes and clamping; the neighbourhood
+    size is nearest_k."""
+    ref, sample, nearest_k = _dc_args("compute_density_coverage", activations_ref, activations_sample, nearest_k)
+    src = manifold_estimator or ManifoldEstimator()
+    est = ManifoldEstimator(src.row_batch_size, src.col_batch_size, (nearest_k,), src.clamp_to_percentile, src.eps)
+    ref, sample = _device_features(ref, "compute_density_coverage"), _device_features(sample, "compute_density_coverage")
+    density, coverage = est.evaluate_dc(ref, est.manifold_radii(ref), sample)
+    return (float(density[0]), float(coverage[0]))
+
+
+KID_WORKSPACE_BYTES = 64 << 20    # most partial-sum workspace of one pairwise_polysum launch: caps the subsets per launch
+POLYSUM_MAX_ROWS = 65536          # rows of a full set per pairwise_polysum launch
+
+
+def _kernel_args(what, width, degree, gamma, coef0):
+    if isinstance(degree, bool) or int(degree) != degree or not 1 <= degree <= ops.POLYSUM_MAX_DEGREE:
+        raise ValueError(f"{what}: degree must be an integer in 1 .. {ops.POLYSUM_MAX_DEGREE}, got {degree}")
+    gamma = 1.0 / width if gamma is None else float(gamma)
+    if not (np.isfinite(gamma) and np.isfinite(coef0)):
+        raise ValueError(f"{what}: gamma = {gamma} and coef0 = {coef0} must be finite")
+    return int(degree), gamma, float(coef0)
+
+
+def _ordered_sum(a, axis=-1):
+    """The float64 sum along an axis, added strictly in index order (np.sum adds pairwise)."""
+    return np.take(np.cumsum(a, axis=axis, dtype=np.float64), -1, axis=axis)
+
+
+def _mmd2(sxx, syy, sxy, m, n):
+    return sxx / (m * (m - 1)) + syy / (n * (n - 1)) - 2 * sxy / (m * n)
+
+
+def polynomial_mmd2(x, y, degree=3, gamma=None, coef0=1.0):
+    """The unbiased MMD^2 of the kernel k(a, b) = (gamma a.b + coef0)^degree between the full sets x [m, D] and y [n, D]:
+    sum_{i != j} k(x_i, x_j) / (m (m - 1)) + sum_{i != j} k(y_i, y_j) / (n (n - 1)) - 2 sum_{i, j} k(x_i, y_j) / (m n).  gamma None is
+    1 / D.  The sets are cut into launches along the rows only, so a row's sum keeps its order; the three totals are the float64 row
+    sums added in row order on the host."""
+    what = "polynomial_mmd2"
+    x, y = _as_tensor(x, what), _as_tensor(y, what)
+    _same_width(what, x, y)
+    degree, gamma, coef0 = _kernel_args(what, x.shape[1], degree, gamma, coef0)
+    if min(x.shape[0], y.shape[0]) < 2:
+        raise ValueError(f"{what}: {x.shape[0]} and {y.shape[0]} points, at least 2 are needed in each set")
+    x, y = _device_features(x, what), _device_features(y, what)
+    _norms(x, what), _norms(y, what)
+
+    def total(u, v, skip):
+        sums = []
+        for r0 in range(0, u.shape[0], POLYSUM_MAX_ROWS):
+            r1 = min(r0 + POLYSUM_MAX_ROWS, u.shape[0])
+            rows = torch.arange(r0, r1, dtype=torch.int32, device=u.device)[None] if skip and (r0 or r1 < u.shape[0]) else None
+            sums.append(ops.pairwise_polysum(u if rows is not None else u[r0:r1], v, gamma, coef0, degree, u_idx=rows, skip_diagonal=skip)[0])
+        return float(_ordered_sum(torch.cat(sums).cpu().numpy()))
+
+    return float(_mmd2(total(x, x, True), total(y, y, True), total(x, y, False), x.shape[0], y.shape[0]))
+
+
+def _kid_args(what, activations_ref, activations_sample, num_subsets=100, subset_size=1000, degree=3, gamma=None, coef0=1.0, seed=0):
+    """The argument checks of kid_subset_scores, made before anything is uploaded."""
+    ref, sample = _as_tensor(activations_ref, what), _as_tensor(activations_sample, what)
+    _same_width(what, ref, sample)
+    degree, gamma, coef0 = _kernel_args(what, ref.shape[1], degree, gamma, coef0)
+    if isinstance(num_subsets, bool) or int(num_subsets) != num_subsets or num_subsets < 1:
+        raise ValueError(f"{what}: num_subsets must be a positive integer, got {num_subsets}")
+    if isinstance(subset_size, bool) or int(subset_size) != subset_size or not 2 <= subset_size <= min(ref.shape[0], sample.shape[0]):
+        raise ValueError(f"{what}: subset_size = {subset_size} outside 2 .. min(N) = {min(ref.shape[0], sample.shape[0])}")
+    np.random.RandomState(seed)          # refuses a seed numpy cannot take
+    return ref, sample, int(num_subsets), int(subset_size), degree, gamma, coef0
+
+
+def kid_subset_indices(n_ref, n_sample, num_subsets=100, subset_size=1000, seed=0):
+    """(ref_idx, sample_idx), int32 [num_subsets, subset_size]: rng = np.random.RandomState(seed), and per subset first
+    rng.choice(n_ref, subset_size, replace=False), then rng.choice(n_sample, subset_size, replace=False)."""
+    rng = np.random.RandomState(seed)
+    ref_idx = np.empty((num_subsets, subset_size), np.int32)
+    sample_idx = np.empty((num_subsets, subset_size), np.int32)
+    for s in range(num_subsets):
+        ref_idx[s] = rng.choice(n_ref, subset_size, replace=False)
+        sample_idx[s] = rng.choice(n_sample, subset_size, replace=False)
+    return ref_idx, sample_idx
+
+
+def kid_subset_scores(activations_ref, activations_sample, num_subsets=100, subset_size=1000, degree=3, gamma=None, coef0=1.0, seed=0):
+    """float64 [num_subsets]: the unbiased polynomial-kernel MMD^2 between a random subset of subset_size reference activations and
+    one of subset_size sample activations, drawn as kid_subset_indices draws them.  All subsets go to the device as two index tables;
+    a batch of subsets is three pairwise_polysum launches and no activation is copied."""
+    what = "kid_subset_scores"
+    ref, sample, num_subsets, m, degree, gamma, coef0 = _kid_args(what, activations_ref, activations_sample, num_subsets, subset_size, degree,
+                                                                  gamma, coef0, seed)
+    ref_idx, sample_idx = kid_subset_indices(ref.shape[0], sample.shape[0], num_subsets, m, seed)
+    ref, sample = _device_features(ref, what), _device_features(sample, what)
+    _norms(ref, what), _norms(sample, what)
+    per_launch = max(1, KID_WORKSPACE_BYTES // (m * 2 * 16 * 8))        # a row has at most 2 * 16 float64 partial sums
+    scores = np.empty(num_subsets, np.float64)
+    for b0 in range(0, num_subsets, per_launch):
+        ri, si = ref_idx[b0:b0 + per_launch], sample_idx[b0:b0 + per_launch]
+        sxx, syy, sxy = (_ordered_sum(ops.pairwise_polysum(u, v, gamma, coef0, degree, ui, vi, skip).cpu().numpy())
+                         for u, v, ui, vi, skip in ((ref, ref, ri, ri, True), (sample, sample, si, si, True), (ref, sample, ri, si, False)))
+        scores[b0:b0 + per_launch] = _mmd2(sxx, syy, sxy, m, m)
+    return scores
+
+
+def compute_kid(activations_ref, activations_sample, num_subsets=100, subset_size=1000, degree=3, gamma=None, coef0=1.0, seed=0):
+    """(mean, std): the kernel inception distance of Binkowski et al. 2018 as the numpy mean and std (ddof 0) of kid_subset_scores."""
+    scores = kid_subset_scores(activations_ref, activations_sample, num_subsets, subset_size, degree, gamma, coef0, seed)
+    return (float(np.mean(scores)), float(np.std(scores)))
+
 
 def compute_prec_recall(activations_ref, activations_sample, manifold_estimator=None):
     """(precision, recall) of the sample set against the reference set, neighbourhood size nhood_sizes[0]."""
@@ -348,11 +500,20 @@ class Evaluator:
     def compute_prec_recall(self, activations_ref, activations_sample):
         return compute_prec_recall(activations_ref, activations_sample, self.manifold_estimator)
 
+    def compute_kid(self, activations_ref, activations_sample, **kwargs):
+        return compute_kid(activations_ref, activations_sample, **kwargs)
 
-def metrics_from_activations(ref_acts, sample_acts, ref_stats=None, ref_stats_spatial=None, softmax_weight=None, split_size=5000):
+    def compute_density_coverage(self, activations_ref, activations_sample, nearest_k=5):
+        return compute_density_coverage(activations_ref, activations_sample, nearest_k, self.manifold_estimator)
+
+
+def metrics_from_activations(ref_acts, sample_acts, ref_stats=None, ref_stats_spatial=None, softmax_weight=None, split_size=5000,
+                             kid=None, density_coverage=None):
     """What calculate_metrics does after compute_activations: ref_acts / sample_acts are (pool [N, 2048], spatial [N, 2023])
     tuples; reference statistics that are given are used instead of being recomputed.  Returns dict(fid, sfid, precision, recall),
-    and with a softmax_weight also inception_score, of the sample pool activations."""
+    and with a softmax_weight also inception_score, of the sample pool activations.  kid=True or a dict of compute_kid keywords adds
+    kid and kid_std, density_coverage=True (nearest_k = 5) or an integer nearest_k adds density and coverage, all of the pool
+    activations."""
     for name, acts in (("ref_acts", ref_acts), ("sample_acts", sample_acts)):
         if not isinstance(acts, (tuple, list)) or len(acts) != 2:
             raise ValueError(f"metrics_from_activations: {name} must be a (pool, spatial) pair")
@@ -366,6 +527,16 @@ def metrics_from_activations(ref_acts, sample_acts, ref_stats=None, ref_stats_sp
         if head.width != shapes[1][0].shape[1]:
             raise ValueError(f"{what}: pool activations are {shapes[1][0].shape[1]} wide, softmax_weight is [{head.width}, {head.classes}]")
         _split_size(what, split_size)
+    if kid is not None:
+        if kid is not True and not isinstance(kid, dict):
+            raise ValueError(f"{what}: kid must be True or a dict of compute_kid keywords, got {type(kid).__name__}")
+        kid = {} if kid is True else dict(kid)
+        try:
+            _kid_args(what, shapes[0][0], shapes[1][0], **kid)
+        except TypeError as e:
+            raise ValueError(f"{what}: kid holds a keyword compute_kid does not take ({e})") from None
+    if density_coverage is not None:
+        density_coverage = _dc_args(what, shapes[0][0], shapes[1][0], 5 if density_coverage is True else density_coverage)[2]
     ref_pool = _device_features(ref_acts[0], "metrics_from_activations")
     sample_pool = _device_features(sample_acts[0], "metrics_from_activations")
     ref_stats = ref_stats if ref_stats is not None else compute_statistics(ref_pool)
@@ -376,4 +547,8 @@ def metrics_from_activations(ref_acts, sample_acts, ref_stats=None, ref_stats_sp
                precision=prec, recall=recall)
     if head is not None:
         out["inception_score"] = compute_inception_score(sample_pool, head, split_size)
+    if kid is not None:
+        out["kid"], out["kid_std"] = compute_kid(ref_pool, sample_pool, **kid)
+    if density_coverage is not None:
+        out["density"], out["coverage"] = compute_density_coverage(ref_pool, sample_pool, density_coverage)
     return out

@@ -1,7 +1,9 @@
 """Tensor-level wrappers over the C ABI (include/vaw_hip.h).  Each takes torch CUDA tensors, checks what the
 kernel assumes about them (shape, dtype, contiguity) on the host, and launches on the current stream."""
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1308,6 +1310,75 @@ def pairwise_within(u, v, norm_u, norm_v, radii_u, radii_v, u_in, v_in):
     _per_row("pairwise_within", "v_in", v_in, nv, Ku, torch.uint8)
     check(L.lib().vaw_pairwise_within(ptr(u), nu, ptr(v), nv, u.shape[1], ptr(norm_u), ptr(norm_v), ptr(radii_u), Ku, ptr(radii_v), Kv,
                                       ptr(u_in), ptr(v_in), stream_ptr()), "vaw_pairwise_within")
+
+
+POLYSUM_MAX_DEGREE = 8  # largest degree of pairwise_polysum
+
+
+def _index_table(what, name, idx, rows, device):
+    """An index table as contiguous int32 [batches, n] on the device.  The values are checked on the host before the upload: the
+    kernel reads the rows they name without a check of its own."""
+    if isinstance(idx, torch.Tensor):
+        if idx.dtype not in (torch.int32, torch.int64) or idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+            raise ValueError(f"{what}: {name} must be a non-empty int32 / int64 [batches, n] table, got {idx.dtype} {tuple(idx.shape)}")
+        lo, hi = int(idx.min()), int(idx.max())
+    else:
+        idx = np.asarray(idx)
+        if idx.dtype.kind not in "iu" or idx.ndim != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+            raise ValueError(f"{what}: {name} must be a non-empty integer [batches, n] table, got {idx.dtype} {idx.shape}")
+        lo, hi = int(idx.min()), int(idx.max())
+        idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32 if hi < 2 ** 31 else np.int64))
+    if lo < 0 or hi >= rows:
+        raise ValueError(f"{what}: {name} holds values {lo} .. {hi} outside the rows 0 .. {rows - 1}")
+    return idx.to(device=device, dtype=torch.int32).contiguous()
+
+
+def pairwise_polysum(u, v, gamma, coef0, degree, u_idx=None, v_idx=None, skip_diagonal=False):
+    """float64 [batches, nu]: out[b][i] = sum_j (gamma * u[u_idx[b][i]] . v[v_idx[b][j]] + coef0)^degree in a fixed order, the dot
+    product the f32 MFMA chain of the distances.  u_idx [batches, nu] / v_idx [batches, nv] pick rows of u / v (None: all rows, in
+    order, for every batch).  skip_diagonal leaves out the pairs whose two indices are equal."""
+    _features("pairwise_polysum", u, v)
+    if isinstance(degree, bool) or int(degree) != degree or not 1 <= degree <= POLYSUM_MAX_DEGREE:
+        raise ValueError(f"pairwise_polysum: degree must be an integer in 1 .. {POLYSUM_MAX_DEGREE}, got {degree}")
+    gamma, coef0 = float(gamma), float(coef0)
+    if not (math.isfinite(gamma) and math.isfinite(coef0)):
+        raise ValueError(f"pairwise_polysum: gamma = {gamma} and coef0 = {coef0} must be finite")
+    if u_idx is not None:
+        u_idx = _index_table("pairwise_polysum", "u_idx", u_idx, u.shape[0], u.device)
+    if v_idx is not None:
+        v_idx = _index_table("pairwise_polysum", "v_idx", v_idx, v.shape[0], u.device)
+    tables = [t for t in (u_idx, v_idx) if t is not None]
+    batches = tables[0].shape[0] if tables else 1
+    if any(t.shape[0] != batches for t in tables):
+        raise ValueError(f"pairwise_polysum: u_idx and v_idx hold {u_idx.shape[0]} and {v_idx.shape[0]} batches")
+    nu = u.shape[0] if u_idx is None else u_idx.shape[1]
+    nv = v.shape[0] if v_idx is None else v_idx.shape[1]
+    nbytes = L.lib().vaw_pairwise_polysum_workspace_bytes(nu, nv, batches)
+    ws = torch.empty(nbytes // 8, device=u.device, dtype=torch.float64)
+    out = torch.empty(batches, nu, device=u.device, dtype=torch.float64)
+    check(L.lib().vaw_pairwise_polysum(ptr(u), nu, ptr(v), nv, u.shape[1], ptr(u_idx), ptr(v_idx), batches, gamma, coef0, int(degree),
+                                       int(bool(skip_diagonal)), ptr(out), ptr(ws), nbytes, stream_ptr()), "vaw_pairwise_polysum")
+    return out
+
+
+def pairwise_count_within(u, v, norm_u, norm_v, radii_v, u_count, v_in):
+    """u_count[i][c] += #{ j : d(i, j) < radii_v[j][c] } (int32) and v_in[j][c] |= any_i d(i, j) < radii_v[j][c] (uint8), strictly
+    below where pairwise_within takes <=; both zeroed by the caller before the first call."""
+    _features("pairwise_count_within", u, v)
+    nu, nv = u.shape[0], v.shape[0]
+    need_cuda(radii_v)
+    if radii_v.dim() != 2 or not 1 <= radii_v.shape[1] <= WITHIN_MAX_RADII:
+        raise ValueError(f"pairwise_count_within: radii_v must be [N, 1 .. {WITHIN_MAX_RADII}], got {tuple(radii_v.shape)}")
+    Kv = radii_v.shape[1]
+    _per_row("pairwise_count_within", "norm_u", norm_u, nu)
+    _per_row("pairwise_count_within", "norm_v", norm_v, nv)
+    _per_row("pairwise_count_within", "radii_v", radii_v, nv, Kv)
+    _per_row("pairwise_count_within", "u_count", u_count, nu, Kv, torch.int32)
+    _per_row("pairwise_count_within", "v_in", v_in, nv, Kv, torch.uint8)
+    nbytes = L.lib().vaw_pairwise_count_workspace_bytes(nu, nv, Kv)
+    ws = torch.empty(nbytes // 4, device=u.device, dtype=torch.int32)
+    check(L.lib().vaw_pairwise_count_within(ptr(u), nu, ptr(v), nv, u.shape[1], ptr(norm_u), ptr(norm_v), ptr(radii_v), Kv, ptr(u_count),
+                                            ptr(v_in), ptr(ws), nbytes, stream_ptr()), "vaw_pairwise_count_within")
 
 
 def col_mean_f64(x):

@@ -509,6 +509,11 @@ typedef struct {
 int64_t vaw_wgrad_grouped_desc_bytes(int n_problems);
 int vaw_wgrad_grouped(vaw_dtype dt, int n_problems, const vaw_wgrad_problem* problems, int64_t K, float beta, void* desc_dev,
                       int upload, float* workspace, int64_t workspace_floats, vaw_stream stream);
+/* Engine of the bf16 launches of vaw_wgrad_grouped whose tiles are 256 columns wide (every group but the all-N-%-192 ones), process-wide:
+ * -1 by shape (the default; VAW_WGRAD_ENGINE, read once on first use, sets another), 0 the 8-wave persistent kernel, 1 the 4-wave
+ * kernel (one wave per SIMD, 128 x 128 wave tiles).  The two give bitwise equal results; fp8 and 192-column groups always run the
+ * 8-wave kernel.  For measurement and tests. */
+void vaw_debug_wgrad_engine(int mode);
 
 /* fp8 operands (OCP e4m3fn, per-tensor scaling) for the Linear GEMMs: BASELINE.json config 5 "DiT-XL/2, fp8 MFMA GEMMs + bf16
  * accum" (model: models/dit.py:373, recipe run.sh:20-26; the reference itself trains that model in bf16 autocast).

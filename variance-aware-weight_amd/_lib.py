@@ -305,6 +305,9 @@ def lib():
             L.vaw_debug_gn_flat.restype = None
         L.vaw_p8_set_reserved_cus.argtypes = [_i]
         L.vaw_p8_set_reserved_cus.restype = None
+        if hasattr(L, "vaw_debug_wgrad_engine"):      # absent from older measurement builds loaded through VAW_HIP_LIB
+            L.vaw_debug_wgrad_engine.argtypes = [_i]
+            L.vaw_debug_wgrad_engine.restype = None
         L.vaw_debug_cu_hog.argtypes = [_i, _i, _p]
         L.vaw_debug_cu_hog.restype = _i
         _lib = L
@@ -315,7 +318,7 @@ def exported_symbols():
     return sorted(list(_PROTOS) + ["vaw_version", "vaw_last_error_string", "vaw_colsum_workspace_floats",
                                    "vaw_sumsq_workspace_floats", "vaw_groupnorm_workspace_floats", "vaw_wgrad_grouped_desc_bytes",
                                    "vaw_conv3x3_wgrad_small_workspace_floats", "vaw_row_bwd_workspace_floats",
-                                   "vaw_fp8_quantize_workspace_floats", "vaw_p8_set_reserved_cus", "vaw_reduce_rows_batched_desc_bytes", "vaw_fp8_quantize_batched_desc_bytes",
+                                   "vaw_fp8_quantize_workspace_floats", "vaw_p8_set_reserved_cus", "vaw_debug_wgrad_engine", "vaw_reduce_rows_batched_desc_bytes", "vaw_fp8_quantize_batched_desc_bytes",
                                    "vaw_gemm_default_knobs", "vaw_dropout_bits_words", "vaw_pairwise_workspace_bytes", "vaw_rk_partial_count",
                                    "vaw_pairwise_polysum_workspace_bytes", "vaw_pairwise_count_workspace_bytes"])
 

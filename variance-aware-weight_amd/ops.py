@@ -826,6 +826,12 @@ class WgradGroup:
                         float(sum(es * (p.M + p.N) * self.K + 4 * p.M * p.N * (2 if beta else 1) for p in self.table)))
 
 
+def wgrad_engine(mode):
+    """Engine of the bf16 256-column launches of vaw_wgrad_grouped from now on (vaw_debug_wgrad_engine): -1 by shape, 0 the 8-wave
+    kernel, 1 the 4-wave kernel.  Both give the same bits; for tests and A/B measurements."""
+    L.lib().vaw_debug_wgrad_engine(int(mode))
+
+
 def beta_or_plain(bias, act, aux_out, gate, resid, rowadd):
     """True when the epilogue is alpha/beta only: the launches that may run split-K."""
     return not (bias or act or aux_out or gate or resid or rowadd)

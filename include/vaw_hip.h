@@ -28,7 +28,8 @@ extern "C" {
 
 typedef enum { VAW_OK = 0, VAW_ERR_INVALID = -1, VAW_ERR_LAUNCH = -2, VAW_ERR_UNSUPPORTED = -3 } vaw_status;
 typedef enum { VAW_F32 = 0, VAW_BF16 = 1,
-               VAW_FP8 = 2, VAW_BF8 = 3 /* OCP e4m3fn / e5m2: GEMM operand formats of vaw_gemm_fp8 and vaw_wgrad_grouped only */ } vaw_dtype;
+               VAW_FP8 = 2, VAW_BF8 = 3 /* OCP e4m3fn / e5m2: GEMM operand formats of vaw_gemm_fp8 and vaw_wgrad_grouped only */,
+               VAW_F64 = 4 /* output type of vaw_randn_seeded only */ } vaw_dtype;
 typedef void* vaw_stream;
 
 int vaw_version(void);
@@ -238,6 +239,32 @@ int vaw_dpm_step(int pred_type, int clip, const float* cond, const float* uncond
                  const double* x, const float* d1, const float* d2, const double* noise, const double* coef, int row, int rows,
                  double* x_out, float* d0_out, float* model_in, float* model_in_dup, int B, int64_t per_sample,
                  vaw_stream stream);
+
+/* ---------------------------------------------------------------------------
+ * Per-sample seeded noise for the samplers  (the role of StackedRandomGenerator in EDM's generate.py: one stream per sample
+ * seed).  Counter-based, so row b of a draw is a pure function of (seeds[b], draw, tag, element) and of nothing else: not of
+ * B, of the other rows, of the grid, of the stream, or of what was drawn before.
+ * ------------------------------------------------------------------------- */
+#define VAW_NOISE_BITS 0     /* the raw 32-bit words */
+#define VAW_NOISE_UNIFORM 1  /* float32 u = fmaf((float)r, 2^-32, 2^-33): in (0, 1], the float32 of r then one rounding */
+#define VAW_NOISE_NORMAL 2   /* Box-Muller in float32 (logf, sincospif, IEEE sqrt and products; no fast forms):
+                              * (r0, r1) -> sqrt(-2 log u0) * (cos, sin)(2 pi u1), (r2, r3) -> the other two */
+#define VAW_NOISE_TAG_NOISE 0
+#define VAW_NOISE_TAG_LABELS 1
+
+/* out: [B, per_sample] contiguous; seeds: device int64 [B].  Elements 4c .. 4c+3 of row b are the four words of
+ * Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) under the key
+ * (low 32 bits, high 32 bits) of seeds[b] read as an unsigned 64-bit pattern, at the counter (c, draw, tag, 0).  So a row of 5
+ * elements is the first 5 of a row of 8.  dtype: VAW_F32 for modes 0 and 1 (any 4-byte element); VAW_F32, VAW_BF16 (the
+ * round-to-nearest-even of the float32 value) or VAW_F64 (its exact widening) for mode 2.  One lane makes one block and stores
+ * it whole (16 bytes; 8 for bf16; two 16-byte halves for float64) where the row starts on such a boundary and the block lies
+ * inside the row, element by element otherwise; nothing outside out[0 .. B*per_sample) is written.  No atomics and no device
+ * state: `draw` is a kernel argument, so a captured launch replays the same draw number on whatever seeds are in memory then.
+ * Refused before any launch (VAW_ERR_INVALID): a null pointer, B < 1, per_sample < 1, per_sample >= 2^34 (the block counter is
+ * 32 bits), draw outside [0, 2^32), tag < 0, an unknown mode or dtype, mode 0 / 1 with a dtype that is not 4 bytes wide, a
+ * pointer not aligned to its element. */
+int vaw_randn_seeded(void* out, int dtype, const int64_t* seeds, int B, int64_t per_sample, int64_t draw, int tag, int mode,
+                     vaw_stream stream);
 
 /* ---------------------------------------------------------------------------
  * Adaptive explicit Runge-Kutta steps of the flow ODE  (flow_ode_sample(solver="rk45"): Dormand-Prince 5(4), the step

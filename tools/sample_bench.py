@@ -20,6 +20,12 @@ With `--solver heun|euler` (EDM sampler), `--solver dpmpp2m|dpmpp2m_sde|expab` (
      `--tree DIR` imports the package from another checkout (built in place), e.g. the parent commit's, which knows
      neither `fused` nor `hip_graph`: pass neither there.
 
+With `--seeded` beside them the run is
+ (i) the same Sampler.sample four times over, twice (the second round is reported): noise from the torch generator and from
+     SeededNoise (args.sample_seed), each eager and as a captured graph (args.hip_graph): median / min ms per batch of each;
+     then the draw alone on `--batch` x C x S x S, float32 and float64: `normal_()` of the torch generator against
+     ops.randn_seeded in us, device events over `--iters` calls on rotating destinations.
+
 With `--solver rk45` the run is
  (f) flow_ode_sample(solver="rk45") over a stand-in network (0.6 tanh(2x) + 0.5 sin(12 t) + 0.02 y: three tensor operations, so
      the time is the solver's own) on `--batch` x 4 x S x S noise (S = `--image-size` or 32), linear path, VELOCITY,
@@ -126,26 +132,18 @@ def build_model(a, learn_sigma=True):
     return model, C, H
 
 
-def solver_bench(a):
-    """(e): per-batch time of Sampler.sample through the EDM / flow solvers."""
-    import functools
+def solver_run(a, model, C, H, graph, seeded):
+    """Sorted per-batch times in ms of one Sampler.sample of `--batches` batches, the first `--skip` left out."""
     flow = a.mode == "flow"
-    solver = a.solver or "heun"
-    torch.manual_seed(0)
-    model, C, H = build_model(a, learn_sigma=not flow)
     args = SimpleNamespace(weight_type="lambda", gamma=0.0, learn_sigma=not flow, p2_gamma=1, p2_k=1, time_dist=["uniform"], cpu_rng=False,
                            in_chans=3 if C == 3 else 4, class_cond=True, parallel=False, class_labels=None, amp=False, latent_scale=0.18215,
-                           guidance_scale=a.guidance, interval=(-1.0, -1.0), model_mode="flow" if flow else "diffusion", solver=solver,
+                           guidance_scale=a.guidance, interval=(-1.0, -1.0), model_mode="flow" if flow else "diffusion", solver=a.solver or "heun",
                            sample_steps=a.steps, discretization="edm", schedule="linear", scaling="none", path_type="linear" if flow else "cosine",
                            mean_type="VELOCITY" if flow else "EPSILON", sampler_type="sde")
-    if a.graph:
+    if graph:
         args.hip_graph = True
-    if a.fused is not None:
-        import vaw_amd.sampler as sm
-        for name in ("edm_sample", "dpm_sample", "flow_sde_sample", "flow_ode_sample"):
-            if not hasattr(sm, name):          # an older --tree
-                continue
-            setattr(sm, name, functools.partial(getattr(sm, name), fused=bool(a.fused)))
+    if seeded:
+        args.sample_seed = 1234
     diff = vaw_amd.FlowMatching(args=args, model_mean_type=vaw_amd.ModelMeanType.VELOCITY) if flow else None
     s = vaw_amd.Sampler(args, torch.device("cuda"), model, diff, **(dict(decode_fn=(lambda z: z[:, :3])) if C == 4 else {}))
     stamps, gather = [], s._gather_samples
@@ -157,12 +155,49 @@ def solver_bench(a):
     torch.cuda.synchronize()
     stamps.append(time.perf_counter())
     s.sample(a.batch * a.batches, a.batch, H, a.num_classes)
-    ms = sorted(1e3 * (t1 - t0) for t0, t1 in zip(stamps[a.skip:-1], stamps[a.skip + 1:]))
+    return sorted(1e3 * (t1 - t0) for t0, t1 in zip(stamps[a.skip:-1], stamps[a.skip + 1:]))
+
+
+def solver_bench(a):
+    """(e): per-batch time of Sampler.sample through the EDM / flow solvers; (i) with --seeded."""
+    import functools
+    flow = a.mode == "flow"
+    solver = a.solver or "heun"
+    torch.manual_seed(0)
+    model, C, H = build_model(a, learn_sigma=not flow)
+    if a.fused is not None:
+        import vaw_amd.sampler as sm
+        for name in ("edm_sample", "dpm_sample", "flow_sde_sample", "flow_ode_sample"):
+            if not hasattr(sm, name):          # an older --tree
+                continue
+            setattr(sm, name, functools.partial(getattr(sm, name), fused=bool(a.fused)))
     evals = (2 * a.steps - 1 if solver == "heun" else a.steps)          # euler and the multistep solvers: one per step
-    print(json.dumps({"part": "e", "model": a.model, "dtype": "fp32" if a.fp32 else "bf16", "mode": a.mode, "solver": solver, "steps": a.steps,
-                      "batch": a.batch, "guidance": a.guidance, "fused": a.fused, "graph": bool(a.graph), "tree": a.tree or ".",
-                      "evaluations_per_batch": evals, "batches_timed": len(ms), "ms_per_batch_median": ms[len(ms) // 2],
-                      "ms_per_batch_min": ms[0], "ms_per_batch_max": ms[-1]}))
+    res = {"part": "i" if a.seeded else "e", "model": a.model, "dtype": "fp32" if a.fp32 else "bf16", "mode": a.mode, "solver": solver,
+           "steps": a.steps, "batch": a.batch, "guidance": a.guidance, "fused": a.fused, "tree": a.tree or ".", "evaluations_per_batch": evals}
+    if not a.seeded:
+        ms = solver_run(a, model, C, H, a.graph, False)
+        res.update({"graph": bool(a.graph), "batches_timed": len(ms), "ms_per_batch_median": ms[len(ms) // 2], "ms_per_batch_min": ms[0],
+                    "ms_per_batch_max": ms[-1]})
+        return print(json.dumps(res))
+    # (i): the four runs one after the other, twice, the second round reported (the first warms the allocator and the tables)
+    for _ in range(2):
+        for graph in (False, True):
+            for seeded in (False, True):
+                ms = solver_run(a, model, C, H, graph, seeded)
+                name = f"{'seeded' if seeded else 'torch'}_{'graph' if graph else 'eager'}"
+                res.update({f"{name}_ms_per_batch_median": ms[len(ms) // 2], f"{name}_ms_per_batch_min": ms[0], "batches_timed": len(ms)})
+    # the draw alone, over rotating destinations larger than the 256 MiB Infinity Cache: 4 (8) bytes written per element
+    shape = (a.batch, 3 if C == 3 else 4, H, H)
+    seeds = torch.arange(a.batch, device="cuda")
+    res["draw_elements"] = elems = a.batch * shape[1] * H * H
+    with torch.no_grad():
+        for dt, nm in ((torch.float32, "f32"), (torch.float64, "f64")):
+            outs = [torch.empty(shape, device="cuda", dtype=dt) for _ in range(max(2, int(600e6 // (elems * dt.itemsize)) + 1))]
+            us_t = events_us([(lambda o=o: o.normal_()) for o in outs], a.iters)
+            us_s = events_us([(lambda o=o, i=i: ops.randn_seeded(seeds, shape, i, dtype=dt, out=o)) for i, o in enumerate(outs)], a.iters)
+            res.update({f"draw_{nm}_torch_us": us_t, f"draw_{nm}_seeded_us": us_s, f"draw_{nm}_seeded_Gelements_per_s": elems / us_s / 1e3})
+            del outs
+    print(json.dumps(res))
 
 
 def dpm_kernel_bench(a):
@@ -320,6 +355,8 @@ def main():
     ap.add_argument("--mode", choices=["diffusion", "flow"], default="diffusion")
     ap.add_argument("--fused", type=int, choices=[0, 1], default=None, help="(e): 0 = the tensor composition, 1 = the fused solver steps")
     ap.add_argument("--graph", action="store_true", help="(e): args.hip_graph=True")
+    ap.add_argument("--seeded", action="store_true",
+                    help="(i): torch generator against SeededNoise (args.sample_seed), eager and captured, for --solver (default heun) / --mode flow")
     ap.add_argument("--guidance", type=float, default=1.0, help="(e): guidance scale (1.0, the reference's default: unguided)")
     ap.add_argument("--batches", type=int, default=12)
     ap.add_argument("--skip", type=int, default=2)
@@ -344,7 +381,7 @@ def main():
     if a.solver == "rk45":
         with torch.no_grad():
             return rk45_bench(a)
-    if a.solver or a.mode == "flow":
+    if a.solver or a.mode == "flow" or a.seeded:
         return solver_bench(a)
     torch.manual_seed(0)
     model, C, H = build_model(a)

@@ -1,5 +1,5 @@
 """Public names of vaw_amd."""
-from . import dist_util, evaluator, gaussian_diffusion, ops, resample, respace, sampler, utils  # noqa: F401
+from . import dist_util, evaluator, gaussian_diffusion, noise, ops, resample, respace, sampler, utils  # noqa: F401
 from ._lib import LIB_PATH, VawError, exported_symbols, lib  # noqa: F401
 from .dit import DiT, DiT_B, DiT_L, DiT_S, DiT_XL, DiT_models  # noqa: F401
 from .flat import FlatModule  # noqa: F401
@@ -11,6 +11,7 @@ from .optim import FusedAdamW  # noqa: F401
 from .parallel import DistributedDataParallel  # noqa: F401
 from .data import DevicePrefetcher, LatentBatchLoader, LatentH5Dataset, ShardedSampler  # noqa: F401
 from .samplers import EDMDenoiser, dpm_sample, edm_sample, flow_log_likelihood, flow_ode_sample, flow_sde_sample  # noqa: F401
+from .noise import SeededNoise  # noqa: F401
 from .respace import SpacedDiffusion, space_timesteps  # noqa: F401
 from .sampler import IntervalCFG, Sampler, sync_ema_model  # noqa: F401
 from .resample import (DeviceLossSecondMomentResampler, LossSecondMomentResampler, UniformSampler, create_named_schedule_sampler)  # noqa: F401

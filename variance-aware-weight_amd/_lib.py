@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VAW_HIP_LIB") or os.path.join(_HERE, "libvaw_hip.so")   # (override: measurement builds only)
 
 F32, BF16, FP8, BF8 = 0, 1, 2, 3
+F64 = 4          # VAW_F64: output type of vaw_randn_seeded only
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16}
 
 _p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
@@ -171,6 +172,7 @@ _PROTOS = {
     "vaw_dpm_input": [_p, _p, _i, _i, _p, _p, _i, _l, _p],
     "vaw_dpm_step": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _l, _p],
     "vaw_flow_step": [_i, _i, _i, _p, _p, _l, _f, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _l, _p],
+    "vaw_randn_seeded": [_p, _i, _p, _i, _l, _l, _i, _i, _p],
     "vaw_rk_stage": [_i, _i, _p, _p, _l, _f, _p, _p, _p, _i, _i, _p, C.POINTER(_i), C.POINTER(_f), _i, _f, _p, _p, _p, _f, _f, _p, _l, _i, _l, _p],
     "vaw_rk_scaled_sumsq": [_p, _p, _p, _p, _f, _f, _p, _l, _i, _l, _p],
     "vaw_rk_sumsq_finish": [_p, _l, _p, _p],

@@ -244,9 +244,10 @@ class GaussianDiffusion:
         return float(i)
 
     def _reverse_step(self, kind, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0, want_all=False,
-                      t_host=None):
+                      t_host=None, randn_like=None):
         """t_host: the python int every entry of t equals, when the caller knows it (the sampling loops); only a model
-        that offers `guided_halves` (IntervalCFG) uses it."""
+        that offers `guided_halves` (IntervalCFG) uses it.  randn_like: the hook the step's noise is drawn with (the sampling
+        loops pass theirs on); None = the global generator."""
         if denoised_fn is not None or cond_fn is not None:
             raise NotImplementedError("denoised_fn / cond_fn (classifier guidance) are out of scope (SURVEY.md §2)")
         mt, vt = self.model_mean_type, self.model_var_type
@@ -286,7 +287,9 @@ class GaussianDiffusion:
             assert stacked.shape == (2 * B, C * 2 if learned else C, *x.shape[2:])
         noise = None
         if kind:
-            if getattr(self.args, "cpu_rng", False):
+            if randn_like is not None:
+                noise = randn_like(x)
+            elif getattr(self.args, "cpu_rng", False):
                 noise = torch.randn(x.shape, dtype=torch.float32).to(x.device)     # the reference's CPU stream (parity runs)
             else:
                 noise = torch.randn_like(x)
@@ -334,14 +337,21 @@ class GaussianDiffusion:
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
         return self._reverse_step(2, model, x, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta)
 
-    def _loop(self, kind, model, shape, noise, device, progress, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0):
+    def _loop(self, kind, model, shape, noise, device, progress, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=0.0,
+              randn_like=None):
         """The reverse chain of p_sample (kind 1) / ddim_sample (kind 2).  The step index is a host integer here, and
-        _reverse_step gets it beside the device tensor: a guidance interval is decided from it, with no read-back per step."""
+        _reverse_step gets it beside the device tensor: a guidance interval is decided from it, with no read-back per step.
+        randn_like: a hook `randn_like(x) -> noise` (SeededNoise.randn_like) that draws the initial image when `noise` is not
+        given, then the noise of every step, in that order; None = the global generator."""
+        if randn_like is not None and getattr(self.args, "cpu_rng", False):
+            raise ValueError("randn_like together with args.cpu_rng: the noise comes from the hook or from the CPU stream, not both")
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
         if noise is not None:
             img = noise
+        elif randn_like is not None:
+            img = randn_like(torch.empty(*shape, device=device))
         elif getattr(self.args, "cpu_rng", False):
             img = torch.randn(*shape).to(device)
         else:
@@ -353,31 +363,34 @@ class GaussianDiffusion:
         for i in indices:
             t = torch.full((shape[0],), i, device=device, dtype=torch.long)
             with torch.no_grad():
-                out = self._reverse_step(kind, model, img, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta, t_host=i)
+                out = self._reverse_step(kind, model, img, t, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta, t_host=i,
+                                         randn_like=randn_like)
                 yield out
                 img = out["sample"]
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                  model_kwargs=None, device=None, progress=False):
-        return self._loop(1, model, shape, noise, device, progress, clip_denoised, denoised_fn, cond_fn, model_kwargs)
+                                  model_kwargs=None, device=None, progress=False, randn_like=None):
+        return self._loop(1, model, shape, noise, device, progress, clip_denoised, denoised_fn, cond_fn, model_kwargs,
+                          randn_like=randn_like)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                      device=None, progress=False):
+                      device=None, progress=False, randn_like=None):
         final = None
         for final in self.p_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                                                    device, progress):
+                                                    device, progress, randn_like=randn_like):
             pass
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                     model_kwargs=None, device=None, progress=False, eta=0.0):
-        return self._loop(2, model, shape, noise, device, progress, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta)
+                                     model_kwargs=None, device=None, progress=False, eta=0.0, randn_like=None):
+        return self._loop(2, model, shape, noise, device, progress, clip_denoised, denoised_fn, cond_fn, model_kwargs, eta=eta,
+                          randn_like=randn_like)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
-                         device=None, progress=False, eta=0.0):
+                         device=None, progress=False, eta=0.0, randn_like=None):
         final = None
         for final in self.ddim_sample_loop_progressive(model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs,
-                                                       device, progress, eta):
+                                                       device, progress, eta, randn_like=randn_like):
             pass
         return final["sample"]
 

@@ -383,6 +383,46 @@ def flow_step(kind, sde, mean_type, cond, uncond, guidance_scale, x, noise, x_pr
     return x_out
 
 
+NOISE_MODES = {"bits": 0, "uniform": 1, "normal": 2}          # VAW_NOISE_BITS / _UNIFORM / _NORMAL
+NOISE_TAG_NOISE, NOISE_TAG_LABELS = 0, 1                      # VAW_NOISE_TAG_*
+_NOISE_DTYPES = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float64: L.F64}
+
+
+def randn_seeded(seeds, shape_or_like, draw, *, tag=NOISE_TAG_NOISE, mode="normal", dtype=None, out=None):
+    """Draw number `draw` of the per-sample streams `seeds` (vaw_randn_seeded; a device int64 [B]): a [B, ...] tensor whose row b
+    is Philox4x32-10 under the key seeds[b] at the counters (block, draw, tag, 0) -- a function of (seeds[b], draw, tag, element)
+    alone, whatever B, the other seeds or the history.  shape_or_like: the shape, or a tensor whose shape (and dtype, unless
+    `dtype` is given) to take.  mode "normal": N(0, 1) by Box-Muller, float32 (the default), bfloat16 or float64 (the float32
+    value rounded / widened); "uniform": float32 in (0, 1]; "bits": the raw words as int32.  out: an optional contiguous
+    destination of that shape and dtype (any element-aligned address).  GPU only."""
+    like = shape_or_like if torch.is_tensor(shape_or_like) else None
+    need_cuda(seeds, like, out)
+    if mode not in NOISE_MODES:
+        raise L.VawError(f"randn_seeded: mode {mode!r} is not one of {tuple(NOISE_MODES)}")
+    shape = tuple(like.shape) if like is not None else tuple(int(s) for s in shape_or_like)
+    if dtype is None:
+        dtype = torch.int32 if mode == "bits" else like.dtype if (like is not None and mode == "normal") else torch.float32
+    if mode == "normal":
+        if dtype not in _NOISE_DTYPES:
+            raise L.VawError(f"randn_seeded: normals are float32, bfloat16 or float64, not {dtype}")
+        code = _NOISE_DTYPES[dtype]
+    else:
+        if dtype != (torch.int32 if mode == "bits" else torch.float32):
+            raise L.VawError(f"randn_seeded: mode {mode!r} writes {'int32' if mode == 'bits' else 'float32'}, not {dtype}")
+        code = L.F32
+    if not (seeds.dtype == torch.int64 and seeds.dim() == 1 and seeds.is_contiguous() and len(shape) >= 1 and seeds.shape[0] == shape[0]):
+        raise L.VawError(f"randn_seeded: seeds {seeds.dtype} {tuple(seeds.shape)} are not a contiguous int64 [{shape[0] if shape else '?'}] "
+                         f"for a draw of shape {shape}")
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=seeds.device)
+    else:
+        _dense("randn_seeded", dtype, shape, out)
+    B = shape[0]
+    check(L.lib().vaw_randn_seeded(ptr(out), code, ptr(seeds), B, out.numel() // max(B, 1), int(draw), int(tag), NOISE_MODES[mode],
+                                   stream_ptr()), "vaw_randn_seeded")
+    return out
+
+
 RK_STAGES = 7          # VAW_RK_STAGES
 
 

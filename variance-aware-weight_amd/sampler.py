@@ -7,6 +7,7 @@ import torch
 import torch.distributed as dist
 
 from . import dist_util, ops
+from .noise import SeededNoise
 from .samplers import DPM_SOLVERS, EDMDenoiser, dpm_sample, edm_sample, flow_ode_sample, flow_sde_sample
 
 
@@ -97,7 +98,19 @@ class Sampler:
     args.hip_graph=True (EDM, multistep and flow generators, whose loops do not synchronise with the host; not the adaptive
     solver="rk45", whose every step the host decides): the first batch runs eagerly,
     the second is captured into one graph on static label and output buffers, later batches replay it; the labels are drawn
-    outside the graph in the same order, so images and labels are those of the eager run.  "auto" or absent: eager."""
+    outside the graph in the same order, so images and labels are those of the eager run.  "auto" or absent: eager.
+
+    Per-sample seeds (optional attributes of args; absent: the global generator, as above).  args.sample_seed = S, an int in
+    [0, 2^63): the sample with global index k draws its label and all its noise from a stream of its own, seeded S + k
+    (SeededNoise: one counter-based kernel, draw 0 the initial latent, then one draw per hook call of the solver), so image k does
+    not depend on sample_size, on the number of ranks, on args.hip_graph or on what was drawn before it.  Row i of batch n of rank
+    r of w ranks (w = 1 without args.parallel) is k = sample_start + (n * w + r) * sample_size + i, the order _gather_samples
+    lays the batches out in; args.sample_start (default 0) continues an interrupted run; args.sample_shard = (r, w) overrides
+    rank and world in that formula (one process standing in for rank r; refused with args.parallel).  Refused with
+    args.cpu_rng.  What is promised is the noise and the solver arithmetic around the network, both row-independent; a
+    network whose kernels depend on the batch size is its own business.  The adaptive solver="rk45" gets its per-sample
+    initial noise too, but controls its steps by an error norm over the whole batch: its images depend on what else is in
+    the batch, and nothing is promised there."""
 
     def __init__(self, args, device, eval_model, diffusion, classifier=None, decode_fn=None):
         if classifier is not None:
@@ -111,10 +124,50 @@ class Sampler:
         self.diffusion = diffusion
         self.classifier = None
         self.decode_fn = decode_fn if args.in_chans == 4 else None
+        self._noise = None          # the SeededNoise of a run under args.sample_seed (_run)
 
     # ---- pieces -------------------------------------------------------------------------------------------------
     def _cpu_rng(self):
         return bool(getattr(self.args, "cpu_rng", False))
+
+    def _seed_plan(self):
+        """(S, o, r, w) of a run under args.sample_seed -- the base seed, the first global index, the rank and the world of
+        the index formula -- or None without it."""
+        a = self.args
+        S, o, shard = getattr(a, "sample_seed", None), getattr(a, "sample_start", None), getattr(a, "sample_shard", None)
+        if S is None:
+            if o or shard is not None:
+                raise ValueError("args.sample_start / args.sample_shard: only with args.sample_seed")
+            return None
+        is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+        if not (is_int(S) and 0 <= S < 2 ** 63):
+            raise ValueError(f"args.sample_seed: {S!r} is not an int in [0, 2^63)")
+        o = 0 if o is None else o
+        if not (is_int(o) and o >= 0):
+            raise ValueError(f"args.sample_start: {o!r} is not a non-negative int")
+        if self._cpu_rng():
+            raise ValueError("args.sample_seed: not with args.cpu_rng (the noise comes from the per-sample streams or from the CPU "
+                             "stream, not both)")
+        if shard is not None:
+            if a.parallel:
+                raise ValueError("args.sample_shard: not with args.parallel (the process group names rank and world)")
+            if not (isinstance(shard, (tuple, list)) and len(shard) == 2 and all(is_int(v) for v in shard) and 0 <= shard[0] < shard[1]):
+                raise ValueError(f"args.sample_shard: {shard!r} is not (rank, world) with 0 <= rank < world")
+            return S, o, shard[0], shard[1]
+        if a.parallel:
+            return S, o, dist.get_rank(), dist.get_world_size()
+        return S, o, 0, 1
+
+    def _sample_indices(self, n, sample_size):
+        """The global indices of the rows of this rank's batch number n."""
+        _, o, r, w = self._seed_plan()
+        first = o + (n * w + r) * sample_size
+        return range(first, first + sample_size)
+
+    def _sample_seeds(self, n, sample_size):
+        """Their seeds S + k, wrapped to the int64 that holds the same 64-bit pattern."""
+        S = self._seed_plan()[0]
+        return [(S + k + 2 ** 63) % 2 ** 64 - 2 ** 63 for k in self._sample_indices(n, sample_size)]
 
     def _build_cfg_model(self, num_classes):
         return IntervalCFG(self.model, num_classes, self.args.guidance_scale, self.args.interval, self.args.class_cond).eval()
@@ -125,16 +178,22 @@ class Sampler:
                            label_dim=num_classes, noise_schedule=a.path_type, amp=a.amp, pred_type=a.mean_type).to(self.device)
 
     def _randint(self, high, sample_size):
+        if self._noise is not None:
+            return self._noise.randint(high)
         if self._cpu_rng():
             return torch.randint(0, high, (sample_size,)).to(self.device)
         return torch.randint(0, high, (sample_size,), device=self.device)
 
     def _randn(self, shape):
+        if self._noise is not None:
+            return self._noise.randn(shape)
         if self._cpu_rng():
             return torch.randn(shape).to(self.device)
         return torch.randn(shape, device=self.device)
 
     def _randn_like(self, x):
+        if self._noise is not None:
+            return self._noise.randn_like(x)
         if self._cpu_rng():
             return torch.randn(x.shape, dtype=x.dtype).to(x.device)
         return torch.randn_like(x)
@@ -192,7 +251,10 @@ class Sampler:
     def _run(self, draw_batch, num_samples, sample_size, num_classes, progress_bar, desc, graph=False):
         """The loop the reference's three samplers share: sync the EMA weights, then batches of draw_batch(labels) until
         num_samples are there (counted per rank, as the reference does).  graph: from the second batch on draw_batch runs
-        as one captured graph."""
+        as one captured graph.  Under args.sample_seed every batch begins with its rows' seeds copied into the SeededNoise's
+        buffer (which a captured graph reads on replay), and labels and noise come from there."""
+        self._noise = SeededNoise(self.device) if self._seed_plan() is not None else None
+        n_batch = 0
         self.model.eval()
         captured = None          # (graph, static labels, static samples)
         all_samples, all_labels = [], []
@@ -205,6 +267,9 @@ class Sampler:
             from tqdm import tqdm
             pbar = tqdm(total=num_samples, desc=desc)
         while len(all_samples) * sample_size < num_samples:
+            if self._noise is not None:
+                self._noise.begin(self._sample_seeds(n_batch, sample_size))
+                n_batch += 1
             class_labels = self._get_y_cond(sample_size, num_classes)
             with torch.no_grad():
                 if not graph or not all_samples:
@@ -236,7 +301,8 @@ class Sampler:
 
         def draw(class_labels):
             return self.diffusion.ddim_sample_loop(cfg_model, shape, device=self.device,
-                                                   model_kwargs={"y": class_labels} if self.args.class_cond else {}, cond_fn=None)
+                                                   model_kwargs={"y": class_labels} if self.args.class_cond else {}, cond_fn=None,
+                                                   randn_like=self._randn_like if self._noise is not None else None)
 
         return self._run(draw, num_samples, sample_size, num_classes, progress_bar, "Generating Samples (DDIM)")
 

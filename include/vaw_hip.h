@@ -41,7 +41,9 @@ const char* vaw_last_error_string(void);
 
 /* q_sample :234-252 with the table gather of _extract_into_tensor :1059-1072 fused in:
  *   x_t[b,:] = tab_a[t[b]] * x0[b,:] + tab_s[t[b]] * noise[b,:]
- * tab_a/tab_s: f32[T] = float(float64 table).  t out of [0,T) poisons the row with NaN. */
+ * tab_a/tab_s: f32[T] = float(float64 table).  t out of [0,T) poisons the row with NaN.
+ * This entry, vaw_mix_rows, vaw_wmse_fwd(_t) and vaw_wmse_bwd(_t): 16-byte loads and stores when per_sample % 4 == 0 and every
+ * [B, per_sample] tensor is 16-byte aligned, scalar ones otherwise (any alignment, any length). */
 int vaw_qsample_fwd(const float* x0, const float* noise, const int64_t* t, const float* tab_a, const float* tab_s,
                     int num_timesteps, float* x_t, int B, int64_t per_sample, vaw_stream stream);
 

@@ -24,7 +24,7 @@ __device__ __forceinline__ void gather_mix_coef(const float* __restrict__ ca, co
 template <bool GATHER>
 __global__ void mix_rows_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ ca,
                                 const float* __restrict__ cb, const int64_t* __restrict__ t, int T,
-                                float* __restrict__ out, int64_t n) {
+                                float* __restrict__ out, int64_t n, int vec4) {
     const int b = blockIdx.y;
     float a, c;
     if (GATHER) {
@@ -36,7 +36,7 @@ __global__ void mix_rows_kernel(const float* __restrict__ x, const float* __rest
     const float* xr = x + (int64_t)b * n;
     const float* yr = y + (int64_t)b * n;
     float* orow = out + (int64_t)b * n;
-    const int64_t n4 = ((n & 3) == 0) ? n / 4 : 0;
+    const int64_t n4 = vec4 ? n / 4 : 0;                      // the host's vec4_ok: n % 4 == 0 and every pointer 16-byte aligned
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         f32x4 xv = load4(xr + 4 * i), yv = load4(yr + 4 * i);
         store4(orow + 4 * i, a * xv + c * yv);
@@ -51,7 +51,8 @@ extern "C" int vaw_qsample_fwd(const float* x0, const float* noise, const int64_
     VAW_CHECK_ARG(B > 0 && per_sample > 0 && num_timesteps > 0, "qsample: bad sizes B=%d n=%ld", B, (long)per_sample);
     int gx = stream_grid(per_sample / 4 + 1, 256);
     dim3 grid(gx > 64 ? 64 : gx, B);
-    mix_rows_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(x0, noise, tab_a, tab_s, t, num_timesteps, x_t, per_sample);
+    mix_rows_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(x0, noise, tab_a, tab_s, t, num_timesteps, x_t, per_sample,
+                                                                 vec4_ok(per_sample, 0, {x0, noise, x_t}));
     VAW_CHECK_LAUNCH("qsample");
     return VAW_OK;
 }
@@ -61,7 +62,7 @@ extern "C" int vaw_mix_rows(const float* x, const float* y, const float* ca, con
     VAW_CHECK_ARG(B > 0 && per_sample > 0, "mix_rows: bad sizes");
     int gx = stream_grid(per_sample / 4 + 1, 256);
     dim3 grid(gx > 64 ? 64 : gx, B);
-    mix_rows_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(x, y, ca, cb, nullptr, 0, out, per_sample);
+    mix_rows_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(x, y, ca, cb, nullptr, 0, out, per_sample, vec4_ok(per_sample, 0, {x, y, out}));
     VAW_CHECK_LAUNCH("mix_rows");
     return VAW_OK;
 }
@@ -81,7 +82,7 @@ __device__ __forceinline__ WmseCoef wmse_coef(const float* ca, const float* cb, 
 }
 __global__ void wmse_fwd_t_kernel(const float* __restrict__ o, const float* __restrict__ x0, const float* __restrict__ nz,
                                   const float* __restrict__ ca, const float* __restrict__ cb, const float* __restrict__ w,
-                                  const int64_t* __restrict__ t, int T, float* __restrict__ mse, int64_t n) {
+                                  const int64_t* __restrict__ t, int T, float* __restrict__ mse, int64_t n, int vec4) {
     __shared__ float scratch[16];
     const int b = blockIdx.x;
     const WmseCoef k = wmse_coef(ca, cb, w, t, T, b);
@@ -90,7 +91,7 @@ __global__ void wmse_fwd_t_kernel(const float* __restrict__ o, const float* __re
     const float* xr = x0 + (int64_t)b * n;
     const float* nr = nz + (int64_t)b * n;
     float acc = 0.f;
-    const int64_t n4 = ((n & 3) == 0) ? n / 4 : 0;
+    const int64_t n4 = vec4 ? n / 4 : 0;
     for (int64_t i = threadIdx.x; i < n4; i += blockDim.x) {
         f32x4 d = a * load4(xr + 4 * i) + c * load4(nr + 4 * i) - load4(orow + 4 * i);
         acc += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
@@ -108,7 +109,7 @@ __global__ void wmse_fwd_t_kernel(const float* __restrict__ o, const float* __re
 __global__ void wmse_bwd_t_kernel(const float* __restrict__ o, const float* __restrict__ x0, const float* __restrict__ nz,
                                   const float* __restrict__ ca, const float* __restrict__ cb, const float* __restrict__ w,
                                   const int64_t* __restrict__ t, int T, const float* __restrict__ g, int g_per_row, float inv_count,
-                                  float* __restrict__ dout, int64_t n) {
+                                  float* __restrict__ dout, int64_t n, int vec4) {
     const int b = blockIdx.y;
     const WmseCoef kc = wmse_coef(ca, cb, w, t, T, b);
     const float a = kc.a, c = kc.c;
@@ -118,7 +119,7 @@ __global__ void wmse_bwd_t_kernel(const float* __restrict__ o, const float* __re
     const float* xr = x0 + (int64_t)b * n;
     const float* nr = nz + (int64_t)b * n;
     float* dr = dout + (int64_t)b * n;
-    const int64_t n4 = ((n & 3) == 0) ? n / 4 : 0;
+    const int64_t n4 = vec4 ? n / 4 : 0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
         store4(dr + 4 * i, k * (load4(orow + 4 * i) - a * load4(xr + 4 * i) - c * load4(nr + 4 * i)));
     for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -137,7 +138,8 @@ extern "C" int vaw_wmse_fwd(const float* model_out, const float* x0, const float
                             const float* cb, const float* w, float* mse, int B, int64_t per_sample,
                             vaw_stream stream) {
     VAW_CHECK_ARG(B > 0 && per_sample > 0, "wmse_fwd: bad sizes");
-    wmse_fwd_t_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, nullptr, 0, mse, per_sample);
+    wmse_fwd_t_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, nullptr, 0, mse, per_sample,
+                                                           vec4_ok(per_sample, 0, {model_out, x0, noise}));
     VAW_CHECK_LAUNCH("wmse_fwd");
     return VAW_OK;
 }
@@ -148,7 +150,8 @@ extern "C" int vaw_wmse_bwd(const float* model_out, const float* x0, const float
     VAW_CHECK_ARG(B > 0 && per_sample > 0, "wmse_bwd: bad sizes");
     int gx = stream_grid(per_sample / 4 + 1, 256);
     dim3 grid(gx > 64 ? 64 : gx, B);
-    wmse_bwd_t_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, nullptr, 0, gmse, 1, 1.f, dout, per_sample);
+    wmse_bwd_t_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, nullptr, 0, gmse, 1, 1.f, dout, per_sample,
+                                                            vec4_ok(per_sample, 0, {model_out, x0, noise, dout}));
     VAW_CHECK_LAUNCH("wmse_bwd");
     return VAW_OK;
 }
@@ -1121,7 +1124,8 @@ extern "C" int vaw_wmse_fwd_t(const float* model_out, const float* x0, const flo
                               int64_t per_sample, vaw_stream stream) {
     VAW_CHECK_ARG(B > 0 && per_sample > 0 && (!t || num_timesteps > 0) && accum >= 1.f, "wmse_fwd_t: bad sizes");
     VAW_CHECK_ARG(model_out && x0 && noise && ca && cb && w && mse, "wmse_fwd_t: null pointer");
-    wmse_fwd_t_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, t, num_timesteps, mse, per_sample);
+    wmse_fwd_t_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, t, num_timesteps, mse, per_sample,
+                                                           vec4_ok(per_sample, 0, {model_out, x0, noise}));
     if (mean_out) batch_mean_kernel<<<1, 256, 0, (hipStream_t)stream>>>(mse, B, accum, mean_out);
     VAW_CHECK_LAUNCH("wmse_fwd_t");
     return VAW_OK;
@@ -1135,7 +1139,7 @@ extern "C" int vaw_wmse_bwd_t(const float* model_out, const float* x0, const flo
     int gx = stream_grid(per_sample / 4 + 1, 256);
     dim3 grid(gx > 64 ? 64 : gx, B);
     wmse_bwd_t_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(model_out, x0, noise, ca, cb, w, t, num_timesteps, g, 0, inv_count, dout,
-                                                            per_sample);
+                                                            per_sample, vec4_ok(per_sample, 0, {model_out, x0, noise, dout}));
     VAW_CHECK_LAUNCH("wmse_bwd_t");
     return VAW_OK;
 }

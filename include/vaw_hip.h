@@ -280,20 +280,20 @@ int vaw_randn_seeded(void* out, int dtype, const int64_t* seeds, int B, int64_t 
 int64_t vaw_rk_partial_count(int B, int64_t per_sample);
 
 /* The pass after the network evaluation of stage `stage` (0..6) of a step from x with signed step h:
- *   cond != NULL:  k[slots[stage]] = v(output, x_stage) under mean_type (the ODE branch of vaw_flow_step, interpolant from
+ *   cond != NULL:  k[slots_host[stage]] = v(output, x_stage) under mean_type (the ODE branch of vaw_flow_step, interpolant from
  *                  coef[row], a [rows][VAW_FLOW_COLS] table at the stage times); x_stage == NULL: the stage state is x.
- *   cond == NULL:  k[slots[stage]] is there already (a rejected step tried again with another h, or k1 <- k7 after an
- *                  accepted one: the host swaps slots[0] and slots[6], nothing is copied).
- *   dy = sum_{s < ncoef} a[s] * k[slots[s]]   ascending, zero coefficients skipped, left to right (a: host pointer)
+ *   cond == NULL:  k[slots_host[stage]] is there already (a rejected step tried again with another h, or k1 <- k7 after an
+ *                  accepted one: the host swaps slots_host[0] and slots_host[6], nothing is copied).
+ *   dy = sum_{s < ncoef} a_host[s] * k[slots_host[s]]   ascending, zero coefficients skipped, left to right
  *   x_out != NULL:     x_out (and x_out_dup) = x + h*dy, the next stage's state, written straight into the network input
  *                      (x_out may be x_stage: every element is read before it is written)
- *   partials != NULL:  partial sums of ((h*dy) / (atol + rtol*max(|x|, |x_new|)))^2, a = the error weights
+ *   partials != NULL:  partial sums of ((h*dy) / (atol + rtol*max(|x|, |x_new|)))^2, a_host = the error weights
  *   ncoef == 0:        k only.
- * k: [VAW_RK_STAGES][B*per_sample] float32; slots: VAW_RK_STAGES host ints in 0..6.  One coefficient vector per call, so
- * the Euler trial of the first-step selection (a = {1}) and any other explicit tableau are the same kernel. */
+ * k: [VAW_RK_STAGES][B*per_sample] float32; slots_host: VAW_RK_STAGES host ints in 0..6.  One coefficient vector per call, so
+ * the Euler trial of the first-step selection (a_host = {1}) and any other explicit tableau are the same kernel. */
 int vaw_rk_stage(int stage, int mean_type, const float* cond, const float* uncond, int64_t model_ld, float guidance_scale,
-                 const float* x, const float* x_stage, const float* coef, int row, int rows, float* k, const int* slots,
-                 const float* a, int ncoef, float h, float* x_out, float* x_out_dup, const float* x_new, float atol,
+                 const float* x, const float* x_stage, const float* coef, int row, int rows, float* k, const int* slots_host,
+                 const float* a_host, int ncoef, float h, float* x_out, float* x_out_dup, const float* x_new, float atol,
                  float rtol, double* partials, int64_t partials_cap, int B, int64_t per_sample, vaw_stream stream);
 
 /* partials[workgroup] of  sum ((u - v) / (atol + rtol*max(|a|, |b|)))^2  over [B, per_sample] float32 tensors; v == NULL:
@@ -326,13 +326,13 @@ int vaw_rk_sumsq_finish(const double* partials, int64_t count, double* out, vaw_
  * Runge-Kutta step from x with signed step h:
  *   k[stage]    = A*x_stage + B*out            (coef[row]; x_stage == NULL: the stage state is x), float32
  *   d[stage][b] = A*n + B * sum_i eps[b,i]*g[b,i]     float64, n = per_sample
- *   ncoef > 0:  x_out = x + float(h) * sum_{s < ncoef} float(a[s]) * k[s]   ascending, zero coefficients skipped, left to
+ *   ncoef > 0:  x_out = x + float(h) * sum_{s < ncoef} float(a_host[s]) * k[s]   ascending, zero coefficients skipped, left to
  *               right: the next stage's state, written straight into the next network input -- or, on the last stage, x_new
- *   delta != NULL (last stage, a = the step's weights):  delta[b] += h * sum_{s < ncoef} a[s] * d[s][b]   float64, same order
- * k: [VAW_RK_STAGES][B*per_sample] float32; d: [VAW_RK_STAGES][B] float64; a: host pointer; x_out must not overlap an input.
+ *   delta != NULL (last stage, a_host = the step's weights):  delta[b] += h * sum_{s < ncoef} a_host[s] * d[s][b]   float64, same order
+ * k: [VAW_RK_STAGES][B*per_sample] float32; d: [VAW_RK_STAGES][B] float64; a_host: ncoef host doubles; x_out must not overlap an input.
  * partials: vaw_rk_partial_count(B, per_sample) doubles, needed (and touched) only when per_sample > 1024. */
 int vaw_flow_logp_stage(int stage, const float* out, int64_t model_ld, const float* g, const float* eps, const float* x,
-                        const float* x_stage, const float* coef, int row, int rows, float* k, double* d, const double* a, int ncoef,
+                        const float* x_stage, const float* coef, int row, int rows, float* k, double* d, const double* a_host, int ncoef,
                         double h, float* x_out, double* delta, double* partials, int64_t partials_cap, int B, int64_t per_sample,
                         vaw_stream stream);
 
@@ -859,12 +859,12 @@ int vaw_attn_bwd(vaw_dtype dt, const vaw_attn_desc* d_host, const void* q, const
                  vaw_stream stream);
 /* vaw_attn_bwd that also leaves the column sums of dq | dk | dv behind as PARTIAL rows -- the bias gradient of the qkv Linear in
  * front of the attention (timm Attention, models/dit.py:126: db = sum over tokens of dqkv) without a second pass over dqkv:
- * colsum_partial [*rows_out][3*H*hd] f32 in packed-qkv column order [3][H][hd]; at most B*T/64 rows: *rows_out is in / out --
+ * colsum_partial [*rows_out_host][3*H*hd] f32 in packed-qkv column order [3][H][hd]; at most B*T/64 rows: *rows_out_host is in / out --
  * on entry the capacity of the buffer in rows (checked), on return the rows written; fold them with vaw_reduce_rows / vaw_reduce_rows_batched.  Only the bf16 MFMA kernels offer it (token-major or any
  * layout they accept): VAW_ERR_UNSUPPORTED, nothing launched, otherwise -- use vaw_attn_bwd + vaw_colsum then. */
-int vaw_attn_bwd_colsum(vaw_dtype dt, const vaw_attn_desc* d, const void* q, const void* k, const void* v, const void* o,
+int vaw_attn_bwd_colsum(vaw_dtype dt, const vaw_attn_desc* d_host, const void* q, const void* k, const void* v, const void* o,
                         const void* d_o, const float* lse, float* delta, void* dq, void* dk, void* dv, float* colsum_partial,
-                        int64_t* rows_out, vaw_stream stream);
+                        int64_t* rows_out_host, vaw_stream stream);
 
 /* Launch plan of the attention entry points: the one host function vaw_attn_fwd / vaw_attn_bwd / vaw_attn_bwd_colsum take every
  * launch choice from (pure arithmetic: no device call, so it can be asked without a GPU).  q / k / v / o_or_do / dq / dk / dv are the
@@ -1150,6 +1150,20 @@ int vaw_allreduce_bucket_start(void* buf, int64_t count, vaw_dtype dt, vaw_strea
 int vaw_reduce_scatter_bucket_start(void* buf, int64_t count, vaw_dtype dt, vaw_stream stream);
 int vaw_allgather_bucket_start(void* buf, int64_t count, vaw_dtype dt, vaw_stream stream);
 int vaw_allreduce_bucket_wait(vaw_stream stream);
+
+/* ---- debug and measurement switches ------------------------------------------------------------------------------------------
+ * Process-wide state for tests, golden generators and the benchmarks under tools/: no training or sampling path sets them. */
+/* on != 0: every attention call takes the row-wise kernels, whatever the shape (vaw_attn_plan answers accordingly) */
+void vaw_debug_force_rowwise_attention(int on);
+/* on != 0: every vaw_gemm call takes the generic kernel (vaw_gemm_knobs.force_generic) */
+void vaw_debug_force_generic_gemm(int on);
+/* the GEMM kernel family vaw_gemm_plan prefers wherever it applies (vaw_gemm_knobs.tile); -1: by shape */
+void vaw_debug_gemm_tile(int mode);
+/* GroupNorm: -1 the flat kernels by shape, 0 never, 1 wherever they can run (vaw_gn_plan) */
+void vaw_debug_gn_flat(int mode);
+/* n_wgs (1 ... 256) workgroups that each hold a whole CU idle for `microseconds` (<= 2 s) on `stream`: a stand-in for a collective
+ * kernel beside the compute kernels (tools/contention_bench.py) */
+int vaw_debug_cu_hog(int n_wgs, int microseconds, vaw_stream stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@ import math
 import pytest
 import torch
 
+import abi_cases
 import vaw_amd
 from conftest import sampling_model
 from sampler_cases import Standin, build, sampler_args
@@ -291,13 +292,12 @@ def test_refusals():
 def test_entry_points_are_declared_bound_and_check_their_arguments_before_any_launch():
     import re
 
-    from vaw_amd import _lib
     lib = vaw_amd.lib()
     with open(f"{vaw_amd.__path__[0]}/../include/vaw_hip.h") as f:
         header = f.read()
     for name, nargs in (("vaw_dpm_input", 9), ("vaw_dpm_step", 20)):
         assert re.search(rf"\bint {name}\(", header) and name in vaw_amd.exported_symbols() and hasattr(lib, name)
-        assert len(_lib._PROTOS[name]) == nargs and list(getattr(lib, name).argtypes) == _lib._PROTOS[name]
+        assert len(abi_cases.assert_bound_as_declared(lib, name)) == nargs
     assert f"#define VAW_DPM_COLS {ops.DPM_COLS}\n" in header
     p = 4096          # never dereferenced: every call below fails its argument check
 

@@ -31,6 +31,94 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.vaw_version() >= 100 and isinstance(lib.vaw_last_error_string(), bytes)
 
 
+_CONSTANT_ALIASES = {"VAW_ATTN_DIR_FWD": "ATTN_FWD", "VAW_ATTN_DIR_BWD": "ATTN_BWD", "VAW_ATTN_DIR_BWD_COLSUM": "ATTN_BWD_COLSUM"}
+
+
+def test_binding_agrees_with_an_independent_reading_of_every_declaration():
+    """Every function, struct, enumerator and #define of include/vaw_hip.h, read by the regular expressions of tests/abi_cases.py
+    (vaw_amd._abi is not asked): each function is exported by the built library and bound with the restype and argtypes its
+    prototype spells, each struct has a Structure class with the fields in order and kind, each constant has its Python name."""
+    import ctypes as C
+    import abi_cases as ac
+    from vaw_amd import _lib, ops
+    code, structs, kind = ac.CODE, ac.STRUCTS, ac.kind
+    assert len(ac.ENUMS) == 14 and set(structs) == set(ac.STRUCT_CLASSES)
+    names = [n for _, n, _ in ac.PROTOS]
+    assert len(names) == len(set(names)) >= 141 and sorted(names) == vaw_amd.exported_symbols()
+    assert {"vaw_debug_force_rowwise_attention", "vaw_debug_force_generic_gemm", "vaw_debug_gemm_tile", "vaw_debug_gn_flat",
+            "vaw_debug_cu_hog"} <= set(names)
+    lib, raw = vaw_amd.lib(), C.CDLL(vaw_amd.LIB_PATH)
+    typed = 0
+    for name in names:
+        assert hasattr(raw, name), f"libvaw_hip.so does not export {name}"
+        assert name in vars(lib), f"{name} is not bound"
+        want = ac.assert_bound_as_declared(lib, name)
+        typed += sum(t is not C.c_void_p and issubclass(t, C._Pointer) for t in want)
+    assert typed >= 24          # the struct pointers and the five _host arrays: the rule above is not vacuous
+    for cname, body in structs.items():
+        cls = getattr(_lib, ac.STRUCT_CLASSES[cname])
+        assert issubclass(cls, C.Structure) and getattr(ops, ac.STRUCT_CLASSES[cname], cls) is cls
+        fields = []
+        for decl in body.split(";")[:-1]:
+            ctype, first = " ".join(decl.split(",")[0].split()).rsplit(" ", 1)
+            for f in [first] + [f.strip() for f in decl.split(",")[1:]]:
+                # vaw_epilogue.colsum_rows_out is the one HOST address among the fields (read and written by vaw_gemm's host side)
+                fields.append((f, kind(ctype, f, host=(cname, f) == ("vaw_epilogue", "colsum_rows_out"))))
+        assert cls._fields_ == fields, (cname, cls._fields_, fields)
+    # sizeof, as a C compiler prints it for the header on x86-64
+    sizes = {"vaw_epilogue": 128, "vaw_wgrad_problem": 88, "vaw_fp8_quant_job": 72, "vaw_gemm_knobs": 64, "vaw_gemm_launch": 104,
+             "vaw_gemm_fp8_launch": 88, "vaw_reduce_job": 32, "vaw_row_launch": 40, "vaw_attn_desc": 88, "vaw_attn_launch": 56,
+             "vaw_gn_launch": 96, "vaw_conv3x3_launch": 112, "vaw_cast_colsum_launch": 32, "vaw_dit_ws_plan_t": 72}
+    assert {c: C.sizeof(getattr(_lib, p)) for c, p in ac.STRUCT_CLASSES.items()} == sizes
+    constants = re.findall(r"\b(VAW_[A-Z0-9_]+) = (-?\d+)", code) + re.findall(r"#define (VAW_\w+) (-?\d+)\n", code)
+    assert len(constants) >= 75 and len(set(n for n, _ in constants)) == len(constants)
+    for cname, value in constants:
+        assert getattr(_lib, _CONSTANT_ALIASES.get(cname, cname[4:])) == int(value), cname
+    assert (_lib.F32, _lib.BF16, _lib.ERR_INVALID, _lib.GV_WARP_SPEC, _lib.ROW_GATE_LN_FWD, _lib.RESAMPLER_MAX_T) == (0, 1, -1, 7, 8, 4096)
+    assert _lib.AV_NAMES[_lib.AV_BWD_BIG_NT4] == "bwd_big_nt4" and _lib.GV_NAMES[_lib.GV_RING256] == "ring256"
+    assert _lib.CVR_NAMES == ("CVR_NONE", "CVR_F32", "CVR_F32_ROWSUM", "CVR_SLAB_T") and _lib.CVB_NAMES[3] == "CVB_SEPARATE"
+
+
+def test_header_parser_reads_the_subset_and_refuses_the_rest():
+    from vaw_amd._abi import AbiError, Type, parse
+    h = parse("""
+        typedef enum { VAW_A = 0, VAW_B = -3 } vaw_kind;
+        typedef struct { int a, b; const float* p; int64_t n; } vaw_job;
+        /* int vaw_not_declared(int x); */
+        // int vaw_not_declared_either(int x);
+        #define VAW_COLS 12
+        int vaw_nothing(void);
+        int64_t vaw_count(vaw_kind kind, const vaw_job* jobs, vaw_stream stream);
+        const char* vaw_text(void);
+        void vaw_split(
+            int a,
+            const double* b_host
+            , float c);
+    """)
+    assert h.structs == {"vaw_job": [("a", Type("int", False)), ("b", Type("int", False)), ("p", Type("float", True)), ("n", Type("int64_t", False))]}
+    assert h.enums == {"vaw_kind": {"VAW_A": 0, "VAW_B": -3}} and h.defines == {"VAW_COLS": 12}
+    assert sorted(h.functions) == ["vaw_count", "vaw_nothing", "vaw_split", "vaw_text"]
+    assert h.functions["vaw_nothing"] == (Type("int", False), [])
+    assert h.functions["vaw_count"] == (Type("int64_t", False), [(Type("vaw_kind", False), "kind"), (Type("vaw_job", True), "jobs"),
+                                                                 (Type("vaw_stream", False), "stream")])
+    assert h.functions["vaw_text"] == (Type("char", True), [])
+    assert h.functions["vaw_split"] == (Type("void", False), [(Type("int", False), "a"), (Type("double", True), "b_host"), (Type("float", False), "c")])
+    for bad, line, what in (("int vaw_f(size_t n);", 1, "unknown type 'size_t'"),
+                            ("int vaw_f(int a);\n\nunsigned vaw_g(void);", 3, "unknown type 'unsigned'"),
+                            ("int vaw_f(int a);\nstruct s { int a; };", 2, "unrecognised construct"),
+                            ("int vaw_f(int a)\nint vaw_g(void);", 1, "unrecognised construct"),
+                            ("int vaw_f(void (*cb)(int));", 1, "unrecognised construct"),
+                            ("int vaw_f(int a, b);", 1, "unrecognised declarator"),
+                            ("typedef struct { float *a, *b; } vaw_s;", 1, "unrecognised declarator"),
+                            ("typedef enum { VAW_A = 0, VAW_B } vaw_e;", 1, "enumerator 'VAW_B'"),
+                            ("int vaw_f(void);\nint vaw_f(void);", 2, "vaw_f is declared twice"),
+                            ("\n#pragma once", 2, "unrecognised preprocessor line"),
+                            ("#define VAW_X (1 << 4)", 1, "unrecognised preprocessor line"),
+                            ("int vaw_f(int a);\nstatic const int k = 3;", 2, "unrecognised")):
+        with pytest.raises(AbiError, match=re.escape(f"include/vaw_hip.h:{line}: {what}")):
+            parse(bad)
+
+
 def test_no_cpu_fallback():
     m = vaw_amd.DiT(image_size=8, patch_size=2, in_channels=4, hidden_size=64, depth=1, num_heads=2, num_classes=10)
     with pytest.raises(vaw_amd.VawError):

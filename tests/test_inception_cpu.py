@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import inception_cases as ic
+import abi_cases
 import vaw_amd
 from vaw_amd import evaluator as ev
 
@@ -75,7 +76,7 @@ def test_symbols_declared_exported_and_bound():
     for name in INT_ENTRIES:
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
         assert name in vaw_amd.exported_symbols() and hasattr(lib, name)
-        assert list(getattr(lib, name).argtypes) == vaw_amd._lib._PROTOS[name]
+        abi_cases.assert_bound_as_declared(lib, name)
     for name in ("Evaluator", "compute_inception_score", "inception_score_from_probs", "inception_split_scores"):
         assert getattr(vaw_amd, name) is getattr(ev, name)
 

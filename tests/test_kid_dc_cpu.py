@@ -12,6 +12,7 @@ import torch
 
 import kid_dc_cases as kc
 import metrics_cases as mc
+import abi_cases
 import vaw_amd
 from vaw_amd import evaluator as ev, ops
 
@@ -27,14 +28,15 @@ def test_symbols_declared_exported_and_bound():
     for name in INT_ENTRIES:
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
         assert name in vaw_amd.exported_symbols() and hasattr(lib, name)
-        assert list(getattr(lib, name).argtypes) == vaw_amd._lib._PROTOS[name]
+        abi_cases.assert_bound_as_declared(lib, name)
     for name in SIZE_ENTRIES:
         assert re.search(r"\bint64_t\s+" + name + r"\s*\(", hdr), name
         assert name in vaw_amd.exported_symbols() and getattr(lib, name).restype is ctypes.c_int64
+        abi_cases.assert_bound_as_declared(lib, name)
     # the declared parameter lists and the bound ones agree in length and in where the doubles are
     for name in INT_ENTRIES:
         params = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", hdr).group(1).split(",")
-        protos = vaw_amd._lib._PROTOS[name]
+        protos = getattr(lib, name).argtypes
         assert len(params) == len(protos), name
         assert [p.split()[0] == "double" and "*" not in p for p in params] == [t is ctypes.c_double for t in protos], name
     for name in ("polynomial_mmd2", "kid_subset_scores", "kid_subset_indices", "compute_kid", "compute_density_coverage"):

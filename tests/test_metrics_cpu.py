@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import metrics_cases as mc
+import abi_cases
 import vaw_amd
 from vaw_amd import evaluator as ev
 
@@ -23,7 +24,7 @@ def test_symbols_declared_exported_and_built_without_contraction():
     for name in INT_ENTRIES:
         assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), name
         assert name in vaw_amd.exported_symbols() and hasattr(lib, name)
-        assert list(getattr(lib, name).argtypes) == vaw_amd._lib._PROTOS[name]
+        abi_cases.assert_bound_as_declared(lib, name)
     assert re.search(r"\bint64_t\s+vaw_pairwise_workspace_bytes\s*\(", hdr)
     assert "vaw_pairwise_workspace_bytes" in vaw_amd.exported_symbols() and hasattr(lib, "vaw_pairwise_workspace_bytes")
     mk = open(os.path.join(REPO, "variance-aware-weight_amd", "csrc", "Makefile")).read()

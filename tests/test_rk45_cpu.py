@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import rk45_cases as rc
+import abi_cases
 import vaw_amd
 from conftest import GOLDEN
 from vaw_amd import ops, samplers
@@ -193,11 +194,10 @@ def test_sampler_runs_rk45_and_refuses_hip_graph():
 def test_rk_entry_points_have_argtypes_and_reject_bad_arguments_before_any_launch():
     import ctypes as C
 
-    from vaw_amd import _lib
     lib = vaw_amd.lib()
     for name, nargs in (("vaw_rk_stage", 26), ("vaw_rk_scaled_sumsq", 11), ("vaw_rk_sumsq_finish", 4)):
         assert name in vaw_amd.exported_symbols() and hasattr(lib, name)
-        assert len(_lib._PROTOS[name]) == nargs and list(getattr(lib, name).argtypes) == _lib._PROTOS[name]
+        assert len(abi_cases.assert_bound_as_declared(lib, name)) == nargs
     assert "vaw_rk_partial_count" in vaw_amd.exported_symbols() and ops.RK_STAGES == 7
     with open(f"{vaw_amd.__path__[0]}/../include/vaw_hip.h") as f:
         header = f.read()

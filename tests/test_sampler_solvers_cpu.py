@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_cases
 import vaw_amd
 from conftest import sampling_model
 from sampler_cases import Standin, build, sampler_args
@@ -271,11 +272,10 @@ def test_flow_samplers_unfused_are_the_composition_and_fused_needs_the_gpu(solve
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------
 def test_solver_entry_points_have_argtypes_and_reject_bad_arguments_before_any_launch():
-    from vaw_amd import _lib
     lib = vaw_amd.lib()
     for name, nargs in (("vaw_edm_input", 11), ("vaw_edm_step", 17), ("vaw_flow_step", 21)):
         assert name in vaw_amd.exported_symbols() and hasattr(lib, name)
-        assert len(_lib._PROTOS[name]) == nargs and list(getattr(lib, name).argtypes) == _lib._PROTOS[name]
+        assert len(abi_cases.assert_bound_as_declared(lib, name)) == nargs
     assert (ops.EDM_COLS, ops.FLOW_COLS) == (24, 16)
     with open(f"{vaw_amd.__path__[0]}/../include/vaw_hip.h") as f:
         header = f.read()

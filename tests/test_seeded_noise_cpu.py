@@ -14,6 +14,7 @@ import seeded_noise_cases as sc
 from conftest import REPO, load_json, sampling_model
 from sampler_cases import Standin, sampler_args, spaced
 
+import abi_cases
 import vaw_amd
 from vaw_amd import _lib, ops
 from vaw_amd.noise import SeededNoise
@@ -65,7 +66,7 @@ def test_randn_seeded_is_declared_bound_and_exported():
     header = open(os.path.join(REPO, "include", "vaw_hip.h")).read()
     lib = vaw_amd.lib()
     assert re.search(r"\bint vaw_randn_seeded\(", header) and "vaw_randn_seeded" in vaw_amd.exported_symbols() and hasattr(lib, "vaw_randn_seeded")
-    assert len(_lib._PROTOS["vaw_randn_seeded"]) == 9 and list(lib.vaw_randn_seeded.argtypes) == _lib._PROTOS["vaw_randn_seeded"]
+    assert len(abi_cases.assert_bound_as_declared(lib, "vaw_randn_seeded")) == 9
     for name, value in (("VAW_NOISE_BITS", ops.NOISE_MODES["bits"]), ("VAW_NOISE_UNIFORM", ops.NOISE_MODES["uniform"]),
                         ("VAW_NOISE_NORMAL", ops.NOISE_MODES["normal"]), ("VAW_NOISE_TAG_NOISE", ops.NOISE_TAG_NOISE),
                         ("VAW_NOISE_TAG_LABELS", ops.NOISE_TAG_LABELS)):

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from ._lib import BF16, F32, AttnDesc, Epilogue, check, need_cuda, ptr, stream_ptr
+from ._lib import BF16, F32, AttnDesc, Epilogue, Fp8QuantJob, ReduceJob, WgradProblem, check, need_cuda, ptr, stream_ptr
 
 
 def dt_of(t):
@@ -276,7 +276,7 @@ def cfg_combine(cond, uncond, guidance_scale):
     return out
 
 
-EDM_COLS, FLOW_COLS = 24, 16          # VAW_EDM_COLS, VAW_FLOW_COLS
+EDM_COLS, FLOW_COLS = L.EDM_COLS, L.FLOW_COLS
 EDM_PRED = {"EPSILON": 0, "START_X": 1, "VELOCITY": 2}
 FLOW_MEAN = {"START_X": 0, "EPSILON": 1, "VELOCITY": 2, "VECTOR": 3}
 STEP_EULER, STEP_PREDICT, STEP_CORRECT = range(3)
@@ -334,7 +334,7 @@ def edm_step(kind, pred_type, cond, uncond, guidance_scale, x_hat, d_cur, coef, 
     return d_cur if kind == STEP_PREDICT else x_out
 
 
-DPM_COLS = 12          # VAW_DPM_COLS
+DPM_COLS = L.DPM_COLS
 
 
 def dpm_input(x, coef, row, model_in, model_in_dup=None):
@@ -383,8 +383,8 @@ def flow_step(kind, sde, mean_type, cond, uncond, guidance_scale, x, noise, x_pr
     return x_out
 
 
-NOISE_MODES = {"bits": 0, "uniform": 1, "normal": 2}          # VAW_NOISE_BITS / _UNIFORM / _NORMAL
-NOISE_TAG_NOISE, NOISE_TAG_LABELS = 0, 1                      # VAW_NOISE_TAG_*
+NOISE_MODES = {"bits": L.NOISE_BITS, "uniform": L.NOISE_UNIFORM, "normal": L.NOISE_NORMAL}
+NOISE_TAG_NOISE, NOISE_TAG_LABELS = L.NOISE_TAG_NOISE, L.NOISE_TAG_LABELS
 _NOISE_DTYPES = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float64: L.F64}
 
 
@@ -423,7 +423,7 @@ def randn_seeded(seeds, shape_or_like, draw, *, tag=NOISE_TAG_NOISE, mode="norma
     return out
 
 
-RK_STAGES = 7          # VAW_RK_STAGES
+RK_STAGES = L.RK_STAGES
 
 
 def rk_partial_count(B, per_sample):
@@ -489,7 +489,7 @@ def rk_sumsq_finish(partials, count, out):
     return out
 
 
-FLOW_LOGP_COLS = 4          # VAW_FLOW_LOGP_COLS
+FLOW_LOGP_COLS = L.FLOW_LOGP_COLS
 
 
 def flow_logp_stage(stage, out, g, eps, x, x_stage, coef, row, k, d, coeffs, h, x_out=None, delta=None, partials=None):
@@ -742,12 +742,6 @@ class Fp8:
         return self.q.view(torch.float8_e5m2 if self.fmt == L.BF8 else torch.float8_e4m3fn).float() * self.scale
 
 
-class Fp8QuantJob(C.Structure):
-    """vaw_fp8_quant_job of include/vaw_hip.h."""
-    _fields_ = [("src", C.c_void_p), ("q", C.c_void_p), ("qt", C.c_void_p), ("state", C.c_void_p), ("R", C.c_int64), ("C", C.c_int64),
-                ("ld", C.c_int64), ("ldq", C.c_int64), ("ldt", C.c_int64)]
-
-
 class Fp8QuantGroup:
     """Delayed-scaling e4m3 quantisation of many f32 tensors (src address, Fp8 with q and qt) in ONE launch
     (vaw_fp8_quantize_delayed_batched); the addresses stay put between steps, so the device table is uploaded once."""
@@ -761,7 +755,7 @@ class Fp8QuantGroup:
         self.uploaded = False
 
     def launch(self):
-        check(L.lib().vaw_fp8_quantize_delayed_batched(self.n, C.cast(self.table, C.c_void_p), self.desc.data_ptr(),
+        check(L.lib().vaw_fp8_quantize_delayed_batched(self.n, self.table, self.desc.data_ptr(),
                                                        0 if self.uploaded else 1, stream_ptr()), "vaw_fp8_quantize_delayed_batched")
         self.uploaded = True
         for f in self.fp8s:
@@ -831,13 +825,6 @@ def gemm_fp8_plan(M, N, K, A, lda, scale_a, B, ldb, scale_b, Cp, ldc, *, a_forma
     return p
 
 
-class WgradProblem(C.Structure):
-    """vaw_wgrad_problem of include/vaw_hip.h."""
-    _fields_ = [("dy", C.c_void_p), ("x", C.c_void_p), ("dw", C.c_void_p), ("M", C.c_int64), ("N", C.c_int64),
-                ("ld_dy", C.c_int64), ("ld_x", C.c_int64), ("ld_dw", C.c_int64), ("alpha", C.c_float), ("pad_", C.c_int),
-                ("scale_dy", C.c_void_p), ("scale_x", C.c_void_p)]
-
-
 class WgradGroup:
     """The weight gradients dW_p (+)= dy_p^T x_p of many Linear layers as ONE launch (vaw_wgrad_grouped).  `problems` is a list of
     (dy_addr, x_addr, dw_addr, M, N, ld_dy, ld_x, ld_dw); the addresses are workspace / flat-buffer addresses that stay put
@@ -856,7 +843,7 @@ class WgradGroup:
         if tr is not None:
             e0, e1 = tr.events()
             e0.record()
-        check(L.lib().vaw_wgrad_grouped(dt, self.n, C.cast(self.table, C.c_void_p), self.K, float(beta), self.desc.data_ptr(),
+        check(L.lib().vaw_wgrad_grouped(dt, self.n, self.table, self.K, float(beta), self.desc.data_ptr(),
                                         0 if self.uploaded else 1, ws.data_ptr(), ws.numel(), stream_ptr()), "vaw_wgrad_grouped")
         self.uploaded = True
         if tr is not None:
@@ -1106,11 +1093,6 @@ class ColsumPartial:
         self.rows = C.c_int64(0)
 
 
-class ReduceJob(C.Structure):
-    """vaw_reduce_job of include/vaw_hip.h."""
-    _fields_ = [("partial", C.c_void_p), ("out", C.c_void_p), ("R", C.c_int64), ("N", C.c_int64)]
-
-
 class ReduceGroup:
     """out_j = beta * out_j + column sums of partial_j for many (partial, R, N, out) jobs in ONE launch
     (vaw_reduce_rows_batched); addresses are workspace / flat-buffer addresses, so the device table is uploaded once."""
@@ -1122,7 +1104,7 @@ class ReduceGroup:
         self.uploaded = False
 
     def launch(self, beta):
-        check(L.lib().vaw_reduce_rows_batched(self.n, C.cast(self.table, C.c_void_p), float(beta), self.desc.data_ptr(),
+        check(L.lib().vaw_reduce_rows_batched(self.n, self.table, float(beta), self.desc.data_ptr(),
                                               0 if self.uploaded else 1, stream_ptr()), "vaw_reduce_rows_batched")
         self.uploaded = True
 

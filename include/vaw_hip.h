@@ -1102,6 +1102,30 @@ int vaw_cast_colsum_bf16(const float* src, int64_t ld_src, void* dst, int64_t ld
  * collective summed.  src and dst 16-byte aligned. */
 int vaw_uncast_bf16(const void* src, float* dst, int64_t n, float scale, vaw_stream stream);
 
+/* ---- post-hoc EMA (ema.py: PowerEMA, posthoc_ema; Karras et al. 2024, section 3) ---------------------------------------------
+ * Up to VAW_EMA_MAX_PROFILES power-function averages of one flat f32 parameter buffer, tracked every step.  Update number
+ * t = 1, 2, ... of the profile with exponent gamma takes e <- e + (p - e) c_t, c_t = 1 - (1 - 1/t)^(gamma + 1). */
+#define VAW_EMA_MAX_PROFILES 4
+/* step_dev[0] += 1 (that is t), then coef_dev[k] = c_t of gamma_dev[k] for k < K in f64, as -expm1((gamma + 1) log1p(-1/t)):
+ * no cancellation at large t, and exactly 1 at t = 1.  One tiny launch that reads nothing from the host, so it and the update
+ * below replay from a captured hipGraph while t advances.  K outside 1 .. VAW_EMA_MAX_PROFILES or a NULL pointer is refused. */
+int vaw_ema_profiles_coef(int64_t* step_dev, const double* gamma_dev, double* coef_dev, int K, vaw_stream stream);
+/* One pass over n f32: p is read once, each of the K average buffers e0 .. e{K-1} is read and written once ((4 + 8 K) B per
+ * parameter).  Per element and profile, with c = (float)coef_dev[k]:  e = c == 1 ? p : e + (p - e) * c, every operation rounded
+ * on its own -- bitwise the f32 tensor composition e.add((p - e).mul(c)), and an exact copy at t = 1.
+ * Refused with VAW_ERR_INVALID before anything is launched: n <= 0, K outside 1 .. VAW_EMA_MAX_PROFILES, a NULL p / coef_dev /
+ * e_k with k < K, a buffer that is not 16-byte aligned, any two of the K + 1 ranges of n floats overlapping.  e_k with k >= K
+ * is ignored. */
+int vaw_ema_profiles_update(const float* p, float* e0, float* e1, float* e2, float* e3, int K, int64_t n, const double* coef_dev,
+                            vaw_stream stream);
+/* acc[i] += coef * (double)src[i] over n elements, the product and the sum rounded separately: folding snapshots one call at a
+ * time in a given order is bitwise numpy's `acc += coef * src.astype(np.float64)` in that order, with 12 B per parameter resident
+ * however many are folded.  16-byte accesses when acc and src are 16-byte aligned, element accesses otherwise.  n <= 0, a NULL
+ * pointer or overlapping ranges are refused. */
+int vaw_lincomb_accum_f64(double* acc, const float* src, double coef, int64_t n, vaw_stream stream);
+/* out[i] = (float)acc[i] (round to nearest even) over n elements; same refusals. */
+int vaw_f64_to_f32(const double* acc, float* out, int64_t n, vaw_stream stream);
+
 /* ---- activation workspace of the DiT engine (dit.py: _Workspace) -------------------------------------------------------------
  * The one place the engine's buffer sizes are decided (pure host arithmetic: no device call, so it can be asked without a GPU).
  * dtype = the act dtype; B images of T tokens (M = B * T rows), hidden D, MLP width Dm, `depth` blocks, `heads` heads, patch

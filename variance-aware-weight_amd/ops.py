@@ -1207,6 +1207,41 @@ def ema_update(ema, src, decay):
     check(L.lib().vaw_ema_update(ptr(ema), ptr(src), ema.numel(), decay, stream_ptr()), "vaw_ema_update")
 
 
+# ---- post-hoc EMA (ema.py) ---------------------------------------------------------------------
+def ema_profiles_coef(step, gamma, coef):
+    """step i64 [1] += 1 (= t) and coef f64 [K] = c_t of the exponents gamma f64 [K], on the device: no host value in the launch."""
+    need_cuda(step, gamma, coef)
+    assert step.dtype == torch.int64 and step.numel() == 1 and gamma.dtype == coef.dtype == torch.float64
+    assert gamma.is_contiguous() and coef.is_contiguous() and gamma.numel() == coef.numel()
+    check(L.lib().vaw_ema_profiles_coef(ptr(step), ptr(gamma), ptr(coef), gamma.numel(), stream_ptr()), "vaw_ema_profiles_coef")
+
+
+def ema_profiles_update(p, bufs, coef):
+    """bufs[k] = c == 1 ? p : bufs[k] + (p - bufs[k]) * c with c = float32(coef[k]), for the len(bufs) averages in one pass over p.
+    What the kernel cannot take (alignment, overlap, a count outside 1 .. EMA_MAX_PROFILES) it refuses: VawError, nothing launched."""
+    need_cuda(p, coef, *bufs)
+    _f32c(p, *bufs)
+    assert coef.dtype == torch.float64 and coef.is_contiguous() and coef.numel() >= min(len(bufs), L.EMA_MAX_PROFILES)
+    assert all(b.numel() == p.numel() for b in bufs)
+    e = [ptr(b) for b in bufs[:L.EMA_MAX_PROFILES]] + [0] * (L.EMA_MAX_PROFILES - len(bufs))
+    check(L.lib().vaw_ema_profiles_update(ptr(p), *e, len(bufs), p.numel(), ptr(coef), stream_ptr()), "vaw_ema_profiles_update")
+
+
+def lincomb_accum_f64(acc, src, coef):
+    """acc (f64) += coef * float64(src) (src f32), product and sum rounded separately; in place."""
+    need_cuda(acc, src)
+    _f32c(src)
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == src.numel()
+    check(L.lib().vaw_lincomb_accum_f64(ptr(acc), ptr(src), float(coef), acc.numel(), stream_ptr()), "vaw_lincomb_accum_f64")
+
+
+def f64_to_f32(acc, out):
+    need_cuda(acc, out)
+    _f32c(out)
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == out.numel()
+    check(L.lib().vaw_f64_to_f32(ptr(acc), ptr(out), acc.numel(), stream_ptr()), "vaw_f64_to_f32")
+
+
 def cast_bf16(src, dst):
     check(L.lib().vaw_cast_bf16(ptr(src), ptr(dst), src.numel(), stream_ptr()), "vaw_cast_bf16")
 

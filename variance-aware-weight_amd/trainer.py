@@ -13,12 +13,14 @@ Differences that do not change results:
     into ONE hipGraph and replayed; per step the host only copies the next batch into the static input buffers and
     refreshes three optimizer scalars in device memory.  For launch-bound configurations (small models / batches).
 """
+import os
 from contextlib import nullcontext
 
 import torch
 import torch.nn as nn
 
 from . import _lib, dist_util, ops
+from .ema import PowerEMA
 from .flat import FlatModule
 from .optim import FusedAdamW
 
@@ -91,6 +93,22 @@ class Trainer:
                 optimizer.attach_ema_sharded(args.ema_decay, ema_model)
         elif self._fused and ema_model is not None and dist_util.is_main_process():
             optimizer.attach_ema(ema_model, args.ema_decay)
+        # post-hoc EMA (an extension, ema.py): args.ema_sigma_rels = (0.05, 0.10) tracks those power-function averages of the
+        # model's flat buffer right after every optimizer.step() -- two launches with no host value in them, captured with the step
+        # under args.hip_graph -- on the main process only, as the EMA copy.  Absent or empty: nothing is built, nothing changes.
+        # args.ema_snapshot_every = N with args.ema_snapshot_dir writes PowerEMA.save_snapshot every N steps (a host read-back,
+        # outside the captured body)
+        self.power_ema = None
+        rels = getattr(args, "ema_sigma_rels", None)
+        self._ema_snapshot_every = int(getattr(args, "ema_snapshot_every", 0) or 0) if rels else 0
+        if rels:
+            if self._zero:
+                raise ValueError("args.ema_sigma_rels: not with the sharded optimizer (the f32 masters of other ranks' chunks are stale "
+                                 "between consolidations)")
+            if self._ema_snapshot_every and not getattr(args, "ema_snapshot_dir", None):
+                raise ValueError("args.ema_snapshot_every needs args.ema_snapshot_dir")
+            if dist_util.is_main_process():
+                self.power_ema = PowerEMA(model, tuple(rels))
         self.last_mse = None
         self._cpu_rng = bool(getattr(args, "cpu_rng", False))
         # VAW_STEP_FUSED (default on): the latent sample, q_sample and the timestep scaling are one launch, the loss kernels gather
@@ -227,11 +245,17 @@ class Trainer:
                 return
             ema(self.model, self.ema_model, self.args.ema_decay)
 
+    def _snapshot_power_ema(self, step):
+        if self.power_ema is not None and self._ema_snapshot_every and step % self._ema_snapshot_every == 0:
+            self.power_ema.save_snapshot(os.path.join(self.args.ema_snapshot_dir, f"power_ema_{int(step):08d}.pt"))
+
     def _graph_body(self, images, labels):
         """Everything of one step that runs on the GPU, on static inputs; returns (loss, mse) device scalars."""
         loss, mse = self._micro_step(images, labels, 1, False, False)
         self._apply_gradient_clipping()
         self.optimizer.step()
+        if self.power_ema is not None:
+            self.power_ema.update()
         self.optimizer.zero_grad()
         return loss, mse
 
@@ -283,6 +307,7 @@ class Trainer:
         self.scheduler.step()
         if dist_util.is_main_process():
             self._update_ema()
+        self._snapshot_power_ema(step)
         self.last_mse = mse
         if dist_util.is_main_process() and self.pbar is not None:
             self.pbar.update(1)
@@ -315,10 +340,13 @@ class Trainer:
             if (i + 1) % accum == 0:
                 self._apply_gradient_clipping()
                 self.optimizer.step()
+                if self.power_ema is not None:
+                    self.power_ema.update()
                 self.optimizer.zero_grad()
         self.scheduler.step()
         if dist_util.is_main_process():
             self._update_ema()
+        self._snapshot_power_ema(step)
         self.last_mse = mse_avg
         if getattr(a, "defer_loss_sync", False):
             if dist_util.is_main_process() and self.pbar is not None:

@@ -51,11 +51,11 @@ def _strip_module(sd):
     return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
 
 
-def save_checkpoint(args, step, model, optimizer, ema_model=None, scheduler=None, schedule_sampler=None):
+def save_checkpoint(args, step, model, optimizer, ema_model=None, scheduler=None, schedule_sampler=None, power_ema=None):
     """{'model','optimizer','step','ema_model'} with the reference's state_dict keys (a wrapped model saves
     'module.'-prefixed keys, as torch DDP does).  'scheduler' is an addition the reference forgets; 'schedule_sampler' is the
     loss history of a timestep sampler that has a state_dict (the device-resident one), so a resumed run keeps drawing t
-    from where it stopped."""
+    from where it stopped; 'power_ema' is the state of a trainer's PowerEMA (its profiles and update count), handled the same way."""
     zero = getattr(optimizer, "zero", None)
     opt_state = None
     if zero is not None:       # sharded optimizer (ZeRO-1): collectives -- EVERY rank calls save_checkpoint; rank 0 writes the file
@@ -74,12 +74,14 @@ def save_checkpoint(args, step, model, optimizer, ema_model=None, scheduler=None
         state["scheduler"] = scheduler.state_dict()
     if schedule_sampler is not None and hasattr(schedule_sampler, "state_dict"):
         state["schedule_sampler"] = schedule_sampler.state_dict()
+    if power_ema is not None and hasattr(power_ema, "state_dict"):
+        state["power_ema"] = power_ema.state_dict()
     path = os.path.join(d, f"{args.model}_{args.mean_type}_{args.path_type}_{step}.pth")
     torch.save(state, path)
     return path
 
 
-def load_checkpoint(ckpt_path, model=None, optimizer=None, ema_model=None, scheduler=None, schedule_sampler=None):
+def load_checkpoint(ckpt_path, model=None, optimizer=None, ema_model=None, scheduler=None, schedule_sampler=None, power_ema=None):
     assert os.path.exists(ckpt_path), f"Error: checkpoint {ckpt_path} not found"
     ck = torch.load(ckpt_path, map_location="cpu", weights_only=True)
 
@@ -102,4 +104,6 @@ def load_checkpoint(ckpt_path, model=None, optimizer=None, ema_model=None, sched
         scheduler.load_state_dict(ck["scheduler"])
     if schedule_sampler is not None and hasattr(schedule_sampler, "load_state_dict") and "schedule_sampler" in ck:
         schedule_sampler.load_state_dict(ck["schedule_sampler"])       # (files written without a sampler load as before)
+    if power_ema is not None and hasattr(power_ema, "load_state_dict") and "power_ema" in ck:
+        power_ema.load_state_dict(ck["power_ema"])
     return ck

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import model_grad_cases as grad_cases
 from conftest import (Pbar, assert_fingerprints, base_args, load_json, load_pt, perturb_, synth_loader)
 
 pytestmark = pytest.mark.gpu
@@ -77,6 +78,16 @@ def test_dit_tiny_bf16_close_to_reference(tag):
         if p.grad is not None:
             gl2 = float(g[f"{tag}/grads"][k]["stats"][2])
             assert abs(float(p.grad.double().norm()) - gl2) <= 5e-2 * gl2 + 1e-4, k
+    # a norm does not see a swapped, permuted, transposed or sign-flipped gradient: whole tensors against the float64 oracle at the
+    # same weights and inputs, each within twice the oracle's own bf16-autocast distance (tests/model_grad_cases.py)
+    om = odit.DiT(in_channels=4, class_dropout_prob=0.0, num_classes=10, learn_sigma=False, **g[f"{tag}/kw"])
+    om.load_state_dict({k: v.cpu() for k, v in m.state_dict().items()})
+    g64, e_ref = grad_cases.oracle_yardstick("dit", om.train(), *(g[f"{tag}/{k}"] for k in ("x", "t", "y", "gout")))
+    got = {k: p.grad for k, p in m.named_parameters() if p.grad is not None}
+    got.update({grad_cases.OUT: out.detach(), grad_cases.GX: xr.grad})
+    worst, n = grad_cases.hold_whole_tensors(got, g64, e_ref)
+    assert n == len(g64)
+    print(f"\ndit_tiny {tag} bf16: worst rel_err / e_ref {worst[0]:.3f} at {worst[1]} ({worst[2]:.5f} / {worst[3]:.5f})")
 
 
 def _run_trainer(model, args, batches, steps, fused, var_type="FIXED_LARGE"):

@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import model_grad_cases as grad_cases
 from conftest import assert_fingerprints, fingerprint, perturb_
 
 pytestmark = pytest.mark.gpu
@@ -411,6 +412,8 @@ def test_dit_hidden_1280_vs_oracle(dtype):
     t = torch.tensor([17.0, 803.0])
     y = torch.tensor([3, 8])
     gout = torch.randn(2, 4, 8, 8, generator=g)
+    if dtype == "bf16":       # whole tensors: the float64 oracle and its own bf16-autocast distance from it (tests/model_grad_cases.py)
+        g64, e_ref = grad_cases.oracle_yardstick("dit", om, x, t, y, gout)
     om = om.double()          # the oracle in float64 (its timestep embedding is f32 by construction: fed to the MLP as f64)
     om.t_embedder.mlp.register_forward_pre_hook(lambda mod, a: (a[0].double(),))
     xo = x.double().requires_grad_(True)
@@ -440,6 +443,13 @@ def test_dit_hidden_1280_vs_oracle(dtype):
             if k in grads:
                 gl2 = float(grads[k].double().norm())
                 assert abs(float(p.grad.double().norm()) - gl2) <= 5e-2 * gl2 + 1e-4, k
+        # ... and what a norm does not see (a swapped, permuted, transposed or sign-flipped gradient): every tensor within twice the
+        # oracle's bf16 distance from float64
+        got = {k: p.grad for k, p in hm.named_parameters() if k in grads}
+        got.update({grad_cases.OUT: out.detach(), grad_cases.GX: xh.grad})
+        worst, n = grad_cases.hold_whole_tensors(got, g64, e_ref)
+        assert n == len(g64) == len(grads) + 2
+        print(f"\nDiT hidden 1280 bf16: worst rel_err / e_ref {worst[0]:.3f} at {worst[1]} ({worst[2]:.5f} / {worst[3]:.5f})")
 
 
 def test_dit_hidden_1280_fp8_fused_rows_are_bitwise_the_pair():

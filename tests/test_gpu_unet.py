@@ -383,7 +383,8 @@ def test_unet_tiny_bf16_close_to_reference():
     m = vaw_amd.UNetModel(compute_dtype="bf16", **g[f"{tag}/kw"]).to(DEV).train()
     perturb_(m, 77, std=0.03)
     x, t, gout, y = (g[f"{tag}/{k}"].to(DEV) for k in ("x", "t", "gout", "y"))
-    out = m(x, t, y=y)
+    xr = x.clone().requires_grad_(True)
+    out = m(xr, t, y=y)
     (out * gout).sum().backward()
     ref = g[f"{tag}/out"]
     assert float((out.detach().cpu() - ref).norm() / ref.norm()) < 4e-2
@@ -393,6 +394,20 @@ def test_unet_tiny_bf16_close_to_reference():
             if gl2 < 1e-2:
                 continue      # e.g. a conv bias feeding GroupNorm: its exact gradient is 0, bf16 leaves rounding noise
             assert abs(float(p.grad.double().norm()) - gl2) <= 8e-2 * gl2 + 1e-3, k
+    # a norm does not see a swapped, permuted, transposed or sign-flipped gradient, and nothing above looks at the input gradient:
+    # whole tensors against the float64 oracle at the same weights and inputs, each within twice the oracle's own bf16-autocast
+    # distance (tests/model_grad_cases.py; 32 channels = one per GroupNorm group, so the biases in front of a norm are left out there)
+    import model_grad_cases as grad_cases
+    from oracle import unet as ounet
+    om = ounet.UNetModel(**g[f"{tag}/kw"])
+    om.load_state_dict({k: v.cpu() for k, v in m.state_dict().items()})
+    g64, e_ref = grad_cases.oracle_yardstick("unet", om.train(), *(g[f"{tag}/{k}"] for k in ("x", "t", "y", "gout")))
+    torch.testing.assert_close(g64[grad_cases.GX].float(), g[f"{tag}/gx"], rtol=1e-4, atol=2e-5)     # the oracle run is the fixture's
+    got = {k: p.grad for k, p in m.named_parameters() if p.grad is not None}
+    got.update({grad_cases.OUT: out.detach(), grad_cases.GX: xr.grad})
+    worst, n = grad_cases.hold_whole_tensors(got, g64, e_ref)
+    assert n == len(g64) - 6          # the six conv biases in front of a 32-channel GroupNorm: exactly zero in float64
+    print(f"\nunet_tiny bf16: worst rel_err / e_ref {worst[0]:.3f} at {worst[1]} ({worst[2]:.5f} / {worst[3]:.5f}); {n} of {len(g64)} tensors")
 
 
 def _run_trainer(model, args, batches, steps, fused, var_type="FIXED_LARGE"):

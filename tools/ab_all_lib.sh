@@ -1,6 +1,6 @@
 #!/bin/bash
-# The round's A/B table in ONE call (one box): a saved library of the previous round (VAW_HIP_LIB) against this tree's, every
-# workload, interleaved.    bash tools/ab_all_lib.sh variance-aware-weight_amd/libvaw_hip_r3.so
+# The round's A/B table in ONE call (one box): a saved build of another commit (VAW_HIP_LIB; by default the previous round's)
+# against this tree's, every workload, interleaved.    bash tools/ab_all_lib.sh variance-aware-weight_amd/libvaw_hip_r3.so
 BASE=${1:-variance-aware-weight_amd/libvaw_hip_r3.so}
 ab() { echo "== $1"; bash tools/ab_lib.sh "$1" ${2:-2} base:$BASE new:- || exit 1; }
 ab "--steps 40 --warmup 8" 3

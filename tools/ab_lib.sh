@@ -1,5 +1,5 @@
 #!/bin/bash
-# On the GPU box: interleaved A/B of measurement builds of the library on one bench workload.
+# On the GPU box: interleaved A/B of a saved build of another commit against this tree's library on one bench workload.
 #   bash tools/ab_lib.sh "<bench flags>" <rounds> <tag:libpath> [<tag:libpath> ...]      (libpath "-" = the product library)
 FLAGS=$1; ROUNDS=$2; shift; shift
 for r in $(seq 1 $ROUNDS); do

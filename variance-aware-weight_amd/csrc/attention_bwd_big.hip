@@ -34,7 +34,7 @@
 //       set-up, two staged outputs and dispatch gap, nor the serial MFMA / softmax / LDS phases inside a slice (PMC: MFMA pipe busy
 //       19 % of the wave time, VALU 32 %, waiting 33 %).  Two smaller workgroups cover each other; what the big one would need is
 //       the slice loop as a hand-placed software pipeline and a persistent workgroup that prefetches the next pair's owner fragments.
-// Where the default form's time goes (tools/attn_abl.sh: measurement builds -DBIG_ABL=n, results wrong, timing only; DiT-XL/2, DiT-B/2,
+// Where the default form's time goes (ablation builds, since removed; results wrong, timing only; DiT-XL/2, DiT-B/2,
 // ADM_64 32 x 32; base 400 / 350 / 1718 us): no slice barrier -1.5 %; no exp -1..-5 %; no LDS waits -1..-4 %; no barrier and no DMA wait
 // -9 / -3 / -3 %; NO MFMAs at all -22 / -16 / -37 %; no slice DMA in the loop -23 / -6 / -12 %.  No single term dominates: the loop is
 // ~335 vector instructions per slice and wave for 48 MFMAs (95 of them integer address arithmetic), and the fixed costs per workgroup
@@ -95,32 +95,13 @@ __device__ __forceinline__ bf16x4 lds_rd64tr(unsigned addr) {
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr) : "memory");
     return v;
 }
-#ifndef BIG_ABL
-#define BIG_ABL 0
-#endif
-#if BIG_ABL == 3
-#define LDS_WAIT() __builtin_amdgcn_sched_barrier(0)
-#else
 #define LDS_WAIT()                                          \
     do {                                                    \
         __builtin_amdgcn_sched_barrier(0);                  \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  \
         __builtin_amdgcn_sched_barrier(0);                  \
     } while (0)
-#endif
-#if BIG_ABL == 5
-#undef MFMA
-#define MFMA(a, b, c) big_fake_mfma(a, b, c)
-__device__ __forceinline__ f32x4 big_fake_mfma(bf16x8 a, bf16x8 b, f32x4 c) {      // keeps the operands alive, one VALU op
-    c[0] += (float)a[0] * (float)b[0];
-    return c;
-}
-#endif
-#if BIG_ABL == 2
-#define BIG_EXP2(x) (x)
-#else
 #define BIG_EXP2(x) __builtin_amdgcn_exp2f(x)
-#endif
 // frag_rows / frag_cols_perm of attention_mfma.h on an image given by its LDS byte address
 template <int HD>
 __device__ __forceinline__ bf16x8 afrag_rows(unsigned img, int r0, int s, int lane) {
@@ -269,16 +250,9 @@ attn_bwd_big(AttnMfmaArgs a, const bf16_t* __restrict__ q, const bf16_t* __restr
         const unsigned ximg = ring + (unsigned)((sl % NB) * 2 * SIMG), yimg = ximg + SIMG;
         {
             const int last = sl + DEPTH - 1 < n_slices - 1 ? sl + DEPTH - 1 : n_slices - 1;      // youngest slice issued so far
-#if BIG_ABL != 4
             wait_vm((last - sl) * dma_per_slice);        // this wave's pieces of slice sl have landed ...
-#endif
-#if BIG_ABL != 1 && BIG_ABL != 4                         // (measurement builds, -DBIG_ABL=n: 1 no barrier, 2 no exp, 3 no LDS waits, 4 no
-                                                         //  barrier and no DMA wait, 5 no MFMAs, 6 no slice DMA in the loop: wrong results)
             __builtin_amdgcn_s_barrier();                // ... everybody's have; and everybody is done with slice sl - 1
-#endif
-#if BIG_ABL != 6
             if (sl + DEPTH < n_slices) issue(sl + DEPTH);                                       // into the buffer slice sl - 1 used
-#endif
         }
         if (MODE == 0) {
             bf16x8 xa[2][KS], ya[2][KS];
@@ -428,44 +402,19 @@ attn_bwd_big(AttnMfmaArgs a, const bf16_t* __restrict__ q, const bf16_t* __restr
 // in 32-key slices; online softmax per query with the running maximum on the lane (base-2 domain, deferred rescale as in
 // attn_fwd_mfma: the maximum only moves when a slice exceeds it by more than 2^6).  S^T[key][q] = K_s Q_w^T, O^T[hd][q] += V_s^T P^T.
 // ------------------------------------------------------------------------------------------------
-#ifndef ATTN_PROF
-#define ATTN_PROF 0
-#endif
-#if ATTN_PROF
-__device__ unsigned long long attn_prof_buf[1024];
-extern "C" int vaw_debug_attn_prof(unsigned long long* out, int n) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(attn_prof_buf), sizeof(unsigned long long) * n);
-}
-#define ATTN_STAMP(slot)                                                                                                     \
-    do {                                                                                                                     \
-        if (threadIdx.x == 0 && blockIdx.x == 1 && blockIdx.y == 777 && prof_n < 1000)                                       \
-            attn_prof_buf[prof_n++] = ((unsigned long long)(slot) << 56) | (wall_clock64() & 0xffffffffffffffull);           \
-    } while (0)
-#else
-#define ATTN_STAMP(slot) do {} while (0)
-#endif
-// the forward's own ring depth / occupancy target (A/B: -DATTN_FWD_NB=3 -DATTN_FWD_OCC=4 = four workgroups per CU on a 3-deep ring)
-#ifndef ATTN_FWD_NB
-#define ATTN_FWD_NB 4
-#endif
-#ifndef ATTN_FWD_OCC
-#define ATTN_FWD_OCC 2
-#endif
+// the forward's own ring depth (NB = 4) and occupancy target (2 workgroups per CU).  tried: four workgroups per CU on a 3-deep ring;
+// measured: 128 registers leave 72 bytes of scratch inside the slice loop, 2 x slower
 template <int HD, int NT> struct FwdLds {
-    static constexpr int SIMG = BigLds<HD, NT>::SIMG, NB = ATTN_FWD_NB, RING = NB * 2 * SIMG, WGR = BigLds<HD, NT>::WGR;
+    static constexpr int SIMG = BigLds<HD, NT>::SIMG, NB = 4, RING = NB * 2 * SIMG, WGR = BigLds<HD, NT>::WGR;
     static constexpr int STAGE = BigLds<HD, NT>::STAGE, FRONT = RING > STAGE ? RING : STAGE;
 };
 template <int HD, int NT>
-__global__ void __launch_bounds__(256, NT == 2 ? ATTN_FWD_OCC : 1)
+__global__ void __launch_bounds__(256, NT == 2 ? 2 : 1)
 attn_fwd_big(AttnMfmaArgs a, const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
              bf16_t* __restrict__ o, float* __restrict__ lse) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KS = HD / 32, DT = HD / 16, SIMG = FwdLds<HD, NT>::SIMG, WGR = FwdLds<HD, NT>::WGR;
     constexpr int NB = FwdLds<HD, NT>::NB, DEPTH = NB - 1;
-#if ATTN_PROF
-    int prof_n = 0;
-#endif
-    ATTN_STAMP(1);
     char* slices = smem;
     char* stage = smem;
     const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
@@ -510,7 +459,6 @@ attn_fwd_big(AttnMfmaArgs a, const bf16_t* __restrict__ q, const bf16_t* __restr
             const int last = sl + DEPTH - 1 < n_slices - 1 ? sl + DEPTH - 1 : n_slices - 1;
             wait_vm((last - sl) * dma_per_slice);
             __builtin_amdgcn_s_barrier();
-            ATTN_STAMP(2);
             if (sl + DEPTH < n_slices) issue(sl + DEPTH);
         }
         bf16x8 xa[2][KS];
@@ -533,7 +481,6 @@ attn_fwd_big(AttnMfmaArgs a, const bf16_t* __restrict__ q, const bf16_t* __restr
             for (int s = 0; s < KS; ++s)
 #pragma unroll
                 for (int qt = 0; qt < NT; ++qt) c[kt][qt] = MFMA(xa[kt][s], qf[qt][s], s == 0 ? zero4 : c[kt][qt]);      // S^T [key 4g + r][query li]
-        ATTN_STAMP(3);
         bf16x8 pf[NT];
         bool any_rescale = false;
         float alpha[NT];
@@ -566,7 +513,6 @@ attn_fwd_big(AttnMfmaArgs a, const bf16_t* __restrict__ q, const bf16_t* __restr
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) ot[qt][dt] *= alpha[qt];
         }
-        ATTN_STAMP(4);
 #pragma unroll
         for (int dh = 0; dh < DT; dh += 2) {
             const int pp = (dh >> 1) & 1;
@@ -580,10 +526,8 @@ attn_fwd_big(AttnMfmaArgs a, const bf16_t* __restrict__ q, const bf16_t* __restr
             }
         }
     }
-    ATTN_STAMP(5);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();                                     // the last slice's reads: O is staged over the ring
-    ATTN_STAMP(6);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const float lt = group_sum(l[t]);
@@ -594,9 +538,7 @@ attn_fwd_big(AttnMfmaArgs a, const bf16_t* __restrict__ q, const bf16_t* __restr
         if (g == 0) lse[(int64_t)bh * a.T + own0 + 16 * t + li] = m[t] * 0.6931471805599453f + __logf(lt);   // back to the natural log
     }
     __syncthreads();
-    ATTN_STAMP(7);
     out_flush<HD>(stage, WGR, o + obase + (int64_t)blockIdx.x * WGR * a.o_st, a.o_st, a.hd);
-    ATTN_STAMP(8);
 }
 
 static AttnMfmaArgs mk_args_big(const vaw_attn_desc* d) {

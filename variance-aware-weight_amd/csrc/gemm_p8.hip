@@ -115,10 +115,9 @@ void vaw_p8_group_fp8(int ntw, bool a_e5m2, int nk, int grid, const EpiDev& e, c
 void vaw_g4_launch_group(int nk, int grid, const EpiDev& e, const P8Prob* probs_dev, const P8Group& grp, hipStream_t s);                       // gemm_g4.hip
 
 // Engine of the bf16 launches with 256-column tiles: 0 the 8-wave gemm_p8_kernel<..., GRP>, 1 the 4-wave gemm_g4_kernel (bitwise the
-// same results: tests/test_gpu_wgrad_engine.py), -1 by shape -- which is G4_BY_SHAPE for every such launch (DESIGN §6.0 round 7
+// same results: tests/test_gpu_wgrad_engine.py), -1 by shape -- which is the 4-wave kernel for every such launch (DESIGN §6.0 round 7
 // has the measurement behind it).  fp8 and 192-column groups run the 8-wave kernel whatever the switch says.
 // vaw_debug_wgrad_engine(mode) / VAW_WGRAD_ENGINE (read once, on first use).
-#define G4_BY_SHAPE 1
 static int g_wgrad_engine = -2;      // -2: environment not read yet
 static int wgrad_engine() {
     if (g_wgrad_engine == -2) {
@@ -212,7 +211,7 @@ extern "C" int vaw_wgrad_grouped(vaw_dtype dt, int n_problems, const vaw_wgrad_p
     if (f8) vaw_p8_group_fp8(ntw, dt == VAW_BF8, nk, grid, e, (const P8Prob*)desc_dev, grp, s);
     else if (ntw == 4) {
         const int eng = wgrad_engine();
-        if (eng == 1 || (eng < 0 && G4_BY_SHAPE)) vaw_g4_launch_group(nk, grid, e, (const P8Prob*)desc_dev, grp, s);
+        if (eng == 1 || eng < 0) vaw_g4_launch_group(nk, grid, e, (const P8Prob*)desc_dev, grp, s);
         else p8_launch_group<4>(nk, grid, e, (const P8Prob*)desc_dev, grp, s);
     } else p8_launch_group<3>(nk, grid, e, (const P8Prob*)desc_dev, grp, s);
     if (grp.t_rem > 0) {

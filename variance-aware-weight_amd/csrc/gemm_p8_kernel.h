@@ -38,54 +38,6 @@
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
-// -DP8_TIMING (tools/p8_timing.py, never in the product library): wave 0 and wave 4 of workgroup 0 accumulate s_memtime
-// deltas between the five points of a phase and leave them in the first bytes of their output rows.
-#ifdef P8_TIMING
-#define P8_TS(v) const uint64_t v = __builtin_readcyclecounter()
-#define P8_TACC(tA, tB, tC, tD, tE)                                                                       \
-    do { tacc[0] += tB - tA; tacc[1] += tC - tB; tacc[2] += tD - tC; tacc[3] += tE - tD; tacc[5] += 1;     \
-         if (tprev) tacc[4] += tA - tprev; tprev = tE; } while (0)
-#else
-#define P8_TS(v) do { } while (0)
-#define P8_TACC(tA, tB, tC, tD, tE) do { } while (0)
-#endif
-
-#ifndef P8_LATE_AT
-#define P8_LATE_AT 2
-#endif
-// P8_PH2 = 1: the plain k-major-A launches (forward / input gradients of the Linear layers) run TWO phases of 2 x 16 NTW / 4 MFMAs
-// per K tile instead of four of half that: the same DMA stream and LDS images, half the barriers and waits per MFMA
-#ifndef P8_PH2
-#define P8_PH2 0
-#endif
-// steps the epilogue's operand loads (residual, GELU' argument, gate) run ahead of their use
-// (0 = by epilogue kind: 3 for the GELU' input gradient, whose one 16-byte operand per step is the cheapest to hold, 2 otherwise.
-//  Measured on the DiT-B/4 launches, one box, interleaved: depth 1 -> 2 -> 3: GELU' input gradient 111.0 -> 104.7 -> 102.4 us,
-//  gated fc2 forward 99.4 -> 99.7 -> 97.0, step 13.42 -> 13.33 -> 13.37 ms; depth 3 spills 8 bytes in the 256-column gated kernel)
-#ifndef P8_EPI_PD
-#define P8_EPI_PD 0
-#endif
-// 1: the gated-residual epilogue (f32 in, f32 out) works on 4 columns per lane (see the epilogue).  Against the 8-column layout,
-// one box, interleaved: DiT-B/4 proj 53.7 -> 50.2 us, fc2 97.4 -> 94.0; DiT-XL/2 fp8 proj 132.4 -> 115.7, fc2 230.4 -> 217.4
-// (step 98.5 -> 97.5 ms)
-#ifndef P8_GATE_R4
-#define P8_GATE_R4 1
-#endif
-// 1: the same 4-column lanes for the raw f32 slabs of K-split launches (conv weight gradients, half-empty input gradients).  Measured
-// on the UNet_64 conv weight gradients (tools/conv_bench.py, interleaved): +-1 %, i.e. nothing -- the slabs are re-read at once and
-// live in L2 / MALL; off.
-#ifndef P8_SLAB_R4
-#define P8_SLAB_R4 0
-#endif
-// 1: the DMA stream never "ends": past its last item it keeps issuing pieces at out-of-range offsets (zeros into a stage nobody
-// reads), so the K loop needs neither the per-piece `if (iss_done)` nor the two forms of every counted wait -- 12 scalar branches
-// per K tile gone (lesson of gemm_pd_kernel.h, where such branches cost 25 %)
-#ifndef P8_NOBR
-#define P8_NOBR 1
-#endif
-#ifndef P8_NOBR_CONV3
-#define P8_NOBR_CONV3 1
-#endif
 #define P8_BM 256
 #define P8_PART 8192
 #define P8_EPI_BYTES 32768
@@ -108,11 +60,7 @@ struct P8Conv {
 };
 
 __device__ __forceinline__ void p8_dma16(__amdgpu_buffer_rsrc_t rs, char* lds_dst, unsigned voff, unsigned soff) {
-#ifdef P8_ABLATE_DMA       // measurement builds only (tools/p8_timing.py): the main loop without its global -> LDS traffic
-    asm volatile("" :: "v"(voff), "s"(soff));
-#else
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)lds_dst, 16, voff, soff, 0, 0);
-#endif
 }
 
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
@@ -130,6 +78,19 @@ template <int NTW> struct P8Cfg {
     static constexpr int stage_bytes = (4 + NTW) * P8_PART;
     static constexpr int lds_bytes = 2 * stage_bytes + P8_EPI_BYTES;
 };
+
+// vmcnt of the counted wait that ends phase j (0-3) of a K tile: the DMA pieces younger than the part the NEXT phase reads
+// (table in DESIGN.md §5; a set = the LS = 4 + NTW pieces of one K tile, stream order S0.. = B parts, then A parts 0-3; phases
+// 0 / 1 finish set kt + 1 with S4,S5 | S6(,S7), phases 2 / 3 start set kt + 2 with S0,S1 | S2,S3):
+//   phase 0 -> A1(kt):       the two last pieces of set kt + S0-S5(kt+1)         = 8
+//   phase 1 -> A2(kt):       the last piece of set kt + all of set kt + 1        = LS + 1
+//   phase 2 -> A3(kt):       all of set kt + 1 + S0,S1(kt+2)                     = LS + 2
+//   phase 3 -> B, A0(kt+1):  the three last pieces of set kt + 1 + S0-S3(kt+2)   = 7
+// LATE: the phase's own pieces (2, LS - 6, 2, 2) go out after the wait, between its MFMAs, so the wait counts that many fewer.
+template <int LS, bool LATE> constexpr int p8_vmcnt(int j) {
+    const int full[4] = {8, LS + 1, LS + 2, 7}, own[4] = {2, LS - 6, 2, 2};
+    return full[j] - (LATE ? own[j] : 0);
+}
 
 __device__ __forceinline__ int p8_mn_swz(int k) { return (((k >> 1) & 1) | (((k >> 3) & 1) << 1)) << 1; }
 
@@ -162,10 +123,6 @@ __device__ __forceinline__ bf16x8 p8_frag(const char* part, int r16, int s, int 
     if (KMAJOR) {
         const int row = r16 + (lane & 15);
         const int chunk = (4 * s + (lane >> 4)) ^ ((row >> 1) & 7);
-#ifdef P8_ABLATE_FRAG      // measurement builds only: no LDS fragment reads (operands = address bits)
-        const float f = (float)(row + chunk);
-        return bf16x8{(bf16_t)f, (bf16_t)f, (bf16_t)f, (bf16_t)f, (bf16_t)f, (bf16_t)f, (bf16_t)f, (bf16_t)f};
-#endif
         return *reinterpret_cast<const bf16x8*>(part + row * 128 + (chunk << 4));
     } else {
         const int li = lane & 15, q = li >> 2, p = li & 3;
@@ -223,7 +180,10 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
     static_assert(CONV == 0 || (CONV == 1 && AK && BKM) || (CONV == 2 && AK && !BKM) || (CONV == 3 && !AK && !BKM), "conv layouts");
     using Cfg = P8Cfg<NTW>;
     constexpr int LS = 4 + NTW;                                  // DMA pieces per wave and K tile
-    constexpr bool NOBR = P8_NOBR != 0 && (CONV != 3 || (P8_NOBR_CONV3 != 0 && NTW == 3));   // (the 256-column transposed conv weight gradient spills with it)
+    // NOBR: the DMA stream never "ends": past its last item it keeps issuing pieces at out-of-range offsets (zeros into a stage
+    // nobody reads), so the K loop needs neither the per-piece `if (iss_done)` nor the two forms of every counted wait -- 12 scalar
+    // branches per K tile gone (lesson of gemm_pd_kernel.h, where such branches cost 25 %)
+    constexpr bool NOBR = CONV != 3 || NTW == 3;   // (the 256-column transposed conv weight gradient spills with it)
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 stages][A parts 0-3 | B parts] | 8 x 4 KiB epilogue images
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -366,7 +326,7 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
         for (int p = 0; p < NTW; ++p) off_b[p] = p8_src_off<BKM, ES, F8 != 0>(false, p, wid, lane, t.ldb, nvalid);
     };
     if (!iss_done) iss_open();
-    auto iss_close = [&]() {                      // P8_NOBR: every later piece reads out of range
+    auto iss_close = [&]() {                      // NOBR: every later piece reads out of range
 #pragma unroll
         for (int p = 0; p < 4; ++p) off_a[p] = EPI_OOB;
 #pragma unroll
@@ -433,7 +393,7 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
     auto issue_ph2 = [&]() { P8_PIECE(6); if (LS == 8) P8_PIECE(LS - 1); iss_advance(); };
     auto issue_ph3 = [&]() { P8_PIECE(0); P8_PIECE(1); };
     auto issue_ph4 = [&]() { P8_PIECE(2); P8_PIECE(3); };
-    // counted waits: pieces younger than the one the NEXT phase reads (derivation in DESIGN.md §5).
+    // counted waits: pieces younger than the one the NEXT phase reads (p8_vmcnt above).
     // LATE (gather modes and mn-major A -- convs and weight gradients): a phase's two pieces are issued between the two halves of
     // its MFMAs instead of before its wait, so their address arithmetic and any issue stall run under MFMAs already in the pipe
     // (UNet_64 step -4.9 %, plain weight gradients +6 %); the wait then counts two pieces fewer.  Plain k-major A keeps the early
@@ -442,7 +402,7 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
 #define P8_WAIT(n_full)                                                                     \
     do {                                                                                    \
         if (!NOBR && iss_done) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              \
-        else asm volatile("s_waitcnt vmcnt(" #n_full ")" ::: "memory");                     \
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_full) : "memory");                  \
     } while (0)
 
     // prologue: K tile 0 of the stream completely, the ph3/ph4 slots of K tile 1
@@ -459,20 +419,13 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
         while (__builtin_amdgcn_s_memrealtime() - t0 < (uint64_t)team_delay) __builtin_amdgcn_s_sleep(16);
     }
-    constexpr bool PH2 = P8_PH2 != 0 && CONV == 0 && AK && F8 == 0 && !GRP;
-    if (PH2) P8_WAIT(6); else P8_WAIT(7);          // (PH2's first phase also reads A part 1)
+    P8_WAIT(7);
     __builtin_amdgcn_s_barrier();
 
     int stage = 0;
     const int wn0 = wc * Cfg::WN;
-#ifdef P8_TIMING
-    uint64_t tacc[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
-#endif
     for (; it_cur < n_items; it_cur += G) {
         const P8Item item = decode(it_cur);
-#ifdef P8_TIMING
-        tprev = 0;
-#endif
         const int split = item.split, tm = item.tm, nk = item.nk;
         const int64_t m0 = item.m0, n0 = item.n0;
         // per-item view of the epilogue descriptor: in grouped mode the output tensor changes from item to item
@@ -536,7 +489,7 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
                 /* this phase's two DMA pieces go out between the two halves of its MFMAs: an issue stall (the texture \
                    addresser takes 16 cycles per wave-instruction) then overlaps MFMAs already in the pipe */          \
                 _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                                       \
-                    if (2 * s + t == P8_LATE_AT) { ISSUE; }     /* quarter of the MFMA block after which the pieces go out */ \
+                    if (2 * s + t == 2) { ISSUE; }             /* quarter of the MFMA block after which the pieces go out */ \
                     _Pragma("unroll") for (int u = 0; u < NTW; ++u)                                                   \
                         acc[2 * (j) + t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[s][u], af[s][t], acc[2 * (j) + t][u], 0, 0, 0); \
                 }                                                                                                     \
@@ -549,122 +502,35 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
                 _Pragma("unroll") for (int u = 0; u < NTW; ++u) asm volatile("" : "+v"(acc[2 * (j) + t][u]));        \
         }                                                                                                             \
     } while (0)
-            if constexpr (PH2) {
-                // ---- two phases per K tile.  Phase A: B fragments of the whole K tile, A quarters 0 and 1, the stream's pieces
-                // NTW .. LS-1 of the NEXT K tile (its A parts); phase B: A quarters 2 and 3, pieces 0 .. 3 of the K tile after
-                // (B parts (+ A part 0)).  Counted waits (pieces younger than the last one the next phase reads): end of A -- the
-                // whole next set = LS; end of B -- the last two A parts of the next set + the four just issued = 6.
-                // Every wave waits for ITS fragment reads before the barrier: the other wave row issues DMA into the parts they
-                // came from right behind that barrier (in the four-phase schedule a whole phase lies between).
-                bf16x8 af4[2][4];
-                auto load_a2 = [&](int h) {
-#pragma unroll
-                    for (int jq = 0; jq < 2; ++jq)
-#pragma unroll
-                        for (int t = 0; t < 2; ++t)
-#pragma unroll
-                            for (int s = 0; s < 2; ++s)
-                                af4[s][2 * jq + t] = p8_frag<AK>(st + (2 * h + jq) * P8_PART, wr * 32 + 16 * t, s, lane_k);
-                };
-#define P8_MMA2(h)                                                                                                    \
+            // Four phases per K tile.  tried: two phases of twice the MFMAs for the plain k-major-A launches (half the barriers and
+            // counted waits per MFMA); measured: the eight DiT-B/4 shapes -7 ... +3 %, the step +-0.1 % -- the loop is paced by the bytes
+            // in flight between L2 and LDS, not by barriers.
+            // phase j (0-3; its DMA slots are issue_ph<j + 1>): fragments of A quarter j -> this phase's two DMA pieces (LATE: between
+            // its MFMAs) -> counted wait for the part the next phase reads -> barrier -> MFMAs -> barrier
+#define P8_PHASE(j, issue)                                                                                            \
     do {                                                                                                              \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                            \
-        __builtin_amdgcn_s_setprio(1);                                                                                \
-        _Pragma("unroll") for (int s = 0; s < 2; ++s)                                                                 \
-            _Pragma("unroll") for (int i4 = 0; i4 < 4; ++i4)                                                          \
+        load_a(j);                                                                                                    \
+        if (!LATE) issue();                                                                                           \
+        P8_WAIT((p8_vmcnt<LS, LATE>(j)));                                                                             \
+        __builtin_amdgcn_s_barrier();                                                                                 \
+        P8_MMA(j, if (LATE) issue());                                                                                 \
+        if (j == 0 && CONV == 3 && do_colsum_b) {      /* column sums of the B tile (dy): B . ones -- every column of the result holds them */ \
+            _Pragma("unroll") for (int s = 0; s < 2; ++s)                                                             \
                 _Pragma("unroll") for (int u = 0; u < NTW; ++u)                                                       \
-                    acc[4 * (h) + i4][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[s][u], af4[s][i4], acc[4 * (h) + i4][u], 0, 0, 0); \
-        __builtin_amdgcn_s_setprio(0);                                                                                \
+                    accb[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[s][u], ones8, accb[u], 0, 0, 0);           \
+        }                                                                                                             \
+        __builtin_amdgcn_s_barrier();                                                                                 \
     } while (0)
 #pragma unroll
-                for (int u = 0; u < NTW; ++u) {
-                    const int n = wn0 + 16 * u;
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) bfr[s][u] = p8_frag<BKM>(st + Cfg::a_bytes + (n >> 6) * P8_PART, n & 63, s, lane_k);
-                }
-                load_a2(0);
-                issue_ph1();
-                issue_ph2();
-                if (LS == 8) P8_WAIT(8); else P8_WAIT(7);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                P8_MMA2(0);
-                __builtin_amdgcn_s_barrier();
-                load_a2(1);
-                issue_ph3();
-                issue_ph4();
-                P8_WAIT(6);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                P8_MMA2(1);
-                __builtin_amdgcn_s_barrier();
-                continue;
-            }
-            // ---- phase 1: B fragments of the whole K tile + A quarter 0
-#pragma unroll
-            for (int u = 0; u < NTW; ++u) {
+            for (int u = 0; u < NTW; ++u) {         // B fragments of the whole K tile
                 const int n = wn0 + 16 * u;
 #pragma unroll
                 for (int s = 0; s < 2; ++s) bfr[s][u] = p8_frag<BKM>(st + Cfg::a_bytes + (n >> 6) * P8_PART, n & 63, s, lane_k);
             }
-            P8_TS(t1a);
-            load_a(0);
-            if (!LATE) issue_ph1();
-            P8_TS(t1b);
-            if (LATE) P8_WAIT(6); else P8_WAIT(8);
-            P8_TS(t1c);
-            __builtin_amdgcn_s_barrier();
-            P8_TS(t1d);
-            P8_MMA(0, if (LATE) issue_ph1());
-            if (CONV == 3 && do_colsum_b) {      // column sums of the B tile (dy): B . ones -- every column of the result holds them
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                    for (int u = 0; u < NTW; ++u) accb[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[s][u], ones8, accb[u], 0, 0, 0);
-            }
-            P8_TS(t1e);
-            P8_TACC(t1a, t1b, t1c, t1d, t1e);
-            __builtin_amdgcn_s_barrier();
-            // ---- phase 2
-            P8_TS(t2a);
-            load_a(1);
-            if (!LATE) issue_ph2();
-            P8_TS(t2b);
-            if (LATE) P8_WAIT(7); else if (LS == 8) P8_WAIT(9); else P8_WAIT(8);
-            P8_TS(t2c);
-            __builtin_amdgcn_s_barrier();
-            P8_TS(t2d);
-            P8_MMA(1, if (LATE) issue_ph2());
-            P8_TS(t2e);
-            P8_TACC(t2a, t2b, t2c, t2d, t2e);
-            __builtin_amdgcn_s_barrier();
-            // ---- phase 3
-            P8_TS(t3a);
-            load_a(2);
-            if (!LATE) issue_ph3();
-            P8_TS(t3b);
-            if (LATE) { if (LS == 8) P8_WAIT(8); else P8_WAIT(7); } else { if (LS == 8) P8_WAIT(10); else P8_WAIT(9); }
-            P8_TS(t3c);
-            __builtin_amdgcn_s_barrier();
-            P8_TS(t3d);
-            P8_MMA(2, if (LATE) issue_ph3());
-            P8_TS(t3e);
-            P8_TACC(t3a, t3b, t3c, t3d, t3e);
-            __builtin_amdgcn_s_barrier();
-            // ---- phase 4
-            P8_TS(t4a);
-            load_a(3);
-            if (!LATE) issue_ph4();
-            P8_TS(t4b);
-            if (LATE) P8_WAIT(5); else P8_WAIT(7);
-            P8_TS(t4c);
-            __builtin_amdgcn_s_barrier();
-            P8_TS(t4d);
-            P8_MMA(3, if (LATE) issue_ph4());
-            P8_TS(t4e);
-            P8_TACC(t4a, t4b, t4c, t4d, t4e);
-            __builtin_amdgcn_s_barrier();
+            P8_PHASE(0, issue_ph1);
+            P8_PHASE(1, issue_ph2);
+            P8_PHASE(2, issue_ph3);
+            P8_PHASE(3, issue_ph4);
         }
         if (wr == 0) __builtin_amdgcn_s_barrier();       // level the two wave rows: both run their epilogues together
 
@@ -734,36 +600,15 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
                     : epi_rsrc(EK::out_q ? (const void*)((const unsigned char*)ei.C + tile_off)
                                          : c_f32 ? (const void*)((const float*)ei.C + tile_off) : (const void*)((const bf16_t*)ei.C + tile_off));
         const __amdgpu_buffer_rsrc_t rs_aux = epi_rsrc(EK::aux_out(ei) ? (const void*)((const bf16_t*)ei.aux_out + tile_off) : (const void*)ei.C);
-        if constexpr (EPI == P8_SLAB && P8_SLAB_R4 != 0 && !GRP) {
-            // ---- raw f32 partial sums of a K split, FOUR columns per lane: one 16-byte store per lane and row, 16 lanes = one
-            // 256-byte row piece of the slab (the 8-column layout writes every other 16 bytes of a row per instruction)
-            const int r4 = lane_e >> 4, c4 = lane_e & 15;
-            const int64_t n4 = n0 + wn0 + 4 * c4;
-            const bool col_ok4 = 4 * c4 < Cfg::WN && n4 < ei.N;
-            const int loc_col4 = wn0 + 4 * c4;
-            const int64_t mrow4 = m0 + wr * 128 + r4, m_last4 = ei.M - 1;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                for (int u = 0; u < NTW; ++u)
-                    asm volatile("ds_write_b128 %0, %1" ::"v"(ep_w + (unsigned)(((4 * u) ^ (wr_row & 12)) << 4)), "v"(acc[i][u]) : "memory");
-#pragma unroll
-                for (int pass = 0; pass < 4; ++pass) {
-                    const int64_t m = mrow4 + 4 * (4 * i + pass);
-                    const int rr = 4 * pass + r4;
-                    f32x4 v;
-                    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(ep_base + (unsigned)(rr * 256 + ((c4 ^ rr) << 4))) : "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    const bool ok = col_ok4 && m <= m_last4;
-                    buf_store16(rs_c, ok ? 4u * (unsigned)((m - m0) * slab_ld + loc_col4) : EPI_OOB, v, false);
-                }
-            }
-            continue;
-        }
-        if constexpr (EPI == P8_GATE && P8_GATE_R4 != 0) {
+        if constexpr (EPI == P8_GATE) {
             // ---- gated-residual epilogue, FOUR columns per lane: the f32 output (and the f32 residual it reads) then moves as
             // whole 256-byte row pieces per 16 lanes -- one 16-byte access per lane and row -- where the 8-column layout below
             // issues two accesses per lane that each touch every other 16 bytes of the row.  32 steps of 4 rows; operands 4 steps ahead.
+            // tried: the 8-column layout for this kind too; measured, one box, interleaved, 8 -> 4 columns: DiT-B/4 proj 53.7 -> 50.2 us,
+            // fc2 97.4 -> 94.0; DiT-XL/2 fp8 proj 132.4 -> 115.7, fc2 230.4 -> 217.4 (step 98.5 -> 97.5 ms).
+            // tried: the same 4-column lanes for the raw f32 slabs of K-split launches (conv weight gradients, half-empty input
+            // gradients); measured on the UNet_64 conv weight gradients (tools/conv_bench.py, interleaved): +-1 %, i.e. nothing -- the
+            // slabs are re-read at once and live in L2 / MALL; they keep the 8-column layout below.
             const int r4 = lane_e >> 4, c4 = lane_e & 15;
             const int64_t n4 = n0 + wn0 + 4 * c4;
             const bool col_ok4 = 4 * c4 < Cfg::WN && n4 < ei.N;
@@ -842,8 +687,11 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
         unsigned smp = 0, rin = 0;
         // operand loads run PD steps ahead of the step that uses them (ring of PD + 1 operand sets).  vmcnt retires in order and
         // counts stores: the wait for step k's operands also waits for every store issued before their load, i.e. for the stores
-        // of step k - PD - 1 and older -- the depth is the slack the stores get to be acknowledged
-        constexpr int PD = P8_EPI_PD > 0 ? P8_EPI_PD : (EPI == P8_DGELU || EPI == P8_DGELU_Q) ? 3 : 2;
+        // of step k - PD - 1 and older -- the depth is the slack the stores get to be acknowledged.  3 for the GELU' input gradient,
+        // whose one 16-byte operand per step is the cheapest to hold, 2 otherwise.  tried: depths 1 / 2 / 3 for every kind; measured on
+        // the DiT-B/4 launches, one box, interleaved: GELU' input gradient 111.0 -> 104.7 -> 102.4 us, gated fc2 forward 99.4 -> 99.7 ->
+        // 97.0, step 13.42 -> 13.33 -> 13.37 ms; depth 3 spills 8 bytes in the 256-column gated kernel
+        constexpr int PD = (EPI == P8_DGELU || EPI == P8_DGELU_Q) ? 3 : 2;
         EpiOps ops[PD + 1];
         const bool with_ops = EK::loads && (EK::act2(ei) || EK::gate(ei) || EK::resid(ei) || EK::rowadd(ei));
         int64_t m_ld = mrow0;                // row of the next operand load
@@ -936,13 +784,6 @@ gemm_p8_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
         }
     }
     if (NOBR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the stream's trailing out-of-range pieces still target this workgroup's LDS
-#ifdef P8_TIMING
-    if (blockIdx.x == 0 && lane == 0 && (wid == 0 || wid == 4)) {
-        __builtin_amdgcn_s_waitcnt(0);
-        uint64_t* out = reinterpret_cast<uint64_t*>((char*)e.C + (int64_t)(wid == 4 ? 128 : 0) * e.ldc * (e.out_f32 ? 4 : 2));
-        for (int i = 0; i < 6; ++i) out[i] = tacc[i];
-    }
-#endif
 }
 
 

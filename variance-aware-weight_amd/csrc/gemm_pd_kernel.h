@@ -28,18 +28,12 @@
 #include "gemm_p8_kernel.h"
 
 #define PD_BM 128
-// measurement / bisecting builds only (make exp XSRC="gemm_pd gemm_pd_dgrad" XF=-DPD_DBG=n): 1 = K loops only, nothing parked or stored;
-// 2 = no bias load; 3 = parked tiles leave in the open (no drain slots inside the K loop); 4 = every drain store out of range (dropped)
-#ifndef PD_DBG
-#define PD_DBG 0
-#endif
-// 1: ONE barrier per K tile.  With three ring stages a piece is issued into the stage that was read a whole K tile ago, so the
-// barrier that makes a K tile's pieces visible to every wave also proves that everybody has left the stage the next pieces go
-// into: wait -> barrier -> issue the whole set two K tiles ahead -> all fragment reads of the K tile -> 8 NTW MFMAs, the waves
-// free-running in between (no phase structure, no wave-row stagger).  0: the two-phase, four-barrier form.
-#ifndef PD_ONEBAR
-#define PD_ONEBAR 0
-#endif
+// The K tile is the two-phase, four-barrier form.  tried: ONE barrier per K tile (with three ring stages the barrier that makes a K
+// tile's pieces visible also proves that everybody has left the stage the next pieces go into: wait -> barrier -> issue the whole set
+// two K tiles ahead -> all fragment reads -> 8 NTW MFMAs, no phases, no wave-row stagger); measured: bitwise the same results, +-3 %
+// on every shape (K = 3072 input gradient 78.0 vs 75.9 us) -- the barriers were not the limit.
+// tried: the parked tile leaving in the open after the K loop, and every drain store dropped; measured: draining under the K loop
+// costs about what it hides (a store-only drain nets -6 %, VALU-heavy ones lose), and without its stores the kernel is no faster.
 template <int NTW> struct PdCfg {
     static constexpr int BN = 64 * NTW, WN = 16 * NTW;
     static constexpr int LS = 2 + NTW;                      // DMA pieces per wave and K tile: B parts 0..NTW-1, A parts 0, 1
@@ -319,7 +313,7 @@ gemm_pd_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
                 asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(w) : "v"(ra) : "memory");
                 __builtin_amdgcn_sched_barrier(0);
                 const int row = 16 * I + rs;
-                const bool ok = PD_DBG != 4 && cok && row < mrem;
+                const bool ok = cok && row < mrem;
                 const unsigned loc = (unsigned)((wr * 64 + row) * e.ldc + wc * WN + 4 * c4);
                 if (!e.nt_off || e.nt_aux) __builtin_amdgcn_raw_buffer_store_b64(w, rs_aux, ok ? 2u * loc : EPI_OOB, 0, 2);
                 else __builtin_amdgcn_raw_buffer_store_b64(w, rs_aux, ok ? 2u * loc : EPI_OOB, 0, 0);
@@ -341,7 +335,7 @@ gemm_pd_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
             __builtin_amdgcn_sched_barrier(0);
             if (p == 1) w = u32x4_t{w[2], w[3], w[0], w[1]};             // rows 8-15: the 8-byte halves of a chunk are stored swapped
             const int row = 16 * I + 8 * p + rd_row;
-            const bool ok = PD_DBG != 4 && col_ok && row < mrem;
+            const bool ok = col_ok && row < mrem;
             const unsigned loc = (unsigned)((wr * 64 + row) * e.ldc + wc * WN + 8 * c8);
             if (EPI == P8_GELU) {
                 buf_store16(rs_aux, ok ? 2u * loc : EPI_OOB, __builtin_bit_cast(f32x4, w), !e.nt_off || e.nt_aux);
@@ -385,7 +379,7 @@ gemm_pd_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
         int tm, tn;
         decode(it_cur, tm, tn);
         const int64_t m0 = (int64_t)tm * PD_BM, n0 = (int64_t)tn * Cfg::BN;
-        if (PD_DBG != 2 && PD_DBG != 1 && EPI != P8_DGELU && e.bias) {     // in flight during the K loop (>= 4 K tiles: covered by its counted waits long before the park)
+        if (EPI != P8_DGELU && e.bias) {     // in flight during the K loop (>= 4 K tiles: covered by its counted waits long before the park)
             const int col = lane < WN ? lane : 0;
             pd_load4<PD_R_BIAS>(pd_uniform(e.bias), (n0 + wn0 + col < e.N) ? 4u * (unsigned)(n0 + wn0 + col) : 0u);
         }
@@ -394,7 +388,7 @@ gemm_pd_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int u = 0; u < NTW; ++u) acc[i][u] = f32x4{0, 0, 0, 0};
-        if (!PD_ONEBAR && wr == 1) __builtin_amdgcn_s_barrier();       // waves 4-7 run half a phase behind waves 0-3
+        if (wr == 1) __builtin_amdgcn_s_barrier();       // waves 4-7 run half a phase behind waves 0-3
         int lane_k = lane;
         asm volatile("" : "+v"(lane_k));
         // One K tile.  J >= 0: the J-th K tile of an item whose predecessor is parked -- its drain slot J (J < DMAX) runs in phase 2 and
@@ -404,7 +398,7 @@ gemm_pd_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
         // paid for ~10 taken branches, 96.7 against 75.5 us on the K = 3072 input gradient with the stores switched off).
         auto ktile = [&](auto jj) __attribute__((always_inline)) {
             constexpr int J = decltype(jj)::value;
-            constexpr auto live = [](int j) { return (J >= 0 && j >= 0 && j < DMAX && PD_DBG != 3) ? 1 : 0; };
+            constexpr auto live = [](int j) { return (J >= 0 && j >= 0 && j < DMAX) ? 1 : 0; };
             constexpr int C1 = live(J - 2) + live(J - 1), C2 = live(J - 1) + live(J);
             const char* st = smem + cstage * Cfg::stage_bytes;
             cstage = cstage == 2 ? 0 : cstage + 1;
@@ -428,32 +422,6 @@ gemm_pd_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
                     acc[2 * (j) + t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[s][u], af[s][t], acc[2 * (j) + t][u], 0, 0, 0); \
         __builtin_amdgcn_s_setprio(0);                                                                                \
     } while (0)
-            if (PD_ONEBAR) {
-                pd_vmwait<LS + C1 * ND>();     // every piece of this K tile's set (its last one was issued two K tiles ago); younger: the next set
-                __builtin_amdgcn_s_barrier();
-                issue_p1();
-                issue_p2();
-                bf16x8 af1[2][2];
-#pragma unroll
-                for (int u = 0; u < NTW; ++u) {
-                    const int n = wn0 + 16 * u;
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) bfr[s][u] = p8_frag<BKM>(st + Cfg::a_bytes + (n >> 6) * P8_PART, n & 63, s, lane_k);
-                }
-                load_a(0);
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) af1[s][t] = p8_frag<true>(st + P8_PART, wr * 32 + 16 * t, s, lane_k);
-                if (live(J)) run_slot(std::integral_constant<int, (J >= 0 && J < DMAX ? J : 0)>{}, std::false_type{});
-                PD_MMA(0);
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) af[s][t] = af1[s][t];
-                PD_MMA(1);
-                return;
-            }
             // ---- phase 1: B fragments of the whole K tile, A rows 0-31 of the wave's 64; pieces B0-B2 of the set two K tiles ahead
 #pragma unroll
             for (int u = 0; u < NTW; ++u) {
@@ -477,22 +445,18 @@ gemm_pd_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
             __builtin_amdgcn_s_barrier();
         };
         int kt = 0;
-        if (parked && PD_DBG != 3) {           // (the host guarantees nk >= DMAX + 2)
+        if (parked) {         // (the host guarantees nk >= DMAX + 2)
             pd_unroll(ktile, std::make_integer_sequence<int, DMAX + 2>{});
             kt = DMAX + 2;
         }
         for (; kt < nk; ++kt) ktile(std::integral_constant<int, -1>{});
-        if (!PD_ONEBAR && wr == 0) __builtin_amdgcn_s_barrier();       // level the two wave rows
-        // ---- the finished tile is parked (measurement builds with PD_DBG = 3 drain the previous one in the open first) ----
-        if (PD_DBG == 3 && parked) {
-            pd_unroll([&](auto dd) __attribute__((always_inline)) { run_slot(dd, std::true_type{}); }, std::make_integer_sequence<int, DMAX>{});
-            pd_vmwait<0>();
-        }
+        if (wr == 0) __builtin_amdgcn_s_barrier();       // level the two wave rows
+        // ---- the finished tile is parked ----
         {
             int lane_p = lane;
             asm volatile("" : "+v"(lane_p));
             const int g = lane_p >> 4;
-            const float bv = (PD_DBG != 2 && PD_DBG != 1 && EPI != P8_DGELU && e.bias) ? pd_take4<PD_R_BIAS>() : 0.f;
+            const float bv = (EPI != P8_DGELU && e.bias) ? pd_take4<PD_R_BIAS>() : 0.f;
 #pragma unroll
             for (int u = 0; u < NTW; ++u) {
                 f32x4 b4 = {0, 0, 0, 0};
@@ -523,7 +487,7 @@ gemm_pd_kernel(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restri
                 g_rin = r0 % (unsigned)e.rpb;
             }
         }
-        parked = PD_DBG != 1;
+        parked = true;
     }
     // the last tile of this workgroup: nothing left to hide it under
     if (parked) pd_unroll([&](auto dd) __attribute__((always_inline)) { run_slot(dd, std::true_type{}); }, std::make_integer_sequence<int, DMAX>{});

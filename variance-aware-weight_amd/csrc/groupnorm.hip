@@ -20,14 +20,10 @@
 // ---------------------------------------------------------------------------------------------
 #define GN_ROWS 512
 // SiLU and its derivative through v_rcp_f32 (1 ulp) instead of an IEEE division (~10 more instructions per element): the
-// GroupNorm passes are close enough to VALU-bound at 4 waves per SIMD for that to show (GN_FAST_SILU=0: the exact forms)
-#ifndef GN_FAST_SILU
-#define GN_FAST_SILU 1
-#endif
+// GroupNorm passes are close enough to VALU-bound at 4 waves per SIMD for that to show
 __device__ __forceinline__ float gn_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float gn_silu(float x) { return GN_FAST_SILU ? x * gn_sigmoid(x) : silu_f(x); }
+__device__ __forceinline__ float gn_silu(float x) { return x * gn_sigmoid(x); }
 __device__ __forceinline__ float gn_silu_grad(float x) {
-    if (!GN_FAST_SILU) return silu_grad_f(x);
     const float s = gn_sigmoid(x);
     return s * (1.f + x * (1.f - s));
 }

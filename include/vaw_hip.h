@@ -523,7 +523,11 @@ int vaw_gemm(vaw_dtype dt, int a_kmajor, int b_kmajor, int64_t M, int64_t N, int
  * f32 slab; all layers together give enough whole tiles for every CU, and only the tiles of the last, partial round are
  * K-split (folded in a fixed order: results do not depend on scheduling).
  * problems: HOST array; desc_dev: device scratch of vaw_wgrad_grouped_desc_bytes(n) bytes that holds the device copy
- * of the table -- upload != 0 (re)writes it on `stream` (pass 1 the first time and whenever a pointer changed).
+ * of the table -- upload != 0 (re)writes it on `stream` (pass 1 the first time and whenever a pointer changed).  An upload
+ * goes through a pinned staging buffer taken from a pool and returned to it once the copy has completed, so uploading often
+ * costs no pinned memory beyond what is in flight at once; the first upload of a table needs memory the pool may have to
+ * allocate, which a global-mode stream capture refuses (make a group's first launch outside the capture; later launches with
+ * upload == 0 capture).  The same holds for vaw_reduce_rows_batched and vaw_fp8_quantize_delayed_batched.
  * workspace: f32 slabs for the K-split tiles (256 * 256 * n_CUs floats are always enough; smaller ones lower the split). */
 typedef struct {
     const void* dy;        /* act dtype (bf16) [K][M], row stride ld_dy */
@@ -566,8 +570,8 @@ int vaw_fp8_quantize_delayed(vaw_dtype src_dt, vaw_dtype dst_format, const void*
 int vaw_fp8_scale_update(float* states, int64_t n, vaw_stream stream);
 /* vaw_fp8_quantize_delayed for MANY f32 tensors in one launch (e4m3): the once-per-step re-quantisation of all Linear weights from
  * their f32 masters (the reference's autocast casts the same weights to bf16 on every use, tools/trainer.py:104-108).  jobs: host
- * array; desc_dev: device buffer of vaw_fp8_quantize_batched_desc_bytes(n_jobs) bytes, written when upload != 0 (addresses are
- * static between steps).  Bytes, transposed copies and running maxima equal the per-tensor calls'. */
+ * array; desc_dev: device buffer of vaw_fp8_quantize_batched_desc_bytes(n_jobs) bytes, written when upload != 0 (as for
+ * vaw_wgrad_grouped; the addresses are static between steps).  Bytes, transposed copies and running maxima equal the per-tensor calls'. */
 typedef struct {
     const float* src;      /* f32 [R][C], row stride ld */
     void* q;               /* e4m3 bytes [R][C], row stride ldq */
@@ -701,8 +705,8 @@ int vaw_reduce_rows(const float* partial, int64_t R, int64_t N, float* out, floa
  * vaw_reduce_rows' summation tree (bitwise the same results).  Used for the bias gradients of all Linear layers of a group of
  * DiT blocks (autograd of `x W^T + b`, models/dit.py:126-137: db = sum_rows dy), whose partial rows the dy-producing kernels
  * leave behind: one launch per group instead of one per layer.  jobs: host array; desc_dev: device buffer of
- * vaw_reduce_rows_batched_desc_bytes(n_jobs) bytes that receives the table when upload != 0 (addresses are static between
- * steps: upload once). */
+ * vaw_reduce_rows_batched_desc_bytes(n_jobs) bytes that receives the table when upload != 0 (as for vaw_wgrad_grouped: once
+ * per table; a table whose row counts or addresses moved is a new table). */
 typedef struct {
     const float* partial;  /* f32 [R][N] */
     float* out;            /* f32 [N] */
@@ -1188,6 +1192,9 @@ void vaw_debug_gn_flat(int mode);
 /* n_wgs (1 ... 256) workgroups that each hold a whole CU idle for `microseconds` (<= 2 s) on `stream`: a stand-in for a collective
  * kernel beside the compute kernels (tools/contention_bench.py) */
 int vaw_debug_cu_hog(int n_wgs, int microseconds, vaw_stream stream);
+/* The pinned staging buffers of the descriptor-table uploads (upload != 0 above), process-wide: how many were ever allocated, their
+ * bytes, and how many of them a stream capture holds for good (the others are recycled).  Any pointer may be NULL.  For tests. */
+void vaw_debug_upload_table_stats(int64_t* buffers, int64_t* bytes, int64_t* captured);
 
 #ifdef __cplusplus
 }

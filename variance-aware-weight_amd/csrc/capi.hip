@@ -84,24 +84,71 @@ extern "C" int vaw_debug_cu_hog(int n_wgs, int microseconds, vaw_stream stream) 
     return VAW_OK;
 }
 
-// One-time uploads of descriptor tables (vaw_wgrad_grouped, vaw_reduce_rows_batched, vaw_fp8_quantize_delayed_batched): the callers
-// build the table in a reused pageable array, and an asynchronous copy from pageable memory is only guaranteed to have been STAGED
-// when the call returns for small sizes -- a later call that rewrites the array could corrupt a table that is uploaded exactly once.
-// The table is therefore copied into a pinned buffer of its own that is never reused (a few KiB per group, groups are built once per
-// workspace) and the asynchronous copy reads from there: no host synchronisation, legal inside a stream capture.
+// Uploads of descriptor tables (vaw_wgrad_grouped, vaw_reduce_rows_batched, vaw_fp8_quantize_delayed_batched).  The callers build the
+// table in a reused pageable array, and an asynchronous copy from pageable memory is only guaranteed to have been STAGED when the
+// call returns for small sizes -- a later call that rewrites the array could corrupt a table in flight.  The table is therefore
+// copied into a pinned buffer and the asynchronous copy reads from there: no host synchronisation.
+// Groups are built again and again over a long run (row counts that alternate, activation addresses that move), so the pinned
+// buffers are recycled: a pool of {pointer, size class, device, event}.  Size classes are powers of two from 4 KiB and a buffer serves only
+// its own class, so a fixed sequence of uploads needs a fixed set of buffers.  An upload takes a buffer of its class whose event has
+// completed (hipEventQuery: never a host wait), allocates one if none has, and records the buffer's event behind its copy.
+// Stream capture: the copy itself is a legal node, but a replay reads the pinned buffer AGAIN, so an upload made while `s` is
+// capturing gets a buffer of its own that stays out of the pool for the life of the process.  Allocating it is a different matter:
+// hipHostMalloc is one of the calls a global-mode capture (what torch.cuda.graph begins) refuses, and it invalidates that capture.
+// So a group has to make its first launch outside such a capture; unet.py does not defer weight gradients under capture for
+// this reason.
 #include <mutex>
 #include <string.h>
 #include <vector>
-hipError_t vaw_upload_table(void* dev, const void* host, size_t bytes, hipStream_t s) {
-    static std::mutex mu;
-    static std::vector<void*> keep;
-    void* pinned = nullptr;
-    hipError_t rc = hipHostMalloc(&pinned, bytes, hipHostMallocDefault);
+namespace {
+struct TableBuf { void* p; size_t cls; int device; hipEvent_t done; };      // (an event records only on streams of its own device)
+std::mutex g_tab_mu;
+std::vector<TableBuf> g_tab_pool;
+int64_t g_tab_buffers = 0, g_tab_bytes = 0, g_tab_captured = 0;      // all pinned buffers ever made | their bytes | those a capture holds
+
+hipError_t upload_table_locked(void* dev, const void* host, size_t bytes, hipStream_t s) {
+    size_t cls = 4096;
+    while (cls < bytes) cls <<= 1;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t rc = hipStreamIsCapturing(s, &cap);
     if (rc != hipSuccess) return rc;
-    memcpy(pinned, host, bytes);
-    {
-        std::lock_guard<std::mutex> g(mu);
-        keep.push_back(pinned);
+    const bool capturing = cap != hipStreamCaptureStatusNone;
+    int device = 0;
+    if ((rc = hipGetDevice(&device)) != hipSuccess) return rc;
+    TableBuf* b = nullptr;
+    if (!capturing)
+        for (TableBuf& t : g_tab_pool)
+            if (t.cls == cls && t.device == device && hipEventQuery(t.done) == hipSuccess) { b = &t; break; }
+    TableBuf made{nullptr, cls, device, nullptr};
+    if (!b) {
+        if ((rc = hipHostMalloc(&made.p, cls, hipHostMallocDefault)) != hipSuccess) return rc;
+        if (!capturing && (rc = hipEventCreateWithFlags(&made.done, hipEventDisableTiming)) != hipSuccess) {
+            (void)hipHostFree(made.p);
+            return rc;
+        }
+        g_tab_buffers += 1;
+        g_tab_bytes += (int64_t)cls;
+        if (capturing) g_tab_captured += 1;
+        else { g_tab_pool.push_back(made); b = &g_tab_pool.back(); }
     }
-    return hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, s);
+    void* pinned = b ? b->p : made.p;
+    memcpy(pinned, host, bytes);
+    if ((rc = hipMemcpyAsync(dev, pinned, bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return rc;
+    return b ? hipEventRecord(b->done, s) : hipSuccess;
+}
+}  // namespace
+
+int vaw_upload_table(const char* who, int upload, void* dev, const void* host, size_t bytes, hipStream_t s) {
+    if (!upload) return VAW_OK;
+    std::lock_guard<std::mutex> g(g_tab_mu);       // held up to the event record: nobody else may take the buffer before
+    const hipError_t rc = upload_table_locked(dev, host, bytes, s);
+    VAW_CHECK_ARG(rc == hipSuccess, "%s: descriptor upload failed: %s", who, hipGetErrorString(rc));
+    return VAW_OK;
+}
+
+extern "C" void vaw_debug_upload_table_stats(int64_t* buffers, int64_t* bytes, int64_t* captured) {
+    std::lock_guard<std::mutex> g(g_tab_mu);
+    if (buffers) *buffers = g_tab_buffers;
+    if (bytes) *bytes = g_tab_bytes;
+    if (captured) *captured = g_tab_captured;
 }

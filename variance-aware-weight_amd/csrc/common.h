@@ -33,8 +33,9 @@ void vaw_set_error(const char* fmt, ...);
         }                                                                            \
     } while (0)
 
-// one-time upload of a descriptor table from a pinned copy that stays alive (capi.hip)
-hipError_t vaw_upload_table(void* dev, const void* host, size_t bytes, hipStream_t s);
+// upload != 0: copy a descriptor table to `dev` on `s` through a recycled pinned buffer (capi.hip).  VAW_OK, or VAW_ERR_INVALID
+// with "<who>: descriptor upload failed: ..." as the error text
+int vaw_upload_table(const char* who, int upload, void* dev, const void* host, size_t bytes, hipStream_t s);
 
 // ---- element access by activation dtype ------------------------------------
 __device__ __forceinline__ float to_f32(float v) { return v; }

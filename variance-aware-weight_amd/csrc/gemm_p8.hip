@@ -170,10 +170,7 @@ extern "C" int vaw_wgrad_grouped(vaw_dtype dt, int n_problems, const vaw_wgrad_p
         VAW_CHECK_ARG(t_total < (1 << 30), "wgrad_grouped: too many tiles");
     }
     hipStream_t s = (hipStream_t)stream;
-    if (upload) {
-        const hipError_t rc = vaw_upload_table(desc_dev, host.data(), sizeof(P8Prob) * n_problems, s);
-        VAW_CHECK_ARG(rc == hipSuccess, "wgrad_grouped: descriptor upload failed: %s", hipGetErrorString(rc));
-    }
+    if (const int rc = vaw_upload_table("wgrad_grouped", upload, desc_dev, host.data(), sizeof(P8Prob) * n_problems, s)) return rc;
     const int cus = p8_num_cus(), nk = (int)(K / kt);
     P8Group grp{};
     grp.n_prob = n_problems;

@@ -1049,10 +1049,7 @@ extern "C" int vaw_reduce_rows_batched(int n_jobs, const vaw_reduce_job* jobs, f
         VAW_CHECK_ARG(blocks < (1 << 30), "reduce_rows_batched: too many columns");
     }
     hipStream_t s = (hipStream_t)stream;
-    if (upload) {
-        const hipError_t rc = vaw_upload_table(desc_dev, host, sizeof(ReduceJobDev) * n_jobs, s);
-        VAW_CHECK_ARG(rc == hipSuccess, "reduce_rows_batched: descriptor upload failed: %s", hipGetErrorString(rc));
-    }
+    if (const int rc = vaw_upload_table("reduce_rows_batched", upload, desc_dev, host, sizeof(ReduceJobDev) * n_jobs, s)) return rc;
     colsum_final_batched_kernel<<<(unsigned)blocks, 1024, 0, s>>>((const ReduceJobDev*)desc_dev, n_jobs, beta);
     VAW_CHECK_LAUNCH("reduce_rows_batched");
     return VAW_OK;

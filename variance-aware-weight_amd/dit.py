@@ -185,12 +185,12 @@ class _Workspace:
         elif plan.own_dy:
             for b in self.blk[:plan.records]:
                 b.update(dy2=e(M, D), dDm=e(M, m.Dm), dy1=e(M, D), dqkv=e(M, 3 * D))
-        self.wgrad_groups = {}
+        self.wgrad_groups = ops.GroupCache(2 * Lyr + 2)      # at most one per block (recomputation), for two gradient buffers
         # bias gradients: the kernels that produce dy leave partial column sums per block (gate backward: one row per sample;
         # fc2's GELU' epilogue: one per 64 or 128 token rows; attention backward: one per sample and 64-token block); ONE batched fold
         # per group of blocks turns them into the four bias gradients of every block (ops.ReduceGroup).  With activation
         # recomputation a block folds its own right after its backward, so all blocks share one set
-        self.bias_groups = {}
+        self.bias_groups = ops.GroupCache(8 * (2 * Lyr + 2))      # ... with / without qkv, at up to four tuples of row counts
 
         def cp_set():
             cps = dict(fc2=ops.ColsumPartial(B, D, dev), proj=ops.ColsumPartial(B, D, dev),
@@ -277,7 +277,6 @@ class DiT(FlatModule):
         # byte-identical to quantising the bf16 tensor, which is then never written or read
         self.fp8_fuse_epilogue = os.environ.get("VAW_FP8_FUSE", "1") != "0"
         self.fp8_fuse_rows = os.environ.get("VAW_FP8_FUSE_ROWS", "1") != "0"      # ... and LN-modulate / gate backward their outputs
-        self._fp8_w, self._fp8_epoch, self._fp8_wstates, self._fp8_wgroup = {}, None, None, None
         self.activation_checkpointing = False
         self.set_compute_dtype(compute_dtype)
         self._anchor = torch.zeros(1, requires_grad=True)
@@ -330,7 +329,7 @@ class DiT(FlatModule):
         self.compute_dtype = name
         self._dt = F32 if name == "fp32" else BF16
         self._fp8 = name == "fp8"
-        self._fp8_w, self._fp8_epoch, self._fp8_wstates, self._fp8_wgroup = {}, None, None, None
+        self._fp8_w, self._fp8_epoch, self._fp8_wstates, self._fp8_wgroup = {}, None, None, ops.GroupCache(2)
         self._ws = {}
 
     _ONLY_DX_FP8 = ("input_grad_only() does not combine with compute_dtype='fp8': the delayed-scaling state of the fp8 tensors would "
@@ -463,16 +462,12 @@ class DiT(FlatModule):
         self.require_fresh_masters("re-quantising the fp8 weights")
         dev = self._flat.device
         if self._fp8_wstates is None or self._fp8_wstates.device != dev:
-            self._fp8_wstates, self._fp8_w, self._fp8_wgroup = ops.fp8_states([L.FP8] * (4 * self.depth), dev, self.fp8_margin), {}, None
+            self._fp8_wstates, self._fp8_w, self._fp8_wgroup = ops.fp8_states([L.FP8] * (4 * self.depth), dev, self.fp8_margin), {}, ops.GroupCache(2)
         delayed = self.fp8_scaling == "delayed" and bool(self._fp8_w)
         if delayed:
             ops.fp8_scale_update(self._fp8_wstates)
-            grp = getattr(self, "_fp8_wgroup", None)
-            if grp is None or grp[0] != self._flat.data_ptr():
-                pairs = [(self._p32(f"blocks.{l}.{nm}weight"), self._fp8_w[f"blocks.{l}.{nm}weight"])
-                         for l in range(self.depth) for nm, _, _ in self._FP8_LINEARS]
-                grp = self._fp8_wgroup = (self._flat.data_ptr(), ops.Fp8QuantGroup(pairs, dev))
-            grp[1].launch()          # all 4 L weight matrices in one launch
+            names = [f"blocks.{l}.{nm}weight" for l in range(self.depth) for nm, _, _ in self._FP8_LINEARS]      # all 4 L in one launch
+            self._fp8_wgroup.get(self._flat.data_ptr(), lambda: ops.Fp8QuantGroup([(self._p32(n), self._fp8_w[n]) for n in names], dev)).launch()
             self._fp8_epoch = epoch
             return
         i = 0
@@ -749,32 +744,23 @@ class DiT(FlatModule):
 
         def fold_bias(blocks, qkv_too):
             """The bias gradients of `blocks` from the partial column sums their backward left behind: one launch."""
-            key = (blocks[0], blocks[-1], self._gbase, qkv_too)
-            cps = []
-            for l in blocks:
-                cp, pre = ws.cp[l], f"blocks.{l}."
-                names = [("fc2", "mlp.fc2."), ("fc1", "mlp.fc1."), ("proj", "attn.proj.")] + ([("qkv", "attn.qkv.")] if qkv_too else [])
-                cps += [(cp[key_cp], pre + nm) for key_cp, nm in names]
+            names = (("fc2", "mlp.fc2."), ("fc1", "mlp.fc1."), ("proj", "attn.proj."), ("qkv", "attn.qkv."))[:4 if qkv_too else 3]
+            cps = [(ws.cp[l][k], f"blocks.{l}.{nm}bias") for l in blocks for k, nm in names]
             # the number of partial rows a producer leaves is NOT a function of the shape alone: vaw_gemm writes one row per 64, 128
             # or 256 rows of C depending on the kernel it picks (which moves with the CUs reserved for a collective, with
             # vaw_debug_gemm_tile, ...), the attention backward one per 64 / 128 / 256 query rows by VAW_ATTN_BWD_BIG.  The device
-            # table bakes the counts in, so it is rebuilt whenever this backward's counts differ from the ones it was built with
-            # (a host-side integer compare per job; folding stale counts would drop or double-count rows silently).
+            # table bakes the counts in, so they are part of the group's key: stale counts, which would drop or double-count rows
+            # silently, are never folded, and counts that alternate (CUs are reserved on the synchronising backward only) stay resident.
             rows = tuple(int(cp.rows.value) for cp, _ in cps)
-            ent = ws.bias_groups.get(key)
-            if ent is None or ent[1] != rows:
-                jobs = [(cp.buf.data_ptr(), self._g(nm + "bias"), r, cp.N) for (cp, nm), r in zip(cps, rows)]
-                ent = ws.bias_groups[key] = (ops.ReduceGroup(jobs, dout.device), rows)
-            grp = ent[0]
-            grp.launch(beta)
+            ws.bias_groups.get((blocks[0], blocks[-1], self._gbase, qkv_too, rows), lambda: ops.ReduceGroup(
+                [(cp.buf.data_ptr(), self._g(nm), r, cp.N) for (cp, nm), r in zip(cps, rows)], dout.device)).launch(beta)
 
         def flush():
             """One grouped launch for the weight gradients of the blocks in `pending`, then their gradient-ready stages."""
             if not pending:
                 return
-            key = (pending[0], pending[-1], self._gbase)
-            grp = ws.wgrad_groups.get(key)
-            if grp is None:
+
+            def build():
                 probs = []
                 for l in pending:
                     b, pre = ws.blk[l], f"blocks.{l}."
@@ -786,8 +772,8 @@ class DiT(FlatModule):
                     for name, dy, x, Nw, Kw in ((pre + "mlp.fc2.", b["dy2"], b["a"], D, Dm), (pre + "mlp.fc1.", b["dDm"], b["xm2"], Dm, D),
                                                 (pre + "attn.proj.", b["dy1"], b["ao"], D, D), (pre + "attn.qkv.", b["dqkv"], b["xm"], 3 * D, D)):
                         probs.append((ptr(dy), ptr(x), self._g(name + "weight"), Nw, Kw, Nw, Kw, Kw))
-                grp = ws.wgrad_groups[key] = ops.WgradGroup(probs, M, dout.device)
-            grp.launch((L.BF8 if self.fp8_grad_format == "e5m2" else L.FP8) if fp8 else dt, beta)
+                return ops.WgradGroup(probs, M, dout.device)
+            ws.wgrad_groups.get((pending[0], pending[-1], self._gbase), build).launch((L.BF8 if self.fp8_grad_format == "e5m2" else L.FP8) if fp8 else dt, beta)
             fold_bias(list(pending), True)
             if hook:
                 for l in pending:

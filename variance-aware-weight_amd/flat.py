@@ -113,8 +113,9 @@ class FlatModule(nn.Module):
         memo[id(self)] = new
         import copy
         skip = {"_flat", "_flat_grad", "_flat_shadow", "_flat_params"}
-        # per-batch workspaces / tapes / descriptors hold activations of the source model: the copy starts with none
-        fresh = {"_ws": dict, "_ws_cur": lambda: None, "_adesc": lambda: None, "_tape": list, "_fp8_w": dict, "_fp8_epoch": lambda: None, "_fp8_wstates": lambda: None, "_fp8_wgroup": lambda: None, "_zero": lambda: None, "grad_ready_hook": lambda: None}
+        # per-batch workspaces / tapes / descriptors hold activations of the source model: the copy starts with none (the launch-group
+        # caches _fp8_wgroup and _wgrad_groups see to that themselves: ops.GroupCache.__deepcopy__)
+        fresh = {"_ws": dict, "_ws_cur": lambda: None, "_adesc": lambda: None, "_tape": list, "_pend_wgrad": dict, "_fp8_w": dict, "_fp8_epoch": lambda: None, "_fp8_wstates": lambda: None, "_zero": lambda: None, "grad_ready_hook": lambda: None}
         for k, v in self.__dict__.items():
             new.__dict__[k] = None if k in skip else fresh[k]() if k in fresh else copy.deepcopy(v, memo)
         new._flat_dirty = True

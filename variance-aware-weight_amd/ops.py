@@ -1,5 +1,6 @@
 """Tensor-level wrappers over the C ABI (include/vaw_hip.h).  Each takes torch CUDA tensors, checks what the
 kernel assumes about them (shape, dtype, contiguity) on the host, and launches on the current stream."""
+import collections
 import ctypes as C
 import math
 
@@ -742,22 +743,53 @@ class Fp8:
         return self.q.view(torch.float8_e5m2 if self.fmt == L.BF8 else torch.float8_e4m3fn).float() * self.scale
 
 
-class Fp8QuantGroup:
-    """Delayed-scaling e4m3 quantisation of many f32 tensors (src address, Fp8 with q and qt) in ONE launch
-    (vaw_fp8_quantize_delayed_batched); the addresses stay put between steps, so the device table is uploaded once."""
+class TableGroup:
+    """Base of the "one launch for many problems" groups: the host table of `rows` (records of type `rec`), its device copy `desc`
+    and the upload flag.  The addresses in a table stay put while its group lives, so only the group's first launch uploads."""
+
+    def __init__(self, rec, rows, desc_bytes, device):
+        self.n, self.uploaded = len(rows), False
+        self.table = (rec * self.n)(*rows)
+        self.desc = torch.empty(desc_bytes(self.n), device=device, dtype=torch.uint8)
+
+    def _call(self, name, *pre, post=()):        # lib.<name>(*pre, desc, upload, *post, stream): upload = 1 until one call succeeded
+        check(getattr(L.lib(), name)(*pre, self.desc.data_ptr(), 0 if self.uploaded else 1, *post, stream_ptr()), name)
+        self.uploaded = True
+
+
+class GroupCache(collections.OrderedDict):
+    """key -> launch group, at most `bound` of them: get() builds a missing one and drops the least recently used beyond the bound
+    (torch frees its device table like any tensor, in stream order).  A model's copy (EMA) has other addresses: it starts empty."""
+
+    def __init__(self, bound):
+        super().__init__()
+        self.bound, self.hits, self.misses = int(bound), 0, 0
+
+    def get(self, key, build):
+        if key in self:
+            self.hits += 1
+            self.move_to_end(key)
+            return self[key]
+        self.misses += 1
+        grp = self[key] = build()
+        while len(self) > self.bound:
+            self.popitem(last=False)
+        return grp
+
+    def __deepcopy__(self, memo):
+        return GroupCache(self.bound)
+
+
+class Fp8QuantGroup(TableGroup):
+    """Delayed-scaling e4m3 quantisation of many f32 tensors (src address, Fp8 with q and qt) in ONE vaw_fp8_quantize_delayed_batched."""
 
     def __init__(self, pairs, device):
         jobs = [Fp8QuantJob(src, f.q.data_ptr(), ptr(f.qt), f.state.data_ptr(), f.R, f.C, f.C, f.C, f.R) for src, f in pairs]
-        self.n = len(jobs)
-        self.table = (Fp8QuantJob * self.n)(*jobs)
+        super().__init__(Fp8QuantJob, jobs, L.lib().vaw_fp8_quantize_batched_desc_bytes, device)
         self.fp8s = [f for _, f in pairs]
-        self.desc = torch.empty(L.lib().vaw_fp8_quantize_batched_desc_bytes(self.n), device=device, dtype=torch.uint8)
-        self.uploaded = False
 
     def launch(self):
-        check(L.lib().vaw_fp8_quantize_delayed_batched(self.n, self.table, self.desc.data_ptr(),
-                                                       0 if self.uploaded else 1, stream_ptr()), "vaw_fp8_quantize_delayed_batched")
-        self.uploaded = True
+        self._call("vaw_fp8_quantize_delayed_batched", self.n, self.table)
         for f in self.fp8s:
             f.last_q = f.q.data_ptr()
 
@@ -825,17 +857,14 @@ def gemm_fp8_plan(M, N, K, A, lda, scale_a, B, ldb, scale_b, Cp, ldc, *, a_forma
     return p
 
 
-class WgradGroup:
+class WgradGroup(TableGroup):
     """The weight gradients dW_p (+)= dy_p^T x_p of many Linear layers as ONE launch (vaw_wgrad_grouped).  `problems` is a list of
-    (dy_addr, x_addr, dw_addr, M, N, ld_dy, ld_x, ld_dw); the addresses are workspace / flat-buffer addresses that stay put
-    between steps, so the device copy of the table is uploaded once."""
+    (dy_addr, x_addr, dw_addr, M, N, ld_dy, ld_x, ld_dw)."""
 
     def __init__(self, problems, K, device):
-        self.n, self.K, self.device = len(problems), int(K), device
-        self.table = (WgradProblem * self.n)(*[WgradProblem(*p) for p in problems])
+        super().__init__(WgradProblem, [WgradProblem(*p) for p in problems], L.lib().vaw_wgrad_grouped_desc_bytes, device)
+        self.K, self.device = int(K), device
         self.flop = sum(2.0 * p[3] * p[4] * K for p in problems)
-        self.desc = torch.empty(L.lib().vaw_wgrad_grouped_desc_bytes(self.n), device=device, dtype=torch.uint8)
-        self.uploaded = False
 
     def launch(self, dt, beta):
         ws = scratch_f32(self.device, 0)
@@ -843,9 +872,7 @@ class WgradGroup:
         if tr is not None:
             e0, e1 = tr.events()
             e0.record()
-        check(L.lib().vaw_wgrad_grouped(dt, self.n, self.table, self.K, float(beta), self.desc.data_ptr(),
-                                        0 if self.uploaded else 1, ws.data_ptr(), ws.numel(), stream_ptr()), "vaw_wgrad_grouped")
-        self.uploaded = True
+        self._call("vaw_wgrad_grouped", dt, self.n, self.table, self.K, float(beta), post=(ws.data_ptr(), ws.numel()))
         if tr is not None:
             e1.record()
             es = 1 if dt in (L.FP8, L.BF8) else 2
@@ -1093,20 +1120,14 @@ class ColsumPartial:
         self.rows = C.c_int64(0)
 
 
-class ReduceGroup:
-    """out_j = beta * out_j + column sums of partial_j for many (partial, R, N, out) jobs in ONE launch
-    (vaw_reduce_rows_batched); addresses are workspace / flat-buffer addresses, so the device table is uploaded once."""
+class ReduceGroup(TableGroup):
+    """out_j = beta * out_j + column sums of partial_j for many (partial, out, R, N) jobs in ONE launch (vaw_reduce_rows_batched)."""
 
     def __init__(self, jobs, device):
-        self.n = len(jobs)
-        self.table = (ReduceJob * self.n)(*[ReduceJob(*j) for j in jobs])
-        self.desc = torch.empty(L.lib().vaw_reduce_rows_batched_desc_bytes(self.n), device=device, dtype=torch.uint8)
-        self.uploaded = False
+        super().__init__(ReduceJob, [ReduceJob(*j) for j in jobs], L.lib().vaw_reduce_rows_batched_desc_bytes, device)
 
     def launch(self, beta):
-        check(L.lib().vaw_reduce_rows_batched(self.n, self.table, float(beta), self.desc.data_ptr(),
-                                              0 if self.uploaded else 1, stream_ptr()), "vaw_reduce_rows_batched")
-        self.uploaded = True
+        self._call("vaw_reduce_rows_batched", self.n, self.table, float(beta))
 
 
 def gate_bwd(dt, dres, y, gate, mod_ld, dy, dgate, dmod_ld, B, T, D, dy_colpart=0):

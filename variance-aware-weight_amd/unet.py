@@ -238,7 +238,7 @@ class UNetModel(FlatModule):
         # order and shapes the reference's CPU run draws them (parity runs; set by Trainer from args.cpu_rng); False = device RNG
         self.host_dropout_rng = False
         self.grad_ready_hook = None
-        self._pend_wgrad, self._wgrad_groups, self._grouped_wgrad = {}, {}, None
+        self._pend_wgrad, self._wgrad_groups, self._grouped_wgrad = {}, ops.GroupCache(64), None
 
     # ---- flat storage -----------------------------------------------------------------------
     @property
@@ -677,7 +677,7 @@ class UNetModel(FlatModule):
             import os
             self._grouped_wgrad = os.environ.get("VAW_UNET_GROUPED_WGRAD", "1") != "0"
         if torch.cuda.is_current_stream_capturing():
-            return False          # a new group uploads its descriptor table from pinned memory it allocates: not capturable
+            return False          # a new group's table upload may allocate pinned memory, which this capture refuses (capi.hip)
         if not (self._grouped_wgrad and self._dt == L.BF16 and M % 64 == 0 and Co % 8 == 0 and Ci % 8 == 0 and Co >= 16 and Ci >= 16
                 and (dy.data_ptr() | x.data_ptr()) % 16 == 0):
             return False
@@ -689,18 +689,11 @@ class UNetModel(FlatModule):
         return tiles < 10 or M <= 65536
 
     def _flush_wgrads(self):
-        pend = self._pend_wgrad
-        if not pend:
-            return
-        for K, items in pend.items():
+        for K, items in self._pend_wgrad.items():
             probs = tuple((ptr(dy), ptr(x), gw, Co, Ci, Co, Ci, Ci) for dy, x, gw, Co, Ci in items)
-            grp = self._wgrad_groups.get(probs)
-            if grp is None:
-                if len(self._wgrad_groups) >= 64:         # (addresses moved: activations are allocated per step)
-                    self._wgrad_groups.clear()
-                grp = self._wgrad_groups[probs] = ops.WgradGroup(list(probs), K, self._flat.device)
-            grp.launch(self._dt, self._beta)
-        pend.clear()                                        # the operands may go: the launches are enqueued on this stream
+            # (activations are allocated per step: when the addresses moved, new groups push the least recently used ones out)
+            self._wgrad_groups.get(probs, lambda: ops.WgradGroup(list(probs), K, self._flat.device)).launch(self._dt, self._beta)
+        self._pend_wgrad.clear()                            # the operands may go: the launches are enqueued on this stream
 
     def _needs_grad(self, a):
         return a is not self._x_act or self._need_dx
@@ -756,7 +749,7 @@ class UNetModel(FlatModule):
         assert C == self.in_channels and H == W == self.image_size
         self._need_dx = need_dx
         if self._rec:
-            self._tape = []
+            self._tape, self._pend_wgrad = [], {}       # (what a backward that raised left queued belongs to no step any more)
         ted, mc, f32 = self.time_embed_dim, self.model_channels, torch.float32
         x = x.float().contiguous()
         tf = t.float().contiguous()
@@ -804,7 +797,7 @@ class UNetModel(FlatModule):
     def _backward_impl(self, dout):
         dt, lib, st, s = self._dt, L.lib(), L.stream_ptr(), self._s
         B, ted, mc, f32 = dout.shape[0], self.time_embed_dim, self.model_channels, torch.float32
-        only_dx = self._only_dx
+        only_dx, self._pend_wgrad = self._only_dx, {}      # (nothing queued: as at the start of a recording forward)
         if only_dx:
             # FlatModule.input_grad_only: the closures skip every weight- / bias-gradient launch and queue nothing (_pend_wgrad stays
             # empty), GroupNorm's d gamma / d beta go to scratch, the FiLM gradients (fused into GroupNorm backward) into demb_t below,

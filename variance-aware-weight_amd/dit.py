@@ -16,6 +16,7 @@ Data layout in HBM (B images, T tokens, D hidden, M = B*T rows):
                     copy (W^T for dgrad; x^T, dy^T [*, M] per block for the deferred grouped weight gradients).  Everything else
                     -- attention, LayerNorm, embedders, final layer, adaLN, optimizer -- is the bf16 mode's.
 """
+import collections
 import os
 
 import numpy as np
@@ -107,6 +108,38 @@ class _FinalLayer(_Holder):
         self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(dim, 2 * dim, bias=True))
 
 
+# Slots of the packed adaLN buffer [B, (6L+2) D] (ws.mod, and ws.dmod for its gradient), in the reference's chunk(6) order.  Block l
+# owns columns [6 l D, 6 (l+1) D), the outputs of rows 6 l D ... of the packed adaLN weight matrix (_flat_groups: _adaln_wgrad and
+# grad_stage_bounds index those parameter rows by the same convention); the final layer's (shift, scale) pair follows at l = L.
+SHIFT_MSA, SCALE_MSA, GATE_MSA, SHIFT_MLP, SCALE_MLP, GATE_MLP = range(6)
+FINAL_SHIFT, FINAL_SCALE = 0, 1
+
+
+def mod_offset(l, slot, D):
+    """Column of slot (l, slot) in the packed adaLN buffer."""
+    return (6 * l + slot) * D
+
+
+class _Site(collections.namedtuple("_Site", "key prefix n k x dy f_x f_dy cp s_x s_dy gate y")):
+    """One Linear layer of a block, y[M,N] = x[M,K] W^T + b: parameter prefix; N and K as (multiple of D, multiple of Dm); record
+    keys of x and of dy (bf16 operands of the deferred weight gradient) and of their fp8 copies; key of the partial column sums
+    of dy (ws.cp: the bias gradient); rows of x's and dy's scaling state among the block's eight (ws.fp8_states); and, for the two
+    layers that end a gated branch, the slot of the gate and the record key of the branch value y in front of it."""
+
+    def shape(self, D, Dm):
+        return self.n[0] * D + self.n[1] * Dm, self.k[0] * D + self.k[1] * Dm
+
+
+# In forward order: the order of the blocks' fp8 weights and their scaling states (_refresh_fp8_weights).  The eight activation /
+# gradient states of a block run xm, ao, xm2, a, dy2, dhid, dy1, dqkv (s_x, s_dy).  Backward, the grouped weight gradients and
+# the bias fold walk SITES_BWD.  All three orders fix rows of device tables and cache keys: they are part of the engine's behaviour.
+SITES = QKV, PROJ, FC1, FC2 = (_Site("qkv", "attn.qkv.", (3, 0), (1, 0), "xm", "dqkv", "f_xm", "f_dqkv", "qkv", 0, 7, None, None),
+                               _Site("proj", "attn.proj.", (1, 0), (1, 0), "ao", "dy1", "f_ao", "f_dy1", "proj", 1, 6, GATE_MSA, "y1"),
+                               _Site("fc1", "mlp.fc1.", (0, 1), (1, 0), "xm2", "dDm", "f_xm2", "f_dhid", "fc1", 2, 5, None, None),
+                               _Site("fc2", "mlp.fc2.", (1, 0), (0, 1), "a", "dy2", "f_a", "f_dy2", "fc2", 3, 4, GATE_MLP, "y2"))
+SITES_BWD = SITES[::-1]
+
+
 class _Workspace:
     """Activation buffers for one batch size; reused every step (no allocator traffic in the loop).  How many block records
     there are, whether they carry their dy operands and how many bytes all of it takes is decided by ops.dit_ws_plan
@@ -123,7 +156,7 @@ class _Workspace:
             self._bufs.append(t)
             return t
 
-        self.B, self.adt, self.gen = B, adt, 0
+        self.B, self.M, self.D, self.adt, self.gen = B, M, D, adt, 0
         self.fp8 = bool(m._fp8)
         self.ckpt = ckpt = bool(m.activation_checkpointing)
         # (fp8 mode keeps transposed fp8 copies instead of dy operands, on top of what the plan counts)
@@ -174,17 +207,17 @@ class _Workspace:
             # per block: the transposed fp8 copies the grouped weight gradients read (x^T and dy^T, [features][M]); the row-major
             # copies live in a shared scratch just long enough for the GEMM that follows the quantiser
             gf = L.BF8 if m.fp8_grad_format == "e5m2" else L.FP8
-            fmts = [L.FP8] * 4 + [gf] * 4
-            self.fp8_states = ops.fp8_states(fmts * Lyr, dev, m.fp8_margin)     # delayed scaling: one update launch per step
+            # a block's eight copies in the order of their scaling states: x [M, K] of every site (e4m3), then dy [M, N] (gradient format)
+            copies = sorted([(s.s_x, s.f_x, s.shape(D, m.Dm)[1], L.FP8) for s in SITES] + [(s.s_dy, s.f_dy, s.shape(D, m.Dm)[0], gf) for s in SITES])
+            self.fp8_states = ops.fp8_states([c[3] for c in copies] * Lyr, dev, m.fp8_margin)     # delayed scaling: one update launch per step
             self.calib_fwd = self.calib_bwd = False                             # first pass: scales taken just in time
             self.d_fwd = self.d_bwd = False
             for l, b in enumerate(self.blk):
-                F = lambda i, cols: ops.Fp8(M, cols, dev, transposed=True, plain=False, fmt=fmts[i], state=self.fp8_states[8 * l + i])
-                b.update(f_xm=F(0, D), f_ao=F(1, D), f_xm2=F(2, D), f_a=F(3, m.Dm), f_dy2=F(4, D), f_dhid=F(5, m.Dm), f_dy1=F(6, D),
-                         f_dqkv=F(7, 3 * D))
+                for i, key, cols, fmt in copies:
+                    b[key] = ops.Fp8(M, cols, dev, transposed=True, plain=False, fmt=fmt, state=self.fp8_states[8 * l + i])
         elif plan.own_dy:
             for b in self.blk[:plan.records]:
-                b.update(dy2=e(M, D), dDm=e(M, m.Dm), dy1=e(M, D), dqkv=e(M, 3 * D))
+                b.update((s.dy, e(M, s.shape(D, m.Dm)[0])) for s in SITES_BWD)
         self.wgrad_groups = ops.GroupCache(2 * Lyr + 2)      # at most one per block (recomputation), for two gradient buffers
         # bias gradients: the kernels that produce dy leave partial column sums per block (gate backward: one row per sample;
         # fc2's GELU' epilogue: one per 64 or 128 token rows; attention backward: one per sample and 64-token block); ONE batched fold
@@ -209,6 +242,13 @@ class _Workspace:
         self.dxp = e(M, m.Kp, dtype=f32)
         if not self.fp8 and self.nbytes() != plan.total:
             raise L.VawError(f"DiT workspace: allocated {self.nbytes()} bytes, vaw_dit_ws_plan says {plan.total}")
+
+    def mod_at(self, l, slot):
+        """Address of slot (l, slot) of the modulation buffer (row stride: the model's mod_cols); dmod_at: of its gradient."""
+        return self.mod.data_ptr() + 4 * mod_offset(l, slot, self.D)
+
+    def dmod_at(self, l, slot):
+        return self.dmod.data_ptr() + 4 * mod_offset(l, slot, self.D)
 
     def nbytes(self):
         """Bytes of the workspace's buffers (not the launch descriptor tables of the cached groups, nor the fp8 copies)."""
@@ -332,9 +372,6 @@ class DiT(FlatModule):
         self._fp8_w, self._fp8_epoch, self._fp8_wstates, self._fp8_wgroup = {}, None, None, ops.GroupCache(2)
         self._ws = {}
 
-    _ONLY_DX_FP8 = ("input_grad_only() does not combine with compute_dtype='fp8': the delayed-scaling state of the fp8 tensors would "
-                    "move during an evaluation")
-
     _CKPT_FP8 = ("activation_checkpointing does not combine with compute_dtype='fp8': re-running a block's forward would update its "
                  "delayed-scaling state twice per step, and the per-block transposed fp8 copies would have to be shared too")
 
@@ -414,19 +451,6 @@ class DiT(FlatModule):
         if z is not None:
             z.wait_stage(stage)
 
-    def _w(self, name):
-        """device address of a parameter in the dtype the kernels read (bf16 shadow or f32 master)."""
-        o, _ = self._flat_offsets[name]
-        return self._wbase + o * self._wsize
-
-    def _g(self, name):
-        o, _ = self._flat_offsets[name]
-        return self._gbase + 4 * o
-
-    def _p32(self, name):
-        o, _ = self._flat_offsets[name]
-        return self._flat.data_ptr() + 4 * o
-
     def _prepare(self, B):
         self.ensure_flat()
         if self._dt == BF16:
@@ -451,7 +475,13 @@ class DiT(FlatModule):
                 ops.fp8_scale_update(ws.fp8_states)
         return ws
 
-    _FP8_LINEARS = (("attn.qkv.", 3, 1), ("attn.proj.", 1, 1), ("mlp.fc1.", 0, 1), ("mlp.fc2.", 1, 0))   # (name, N / D or 0 = Dm, K / D or 0 = Dm)
+    def _fuse(self, ws, calibrated, rows):
+        """fp8 fusion: a producer writes its output as fp8 itself, and only the transpose (vaw_fp8_transpose: rows % 64, columns % 128)
+        follows.  Asked once per pass with calibrated = ws.d_fwd | ws.d_bwd (_prepare): delayed scaling is on and a first pass has
+        calibrated that direction, so the tensor's scale is known before the tensor is.  rows = False: a GEMM epilogue's [M, Dm]
+        output -- `a` of fc1, d hidden of fc2's input gradient -- needs M % 64 (Dm % 128 holds in fp8 mode); rows = True: a row
+        kernel's [M, D] -- xm / xm2 of LN + modulate, dy1 / dy2 of LN backward + gate backward -- also D % 128 and fp8_fuse_rows."""
+        return ws.fp8 and calibrated and self.fp8_fuse_epilogue and ws.M % 64 == 0 and (not rows or (self.fp8_fuse_rows and self.D % 128 == 0))
 
     def _refresh_fp8_weights(self):
         """e4m3 copies W [N][K] and W^T [K][N] of the blocks' Linear weights, re-quantised from the f32 masters whenever the
@@ -466,18 +496,17 @@ class DiT(FlatModule):
         delayed = self.fp8_scaling == "delayed" and bool(self._fp8_w)
         if delayed:
             ops.fp8_scale_update(self._fp8_wstates)
-            names = [f"blocks.{l}.{nm}weight" for l in range(self.depth) for nm, _, _ in self._FP8_LINEARS]      # all 4 L in one launch
+            names = [f"blocks.{l}.{s.prefix}weight" for l in range(self.depth) for s in SITES]      # all 4 L in one launch
             self._fp8_wgroup.get(self._flat.data_ptr(), lambda: ops.Fp8QuantGroup([(self._p32(n), self._fp8_w[n]) for n in names], dev)).launch()
             self._fp8_epoch = epoch
             return
         i = 0
         for l in range(self.depth):
-            for nm, nf, kf in self._FP8_LINEARS:
-                name = f"blocks.{l}.{nm}weight"
-                N, K = (nf * self.D or self.Dm), (kf * self.D or self.Dm)
+            for s in SITES:
+                name = f"blocks.{l}.{s.prefix}weight"
                 f = self._fp8_w.get(name)
                 if f is None:
-                    f = self._fp8_w[name] = ops.Fp8(N, K, dev, state=self._fp8_wstates[i])
+                    f = self._fp8_w[name] = ops.Fp8(*s.shape(self.D, self.Dm), dev, state=self._fp8_wstates[i])
                 f.quantize(self._p32(name), src_dt=F32, delayed=False)
                 i += 1
         self._fp8_epoch = epoch
@@ -490,8 +519,7 @@ class DiT(FlatModule):
         ws.gen += 1
         dt, D, T, Dm, Lyr, ld = self._dt, self.D, self.T, self.Dm, self.depth, self.mod_cols
         M, lib, st = B * T, L.lib(), L.stream_ptr()
-        x = x.float().contiguous()
-        tf = t.float().contiguous()
+        x, tf = x.float().contiguous(), t.float().contiguous()
         ye = self.y_embedder
         if (self.training and ye.dropout_prob > 0):
             drop = torch.rand(B, device=y.device) < ye.dropout_prob      # reference: dit.py:94-103
@@ -515,22 +543,21 @@ class DiT(FlatModule):
         L.check(lib.vaw_patchify(dt, ptr(x), ptr(ws.xp), B, C, H, W, self.patch_size, st), "patchify")
         ops.gemm(dt, 1, 1, M, D, self.Kp, ptr(ws.xp), self.Kp, self._w("x_embedder.proj.weight"), self.Kp, ptr(ws.xres[0]), D,
                  bias=self._p32("x_embedder.proj.bias"), rowadd=self._p32("pos_embed"), rows_per_batch=T, out_f32=True)
-        mod = ptr(ws.mod)
-        mo = mod + 4 * (6 * Lyr * D)
+        fin = (ws.mod_at(Lyr, FINAL_SHIFT), ws.mod_at(Lyr, FINAL_SCALE))
         # (bf16 mode, VAW_ROWS_FWD_FUSED: the row pass behind a block's fc2 also writes the LayerNorm of the NEXT consumer of the
         # residual stream -- the next block's LN1 into that block's record, the final layer's after the last block)
         ln_done = False
         for l in range(Lyr):
             self._need(l + 1)
             if l + 1 < Lyr:
-                nb, mn = ws.blk[l + 1], mod + 4 * (6 * (l + 1) * D)
-                nxt = (mn, mn + 4 * D, ptr(nb["xm"]), ptr(nb["mean1"]), ptr(nb["rstd1"]))
+                nb = ws.blk[l + 1]
+                nxt = (ws.mod_at(l + 1, SHIFT_MSA), ws.mod_at(l + 1, SCALE_MSA), ptr(nb["xm"]), ptr(nb["mean1"]), ptr(nb["rstd1"]))
             else:
-                nxt = (mo, mo + 4 * D, ptr(ws.xf), ptr(ws.meanf), ptr(ws.rstdf))
+                nxt = fin + (ptr(ws.xf), ptr(ws.meanf), ptr(ws.rstdf))
             ln_done = self._block_fwd(ws, l, ln1=not ln_done, nxt=nxt)
         self._need(Lyr + 1)
         if not ln_done:
-            ops.ln_modulate_fwd(dt, ptr(ws.xres[2 * Lyr]), mo, mo + 4 * D, ld, ptr(ws.xf), ptr(ws.meanf), ptr(ws.rstdf), B, T, D)
+            ops.ln_modulate_fwd(dt, ptr(ws.xres[2 * Lyr]), *fin, ld, ptr(ws.xf), ptr(ws.meanf), ptr(ws.rstdf), B, T, D)
         ops.gemm(dt, 1, 1, M, self.No, D, ptr(ws.xf), D, self._w("final_layer.linear.weight"), D, ptr(ws.otok), self.No,
                  bias=self._p32("final_layer.linear.bias"), out_f32=True)
         out = torch.empty(B, self.out_channels, H, W, device=x.device, dtype=torch.float32)
@@ -550,7 +577,7 @@ class DiT(FlatModule):
         if not L.lib().vaw_gate_resid_fwd_contracts(ws.B, self.T, self.D):
             return False, False
         D, Dm, M, T, ld = self.D, self.Dm, ws.B * self.T, self.T, self.mod_cols
-        b, mo = ws.blk[l], ptr(ws.mod) + 4 * (6 * l * D)
+        b = ws.blk[l]
         xin, xmid, xo = ptr(ws.xres[2 * l]), ptr(ws.xres[2 * l + 1]), ptr(ws.xres[2 * l + 2])
 
         def persistent(name, K, x, out, y, gate, resid):
@@ -559,8 +586,8 @@ class DiT(FlatModule):
                               aux_out=ptr(y), gate=gate, gate_ld=ld, resid=resid, rows_per_batch=T, out_f32=True, check_status=False)
             return p.status == 0 and p.variant == L.GV_PERSISTENT and p.epi_kind == L.P8_GATE
 
-        return (persistent(f"blocks.{l}.attn.proj.", D, b["ao"], xmid, b["y1"], mo + 4 * 2 * D, xin),
-                persistent(f"blocks.{l}.mlp.fc2.", Dm, b["a"], xo, b["y2"], mo + 4 * 5 * D, xmid))
+        return (persistent(f"blocks.{l}.attn.proj.", D, b["ao"], xmid, b["y1"], ws.mod_at(l, GATE_MSA), xin),
+                persistent(f"blocks.{l}.mlp.fc2.", Dm, b["a"], xo, b["y2"], ws.mod_at(l, GATE_MLP), xmid))
 
     def _block_fwd(self, ws, l, xout=None, ln1=True, nxt=None):
         """Forward of block l from its input row ws.xres[2l] and the resident modulation into its record: seven launches (LN +
@@ -573,51 +600,47 @@ class DiT(FlatModule):
         is already in its record).  Returns whether nxt was written.  A recomputed block (`xout`) refills its own LN1 with the
         plain launch (the same bits), and its fc2 stops at y2: nothing reads the scratch row, and the record behind it is not its own."""
         B, dt, D, T, Dm, ld = ws.B, self._dt, self.D, self.T, self.Dm, self.mod_cols
-        M = B * T
-        b, pre = ws.blk[l], f"blocks.{l}."
-        mo = ptr(ws.mod) + 4 * (6 * l * D)
+        b = ws.blk[l]
+        sh1, sc1, g1, sh2, sc2, g2 = (ws.mod_at(l, j) for j in (SHIFT_MSA, SCALE_MSA, GATE_MSA, SHIFT_MLP, SCALE_MLP, GATE_MLP))
         xin, xmid = ptr(ws.xres[2 * l]), ptr(ws.xres[2 * l + 1])
         recompute = xout is not None
         if xout is None:
             xout = ptr(ws.xres[2 * l + 2])
         rows_proj, rows_fc2 = self._rows_fwd_sites(ws, l)
-        fuse_rows = ws.fp8 and ws.d_fwd and self.fp8_fuse_epilogue and self.fp8_fuse_rows and M % 64 == 0 and D % 128 == 0    # LN writes fp8 itself
+        fuse_rows, fuse_a = (self._fuse(ws, ws.fp8 and ws.d_fwd, rows) for rows in (True, False))
         if fuse_rows:
-            ops.ln_modulate_fwd_fp8(xin, mo, mo + 4 * D, ld, b["f_xm"], ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
+            ops.ln_modulate_fwd_fp8(xin, sh1, sc1, ld, b["f_xm"], ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
         elif ln1 or recompute:
-            ops.ln_modulate_fwd(dt, xin, mo, mo + 4 * D, ld, ptr(b["xm"]), ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
-        self._linear_fwd(ws, b, "f_xm", None if fuse_rows else b["xm"], pre + "attn.qkv.", M, 3 * D, D, ptr(b["qkv"]), 3 * D)
-        q = ptr(b["qkv"])
-        es = self._wsize
+            ops.ln_modulate_fwd(dt, xin, sh1, sc1, ld, ptr(b["xm"]), ptr(b["mean1"]), ptr(b["rstd1"]), B, T, D)
+        self._linear_fwd(ws, l, QKV, None if fuse_rows else b["xm"], ptr(b["qkv"]), 3 * D)
+        q, es = ptr(b["qkv"]), self._wsize
         ops.attn_fwd(dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(b["lse"]))
         if rows_proj:
-            self._linear_fwd(ws, b, "f_ao", b["ao"], pre + "attn.proj.", M, D, D, ptr(b["y1"]), D)
-            ops.gate_resid_ln_modulate_fwd(dt, ptr(b["y1"]), mo + 4 * 2 * D, ld, xin, xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld,
+            self._linear_fwd(ws, l, PROJ, b["ao"], ptr(b["y1"]), D)
+            ops.gate_resid_ln_modulate_fwd(dt, ptr(b["y1"]), g1, ld, xin, xmid, sh2, sc2, ld,
                                            ptr(b["xm2"]), ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
         else:
-            self._linear_fwd(ws, b, "f_ao", b["ao"], pre + "attn.proj.", M, D, D, xmid, D, aux_out=ptr(b["y1"]), gate=mo + 4 * 2 * D,
-                             gate_ld=ld, resid=xin, rows_per_batch=T, out_f32=True)
+            self._linear_fwd(ws, l, PROJ, b["ao"], xmid, D, aux_out=ptr(b["y1"]), gate=g1, gate_ld=ld, resid=xin, rows_per_batch=T, out_f32=True)
             if fuse_rows:
-                ops.ln_modulate_fwd_fp8(xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, b["f_xm2"], ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
+                ops.ln_modulate_fwd_fp8(xmid, sh2, sc2, ld, b["f_xm2"], ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
             else:
-                ops.ln_modulate_fwd(dt, xmid, mo + 4 * 3 * D, mo + 4 * 4 * D, ld, ptr(b["xm2"]), ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
-        fuse_a = ws.fp8 and ws.d_fwd and self.fp8_fuse_epilogue and M % 64 == 0      # fc1's epilogue writes `a` as e4m3 itself
-        self._linear_fwd(ws, b, "f_xm2", None if fuse_rows else b["xm2"], pre + "mlp.fc1.", M, Dm, D, b["f_a"].epilogue_target() if fuse_a else ptr(b["a"]), Dm,
+                ops.ln_modulate_fwd(dt, xmid, sh2, sc2, ld, ptr(b["xm2"]), ptr(b["mean2"]), ptr(b["rstd2"]), B, T, D)
+        self._linear_fwd(ws, l, FC1, None if fuse_rows else b["xm2"], b["f_a"].epilogue_target() if fuse_a else ptr(b["a"]), Dm,
                          act=1, aux_out=ptr(b["hpre"]), **({"out_fp8": b["f_a"]} if fuse_a else {}))
         if rows_fc2:
-            self._linear_fwd(ws, b, "f_a", b["a"], pre + "mlp.fc2.", M, D, Dm, ptr(b["y2"]), D)
+            self._linear_fwd(ws, l, FC2, b["a"], ptr(b["y2"]), D)
             if recompute:
                 return False
             sh, sc, out, mean, rstd = nxt if nxt is not None else (0, 0, 0, 0, 0)
-            ops.gate_resid_ln_modulate_fwd(dt, ptr(b["y2"]), mo + 4 * 5 * D, ld, xmid, xout, sh, sc, ld, out, mean, rstd, B, T, D)
+            ops.gate_resid_ln_modulate_fwd(dt, ptr(b["y2"]), g2, ld, xmid, xout, sh, sc, ld, out, mean, rstd, B, T, D)
             return nxt is not None
-        self._linear_fwd(ws, b, "f_a", None if fuse_a else b["a"], pre + "mlp.fc2.", M, D, Dm, xout, D, aux_out=ptr(b["y2"]),
-                         gate=mo + 4 * 5 * D, gate_ld=ld, resid=xmid, rows_per_batch=T, out_f32=True)
+        self._linear_fwd(ws, l, FC2, None if fuse_a else b["a"], xout, D, aux_out=ptr(b["y2"]), gate=g2, gate_ld=ld, resid=xmid, rows_per_batch=T, out_f32=True)
         return False
 
-    def _linear_fwd(self, ws, b, fkey, x, name, M, N, K, out, ldc, **epi):
-        """y = x W^T + bias with the block's epilogue: bf16 / f32 MFMA GEMM, or (fp8 mode) quantise x (keeping x^T for the weight
-        gradient) and run the e4m3 x e4m3 GEMM."""
+    def _linear_fwd(self, ws, l, s, x, out, ldc, **epi):
+        """Site s of block l, y = x W^T + bias with the block's epilogue: bf16 / f32 MFMA GEMM, or (fp8 mode) quantise x (keeping x^T for
+        the weight gradient) and run the e4m3 x e4m3 GEMM."""
+        b, fkey, name, M, (N, K) = ws.blk[l], s.f_x, f"blocks.{l}.{s.prefix}", ws.M, s.shape(self.D, self.Dm)
         if not ws.fp8:
             ops.gemm(self._dt, 1, 1, M, N, K, ptr(x), K, self._w(name + "weight"), K, out, ldc, bias=self._p32(name + "bias"), **epi)
             return
@@ -626,8 +649,9 @@ class DiT(FlatModule):
         w = self._fp8_w[name + "weight"]
         ops.gemm_fp8(M, N, K, f.last_q, K, ptr(f.scale), ptr(w.q), K, ptr(w.scale), out, ldc, bias=self._p32(name + "bias"), **epi)
 
-    def _linear_dgrad(self, ws, b, fkey, dy, name, M, N, K, out, **epi):
-        """dx[M,K] = dy[M,N] W[N,K] (+ epilogue).  fp8 mode: quantise dy (keeping dy^T for the weight gradient), contract with W^T."""
+    def _linear_dgrad(self, ws, l, s, dy, out, **epi):
+        """Site s of block l, dx[M,K] = dy[M,N] W[N,K] (+ epilogue).  fp8: quantise dy (keeping dy^T for the weight gradient), contract with W^T."""
+        b, fkey, name, M, (N, K) = ws.blk[l], s.f_dy, f"blocks.{l}.{s.prefix}", ws.M, s.shape(self.D, self.Dm)
         if not ws.fp8:
             ops.gemm(self._dt, 1, 0, M, K, N, ptr(dy) if isinstance(dy, torch.Tensor) else dy, N, self._w(name + "weight"), K, out, K, **epi)
             return
@@ -677,10 +701,8 @@ class DiT(FlatModule):
         by-products -- dgate / dshift / dscale in ws.dmod, partial column sums in ws.cp -- land in the workspace as always), so dx
         has the full backward's bits."""
         ws = self._ws_cur
-        B = ws.B
-        dt, D, T, Dm, Lyr, ld = self._dt, self.D, self.T, self.Dm, self.depth, self.mod_cols
-        M, lib, st = B * T, L.lib(), L.stream_ptr()
-        H = W = self.image_size
+        B, M, dt, D, T, Lyr, ld = ws.B, ws.M, self._dt, self.D, self.T, self.depth, self.mod_cols
+        lib, st, H, W = L.lib(), L.stream_ptr(), self.image_size, self.image_size
         if only_dx:
             if ws.fp8:
                 raise ValueError(self._ONLY_DX_FP8)
@@ -690,53 +712,46 @@ class DiT(FlatModule):
             self._gbase = self.flat_grads().data_ptr()
             hook = self.grad_ready_hook
         ada_half = self._ada_split_block() if hook else None      # early adaLN bucket only when somebody listens (DDP)
-        # (ws.dDm / ws.dqkv / ws.dyb are None, and ptr() of them 0, when the shared record carries its own dy operands: activation
-        # recomputation in the deferred mode.  They are read only on the `not own_dy` side below, which that mode never takes.)
-        dres, dD, dDm, dmod = ptr(ws.dres), ptr(ws.dD), ptr(ws.dDm), ptr(ws.dmod)
-        mod = ptr(ws.mod)
-        es = self._wsize
+        dres, dD, es, fp8, ckpt = ptr(ws.dres), ptr(ws.dD), self._wsize, ws.fp8, ws.ckpt
         defer = ws.defer and dt == BF16
-        fp8 = ws.fp8
         own_dy = defer and not fp8            # every block keeps its four dy operands for the grouped weight-gradient launch
-        # activation recomputation: block l's record is refilled (_block_fwd) at the top of its iteration below.  The fused
+        # where dy of a site goes without that: scratch shared by all blocks.  (ws.dDm / ws.dqkv / ws.dyb are None, and ptr() of them
+        # 0, when the shared record carries its own dy operands: activation recomputation in the deferred mode, which never reads them.)
+        shared = {FC2: ptr(ws.dyb), FC1: ptr(ws.dDm), PROJ: ptr(ws.dyb), QKV: ptr(ws.dqkv)}
+        # activation recomputation (ckpt): block l's record is refilled (_block_fwd) at the top of its iteration below.  The fused
         # LayerNorm-backward + gate-backward pass hands block l+1's residual gradient to block l's MLP branch and reads y2 of block l
         # together with the statistics of block l+1 -- two blocks' records at once, which the shared record cannot hold.  So with the
         # flag on that hand-off runs as the unfused pair (bitwise the same results): LayerNorm backward of block l+1, recompute of
         # block l, gate backward of block l.  The weight gradients of a block then run right after its own backward.
-        ckpt = ws.ckpt
-        # fp8, delayed scaling: the row kernels write dy as fp8 themselves
-        fuse_rows = fp8 and ws.d_bwd and self.fp8_fuse_epilogue and self.fp8_fuse_rows and M % 64 == 0 and D % 128 == 0
+        fuse_rows, fuse_dh = (self._fuse(ws, fp8 and ws.d_bwd, rows) for rows in (True, False))      # dy / dhid leave their producers as fp8
         fuse_tail = L.STEP_FUSED and dt == BF16      # the conversions of the conditioning path and of d(x0) ride on their producers
 
         def ln_bwd_and_gate(dout_p, x_p, mean_p, rstd_p, scale_p, dres_in, dsh, dsc, nxt, dx_act=0):
             """Backward of one LayerNorm+modulate (d of its output -> residual-stream gradient, dshift, dscale) and, in the same
-            pass over the rows, the gate backward of the branch in FRONT of it (nxt = (block index, "mlp" | "attn") or None):
+            pass over the rows, the gate backward of the branch in FRONT of it (nxt = (block index, FC2 | PROJ) or None):
             dy of that branch, its dgate and the per-sample column sums of dy (the bias gradient of fc2 / proj)."""
             if nxt is None:
                 ops.ln_modulate_bwd(dt, dout_p, x_p, mean_p, rstd_p, scale_p, ld, dres_in, dres, dsh, dsc, ld, B, T, D, dx_act=dx_act)
                 return
-            l2, which = nxt
-            nb = ws.blk[l2]
-            mo2, dmo2 = mod + 4 * (6 * l2 * D), dmod + 4 * (6 * l2 * D)
-            gcol = 5 if which == "mlp" else 2
-            y, cp = (nb["y2"], ws.cp[l2]["fc2"]) if which == "mlp" else (nb["y1"], ws.cp[l2]["proj"])
+            l2, s = nxt
+            nb, gate, dgate, cp = ws.blk[l2], ws.mod_at(l2, s.gate), ws.dmod_at(l2, s.gate), ws.cp[l2][s.cp].buf.data_ptr()
             if fuse_rows:
-                ops.ln_modulate_bwd_gate_fp8(dout_p, x_p, mean_p, rstd_p, scale_p, ld, dres_in, dres, dsh, dsc, ld, ptr(y),
-                                             mo2 + 4 * gcol * D, nb["f_dy2" if which == "mlp" else "f_dy1"], dmo2 + 4 * gcol * D,
-                                             B, T, D, cp.buf.data_ptr())
+                ops.ln_modulate_bwd_gate_fp8(dout_p, x_p, mean_p, rstd_p, scale_p, ld, dres_in, dres, dsh, dsc, ld, ptr(nb[s.y]),
+                                             gate, nb[s.f_dy], dgate, B, T, D, cp)
             else:
-                dy = ptr(nb["dy2" if which == "mlp" else "dy1"]) if own_dy else ptr(ws.dyb)
-                ops.ln_modulate_bwd_gate(dt, dout_p, x_p, mean_p, rstd_p, scale_p, ld, dres_in, dres, dsh, dsc, ld, ptr(y),
-                                         mo2 + 4 * gcol * D, dy, dmo2 + 4 * gcol * D, B, T, D, cp.buf.data_ptr())
+                ops.ln_modulate_bwd_gate(dt, dout_p, x_p, mean_p, rstd_p, scale_p, ld, dres_in, dres, dsh, dsc, ld, ptr(nb[s.y]),
+                                         gate, ptr(nb[s.dy]) if own_dy else shared[s], dgate, B, T, D, cp)
+
+        def wgrad(l, s, dy, bias=False):      # per layer, for site s of block l (its bias gradient: from the producer of dy unless bias)
+            self._wgrad(dt, f"blocks.{l}.{s.prefix}", dy, ptr(ws.blk[l][s.x]), *s.shape(D, self.Dm), M, beta, bias=bias)
 
         # head: unpatchify^T, final linear, final LN+modulate (+ the gate backward of the last block's MLP branch)
         L.check(lib.vaw_unpatchify_bwd(dt, ptr(dout), ptr(ws.dotok), B, self.out_channels, H, W, self.patch_size, st), "unpatchify_bwd")
         if not only_dx:
             self._wgrad(dt, "final_layer.linear.", ptr(ws.dotok), ptr(ws.xf), self.No, D, M, beta)
         ops.gemm(dt, 1, 0, M, D, self.No, ptr(ws.dotok), self.No, self._w("final_layer.linear.weight"), D, dD, D)
-        mo, dmo = mod + 4 * (6 * Lyr * D), dmod + 4 * (6 * Lyr * D)
-        ln_bwd_and_gate(dD, ptr(ws.xres[2 * Lyr]), ptr(ws.meanf), ptr(ws.rstdf), mo + 4 * D, 0, dmo, dmo + 4 * D,
-                        (Lyr - 1, "mlp") if (Lyr and not ckpt) else None)
+        ln_bwd_and_gate(dD, ptr(ws.xres[2 * Lyr]), ptr(ws.meanf), ptr(ws.rstdf), ws.mod_at(Lyr, FINAL_SCALE), 0, ws.dmod_at(Lyr, FINAL_SHIFT),
+                        ws.dmod_at(Lyr, FINAL_SCALE), (Lyr - 1, FC2) if (Lyr and not ckpt) else None)
         if hook:
             hook(Lyr + 1)
         pending = []                      # blocks whose weight gradients wait for the next grouped launch
@@ -744,8 +759,7 @@ class DiT(FlatModule):
 
         def fold_bias(blocks, qkv_too):
             """The bias gradients of `blocks` from the partial column sums their backward left behind: one launch."""
-            names = (("fc2", "mlp.fc2."), ("fc1", "mlp.fc1."), ("proj", "attn.proj."), ("qkv", "attn.qkv."))[:4 if qkv_too else 3]
-            cps = [(ws.cp[l][k], f"blocks.{l}.{nm}bias") for l in blocks for k, nm in names]
+            cps = [(ws.cp[l][s.cp], f"blocks.{l}.{s.prefix}bias") for l in blocks for s in SITES_BWD[:4 if qkv_too else 3]]
             # the number of partial rows a producer leaves is NOT a function of the shape alone: vaw_gemm writes one row per 64, 128
             # or 256 rows of C depending on the kernel it picks (which moves with the CUs reserved for a collective, with
             # vaw_debug_gemm_tile, ...), the attention backward one per 64 / 128 / 256 query rows by VAW_ATTN_BWD_BIG.  The device
@@ -762,16 +776,13 @@ class DiT(FlatModule):
 
             def build():
                 probs = []
-                for l in pending:
-                    b, pre = ws.blk[l], f"blocks.{l}."
+                for l, s in ((l, s) for l in pending for s in SITES_BWD):
+                    b, (Nw, Kw), dw = ws.blk[l], s.shape(D, self.Dm), self._g(f"blocks.{l}.{s.prefix}weight")
                     if fp8:     # dy^T [Nw][M] and x^T [Kw][M], with their device scales
-                        for name, fdy, fx, Nw, Kw in ((pre + "mlp.fc2.", b["f_dy2"], b["f_a"], D, Dm), (pre + "mlp.fc1.", b["f_dhid"], b["f_xm2"], Dm, D),
-                                                      (pre + "attn.proj.", b["f_dy1"], b["f_ao"], D, D), (pre + "attn.qkv.", b["f_dqkv"], b["f_xm"], 3 * D, D)):
-                            probs.append((ptr(fdy.qt), ptr(fx.qt), self._g(name + "weight"), Nw, Kw, M, M, Kw, 0.0, 0, ptr(fdy.scale), ptr(fx.scale)))
-                        continue
-                    for name, dy, x, Nw, Kw in ((pre + "mlp.fc2.", b["dy2"], b["a"], D, Dm), (pre + "mlp.fc1.", b["dDm"], b["xm2"], Dm, D),
-                                                (pre + "attn.proj.", b["dy1"], b["ao"], D, D), (pre + "attn.qkv.", b["dqkv"], b["xm"], 3 * D, D)):
-                        probs.append((ptr(dy), ptr(x), self._g(name + "weight"), Nw, Kw, Nw, Kw, Kw))
+                        fdy, fx = b[s.f_dy], b[s.f_x]
+                        probs.append((ptr(fdy.qt), ptr(fx.qt), dw, Nw, Kw, M, M, Kw, 0.0, 0, ptr(fdy.scale), ptr(fx.scale)))
+                    else:
+                        probs.append((ptr(b[s.dy]), ptr(b[s.x]), dw, Nw, Kw, Nw, Kw, Kw))
                 return ops.WgradGroup(probs, M, dout.device)
             ws.wgrad_groups.get((pending[0], pending[-1], self._gbase), build).launch((L.BF8 if self.fp8_grad_format == "e5m2" else L.FP8) if fp8 else dt, beta)
             fold_bias(list(pending), True)
@@ -781,61 +792,52 @@ class DiT(FlatModule):
             pending.clear()
 
         for l in reversed(range(Lyr)):
-            b, cp, pre = ws.blk[l], ws.cp[l], f"blocks.{l}."
-            mo, dmo = mod + 4 * (6 * l * D), dmod + 4 * (6 * l * D)
-            xin, xmid = ptr(ws.xres[2 * l]), ptr(ws.xres[2 * l + 1])
-            dy2, dhid, dy1, dq = ((ptr(b["dy2"]), ptr(b["dDm"]), ptr(b["dy1"]), ptr(b["dqkv"])) if own_dy
-                                  else (ptr(ws.dyb), dDm, ptr(ws.dyb), ptr(ws.dqkv)))
+            b, cp, xin, xmid = ws.blk[l], ws.cp[l], ptr(ws.xres[2 * l]), ptr(ws.xres[2 * l + 1])
+            dy2, dhid, dy1, dq = (ptr(b[s.dy]) if own_dy else shared[s] for s in SITES_BWD)
             if ckpt:
                 self._block_fwd(ws, l, xout=ptr(ws.xscr))
                 if self._ckpt_debug_hook is not None:
                     self._ckpt_debug_hook(l, b)
-                ops.gate_bwd(dt, dres, ptr(b["y2"]), mo + 4 * 5 * D, ld, dy2, dmo + 4 * 5 * D, ld, B, T, D, cp["fc2"].buf.data_ptr())
+                ops.gate_bwd(dt, dres, ptr(b["y2"]), ws.mod_at(l, GATE_MLP), ld, dy2, ws.dmod_at(l, GATE_MLP), ld, B, T, D, cp["fc2"].buf.data_ptr())
             # MLP branch.  dy2, dgate and the partial column sums of dy2 (fc2's bias gradient) came out of the row kernel that
             # produced this block's incoming residual gradient; bias gradients are folded per group (fold_bias)
             if not defer and not only_dx:
-                self._wgrad(dt, pre + "mlp.fc2.", dy2, ptr(b["a"]), D, Dm, M, beta, bias=False)
-            fuse_dh = fp8 and ws.d_bwd and self.fp8_fuse_epilogue and M % 64 == 0       # fc2's input-gradient epilogue writes dhid as fp8
-            self._linear_dgrad(ws, b, "f_dy2", None if fuse_rows else dy2, pre + "mlp.fc2.", M, D, Dm, b["f_dhid"].epilogue_target() if fuse_dh else dhid, act=2,
+                wgrad(l, FC2, dy2)
+            self._linear_dgrad(ws, l, FC2, None if fuse_rows else dy2, b["f_dhid"].epilogue_target() if fuse_dh else dhid, act=2,
                                aux_in=ptr(b["hpre"]), colsum_partial=cp["fc1"], **({"out_fp8": b["f_dhid"]} if fuse_dh else {}))
             if not defer and not only_dx:
-                self._wgrad(dt, pre + "mlp.fc1.", dhid, ptr(b["xm2"]), Dm, D, M, beta, bias=False)
-            self._linear_dgrad(ws, b, "f_dhid", None if (fp8 and fuse_dh) else dhid, pre + "mlp.fc1.", M, Dm, D, dD)
-            ln_bwd_and_gate(dD, xmid, ptr(b["mean2"]), ptr(b["rstd2"]), mo + 4 * 4 * D, dres, dmo + 4 * 3 * D, dmo + 4 * 4 * D, (l, "attn"))
+                wgrad(l, FC1, dhid)
+            self._linear_dgrad(ws, l, FC1, None if fuse_dh else dhid, dD)
+            ln_bwd_and_gate(dD, xmid, ptr(b["mean2"]), ptr(b["rstd2"]), ws.mod_at(l, SCALE_MLP), dres, ws.dmod_at(l, SHIFT_MLP),
+                            ws.dmod_at(l, SCALE_MLP), (l, PROJ))
             # attention branch (dy1 etc. from the fused row kernel just above)
             if not defer and not only_dx:
-                self._wgrad(dt, pre + "attn.proj.", dy1, ptr(b["ao"]), D, D, M, beta, bias=False)
-            self._linear_dgrad(ws, b, "f_dy1", None if fuse_rows else dy1, pre + "attn.proj.", M, D, D, ptr(ws.dao))
+                wgrad(l, PROJ, dy1)
+            self._linear_dgrad(ws, l, PROJ, None if fuse_rows else dy1, ptr(ws.dao))
             q = ptr(b["qkv"])
-            qkv_bias_folded = False
-            if defer:      # the qkv bias gradient = column sums of dqkv: partial rows from the attention kernels where they offer it
-                qkv_bias_folded = ops.attn_bwd_colsum(dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(ws.dao),
-                                                      ptr(b["lse"]), ptr(ws.delta), dq, dq + es * D, dq + 2 * es * D, cp["qkv"])
-            if not qkv_bias_folded:
-                ops.attn_bwd(dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(ws.dao), ptr(b["lse"]),
-                             ptr(ws.delta), dq, dq + es * D, dq + 2 * es * D)
-                if only_dx:
-                    pass
-                elif defer:
+            attn = (dt, self._attn_desc(B), q, q + es * D, q + 2 * es * D, ptr(b["ao"]), ptr(ws.dao), ptr(b["lse"]), ptr(ws.delta), dq, dq + es * D,
+                    dq + 2 * es * D)
+            # the qkv bias gradient = column sums of dqkv: deferred, partial rows from the attention kernels where they offer it
+            if not (defer and ops.attn_bwd_colsum(*attn, cp["qkv"])):
+                ops.attn_bwd(*attn)
+                if defer and not only_dx:
                     ops.colsum(dt, dq, M, 3 * D, 3 * D, cp["qkv"].buf.data_ptr(), 0.0, device=dout.device)     # one complete row
                     cp["qkv"].rows.value = 1
-                else:      # (the per-layer launch takes the bias gradient from its staged dy tiles)
-                    self._wgrad(dt, pre + "attn.qkv.", dq, ptr(b["xm"]), 3 * D, D, M, beta)
-            self._linear_dgrad(ws, b, "f_dqkv", dq, pre + "attn.qkv.", M, 3 * D, D, dD)
+                elif not only_dx:      # (the per-layer launch takes the bias gradient from its staged dy tiles)
+                    wgrad(l, QKV, dq, bias=True)
+            self._linear_dgrad(ws, l, QKV, dq, dD)
             # block 0's LayerNorm backward ends the residual stream: its dx is the patch embedding's output gradient, and the bf16
             # operand of that layer's two GEMMs leaves the same launch, in ws.dao (free since this block's attention backward; dD
             # is the launch's own input), instead of a cast pass over dres
             last_cast = fuse_tail and l == 0
-            ln_bwd_and_gate(dD, xin, ptr(b["mean1"]), ptr(b["rstd1"]), mo + 4 * D, dres, dmo, dmo + 4 * D,
-                            (l - 1, "mlp") if (l and not ckpt) else None, dx_act=ptr(ws.dao) if last_cast else 0)
-            if only_dx:
-                pass
-            elif defer:
+            ln_bwd_and_gate(dD, xin, ptr(b["mean1"]), ptr(b["rstd1"]), ws.mod_at(l, SCALE_MSA), dres, ws.dmod_at(l, SHIFT_MSA),
+                            ws.dmod_at(l, SCALE_MSA), (l - 1, FC2) if (l and not ckpt) else None, dx_act=ptr(ws.dao) if last_cast else 0)
+            if defer and not only_dx:
                 pending.append(l)
                 if ckpt or l == group_cut:      # (recomputation: the operands are gone once the next block is re-run)
                     pending.reverse()
                     flush()
-            else:
+            elif not only_dx:
                 fold_bias([l], False)
             if hook:
                 if not defer:
@@ -843,7 +845,7 @@ class DiT(FlatModule):
                 if l == ada_half:
                     # data-parallel runs: the adaLN rows of blocks >= l (and the final layer's) are final now -- weight and
                     # bias gradients of that part of the packed matrix leave with their own bucket while blocks l-1..0 run
-                    r0 = 6 * l * D
+                    r0 = mod_offset(l, SHIFT_MSA, D)      # (= its first row of the packed matrix: see SHIFT_MSA)
                     self._adaln_wgrad(dt, ws, r0, ld - r0, B, beta)
                     hook("ada_hi")
         pending.reverse()
@@ -866,13 +868,12 @@ class DiT(FlatModule):
         if only_dx:
             return dx
         # conditioning path: adaLN (all blocks at once, or the rows the early bucket has not covered), label table, timestep MLP
-        rows = ld if ada_half is None else 6 * ada_half * D
+        rows = ld if ada_half is None else mod_offset(ada_half, SHIFT_MSA, D)
         dmod_a = self._adaln_wgrad(dt, ws, 0, rows, B, beta)
         ops.gemm(dt, 1, 0, B, D, ld, dmod_a, ld, self._w("blocks.0.adaLN_modulation.1.weight"), D, ptr(ws.dcs), D, out_f32=True)
         ops.silu_bwd(ws.c, ws.dcs, ws.dc, ws.dc_a[:B] if fuse_tail else None)
-        ye = self.y_embedder.embedding_table
         L.check(lib.vaw_embedding_bwd(ptr(ws.dc), ptr(ws.y), self._g("y_embedder.embedding_table.weight"), B, D,
-                                      ye.num_embeddings, beta, st), "embedding_bwd")
+                                      self.y_embedder.embedding_table.num_embeddings, beta, st), "embedding_bwd")
         if dt == BF16 and not fuse_tail:
             ops.cast_bf16(ws.dc, ws.dc_a)
         dc_a = ptr(ws.dc_a) if dt == BF16 else ptr(ws.dc)

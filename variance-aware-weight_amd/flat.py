@@ -158,8 +158,20 @@ class FlatModule(nn.Module):
         for p in self._flat_params:
             p.grad = None
 
+    # ---- device addresses of a parameter for the engines (dit.py, unet.py), which set _wbase / _wsize at forward and _gbase at backward
+    def _w(self, name):      # in the dtype the kernels read (bf16 shadow or f32 master)
+        return self._wbase + self._flat_offsets[name][0] * self._wsize
+
+    def _g(self, name):      # of its gradient (_gbase = None under input_grad_only(): a weight-gradient launch that slipped through raises)
+        return self._gbase + 4 * self._flat_offsets[name][0]
+
+    def _p32(self, name):      # of its f32 master
+        return self._flat.data_ptr() + 4 * self._flat_offsets[name][0]
+
     # ---- evaluation backward: dx and nothing else --------------------------------------------------------------------------
     _input_grad_only = False
+    _ONLY_DX_FP8 = ("input_grad_only() does not combine with compute_dtype='fp8': the delayed-scaling state of the fp8 tensors would "
+                    "move during an evaluation")
 
     @contextlib.contextmanager
     def input_grad_only(self):
@@ -171,8 +183,7 @@ class FlatModule(nn.Module):
         forward and checked at backward: entering or leaving in between raises VawError.  Refuses compute_dtype='fp8' with a
         ValueError (the delayed-scaling state would move during an evaluation)."""
         if getattr(self, "compute_dtype", None) == "fp8":
-            raise ValueError("input_grad_only() does not combine with compute_dtype='fp8': the delayed-scaling state of the fp8 "
-                             "tensors would move during an evaluation")
+            raise ValueError(self._ONLY_DX_FP8)
         before = self._input_grad_only
         self._input_grad_only = True
         try:

@@ -612,21 +612,46 @@ def ddim_reverse_step(mean_out, x, coef, clip_denoised):
 
 
 # ---- dense -------------------------------------------------------------------------------------
+def epilogue(*, bias=None, act=0, aux_in=None, aux_out=None, gate=None, gate_ld=0, resid=None, rowadd=None, rows_per_batch=0, alpha=1.0,
+             beta=0.0, out_f32=False, colsum_out=None, colsum_beta=0.0, resid_is_act=False, rowsum_a_out=None, rowsum_a_beta=0.0,
+             colsum_partial=None, colsum_partial_out=16):
+    """vaw_epilogue from keywords named as its fields (addresses as integers, 0 / None = NULL): alpha = 1, everything else zero or
+    null; any other keyword is a TypeError.  Every launch and its *_plan twin build theirs here, so a plan sees its launch's epilogue.
+    colsum_partial = a ColsumPartial (its buffer and its host row count: in the capacity, out the rows written) or, for a plan, a
+    bare row capacity, which stands at the address colsum_partial_out (any non-zero one serves)."""
+    e = Epilogue(bias=bias or None, act=act, aux_in=aux_in or None, aux_out=aux_out or None, gate=gate or None, gate_ld=gate_ld,
+                 resid=resid or None, rowadd=rowadd or None, rows_per_batch=rows_per_batch, alpha=alpha, beta=beta,
+                 out_f32=1 if out_f32 else 0, colsum_out=colsum_out or None, colsum_beta=colsum_beta,
+                 resid_is_act=1 if resid_is_act else 0, rowsum_a_out=rowsum_a_out or None, rowsum_a_beta=rowsum_a_beta)
+    if colsum_partial is not None:
+        if isinstance(colsum_partial, ColsumPartial):
+            rows, colsum_partial_out = colsum_partial.rows, colsum_partial.buf.data_ptr()
+            rows.value = colsum_partial.buf.shape[0]
+        else:
+            rows = C.c_int64(colsum_partial)
+        e.colsum_partial_out, e.colsum_rows_out, e.rows = colsum_partial_out, C.pointer(rows), rows     # (e.rows keeps the count alive)
+    return e
+
+
+def _trace_open():
+    """(GemmTrace that listens, e0, e1) with e0 recorded on the launch stream -- the caller launches, records e1, adds its row -- or Nones."""
+    tr = gemm_trace
+    if tr is None:
+        return None, None, None
+    e0, e1 = tr.events()
+    e0.record()
+    return tr, e0, e1
+
+
 def gemm(dt, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, Cp, ldc, *, bias=None, act=0, aux_in=None, aux_out=None,
          gate=None, gate_ld=0, resid=None, rowadd=None, rows_per_batch=0, alpha=1.0, beta=0.0, out_f32=False,
          colsum_out=None, colsum_beta=0.0, resid_is_act=False, rowsum_a_out=None, rowsum_a_beta=0.0, colsum_partial=None):
     """Raw-pointer GEMM; A, B, Cp, bias... are integers (device addresses).  See vaw_gemm in the header.
     colsum_partial = ColsumPartial: the column sums of C stay as partial rows in its buffer (folded later, many at once)."""
-    e = Epilogue(bias or None, act, aux_in or None, aux_out or None, gate or None, gate_ld, resid or None,
-                 rowadd or None, rows_per_batch, alpha, beta, 1 if out_f32 else 0, colsum_out or None, colsum_beta,
-                 1 if resid_is_act else 0, rowsum_a_out or None, rowsum_a_beta)
-    if colsum_partial is not None:
-        colsum_partial.rows.value = colsum_partial.buf.shape[0]           # in: capacity; out: rows written
-        e.colsum_partial_out, e.colsum_rows_out = colsum_partial.buf.data_ptr(), C.pointer(colsum_partial.rows)
-    tr = gemm_trace
-    if tr is not None:
-        e0, e1 = tr.events()
-        e0.record()
+    e = epilogue(bias=bias, act=act, aux_in=aux_in, aux_out=aux_out, gate=gate, gate_ld=gate_ld, resid=resid, rowadd=rowadd,
+                 rows_per_batch=rows_per_batch, alpha=alpha, beta=beta, out_f32=out_f32, colsum_out=colsum_out, colsum_beta=colsum_beta,
+                 resid_is_act=resid_is_act, rowsum_a_out=rowsum_a_out, rowsum_a_beta=rowsum_a_beta, colsum_partial=colsum_partial)
+    tr, e0, e1 = _trace_open()
     ws_ptr, ws_n = 0, 0
     if colsum_out or colsum_partial is not None or rowsum_a_out or (beta_or_plain(bias, act, aux_out, gate, resid, rowadd) and K >= 2048):     # may run split-K
         ws = scratch_f32(torch.device("cuda", torch.cuda.current_device()), 0)
@@ -656,14 +681,7 @@ def gemm_plan(dt, a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, Cp, ldc, *, works
     for null-ness and alignment only; colsum_partial_rows = capacity of a colsum_partial buffer (any non-zero address stands for
     it); knobs = None: the process's own, else a GemmKnobs (default_gemm_knobs).  check_status = False returns the plan of a
     refused call (status != 0) instead of raising."""
-    e = Epilogue(epi.get("bias") or None, epi.get("act", 0), epi.get("aux_in") or None, epi.get("aux_out") or None, epi.get("gate") or None,
-                 epi.get("gate_ld", 0), epi.get("resid") or None, epi.get("rowadd") or None, epi.get("rows_per_batch", 0),
-                 epi.get("alpha", 1.0), epi.get("beta", 0.0), 1 if epi.get("out_f32") else 0, epi.get("colsum_out") or None,
-                 epi.get("colsum_beta", 0.0), 1 if epi.get("resid_is_act") else 0, epi.get("rowsum_a_out") or None,
-                 epi.get("rowsum_a_beta", 0.0))
-    rows = C.c_int64(colsum_partial_rows or 0)
-    if colsum_partial_rows is not None:
-        e.colsum_partial_out, e.colsum_rows_out = epi.get("colsum_partial_out", 16), C.pointer(rows)
+    e = epilogue(colsum_partial=colsum_partial_rows, **epi)
     p = L.GemmLaunch()
     rc = L.lib().vaw_gemm_plan(dt, 1 if a_kmajor else 0, 1 if b_kmajor else 0, M, N, K, lda, ldb, ldc, A, B, Cp, C.byref(e),
                                workspace_floats, C.byref(knobs) if knobs is not None else None, C.byref(p))
@@ -811,15 +829,10 @@ def gemm_fp8(M, N, K, A, lda, scale_a, B, ldb, scale_b, Cp, ldc, *, a_format=L.F
              out_fp8=None, colsum_partial=None):
     """Raw-pointer fp8 GEMM (vaw_gemm_fp8): A [M][K] bytes of a_format, B [N][K] e4m3 bytes; scale_a / scale_b device scalars.
     out_fp8 = an Fp8 whose delayed-scaling state is current: C (= its row-major bytes) is written as fp8 by the epilogue."""
-    e = Epilogue(bias or None, act, aux_in or None, aux_out or None, gate or None, gate_ld, resid or None, None, rows_per_batch,
-                 alpha, 0.0, 1 if out_f32 else 0, colsum_out or None, colsum_beta, 0, None, 0.0)
-    if colsum_partial is not None:
-        colsum_partial.rows.value = colsum_partial.buf.shape[0]           # in: capacity; out: rows written
-        e.colsum_partial_out, e.colsum_rows_out = colsum_partial.buf.data_ptr(), C.pointer(colsum_partial.rows)
-    tr = gemm_trace
-    if tr is not None:
-        e0, e1 = tr.events()
-        e0.record()
+    # (the fp8 launch has no rowadd, beta, resid_is_act or rowsum_a_out keyword: they stay null / zero)
+    e = epilogue(bias=bias, act=act, aux_in=aux_in, aux_out=aux_out, gate=gate, gate_ld=gate_ld, resid=resid, rows_per_batch=rows_per_batch,
+                 alpha=alpha, out_f32=out_f32, colsum_out=colsum_out, colsum_beta=colsum_beta, colsum_partial=colsum_partial)
+    tr, e0, e1 = _trace_open()
     ws_ptr, ws_n = 0, 0
     if colsum_out:
         ws = scratch_f32(torch.device("cuda", torch.cuda.current_device()), 0)
@@ -841,14 +854,8 @@ def gemm_fp8_plan(M, N, K, A, lda, scale_a, B, ldb, scale_b, Cp, ldc, *, a_forma
     and out_fp8_format its format; colsum_partial_rows = capacity of a colsum_partial buffer (any non-zero address stands for it);
     workspace_floats = 0 stands for no workspace; cus = 0: the CUs the process may use now, else a stated count.
     check_status = False returns the plan of a refused call (status != 0) instead of raising."""
-    e = Epilogue(epi.get("bias") or None, epi.get("act", 0), epi.get("aux_in") or None, epi.get("aux_out") or None, epi.get("gate") or None,
-                 epi.get("gate_ld", 0), epi.get("resid") or None, epi.get("rowadd") or None, epi.get("rows_per_batch", 0),
-                 epi.get("alpha", 1.0), epi.get("beta", 0.0), 1 if epi.get("out_f32") else 0, epi.get("colsum_out") or None,
-                 epi.get("colsum_beta", 0.0), 1 if epi.get("resid_is_act") else 0, epi.get("rowsum_a_out") or None,
-                 epi.get("rowsum_a_beta", 0.0))
-    rows = C.c_int64(colsum_partial_rows or 0)
-    if colsum_partial_rows is not None:
-        e.colsum_partial_out, e.colsum_rows_out = epi.get("colsum_partial_out", 16), C.pointer(rows)
+    # (what gemm_fp8 has no keyword for -- rowadd, beta, ... -- is passed on, so that the plan can be asked why it refuses them)
+    e = epilogue(colsum_partial=colsum_partial_rows, **epi)
     p = L.GemmFp8Launch()
     rc = L.lib().vaw_gemm_fp8_plan(a_format, M, N, K, A, lda, scale_a, B, ldb, scale_b, Cp, ldc, C.byref(e), out_fp8_state, out_fp8_format,
                                    workspace if workspace_floats > 0 else 0, workspace_floats, cus, C.byref(p))
@@ -868,10 +875,7 @@ class WgradGroup(TableGroup):
 
     def launch(self, dt, beta):
         ws = scratch_f32(self.device, 0)
-        tr = gemm_trace
-        if tr is not None:
-            e0, e1 = tr.events()
-            e0.record()
+        tr, e0, e1 = _trace_open()
         self._call("vaw_wgrad_grouped", dt, self.n, self.table, self.K, float(beta), post=(ws.data_ptr(), ws.numel()))
         if tr is not None:
             e1.record()
@@ -895,13 +899,11 @@ def conv3x3(dt, mode, act, act2, w, out, B, H, W, Ci, Co, *, bias=None, resid=No
             colsum_out=None, colsum_beta=0.0, rowsum_a_out=None, rowsum_a_beta=0.0):
     """Implicit-GEMM conv3x3 (vaw_conv3x3).  Returns False -- nothing launched -- when the shape needs the explicit
     im2col + GEMM path.  mode 0 forward, 1 input gradient, 2 weight gradient (f32 out, beta accumulates)."""
-    e = Epilogue(bias or None, 0, None, None, None, 0, resid or None, None, 0, 1.0, beta, 1 if mode == 2 else 0,
-                 colsum_out or None, colsum_beta, 1 if resid_is_act else 0, rowsum_a_out or None, rowsum_a_beta)
+    # (act stays 0 in the struct: the convolution's activations are operands of the call; the weight gradient is f32)
+    e = epilogue(bias=bias, resid=resid, resid_is_act=resid_is_act, beta=beta, out_f32=mode == 2, colsum_out=colsum_out, colsum_beta=colsum_beta,
+                 rowsum_a_out=rowsum_a_out, rowsum_a_beta=rowsum_a_beta)
     ws = scratch_f32(torch.device("cuda", torch.cuda.current_device()), 0)
-    tr = gemm_trace
-    if tr is not None:
-        e0, e1 = tr.events()
-        e0.record()
+    tr, e0, e1 = _trace_open()
     rc = L.lib().vaw_conv3x3(dt, mode, act, act2 or None, w, out, B, H, W, Ci, Co, C.byref(e), ws.data_ptr(), ws.numel(), stream_ptr())
     if rc == -3:
         if dt == L.BF16:       # the f32 parity mode always takes the explicit path; in bf16 it is a performance cliff worth a word
@@ -928,10 +930,8 @@ def conv3x3_plan(dt, mode, act, act2, w, out, B, H, W, Ci, Co, *, workspace=16, 
     for conv3x3(), the addresses used for null-ness and alignment only; workspace_floats = 0 stands for no workspace; knobs = None:
     the process's own, else a GemmKnobs (default_gemm_knobs); cus = 0: the CUs the process may use now (or the knobs' count).
     check_status = False returns the plan of a refused call (status -1 invalid, -3 the explicit path) instead of raising."""
-    e = Epilogue(epi.get("bias") or None, epi.get("act", 0), None, epi.get("aux_out") or None, epi.get("gate") or None, epi.get("gate_ld", 0),
-                 epi.get("resid") or None, epi.get("rowadd") or None, 0, 1.0, epi.get("beta", 0.0),
-                 1 if (mode == 2 or epi.get("out_f32")) else 0, epi.get("colsum_out") or None, epi.get("colsum_beta", 0.0),
-                 1 if epi.get("resid_is_act", True) else 0, epi.get("rowsum_a_out") or None, epi.get("rowsum_a_beta", 0.0))
+    # (as conv3x3 forces them: residual in the act dtype by default, mode 2 in f32; aux_in, rows_per_batch and alpha are not the caller's)
+    e = epilogue(**dict(epi, resid_is_act=epi.get("resid_is_act", True), out_f32=mode == 2 or epi.get("out_f32"), aux_in=None, rows_per_batch=0, alpha=1.0))
     p = L.Conv3x3Launch()
     rc = L.lib().vaw_conv3x3_plan(dt, mode, act or 0, act2 or 0, w or 0, out or 0, B, H, W, Ci, Co, C.byref(e),
                                   workspace if workspace_floats > 0 else 0, workspace_floats, C.byref(knobs) if knobs is not None else None,

@@ -309,19 +309,7 @@ class UNetModel(FlatModule):
         such a step cannot be captured into a hipGraph (the mask would freeze at its capture-time value)."""
         return (self.num_classes > 0 and self.drop_label_prob > 0) or (self.dropout > 0 and self.host_dropout_rng)
 
-    # ---- engine helpers -----------------------------------------------------------------------
-    def _w(self, name):
-        o, _ = self._flat_offsets[name]
-        return self._wbase + o * self._wsize
-
-    def _g(self, name):
-        o, _ = self._flat_offsets[name]
-        return self._gbase + 4 * o
-
-    def _p32(self, name):
-        o, _ = self._flat_offsets[name]
-        return self._flat.data_ptr() + 4 * o
-
+    # ---- engine helpers (parameter addresses: FlatModule._w / _g / _p32) -----------------------
     def _new(self, *shape, dtype=None):
         return torch.empty(*shape, device=self._flat.device, dtype=dtype or self._adt)
 

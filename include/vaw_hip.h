@@ -354,6 +354,10 @@ int vaw_flow_logp_prior(const float* z, double* logp, double* partials, int64_t 
  * reproducible whatever the launch shape.  An entry with t outside [0, T) is skipped and counted: bad[0] += 1. */
 int vaw_resampler_update(const int64_t* ts, const float* losses, int n, int T, int H, double* ring, int64_t* seen, int* bad,
                          vaw_stream stream);
+/* vaw_resampler_update for a run behind the step guard: a pair whose loss is inf or NaN is not recorded either; it is counted in
+ * bad[0] like a pair with t outside [0, T). */
+int vaw_resampler_update_finite(const int64_t* ts, const float* losses, int n, int T, int H, double* ring, int64_t* seen, int* bad,
+                                vaw_stream stream);
 
 /* weights() :116-125 + ScheduleSampler.sample :38-50 with the uniforms supplied (np.random.choice(p=...) is a right-sided
  * search of the normalised running sum of p):
@@ -568,6 +572,9 @@ int vaw_fp8_quantize(vaw_dtype src_dt, vaw_dtype dst_format, const void* src, in
 int vaw_fp8_quantize_delayed(vaw_dtype src_dt, vaw_dtype dst_format, const void* src, int64_t R, int64_t C, int64_t ld, void* q,
                              int64_t ldq, void* qt, int64_t ldt, float* state, vaw_stream stream);
 int vaw_fp8_scale_update(float* states, int64_t n, vaw_stream stream);
+/* vaw_fp8_scale_update for a run behind the step guard: a running max that is not finite (an overflowed tensor of a step the guard
+ * refuses) keeps the scale in use, like an all-zero one, instead of making the scale infinite; it is cleared all the same. */
+int vaw_fp8_scale_update_finite(float* states, int64_t n, vaw_stream stream);
 /* vaw_fp8_quantize_delayed for MANY f32 tensors in one launch (e4m3): the once-per-step re-quantisation of all Linear weights from
  * their f32 masters (the reference's autocast casts the same weights to bf16 on every use, tools/trainer.py:104-108).  jobs: host
  * array; desc_dev: device buffer of vaw_fp8_quantize_batched_desc_bytes(n_jobs) bytes, written when upload != 0 (as for
@@ -1084,6 +1091,37 @@ int vaw_adamw_ema_step(float* p, float* g, float* m, float* v, float* ema, void*
 int vaw_adamw_ema_step_dev(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t n,
                            const float* hyper, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
                            const float* sumsq, float clip_max_norm, int zero_grad, vaw_stream stream);
+
+/* ---- step guard (guard.py: StepGuard; FusedAdamW.attach_guard) -----------------------------------------------------------------
+ * The device refuses an optimizer step whose gradient is not finite, or whose norm jumps above a running mean, before the update
+ * touches the masters, the moments, the EMA or the shadow.  No host value is read or produced: the launches can be captured.
+ *
+ * vaw_step_guard: one thread reads sumsq[0] (vaw_sumsq of the step's flat gradient) and writes the verdict.  IEEE f64, every
+ * operation rounded on its own:
+ *   norm = sqrt((double)sumsq[0]);  finite = isfinite(sumsq[0])
+ *   spike = finite && spike_factor > 0 && applied >= spike_warmup && norm > spike_factor * mean
+ *   ok = finite && !spike
+ *   ok:      mean = applied == 0 ? norm : spike_beta * mean + (1 - spike_beta) * norm;  max_norm = max(max_norm, norm);
+ *            applied += 1;  in_a_row = 0
+ *   not ok:  skipped_nonfinite += 1 (not finite) or skipped_spike += 1;  in_a_row += 1
+ *   always:  steps += 1;  last_norm = norm
+ * counters: int32 [VAW_GUARD_COUNTERS] = {ok, steps, applied, skipped_nonfinite, skipped_spike, in_a_row};
+ * stats: f64 [VAW_GUARD_STATS] = {last_norm, mean, max_norm, 0}.  spike_factor <= 0: no spike test; otherwise it must be > 1;
+ * spike_beta in [0, 1); spike_warmup >= 0 (VAW_ERR_INVALID otherwise). */
+#define VAW_GUARD_COUNTERS 6
+#define VAW_GUARD_STATS 4
+int vaw_step_guard(const float* sumsq, int32_t* counters, double* stats, float spike_factor, double spike_beta, int spike_warmup,
+                   vaw_stream stream);
+/* vaw_adamw_ema_step / _dev behind the verdict ok[0] (device int32, counters[0] of vaw_step_guard).  ok[0] != 0: bitwise the
+ * unguarded call on every stream.  ok[0] == 0: nothing is read or written except g = 0 when zero_grad.  The branch is uniform
+ * across the grid; the pass is the same device text as the unguarded kernel's. */
+int vaw_adamw_ema_step_guarded(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t n, float lr,
+                               float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2,
+                               float ema_decay, const float* sumsq, float clip_max_norm, int zero_grad, const int32_t* ok,
+                               vaw_stream stream);
+int vaw_adamw_ema_step_guarded_dev(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t n,
+                                   const float* hyper, float beta1, float beta2, float eps, float weight_decay, float ema_decay,
+                                   const float* sumsq, float clip_max_norm, int zero_grad, const int32_t* ok, vaw_stream stream);
 /* ema = ema*decay + src*(1-decay) over n f32 (buffers that are not optimizer-owned, e.g. frozen pos_embed) */
 int vaw_ema_update(float* ema, const float* src, int64_t n, float decay, vaw_stream stream);
 /* dst(bf16) = src(f32) */

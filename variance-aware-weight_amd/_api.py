@@ -8,6 +8,7 @@ from .unet import (ADM_32, ADM_64, ADM_128, ADM_256, ADM_512, LDM, UNet_32, UNet
 from .gaussian_diffusion import (FlowMatching, GaussianDiffusion, LossType, ModelMeanType, ModelVarType,  # noqa: F401
                                  compute_mse_loss_weight, get_named_beta_schedule, mean_flat)
 from .optim import FusedAdamW  # noqa: F401
+from .guard import StepGuard  # noqa: F401
 # (`vaw_amd.ema` stays trainer.ema, the function, imported below: reach the module as `from vaw_amd.ema import ...`)
 from .ema import (PowerEMA, gamma_to_sigma_rel, lincomb_fold, posthoc_coefficients, posthoc_ema, power_ema_coefficient,  # noqa: F401
                   profile_dot, sigma_rel_to_gamma)

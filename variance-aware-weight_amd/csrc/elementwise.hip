@@ -920,10 +920,25 @@ __device__ __forceinline__ void adam_one(float& p, float& g, float& m, float& v,
 // stores.  Round 3's one-float4-per-iteration grid-stride loop ran at 5.0 TB/s of these bytes.
 #define ADAM_U 4
 __device__ __forceinline__ f32x4 nt_load4(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); }
+// GUARDED (vaw_adamw_ema_step_guarded; guard.hip: vaw_step_guard writes the verdict): ok[0] is one word every lane of every workgroup
+// reads, so the branch is uniform across the grid.  ok[0] != 0: the pass below, bit for bit.  ok[0] == 0: the step is refused --
+// nothing is read and nothing written but the zero_grad store of g, so the masters, the moments, the EMA and the shadow keep the
+// last good step's bits.  One text, two instantiations; the unguarded one never looks at `ok`.
+template <bool GUARDED>
 __global__ void __launch_bounds__(256)
 adamw_ema_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                  float* __restrict__ ema, bf16_t* __restrict__ shadow, int64_t n, const float* __restrict__ sumsq, AdamArgs a,
-                 const float* __restrict__ hyper) {
+                 const float* __restrict__ hyper, const int32_t* __restrict__ ok) {
+    if (GUARDED && ok[0] == 0) {
+        if (a.zero_grad) {
+            const int64_t n4 = n / 4;
+            for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+                store4(g + 4 * i, f32x4{0, 0, 0, 0});
+            for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+                g[i] = 0.f;
+        }
+        return;
+    }
     if (hyper) {          // step-dependent scalars from device memory: the launch can then sit in a replayed hipGraph
         a.lr = hyper[0];
         a.bc1 = hyper[1];
@@ -996,32 +1011,55 @@ static inline int adam_grid(int64_t n) {
     return (int)(tiles < 1 ? 1 : (tiles > cap ? cap : tiles));
 }
 
+// One host side for the four entry points: hyper == nullptr takes the step-dependent scalars from `a`, `guarded` picks the
+// instantiation (and then insists on a verdict to read).
+static int adamw_launch(const char* what, float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t n,
+                        const float* hyper, const AdamArgs& a, const float* sumsq, const int32_t* ok, bool guarded, vaw_stream stream) {
+    VAW_CHECK_ARG(n > 0, "%s: n<=0", what);
+    VAW_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0 &&
+                      ((uintptr_t)shadow_bf16 & 7) == 0, "%s: buffers must be 16-byte aligned", what);
+    VAW_CHECK_ARG(a.clip <= 0.f || sumsq != nullptr, "%s: clip needs sumsq", what);
+    VAW_CHECK_ARG(!guarded || (ok != nullptr && ((uintptr_t)ok & 3) == 0), "%s: ok must be a 4-byte aligned device int32", what);
+    if (guarded)
+        adamw_ema_kernel<true><<<adam_grid(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, ema, (bf16_t*)shadow_bf16, n, sumsq, a, hyper, ok);
+    else
+        adamw_ema_kernel<false><<<adam_grid(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, ema, (bf16_t*)shadow_bf16, n, sumsq, a, hyper, nullptr);
+    VAW_CHECK_LAUNCH(what);
+    return VAW_OK;
+}
+
 extern "C" int vaw_adamw_ema_step(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t n,
                                   float lr, float beta1, float beta2, float eps, float weight_decay, float bc1,
                                   float bc2, float ema_decay, const float* sumsq, float clip_max_norm, int zero_grad,
                                   vaw_stream stream) {
-    VAW_CHECK_ARG(n > 0, "adamw: n<=0");
-    VAW_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0 &&
-                      ((uintptr_t)shadow_bf16 & 7) == 0, "adamw: buffers must be 16-byte aligned");
-    VAW_CHECK_ARG(clip_max_norm <= 0.f || sumsq != nullptr, "adamw: clip needs sumsq");
     AdamArgs a{lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), ema_decay, clip_max_norm, zero_grad};
-    adamw_ema_kernel<<<adam_grid(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, ema, (bf16_t*)shadow_bf16, n, sumsq, a, nullptr);
-    VAW_CHECK_LAUNCH("adamw_ema");
-    return VAW_OK;
+    return adamw_launch("adamw_ema", p, g, m, v, ema, shadow_bf16, n, nullptr, a, sumsq, nullptr, false, stream);
 }
 
 extern "C" int vaw_adamw_ema_step_dev(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t n,
                                       const float* hyper, float beta1, float beta2, float eps, float weight_decay,
                                       float ema_decay, const float* sumsq, float clip_max_norm, int zero_grad,
                                       vaw_stream stream) {
-    VAW_CHECK_ARG(n > 0 && hyper, "adamw_dev: n<=0 or no hyper buffer");
-    VAW_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0 &&
-                      ((uintptr_t)shadow_bf16 & 7) == 0, "adamw_dev: buffers must be 16-byte aligned");
-    VAW_CHECK_ARG(clip_max_norm <= 0.f || sumsq != nullptr, "adamw_dev: clip needs sumsq");
+    VAW_CHECK_ARG(hyper, "adamw_ema_dev: no hyper buffer");
     AdamArgs a{0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, ema_decay, clip_max_norm, zero_grad};
-    adamw_ema_kernel<<<adam_grid(n), 256, 0, (hipStream_t)stream>>>(p, g, m, v, ema, (bf16_t*)shadow_bf16, n, sumsq, a, hyper);
-    VAW_CHECK_LAUNCH("adamw_ema_dev");
-    return VAW_OK;
+    return adamw_launch("adamw_ema_dev", p, g, m, v, ema, shadow_bf16, n, hyper, a, sumsq, nullptr, false, stream);
+}
+
+extern "C" int vaw_adamw_ema_step_guarded(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t n,
+                                          float lr, float beta1, float beta2, float eps, float weight_decay, float bc1,
+                                          float bc2, float ema_decay, const float* sumsq, float clip_max_norm, int zero_grad,
+                                          const int32_t* ok, vaw_stream stream) {
+    AdamArgs a{lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), ema_decay, clip_max_norm, zero_grad};
+    return adamw_launch("adamw_ema_guarded", p, g, m, v, ema, shadow_bf16, n, nullptr, a, sumsq, ok, true, stream);
+}
+
+extern "C" int vaw_adamw_ema_step_guarded_dev(float* p, float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t n,
+                                              const float* hyper, float beta1, float beta2, float eps, float weight_decay,
+                                              float ema_decay, const float* sumsq, float clip_max_norm, int zero_grad,
+                                              const int32_t* ok, vaw_stream stream) {
+    VAW_CHECK_ARG(hyper, "adamw_ema_guarded_dev: no hyper buffer");
+    AdamArgs a{0.f, beta1, beta2, eps, weight_decay, 1.f, 1.f, ema_decay, clip_max_norm, zero_grad};
+    return adamw_launch("adamw_ema_guarded_dev", p, g, m, v, ema, shadow_bf16, n, hyper, a, sumsq, ok, true, stream);
 }
 
 __global__ void ema_kernel(float* __restrict__ ema, const float* __restrict__ src, int64_t n, float d) {

@@ -367,12 +367,15 @@ extern "C" int vaw_fp8_transpose(const void* q, int64_t R, int64_t C, int64_t ld
 }
 
 // Delayed scaling, once per step for all tensors: state = {scale in use, running max |x|, FMAX / margin, unused}.
+// FINITE_ONLY (vaw_fp8_scale_update_finite, the step guard's form): a running max that is not finite -- an overflowed activation or
+// gradient of a step the guard refuses -- keeps the scale in use as well, instead of making it infinite for the steps that follow.
+template <bool FINITE_ONLY>
 __global__ void fp8_scale_update_kernel(float* __restrict__ states, int64_t n) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
     float* st = states + 4 * i;
     const float m = st[1];
-    if (m > 0.f) st[0] = m / st[2];      // an all-zero (or never quantised) tensor keeps its scale
+    if (m > 0.f && (!FINITE_ONLY || m <= 3.402823466e+38f)) st[0] = m / st[2];      // an all-zero (or never quantised) tensor keeps its scale
     st[1] = 0.f;
 }
 
@@ -478,8 +481,14 @@ extern "C" int vaw_fp8_quantize_delayed_batched(int n_jobs, const vaw_fp8_quant_
 
 extern "C" int vaw_fp8_scale_update(float* states, int64_t n, vaw_stream stream) {
     VAW_CHECK_ARG(states && n > 0 && ((uintptr_t)states & 15) == 0, "fp8_scale_update: states [n][4] floats, 16-byte aligned");
-    fp8_scale_update_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(states, n);
+    fp8_scale_update_kernel<false><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(states, n);
     VAW_CHECK_LAUNCH("fp8_scale_update");
+    return VAW_OK;
+}
+extern "C" int vaw_fp8_scale_update_finite(float* states, int64_t n, vaw_stream stream) {
+    VAW_CHECK_ARG(states && n > 0 && ((uintptr_t)states & 15) == 0, "fp8_scale_update_finite: states [n][4] floats, 16-byte aligned");
+    fp8_scale_update_kernel<true><<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(states, n);
+    VAW_CHECK_LAUNCH("fp8_scale_update_finite");
     return VAW_OK;
 }
 

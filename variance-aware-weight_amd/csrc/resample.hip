@@ -18,6 +18,9 @@
 // Thread `me` owns timestep `me`: it walks the whole batch in order (staged through LDS in chunks, every lane reads the same
 // word: a broadcast) and appends the losses whose t is its own.  Nothing depends on the grid or block size.  Entries outside
 // [0, T) are staged as t = -1, which no thread owns; workgroup 0 counts them and its thread 0 adds the count to bad[0].
+// FINITE_ONLY (vaw_resampler_update_finite, the step guard's form): a pair whose loss is inf or NaN is staged and counted the same
+// way, so a poisoned step never enters the history the draws are formed from.
+template <bool FINITE_ONLY>
 __global__ void __launch_bounds__(RS_UPD_THREADS) resampler_update_kernel(const int64_t* __restrict__ ts, const float* __restrict__ losses,
                                                                           int n, int T, int H, double* __restrict__ ring,
                                                                           int64_t* __restrict__ seen, int* __restrict__ bad) {
@@ -33,9 +36,10 @@ __global__ void __launch_bounds__(RS_UPD_THREADS) resampler_update_kernel(const 
         __syncthreads();
         for (int i = threadIdx.x; i < m; i += RS_UPD_THREADS) {
             const int64_t t = ts[c0 + i];
-            const bool ok = t >= 0 && t < T;
+            const int bits = __float_as_int(losses[c0 + i]);
+            const bool ok = t >= 0 && t < T && (!FINITE_ONLY || (bits & 0x7f800000) != 0x7f800000);
             nbad += ok ? 0 : 1;
-            stage[i] = make_int2(ok ? (int)t : -1, __float_as_int(losses[c0 + i]));
+            stage[i] = make_int2(ok ? (int)t : -1, bits);
         }
         __syncthreads();
         if (own) {
@@ -58,15 +62,25 @@ __global__ void __launch_bounds__(RS_UPD_THREADS) resampler_update_kernel(const 
     }
 }
 
+static int resampler_update_launch(const char* what, bool finite_only, const int64_t* ts, const float* losses, int n, int T, int H,
+                                   double* ring, int64_t* seen, int* bad, vaw_stream stream) {
+    VAW_CHECK_ARG(T > 0 && H > 0 && n >= 0, "%s: T %d and H %d must be positive, n %d not negative", what, T, H, n);
+    VAW_CHECK_ARG(ring && seen && bad, "%s: ring / seen / bad is NULL", what);
+    if (n == 0) return VAW_OK;
+    VAW_CHECK_ARG(ts && losses, "%s: ts / losses is NULL", what);
+    const int grid = ceil_div(T, RS_UPD_THREADS);
+    if (finite_only) resampler_update_kernel<true><<<grid, RS_UPD_THREADS, 0, (hipStream_t)stream>>>(ts, losses, n, T, H, ring, seen, bad);
+    else resampler_update_kernel<false><<<grid, RS_UPD_THREADS, 0, (hipStream_t)stream>>>(ts, losses, n, T, H, ring, seen, bad);
+    VAW_CHECK_LAUNCH(what);
+    return VAW_OK;
+}
 extern "C" int vaw_resampler_update(const int64_t* ts, const float* losses, int n, int T, int H, double* ring, int64_t* seen,
                                     int* bad, vaw_stream stream) {
-    VAW_CHECK_ARG(T > 0 && H > 0 && n >= 0, "resampler_update: T %d and H %d must be positive, n %d not negative", T, H, n);
-    VAW_CHECK_ARG(ring && seen && bad, "resampler_update: ring / seen / bad is NULL");
-    if (n == 0) return VAW_OK;
-    VAW_CHECK_ARG(ts && losses, "resampler_update: ts / losses is NULL");
-    resampler_update_kernel<<<ceil_div(T, RS_UPD_THREADS), RS_UPD_THREADS, 0, (hipStream_t)stream>>>(ts, losses, n, T, H, ring, seen, bad);
-    VAW_CHECK_LAUNCH("resampler_update");
-    return VAW_OK;
+    return resampler_update_launch("resampler_update", false, ts, losses, n, T, H, ring, seen, bad, stream);
+}
+extern "C" int vaw_resampler_update_finite(const int64_t* ts, const float* losses, int n, int T, int H, double* ring, int64_t* seen,
+                                           int* bad, vaw_stream stream) {
+    return resampler_update_launch("resampler_update_finite", true, ts, losses, n, T, H, ring, seen, bad, stream);
 }
 
 // ---- draw ----------------------------------------------------------------------------------------------------------------------

@@ -317,6 +317,9 @@ class DiT(FlatModule):
         # byte-identical to quantising the bf16 tensor, which is then never written or read
         self.fp8_fuse_epilogue = os.environ.get("VAW_FP8_FUSE", "1") != "0"
         self.fp8_fuse_rows = os.environ.get("VAW_FP8_FUSE_ROWS", "1") != "0"      # ... and LN-modulate / gate backward their outputs
+        # runs behind the step guard (Trainer, args.skip_nonfinite): a running max that is not finite keeps the scale in use
+        # (vaw_fp8_scale_update_finite) instead of making it infinite for the steps after a refused one
+        self.fp8_finite_scales = False
         self.activation_checkpointing = False
         self.set_compute_dtype(compute_dtype)
         self._anchor = torch.zeros(1, requires_grad=True)
@@ -472,7 +475,7 @@ class DiT(FlatModule):
             delayed = self.fp8_scaling == "delayed"
             ws.d_fwd, ws.d_bwd = delayed and ws.calib_fwd, delayed and ws.calib_bwd
             if ws.d_fwd or ws.d_bwd:
-                ops.fp8_scale_update(ws.fp8_states)
+                ops.fp8_scale_update(ws.fp8_states, finite=getattr(self, "fp8_finite_scales", False))
         return ws
 
     def _fuse(self, ws, calibrated, rows):
@@ -495,7 +498,7 @@ class DiT(FlatModule):
             self._fp8_wstates, self._fp8_w, self._fp8_wgroup = ops.fp8_states([L.FP8] * (4 * self.depth), dev, self.fp8_margin), {}, ops.GroupCache(2)
         delayed = self.fp8_scaling == "delayed" and bool(self._fp8_w)
         if delayed:
-            ops.fp8_scale_update(self._fp8_wstates)
+            ops.fp8_scale_update(self._fp8_wstates, finite=getattr(self, "fp8_finite_scales", False))
             names = [f"blocks.{l}.{s.prefix}weight" for l in range(self.depth) for s in SITES]      # all 4 L in one launch
             self._fp8_wgroup.get(self._flat.data_ptr(), lambda: ops.Fp8QuantGroup([(self._p32(n), self._fp8_w[n]) for n in names], dev)).launch()
             self._fp8_epoch = epoch

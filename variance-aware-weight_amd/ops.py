@@ -710,7 +710,11 @@ def fp8_states(formats, device, margin=2.0):
     return st.to(device)
 
 
-def fp8_scale_update(states):
+def fp8_scale_update(states, finite=False):
+    """finite (runs behind the step guard): a running max that is not finite keeps the scale in use (vaw_fp8_scale_update_finite)."""
+    if finite:
+        check(L.lib().vaw_fp8_scale_update_finite(states.data_ptr(), states.shape[0], stream_ptr()), "vaw_fp8_scale_update_finite")
+        return
     check(L.lib().vaw_fp8_scale_update(states.data_ptr(), states.shape[0], stream_ptr()), "vaw_fp8_scale_update")
 
 
@@ -1210,8 +1214,22 @@ def sumsq(g, out, accumulate=False):
     check(L.lib().vaw_sumsq(ptr(g), g.numel(), ptr(out), 1 if accumulate else 0, ptr(ws), stream_ptr()), "vaw_sumsq")
 
 
-def adamw_ema_step(p, g, m, v, ema, shadow, lr, beta1, beta2, eps, wd, step, ema_decay, sumsq_t, clip, zero_grad, hyper=None):
-    """hyper: device f32[3] {lr, bc1, bc2} -- when given, the kernel reads the step-dependent scalars from it (graph replay)."""
+def adamw_ema_step(p, g, m, v, ema, shadow, lr, beta1, beta2, eps, wd, step, ema_decay, sumsq_t, clip, zero_grad, hyper=None, ok=None):
+    """hyper: device f32[3] {lr, bc1, bc2} -- when given, the kernel reads the step-dependent scalars from it (graph replay).
+    ok: device int32[1], the step guard's verdict -- when given, the guarded entry runs: the same pass where ok[0] != 0, nothing but
+    the zero_grad store where it is 0."""
+    if ok is not None:
+        need_cuda(ok)
+        zg = 1 if zero_grad else 0
+        if hyper is not None:
+            check(L.lib().vaw_adamw_ema_step_guarded_dev(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(shadow), p.numel(), ptr(hyper),
+                                                         beta1, beta2, eps, wd, ema_decay, ptr(sumsq_t), clip or 0.0, zg, ptr(ok),
+                                                         stream_ptr()), "vaw_adamw_ema_step_guarded_dev")
+            return
+        check(L.lib().vaw_adamw_ema_step_guarded(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(shadow), p.numel(), lr, beta1, beta2,
+                                                 eps, wd, 1.0 - beta1 ** step, 1.0 - beta2 ** step, ema_decay, ptr(sumsq_t), clip or 0.0,
+                                                 zg, ptr(ok), stream_ptr()), "vaw_adamw_ema_step_guarded")
+        return
     if hyper is not None:
         check(L.lib().vaw_adamw_ema_step_dev(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), ptr(shadow), p.numel(), ptr(hyper), beta1,
                                              beta2, eps, wd, ema_decay, ptr(sumsq_t), clip or 0.0, 1 if zero_grad else 0,

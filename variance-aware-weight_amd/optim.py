@@ -42,6 +42,7 @@ class FusedAdamW(torch.optim.Optimizer):
         # prepare_step() before every (captured or replayed) step; step() then neither counts nor reads host scalars
         self.device_hyper = None
         self._hyper_host = None
+        self.guard = None                  # attach_guard(): the device's verdict on every step
 
     def enable_device_hyper(self):
         dev = self.model._flat.device
@@ -91,6 +92,20 @@ class FusedAdamW(torch.optim.Optimizer):
             if e._flat.numel() > n:
                 self._ema_frozen = e
 
+    def attach_guard(self, guard):
+        """Put a vaw_amd.StepGuard in front of the update: every step() then forms the sum of squared gradients (the clip's scalar:
+        one result serves both), launches vaw_step_guard on it and runs the guarded update, which leaves the weights, both moments,
+        the EMA and the bf16 shadow untouched when the gradient is not finite or spikes.  Nothing synchronises with the host.  The
+        step count and whatever drives `lr` advance on a refused step too (they are the host's): with nothing refused, a run with
+        the guard attached is bitwise the run without it.  None detaches."""
+        from .guard import StepGuard
+        if guard is not None:
+            if not isinstance(guard, StepGuard):
+                raise TypeError(f"attach_guard needs a vaw_amd.StepGuard, got {type(guard).__name__}")
+            if guard.device != self.model._flat.device:
+                raise ValueError(f"the guard lives on {guard.device}, the model's flat buffer on {self.model._flat.device}")
+        self.guard = guard
+
     def _step_sharded(self):
         """reduce-scattered gradients -> AdamW (+EMA) on this rank's chunks only -> all-gather of the updated weights."""
         m, z, grp = self.model, self.zero, self.param_groups[0]
@@ -102,11 +117,17 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.device_hyper is None:
             self.step_count += 1
         clip = self.max_grad_norm
-        if clip:      # global norm: this rank's chunks hold 1 / world of the averaged gradient; the scalar is summed over ranks
+        guard = self.guard
+        if clip or guard is not None:
+            # global norm: this rank's chunks hold 1 / world of the averaged gradient; the scalar is summed over ranks (with a guard
+            # always: every rank then takes the same decision from the same scalar)
             for i, (lo, hi) in enumerate(self._chunks):
                 ops.sumsq(g[lo:hi], self._sumsq, accumulate=i > 0)
             import torch.distributed as dist
             dist.all_reduce(self._sumsq, group=z.pg)
+        if guard is not None:
+            guard.check(self._sumsq)
+        guarded = {} if guard is None else {"ok": guard.ok}          # (absent: the call is today's, argument for argument)
         shadow = m._flat_shadow
         off = 0
         for lo, hi in self._chunks:
@@ -115,7 +136,7 @@ class FusedAdamW(torch.optim.Optimizer):
                                None if self._ema_shard is None else self._ema_shard[off:off + k],
                                None if shadow is None else shadow[lo:hi], grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"],
                                grp["weight_decay"], self.step_count, self.ema_decay, self._sumsq if clip else None, clip, False,
-                               hyper=self.device_hyper)
+                               hyper=self.device_hyper, **guarded)
             off += k
         # the weights the kernels read: the bf16 shadow in throughput mode (2 B per parameter on the wire; the f32 masters of
         # other ranks' chunks go stale until consolidate()), the f32 parameters in parity mode
@@ -222,8 +243,12 @@ class FusedAdamW(torch.optim.Optimizer):
             self.step_count += 1
         n = m._flat_n_train
         clip = self.max_grad_norm
-        if clip:
-            ops.sumsq(g, self._sumsq)
+        guard = self.guard
+        if clip or guard is not None:
+            ops.sumsq(g, self._sumsq)          # one scalar for the clip and for the guard
+        if guard is not None:
+            guard.check(self._sumsq)
+        guarded = {} if guard is None else {"ok": guard.ok}          # (absent: the call is today's, argument for argument)
         ema_flat = None
         if self.ema_model is not None:
             self.ema_model.ensure_flat()
@@ -232,7 +257,7 @@ class FusedAdamW(torch.optim.Optimizer):
         ops.adamw_ema_step(m._flat[:n], g, self.exp_avg, self.exp_avg_sq, None if ema_flat is None else ema_flat[:n],
                            None if shadow is None else shadow[:n], grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"],
                            grp["weight_decay"], self.step_count, self.ema_decay, self._sumsq if clip else None, clip, False,
-                           hyper=self.device_hyper)
+                           hyper=self.device_hyper, **guarded)
         if ema_flat is not None and ema_flat.numel() > n:
             ops.ema_update(ema_flat[n:], m._flat[n:], self.ema_decay)   # frozen entries (pos_embed) are EMA'd too
         m.mark_shadow_fresh()

@@ -118,6 +118,9 @@ class DeviceLossSecondMomentResampler(ScheduleSampler):
         self.seen = torch.zeros(T, dtype=torch.int64, device=device)
         self._p = torch.zeros(T, dtype=torch.float64, device=device)
         self._bad = torch.zeros(1, dtype=torch.int32, device=device)
+        # runs behind the step guard (Trainer, args.skip_nonfinite): pairs whose loss is inf or NaN are not recorded but counted
+        # (vaw_resampler_update_finite), so a refused step leaves no trace in the history either
+        self.skip_nonfinite = False
 
     def sample(self, batch_size, device=None):
         """(indices i64 [B], weights f32 [B]) on the sampler's device; enqueues one kernel, never synchronises."""
@@ -147,9 +150,9 @@ class DeviceLossSecondMomentResampler(ScheduleSampler):
         losses = torch.as_tensor(losses, device=self.device).to(torch.float32).contiguous()
         if ts.shape != losses.shape or ts.dim() != 1:
             raise L.VawError(f"update_with_all_losses: ts {tuple(ts.shape)} and losses {tuple(losses.shape)} must be equal 1-d shapes")
-        L.check(L.lib().vaw_resampler_update(L.ptr(ts), L.ptr(losses), ts.numel(), self.num_timesteps, self.history_per_term,
-                                             L.ptr(self.ring), L.ptr(self.seen), L.ptr(self._bad), L.stream_ptr()),
-                "vaw_resampler_update")
+        name = "vaw_resampler_update_finite" if self.skip_nonfinite else "vaw_resampler_update"
+        L.check(getattr(L.lib(), name)(L.ptr(ts), L.ptr(losses), ts.numel(), self.num_timesteps, self.history_per_term,
+                                       L.ptr(self.ring), L.ptr(self.seen), L.ptr(self._bad), L.stream_ptr()), name)
 
     def update_with_local_losses(self, local_ts, local_losses):
         """World 1: the update kernel on the given tensors.  World > 1: ONE all_gather_into_tensor of a fixed [n, 2] f64 pack
@@ -171,7 +174,7 @@ class DeviceLossSecondMomentResampler(ScheduleSampler):
         return self._p.cpu().numpy()
 
     def invalid_count(self):
-        """(t, loss) pairs skipped so far because t was outside [0, T).  Synchronises."""
+        """(t, loss) pairs skipped so far because t was outside [0, T) (or, with skip_nonfinite, the loss not finite).  Synchronises."""
         return int(self._bad.item())
 
     def state_dict(self):

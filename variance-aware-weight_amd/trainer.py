@@ -8,6 +8,8 @@ Differences that do not change results:
     torch optimizer is driven exactly as the reference drives it.
   * the two `.item()` host syncs per micro-step become one per step (or none: `args.defer_loss_sync=True`
     makes train_step return a 0-dim device tensor).
+  * `args.skip_nonfinite=True` / `args.skip_grad_spike=F` (an extension, guard.py): the device refuses an update whose gradient is
+    not finite (or whose norm exceeds F times its running mean); absent, nothing is built and every launch is what it was.
   * `args.hip_graph=True` (single GPU, FusedAdamW, grad_accumulation 1): after two eager steps the whole step -- latent
     sampling, q_sample, forward, loss, backward, clip, AdamW+EMA, zero_grad: several hundred launches -- is captured
     into ONE hipGraph and replayed; per step the host only copies the next batch into the static input buffers and
@@ -54,6 +56,14 @@ class Trainer:
     def __init__(self, args, device, model, ema_model, optimizer, scheduler, diffusion, train_loader, pbar=None):
         if getattr(args, "learn_align", False):
             raise NotImplementedError("learn_align needs network-fetched teacher encoders: out of scope (SURVEY.md §2.1 row 12)")
+        # step guard (an extension, guard.py): args.skip_nonfinite = True refuses, on the device, every update whose flat gradient holds
+        # an inf or a NaN; args.skip_grad_spike = F (> 1) also one whose norm exceeds F times the running mean of the applied steps'.
+        # The host reads the guard's counters every args.guard_check_every steps (default 100; the only synchronisation the guard
+        # adds) and raises FloatingPointError once args.max_consecutive_skips (default 20) steps in a row were refused
+        want_guard = bool(getattr(args, "skip_nonfinite", False)) or getattr(args, "skip_grad_spike", None) is not None
+        if want_guard and not isinstance(optimizer, FusedAdamW):
+            raise ValueError("args.skip_nonfinite / args.skip_grad_spike: the step guard is part of vaw_amd.FusedAdamW's update kernel "
+                             f"(got {type(optimizer).__name__})")
         self.args, self.device = args, device
         self.model, self.ema_model = model, ema_model
         self.optimizer, self.scheduler, self.diffusion = optimizer, scheduler, diffusion
@@ -109,6 +119,16 @@ class Trainer:
                 raise ValueError("args.ema_snapshot_every needs args.ema_snapshot_dir")
             if dist_util.is_main_process():
                 self.power_ema = PowerEMA(model, tuple(rels))
+        self.guard = None
+        if want_guard:
+            from .guard import StepGuard
+            self.guard = StepGuard(optimizer.model._flat.device, spike_factor=getattr(args, "skip_grad_spike", None))
+            optimizer.attach_guard(self.guard)
+            self._guard_every = max(1, int(getattr(args, "guard_check_every", 100) or 100))
+            self._guard_limit = max(1, int(getattr(args, "max_consecutive_skips", 20) or 20))
+            self._guard_calls = 0
+            if hasattr(inner, "fp8_finite_scales"):
+                inner.fp8_finite_scales = True          # an overflowed tensor of a refused step must not make its scale infinite
         self.last_mse = None
         self._cpu_rng = bool(getattr(args, "cpu_rng", False))
         # VAW_STEP_FUSED (default on): the latent sample, q_sample and the timestep scaling are one launch, the loss kernels gather
@@ -133,6 +153,8 @@ class Trainer:
             # "loss-second-moment-device" keeps the history in device memory: draw and update are two kernels of the step (no
             # host synchronisation; captured with it under args.hip_graph).  The host sampler reads the losses back every step
             self._device_sampler = hasattr(self.schedule_sampler, "ring")
+            if self.guard is not None and self._device_sampler:
+                self.schedule_sampler.skip_nonfinite = True          # ... nor may its losses enter the sampler's history
             if getattr(args, "hip_graph", False) and not self._device_sampler:
                 raise ValueError("args.schedule_sampler updates its history on the host every step: not with args.hip_graph")
         # hipGraph mode
@@ -249,6 +271,20 @@ class Trainer:
         if self.power_ema is not None and self._ema_snapshot_every and step % self._ema_snapshot_every == 0:
             self.power_ema.save_snapshot(os.path.join(self.args.ema_snapshot_dir, f"power_ema_{int(step):08d}.pt"))
 
+    def _check_guard(self, step):
+        """Every args.guard_check_every calls: read the guard's counters (a host synchronisation, the only one the guard adds) and
+        give up when args.max_consecutive_skips updates in a row were refused -- the run is not recovering by itself."""
+        if self.guard is None:
+            return
+        self._guard_calls += 1
+        if self._guard_calls % self._guard_every:
+            return
+        c = self.guard.counters()
+        if c["in_a_row"] >= self._guard_limit:
+            raise FloatingPointError(f"step {step}: the step guard refused the last {c['in_a_row']} updates in a row "
+                                     f"(args.max_consecutive_skips = {self._guard_limit}; {c['skipped_nonfinite']} non-finite and "
+                                     f"{c['skipped_spike']} spiking gradients in {c['steps']} steps)")
+
     def _graph_body(self, images, labels):
         """Everything of one step that runs on the GPU, on static inputs; returns (loss, mse) device scalars."""
         loss, mse = self._micro_step(images, labels, 1, False, False)
@@ -308,6 +344,7 @@ class Trainer:
         if dist_util.is_main_process():
             self._update_ema()
         self._snapshot_power_ema(step)
+        self._check_guard(step)
         self.last_mse = mse
         if dist_util.is_main_process() and self.pbar is not None:
             self.pbar.update(1)
@@ -347,6 +384,7 @@ class Trainer:
         if dist_util.is_main_process():
             self._update_ema()
         self._snapshot_power_ema(step)
+        self._check_guard(step)
         self.last_mse = mse_avg
         if getattr(a, "defer_loss_sync", False):
             if dist_util.is_main_process() and self.pbar is not None:
